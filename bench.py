@@ -1,12 +1,21 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on its config: Poseidon2-BN254 permutations/s per GPU.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
 `python bench.py --gpus N` with N > 1 and no launcher spawns the N rank processes itself (before anything touches the
 GPU) and relays rank 0's JSON line.
+
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes the outputs if asked and
+prints the line (the headline fields, `roofline` and `valu_issue` below).  --full adds everything else: the oracle check of
+the timed kernel's output, `cpu_baseline`, the extra legs and the committed records (`extra`).
+
+--dump-outputs DIR writes what the last timed step computed, as its caller receives it, to DIR/permute_batch_out.npy (rank 0):
+a fixed, seeded sample of 2^16 of the step's output states (all of them when --states is smaller), in ascending order, each
+state's three canonical little-endian field elements as eight 32-bit words each, in float64 (exact): shape (rows, 3, 8),
+12.6 MB.  The inputs are seeded, so two runs with the same arguments compare output for output.
 
 Nothing after the timed region can lose the line (bench_orchestration.py; the legs themselves are in bench_legs.py): everything after the headline runs under ONE
 deadline (--extra-budget-s, default 240 s: a leg starts only if its worst case fits what is left, else it is recorded as
@@ -22,7 +31,7 @@ A "step" is one pass of the hot path over one batch: the batched permutation ker
 uniform in [0, r) by rejection).  With N ranks every rank runs the same-sized batch on its own GPU (weak scaling, no
 data-path collective: the permutation has no exchange step); value = all states of all ranks / max-over-ranks time.
 
-The JSON line also carries
+The JSON line also carries (cpu_baseline and extra with --full only)
   roofline      the dominant kernel (k_permute_batch) against the HBM roof BASELINE.json prescribes:
                 achieved = 192 algorithmic B/permutation x 2^24 / average launch time (HIP events on the launch
                 stream, measured in this run).  `traffic` is NOT measured in this run: it is the per-launch HBM byte
@@ -77,17 +86,35 @@ from bench_orchestration import (LEG_WORST_S, Budget, BoundedDist, CollectiveTim
 from bench_legs import (big_slots_leg, cli_default_leg, cpu_baseline, dataset_leg, host_threads, ingest_leg, inprocess_child,  # noqa: E402,F401
                         inprocess_leg, newest_profile, slot_root_leg, uniform_felts_device, witness_leg, witnesses_from_files_leg)
 
+DUMP_ROWS = 1 << 16                # --dump-outputs: output states sampled from the last step (12.6 MB as float64)
+DUMP_SEED = 0xD0C5
+
+
+def dump_outputs(torch, np, y, n, out_dir):
+    """--dump-outputs: DIR/permute_batch_out.npy, the same DUMP_ROWS states of `y` (n x 96 B, three canonical little-endian
+    field elements per state) in every run, in ascending order, each element as its eight 32-bit words in float64 (exact)."""
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(n, DUMP_ROWS), replace=False))
+    words = y[torch.from_numpy(rows).to(y.device)].cpu().numpy().view("<u4").reshape(-1, 3, 8)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "permute_batch_out.npy"), words.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--states", type=int, default=N_STATES, help="states per step per GPU (default 2^24)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the config-3 / config-4 / ingest / config-5 extra legs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a seeded sample of the last step's output to DIR/permute_batch_out.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the oracle check of the timed output, the CPU baseline and the extra legs, "
+                         "and add the committed records (off by default)")
+    ap.add_argument("--no-extra", action="store_true", help="(with --full) skip the config-3 / config-4 / ingest / config-5 extra legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU baseline")
     ap.add_argument("--no-child-legs", action="store_true",
-                    help="skip the legs that start child processes (dataset_inprocess, cli_default): for runs under a counter-collecting profiler")
-    ap.add_argument("--legs", default="", help="comma-separated names of the extra legs to run (default: all): " + ", ".join(sorted(LEG_WORST_S)))
+                    help="(with --full) skip the legs that start child processes (dataset_inprocess, cli_default): for runs under a counter-collecting profiler")
+    ap.add_argument("--legs", default="", help="(with --full) comma-separated names of the extra legs to run (default: all): " + ", ".join(sorted(LEG_WORST_S)))
     ap.add_argument("--extra-budget-s", type=float, default=240.0,
                     help="ONE deadline for everything after the headline: a leg starts only if its worst case fits what is left; when it "
                          "passes, the line is printed with what is there (default 240)")
@@ -99,6 +126,10 @@ def main():
                     help="(child mode) main: first + warm build, automatic exchange; rccl / copy / host: one build with that exchange asked for "
                          "BY NAME; few: a dataset of few, large slots cut by units")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.legs and not args.full:
+        ap.error("--legs chooses among the legs of --full")
 
     if args.inprocess_leg:
         return inprocess_child(args.inprocess_leg, args.inprocess_what)
@@ -203,15 +234,18 @@ def main():
     total_perms = n * args.steps * world
     value = total_perms / elapsed
 
-    # ---- sanity: the result of the timed kernel is the reference permutation (a strided sample, vs the oracle).
+    # ---- (--full) sanity: the result of the timed kernel is the reference permutation (a strided sample, vs the oracle).
     # Rank 0 only: the oracle is a checker built on demand, N ranks must not race its build.
-    life.phase("oracle check of the timed kernel's output")
     import numpy as np
     C = None
-    if rank == 0:
+    if args.full and rank == 0:
+        life.phase("oracle check of the timed kernel's output")
         C, P = g.load_oracle()
         idx = torch.cat([torch.tensor([0, 1, n // 2, n - 1], device=dev), torch.arange(0, n, max(1, n // 2048), device=dev)])
         assert np.array_equal(y[idx].cpu().numpy(), C.permute_batch(x[idx].cpu().numpy(), threads=4)), "bench output != oracle"
+    if args.dump_outputs and rank == 0:
+        life.phase("dump outputs")
+        dump_outputs(torch, np, y, n, args.dump_outputs)
 
     avg_ms = sum(kernel_ms) / len(kernel_ms)
     achieved = BYTES_PER_PERM * n / (avg_ms * 1e-3) / 1e9
@@ -257,61 +291,62 @@ def main():
     life.headline(out, args.extra_budget_s + 10.0)           # the watchdog's deadline: the budget plus time to print
     if rank == 0 and os.environ.get("BENCH_HEADLINE_FLAG"):
         open(os.environ["BENCH_HEADLINE_FLAG"], "w").close()  # (self-spawned ranks) tells the parent that rank 0 can finish alone
-    del x, y
-    torch.cuda.empty_cache()
-    def before_collective(what):
-        if inject("gather_error"):          # (rehearsal) this rank fails right where the others enter the collective
-            raise RuntimeError("injected: gather_error before %s" % what)
+    if args.full:                                         # everything the headline does not need
+        del x, y
+        torch.cuda.empty_cache()
+        def before_collective(what):
+            if inject("gather_error"):          # (rehearsal) this rank fails right where the others enter the collective
+                raise RuntimeError("injected: gather_error before %s" % what)
 
-    bdist = BoundedDist(dist, coord, timeout_s=float(os.environ.get("BENCH_COLLECTIVE_TIMEOUT_S", "20")), before=before_collective) if world > 1 else None
-    legs = LegRunner(coord, budget, life, rank, world, after_leg=torch.cuda.empty_cache)
+        bdist = BoundedDist(dist, coord, timeout_s=float(os.environ.get("BENCH_COLLECTIVE_TIMEOUT_S", "20")), before=before_collective) if world > 1 else None
+        legs = LegRunner(coord, budget, life, rank, world, after_leg=torch.cuda.empty_cache)
 
-    only = set(x for x in args.legs.split(",") if x)
-    if only - set(LEG_WORST_S):
-        raise SystemExit("--legs: unknown leg(s) %s" % sorted(only - set(LEG_WORST_S)))
+        only = set(x for x in args.legs.split(",") if x)
+        if only - set(LEG_WORST_S):
+            raise SystemExit("--legs: unknown leg(s) %s" % sorted(only - set(LEG_WORST_S)))
 
-    def run_leg(name, fn, **kw):
-        if only and name not in only:
-            return False
-        return legs.run(name, fn, LEG_WORST_S[name](world), **kw)
+        def run_leg(name, fn, **kw):
+            if only and name not in only:
+                return False
+            return legs.run(name, fn, LEG_WORST_S[name](world), **kw)
 
-    if not args.no_cpu_baseline and world == 1:
-        run_leg("cpu_baseline", lambda: {"cpu_baseline": cpu_baseline(C, np, torch, dev)})
-    if not args.no_extra:
-        def slot_root():
-            leg, hash_roof = slot_root_leg(torch, ctx, pkg, dev, stream)
-            return dict(leg, roofline_hash_cells=hash_roof)
-        run_leg("slot_root", slot_root, all_ranks=False)
-        if world == 1:
-            run_leg("witnesses", lambda: witness_leg(torch, ctx, pkg))
-            run_leg("ingest", lambda: ingest_leg(torch, ctx, pkg, dev))
-            run_leg("witnesses_from_files", lambda: witnesses_from_files_leg(torch, ctx, pkg, dev))
-        run_leg("dataset", lambda: dataset_leg(torch, bdist, coord, ctx, pkg, coll_dev, rank, world), collective=world > 1)
-        run_leg("dataset_big_slots", lambda: big_slots_leg(torch, bdist, coord, ctx, pkg, coll_dev, rank, world), collective=world > 1)
-        if not args.no_child_legs:
-            run_leg("dataset_inprocess", lambda: inprocess_leg(torch, coord, budget, ctx, rank, world))
+        if not args.no_cpu_baseline and world == 1:
+            run_leg("cpu_baseline", lambda: {"cpu_baseline": cpu_baseline(C, np, torch, dev)})
+        if not args.no_extra:
+            def slot_root():
+                leg, hash_roof = slot_root_leg(torch, ctx, pkg, dev, stream)
+                return dict(leg, roofline_hash_cells=hash_roof)
+            run_leg("slot_root", slot_root, all_ranks=False)
             if world == 1:
-                run_leg("cli_default", lambda: cli_default_leg(pkg, g))
-    life.phase("committed records")
-    # config 5 at its nominal slot size (one GPU's share, 32 TiB: 13 minutes, so not run here): the committed record, named as such
-    rec = newest_profile("r*_config5_nominal_share.txt")
-    if rec and rank == 0:
-        try:
-            last = [l for l in open(rec).read().splitlines() if l.startswith("{")][-1]
-            life.record({"config5_nominal_share_record": dict(json.loads(last), source="%s (tools/config5_share.py; NOT measured in this run)" % os.path.relpath(rec, ROOT),
-                                                              workload="configs[4] at its nominal slot size, one GPU's share: 4096 slots x 2^22 cells x 2048 B = 32 TiB; what the build kept of the trees is the record's tree_mode (2 = compact, 0 = roots only)")})
-        except Exception:
-            pass
-    rec = newest_profile("r*_config4_nominal.txt")
-    if rec and rank == 0:
-        try:
-            last = [l for l in open(rec).read().splitlines() if l.startswith("{")][-1]
-            life.record({"config4_nominal_record": dict(json.loads(last), source="%s (tools/config4_nominal.py; NOT measured in this run)" % os.path.relpath(rec, ROOT),
-                                                        workload="configs[3] at configs[2]'s slot size: 4096 slots x 8 GiB, nSamples=100, maxDepth=32, every input.json, streamed build; what it kept of the trees is the record's tree_mode (2 = compact, 0 = roots only)")})
-        except Exception:
-            pass
-    if legs.decisions:
-        life.record({"legs": legs.decisions, "extra_budget_s": args.extra_budget_s, "extra_seconds_used": round(budget.elapsed(), 1)})
+                run_leg("witnesses", lambda: witness_leg(torch, ctx, pkg))
+                run_leg("ingest", lambda: ingest_leg(torch, ctx, pkg, dev))
+                run_leg("witnesses_from_files", lambda: witnesses_from_files_leg(torch, ctx, pkg, dev))
+            run_leg("dataset", lambda: dataset_leg(torch, bdist, coord, ctx, pkg, coll_dev, rank, world), collective=world > 1)
+            run_leg("dataset_big_slots", lambda: big_slots_leg(torch, bdist, coord, ctx, pkg, coll_dev, rank, world), collective=world > 1)
+            if not args.no_child_legs:
+                run_leg("dataset_inprocess", lambda: inprocess_leg(torch, coord, budget, ctx, rank, world))
+                if world == 1:
+                    run_leg("cli_default", lambda: cli_default_leg(pkg, g))
+        life.phase("committed records")
+        # config 5 at its nominal slot size (one GPU's share, 32 TiB: 13 minutes, so not run here): the committed record, named as such
+        rec = newest_profile("r*_config5_nominal_share.txt")
+        if rec and rank == 0:
+            try:
+                last = [l for l in open(rec).read().splitlines() if l.startswith("{")][-1]
+                life.record({"config5_nominal_share_record": dict(json.loads(last), source="%s (tools/config5_share.py; NOT measured in this run)" % os.path.relpath(rec, ROOT),
+                                                                  workload="configs[4] at its nominal slot size, one GPU's share: 4096 slots x 2^22 cells x 2048 B = 32 TiB; what the build kept of the trees is the record's tree_mode (2 = compact, 0 = roots only)")})
+            except Exception:
+                pass
+        rec = newest_profile("r*_config4_nominal.txt")
+        if rec and rank == 0:
+            try:
+                last = [l for l in open(rec).read().splitlines() if l.startswith("{")][-1]
+                life.record({"config4_nominal_record": dict(json.loads(last), source="%s (tools/config4_nominal.py; NOT measured in this run)" % os.path.relpath(rec, ROOT),
+                                                            workload="configs[3] at configs[2]'s slot size: 4096 slots x 8 GiB, nSamples=100, maxDepth=32, every input.json, streamed build; what it kept of the trees is the record's tree_mode (2 = compact, 0 = roots only)")})
+            except Exception:
+                pass
+        if legs.decisions:
+            life.record({"legs": legs.decisions, "extra_budget_s": args.extra_budget_s, "extra_seconds_used": round(budget.elapsed(), 1)})
     # ---- the line first, the teardown after it (destroy_process_group must not be able to block the print) -------------
     life.phase("print")
     text = life.finish()

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generates tests/golden/reference_nim_api.json: the PUBLIC interface (exported names and their normalised signatures, nothing
-else) of the reference modules that nim/overlay/src/** replaces, read from /root/reference as text.  tests/test_nim_binding.py
-compares the overlay against the live reference tree when it exists (this container) and against this list elsewhere.
+else) of the reference modules that nim/overlay/src/** replaces, read from a checkout of the reference as text.
+tests/test_nim_binding.py compares the overlay against this list.
 
   python tests/golden/make_reference_api.py [/root/reference]
 """

@@ -6,7 +6,7 @@ nim/codex_p2.nim and nim/overlay/src/** have never been compiled):
     the opaque handle KINDS, Cp2Config's field order and types against cp2_config);
   * every call of a cp2_* function in the Nim sources passes as many arguments as the prototype takes;
   * every overlay module exports exactly the public procs / types of the reference module it replaces, with the same
-    signatures (the live tree under /root/reference when present, else the committed interface list);
+    signatures (the committed interface list tests/golden/reference_nim_api.json, made by tests/golden/make_reference_api.py);
   * no `unsafeAddr x[0]` on a possibly empty input is left in the binding.
 """
 import json
@@ -77,12 +77,7 @@ def test_every_call_site_passes_the_prototypes_arity():
 
 
 def _reference_api():
-    live = "/root/reference/reference/nim/proof_input/src"
-    fixture = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_nim_api.json")))["modules"]
-    if os.path.isdir(live):
-        api = {m: [list(t) for t in N.public_api(open(os.path.join(live, m)).read())] for m in fixture}
-        assert api == fixture, "tests/golden/reference_nim_api.json is stale: run tests/golden/make_reference_api.py"
-    return fixture
+    return json.load(open(os.path.join(ROOT, "tests", "golden", "reference_nim_api.json")))["modules"]
 
 
 @pytest.mark.parametrize("module", ["types/bn254.nim", "merkle/bn254.nim", "blocks/bn254.nim", "sample/bn254.nim",

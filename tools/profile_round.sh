@@ -12,8 +12,8 @@ if [ "$2" = "kt" ]; then rm -rf $O/kt; else rm -rf $O; fi
 mkdir -p $O
 # which box, which clocks: every pass below runs on THIS box inside this one gpurun call
 { echo "host $(hostname)"; date -u +%FT%TZ; rocm-smi --showclocks 2>/dev/null | grep -E "sclk|mclk|fclk" ; rocm-smi --showproductname 2>/dev/null | grep -E "Card (Series|SKU)|GFX"; } > $O/box.txt 2>&1 || true
-# the kernel trace is of the DRIVER's command (python bench.py --gpus 1 --steps 20 --warmup 5), extra legs and cpu baseline included
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/kt.log 2>&1
+# the kernel trace is of the driver's command with --full (python bench.py --gpus 1 --steps 20 --warmup 5 --full): extra legs and cpu baseline included
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/kt.log 2>&1
 echo "kernel trace done" > $O/progress.txt
 if [ "$2" = "kt" ]; then exit 0; fi
 # (counter passes serialise the kernels: the bench's own deadline for the extra legs is lifted, a watchdog exit would lose the profiler's output)
@@ -24,7 +24,7 @@ echo "traffic done" >> $O/progress.txt
 rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE --output-format csv -d $O/sq -- $B > $O/sq.log 2>&1
 rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_ANY SQ_ACTIVE_INST_ANY --output-format csv -d $O/sq2 -- $B > $O/sq2.log 2>&1 || true
 # config 3's kernel (k_hash_cells over the 8 GiB slot): HBM bytes against the algorithmic 8 GiB + leaves
-H="python3 bench.py --gpus 1 --steps 1 --warmup 0 --no-cpu-baseline --no-child-legs --legs slot_root --extra-budget-s 3000 --hard-limit-s 3000"
+H="python3 bench.py --gpus 1 --steps 1 --warmup 0 --full --no-cpu-baseline --no-child-legs --legs slot_root --extra-budget-s 3000 --hard-limit-s 3000"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/hfetch -- $H > $O/hfetch.log 2>&1 || true
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/hwrite -- $H > $O/hwrite.log 2>&1 || true
 # ... and its issue side: the same `sq` group as for k_permute_batch, over the five launches that cover the whole slot

@@ -9,7 +9,7 @@ CASES=${@:-n1 clean rank_exit rank_hang gather_error child_hang torchrun_rank_ex
 O=gpurun_out/$TAG
 mkdir -p $O
 export BENCH_BACKEND=gloo BENCH_SHARE_GPU=1
-ARGS="--steps 5 --warmup 2"
+ARGS="--steps 5 --warmup 2 --full"
 for c in $CASES; do
   t0=$(date +%s.%N)
   case $c in
