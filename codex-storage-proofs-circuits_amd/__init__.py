@@ -15,7 +15,7 @@ import weakref
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION_MAJOR, ABI_VERSION_MINOR = 1, 0      # CP2_ABI_VERSION_* of the include/codex_p2.h this binding was written against (tests keep them equal)
+ABI_VERSION_MAJOR, ABI_VERSION_MINOR = 1, 1      # CP2_ABI_VERSION_* of the include/codex_p2.h this binding was written against (tests keep them equal)
 LIB_PATH = os.environ.get("CODEX_P2_LIB") or os.path.join(_HERE, "libcodex_p2.so")   # env override: kernel-variant A/B runs
 CLI_PATH = os.path.join(_HERE, "cli")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "codex_p2.h")
@@ -208,6 +208,10 @@ def load_library():
         "cp2_proof_input_json": (i32, [vp, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(sz)]),
         "cp2_free_buffer": (None, [vp]),
         "cp2_write_circom_main": (i32, [ctypes.POINTER(Config), cp]),
+        "cp2_proof_input_parse_json": (i32, [ctypes.POINTER(Config), vp, sz, pvp, vp, sz]),
+        "cp2_proof_input_shape": (i32, [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "cp2_proof_input_cell_felts": (i32, [vp, vp]),
+        "cp2_proof_inputs_verify": (i32, [vp, vp, sz, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         if v is None and name == "cp2_abi_version":
@@ -465,6 +469,17 @@ class Context:
     # -- dataset / proof input
     def dataset(self, cfg, first_slot=0, n_local=None, cache=None):
         return Dataset(self, cfg, first_slot, cfg.n_slots if n_local is None else n_local, cache)
+
+    def verify_proof_inputs(self, proof_inputs):
+        """cp2_proof_inputs_verify: what SampleAndProve accepts.  Returns (status uint32[n]: 0 or CP2_VERIFY_* bits,
+        sample_ok uint8[n, nSamples]: 1 where that sample's cell and path give slotRoot)."""
+        n = len(proof_inputs)
+        ns = int(self.L.cp2_proof_input_nsamples(proof_inputs[0].h)) if n else 0
+        hs = (ctypes.c_void_p * max(n, 1))(*[p.h for p in proof_inputs])
+        status = np.zeros(n, dtype=np.uint32)
+        ok = np.zeros((n, ns), dtype=np.uint8)
+        self._ck(self.L.cp2_proof_inputs_verify(self.h, hs, n, _p(status), _p(ok)), "cp2_proof_inputs_verify")
+        return status, ok
 
     def dataset_streamed(self, cfg, entropy, first_slot=0, n_local=None, threads=1, group_slots=0):
         """cp2_dataset_build_streamed: trees + (overlapped) the proof-input bodies of every local slot for `entropy`."""
@@ -845,13 +860,45 @@ def write_json_batch(ctx, proof_inputs, paths=None, threads=1):
     return total.value
 
 
+VERIFY_DATASET_ROOT, VERIFY_SAMPLE, VERIFY_SHAPE = 1, 2, 4     # CP2_VERIFY_* (include/codex_p2.h)
+
+
+def parse_proof_input(cfg, text):
+    """cp2_proof_input_parse_json: input.json text -> ProofInput (no context needed).  cfg gives maxDepth, maxLog2NSlots, cellSize,
+    blockSize and nSamples (0: as many rows as the text has).  A text the parser refuses raises CodexP2Error naming the key / row."""
+    L = load_library()
+    raw = text.encode() if isinstance(text, str) else bytes(text)
+    buf = ctypes.create_string_buffer(raw, len(raw))
+    msg = ctypes.create_string_buffer(512)
+    h = ctypes.c_void_p()
+    st = L.cp2_proof_input_parse_json(ctypes.byref(cfg), buf, len(raw), ctypes.byref(h), msg, len(msg))
+    if st != CP2_OK:
+        raise CodexP2Error(st, "cp2_proof_input_parse_json", msg.value.decode(errors="replace"))
+    c = Config()
+    ctypes.pointer(c)[0] = cfg
+    n_cells, n_slots, slot_idx = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    L.cp2_proof_input_shape(h, ctypes.byref(n_cells), ctypes.byref(n_slots), ctypes.byref(slot_idx))
+    c.n_cells, c.n_slots, c.n_samples = n_cells.value, n_slots.value, L.cp2_proof_input_nsamples(h)
+    pi = ProofInput(None, h, c)
+    pi.slot_idx = slot_idx.value
+    return pi
+
+
 class ProofInput:
+    """A cp2_proof_input.  Its accessors need no context (the library comes from load_library()); `ctx` is the context that made
+    it, or None for a parsed one."""
+
     def __init__(self, ctx, h, cfg):
         self.ctx, self.h, self.cfg = ctx, h, cfg
+        self.L = ctx.L if ctx is not None else load_library()
+
+    def _ck(self, st, where):
+        if st != CP2_OK:
+            raise CodexP2Error(st, where, self.L.cp2_strerror(st).decode())
 
     def free(self):
         if self.h:
-            self.ctx.L.cp2_proof_input_free(self.h)
+            self.L.cp2_proof_input_free(self.h)
             self.h = None
 
     def __del__(self):
@@ -863,35 +910,55 @@ class ProofInput:
             pass
 
     def _arr(self, ptr, shape, dtype=np.uint8):
+        """A copy of the array at ptr, or None where the object has none (a parsed object's cell indices and leaf hashes, and
+        its cell bytes when some row encodes no bytes)."""
         n = int(np.prod(shape)) * np.dtype(dtype).itemsize
         if n == 0:
             return np.zeros(shape, dtype=dtype)
+        if not ptr:
+            return None
         buf = (ctypes.c_uint8 * n).from_address(ptr)
         return np.frombuffer(buf, dtype=dtype).reshape(shape).copy()
 
     def roots(self):
         d, s, e = (np.empty(32, dtype=np.uint8) for _ in range(3))
-        self.ctx._ck(self.ctx.L.cp2_proof_input_roots(self.h, _p(d), _p(s), _p(e)), "cp2_proof_input_roots")
+        self._ck(self.L.cp2_proof_input_roots(self.h, _p(d), _p(s), _p(e)), "cp2_proof_input_roots")
         return d, s, e
 
     def cell_indices(self):
-        n = self.ctx.L.cp2_proof_input_nsamples(self.h)
-        return self._arr(self.ctx.L.cp2_proof_input_cell_indices(self.h), (n,), np.uint64)
+        n = self.L.cp2_proof_input_nsamples(self.h)
+        return self._arr(self.L.cp2_proof_input_cell_indices(self.h), (n,), np.uint64)
 
     def cell_data(self):
-        n = self.ctx.L.cp2_proof_input_nsamples(self.h)
-        return self._arr(self.ctx.L.cp2_proof_input_cell_data(self.h), (n, self.cfg.cell_size))
+        n = self.L.cp2_proof_input_nsamples(self.h)
+        return self._arr(self.L.cp2_proof_input_cell_data(self.h), (n, self.cfg.cell_size))
 
     def merkle_paths(self):
-        n = self.ctx.L.cp2_proof_input_nsamples(self.h)
-        return self._arr(self.ctx.L.cp2_proof_input_merkle_paths(self.h), (n, self.cfg.max_depth, 32))
+        n = self.L.cp2_proof_input_nsamples(self.h)
+        return self._arr(self.L.cp2_proof_input_merkle_paths(self.h), (n, self.cfg.max_depth, 32))
 
     def slot_proof(self):
-        return self._arr(self.ctx.L.cp2_proof_input_slot_proof(self.h), (self.cfg.max_log2_nslots, 32))
+        return self._arr(self.L.cp2_proof_input_slot_proof(self.h), (self.cfg.max_log2_nslots, 32))
+
+    def nsamples(self):
+        return int(self.L.cp2_proof_input_nsamples(self.h))
+
+    def shape(self):
+        """(nCellsPerSlot, nSlotsPerDataSet, slotIndex) as the object holds them."""
+        v = [ctypes.c_uint64() for _ in range(3)]
+        self._ck(self.L.cp2_proof_input_shape(self.h, *[ctypes.byref(x) for x in v]), "cp2_proof_input_shape")
+        return tuple(x.value for x in v)
+
+    def cell_felts(self):
+        """The sampled cells as the circuit reads them: uint8[nSamples, cp2_felts_per_bytes(cellSize), 32]."""
+        n = self.nsamples()
+        out = np.zeros((n, self.L.cp2_felts_per_bytes(self.cfg.cell_size), 32), dtype=np.uint8)
+        self._ck(self.L.cp2_proof_input_cell_felts(self.h, _p(out)), "cp2_proof_input_cell_felts")
+        return out
 
     def leaf_hashes(self):
-        n = self.ctx.L.cp2_proof_input_nsamples(self.h)
-        return self._arr(self.ctx.L.cp2_proof_input_leaf_hashes(self.h), (n, 32))
+        n = self.L.cp2_proof_input_nsamples(self.h)
+        return self._arr(self.L.cp2_proof_input_leaf_hashes(self.h), (n, 32))
 
     def recreate(self):
         """A copy made through cp2_proof_input_create from this object's accessor arrays (what the Nim shim's
@@ -901,7 +968,7 @@ class ProofInput:
                                          (self.slot_proof(), self.cell_indices(), self.cell_data(), self.merkle_paths(), self.leaf_hashes()))
         slot_idx = getattr(self, "slot_idx", 0)
         h = ctypes.c_void_p()
-        self.ctx._ck(self.ctx.L.cp2_proof_input_create(ctypes.byref(self.cfg), slot_idx, _p(d), _p(e), _p(s), _p(sp), idx.size,
+        self._ck(self.L.cp2_proof_input_create(ctypes.byref(self.cfg), slot_idx, _p(d), _p(e), _p(s), _p(sp), idx.size,
                                                        _p(idx), _p(cells), _p(paths), _p(leaves), ctypes.byref(h)), "cp2_proof_input_create")
         q = ProofInput(self.ctx, h, self.cfg)
         q.slot_idx = slot_idx
@@ -909,13 +976,13 @@ class ProofInput:
 
     def json(self):
         text, ln = ctypes.c_void_p(), ctypes.c_size_t()
-        self.ctx._ck(self.ctx.L.cp2_proof_input_json(self.h, ctypes.byref(text), ctypes.byref(ln)), "cp2_proof_input_json")
+        self._ck(self.L.cp2_proof_input_json(self.h, ctypes.byref(text), ctypes.byref(ln)), "cp2_proof_input_json")
         s = ctypes.string_at(text, ln.value).decode()
-        self.ctx.L.cp2_free_buffer(text)
+        self.L.cp2_free_buffer(text)
         return s
 
     def write_json(self, path):
-        self.ctx._ck(self.ctx.L.cp2_proof_input_write_json(self.h, path.encode()), "cp2_proof_input_write_json")
+        self._ck(self.L.cp2_proof_input_write_json(self.h, path.encode()), "cp2_proof_input_write_json")
 
 
 def write_circom_main(cfg, path):

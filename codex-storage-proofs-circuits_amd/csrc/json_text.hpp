@@ -180,6 +180,22 @@ inline void text_body(std::string& s, const cp2_config& cfg, size_t ns, const ui
   s.resize((size_t)(p - s.data()));
 }
 
+// the same body from cell rows that are already field elements (ns x nf x 32: a parsed input.json, whose rows need not encode bytes)
+inline void text_body_felts(std::string& s, const cp2_config& cfg, size_t ns, const uint8_t* cell_felts, const uint8_t* paths) {
+  const size_t at = s.size();
+  s.resize(at + body_bound(cfg, ns));
+  char* p = &s[at];
+  const size_t nf = cp2_felts_per_bytes(cfg.cell_size), md = (size_t)cfg.max_depth;
+  p = PUT_LIT(p, ", \"cellData\":\n");
+  for (size_t i = 0; i < ns; ++i) p = put_felt_list(p, i == 0 ? "    [ " : "    , ", 6, cell_felts + i * nf * 32, nf);
+  p = PUT_LIT(p, "    ]\n");
+  p = PUT_LIT(p, ", \"merklePaths\":\n");
+  for (size_t i = 0; i < ns; ++i) p = put_felt_list(p, i == 0 ? "    [ " : "    , ", 6, paths + i * md * 32, md);
+  p = PUT_LIT(p, "    ]\n");
+  p = PUT_LIT(p, "}\n");
+  s.resize((size_t)(p - s.data()));
+}
+
 inline size_t body_reserve(const cp2_config& cfg, size_t ns) { return body_bound(cfg, ns); }
 
 }  // namespace cp2text

@@ -6,6 +6,7 @@
 //   k_sponge2_felts   a3  Sponge.hs:30-43 over field elements (sampling, generic byte strings)
 //   k_gen_fake_cells  a10 slot.nim:22-32
 //   k_gather_rows         path / cell gather for proof inputs (merkle.nim:21-42 does this on the host)
+//   k_verify_samples      what SampleAndProve accepts: sample_cells.circom:58-148, single_cell.circom:30-73, merkle.circom:44-114
 //
 // All global-memory field elements are 32-byte little-endian canonical integers (the ABI format).
 #include "kernels.hpp"
@@ -437,6 +438,142 @@ __global__ void __launch_bounds__(TPB) k_gather_rows(const uint8_t* __restrict__
 }
 
 // ------------------------------------------------------------------------------------------------
+// What SampleAndProve accepts (circuit/codex/sample_cells.circom:58-148, single_cell.circom:30-73, merkle.circom:44-114), checked
+// in one launch: lane t < n*ns takes sample t % ns of input t / ns from its cell felts to the slot-root comparison (index sponge,
+// leaf sponge, bottom and middle reconstructions); lane n*ns + i checks input i's slot root against its dataset root.  One byte per
+// lane: 1 = that equation holds.  Inputs whose shape the circuit's witness generation refuses (VerifyGeom: prm[3] == 0) get 0.
+
+// RootFromMerklePath(depth) (merkle.circom:44-114) for the masks SampleAndProve feeds it: after maskBitsCorrected[0] = 1 they are
+// [1,..,1,0,..,0], so recRoot is aux[sel] with sel = the number of ones, and only sel compressions are needed (depth 0: the empty
+// sum, 0).  isLast[i] = bits i..depth-1 of the index equal those of the last index (diff >> i == 0); the switch by the path bit
+// and the key bottom + 2*odd are selects, not branches.
+struct PathWalk {
+  uint64_t bits, diff;   // index bits; (index ^ last index) over the tree's depth
+  const uint4* path;
+  uint32_t sel;          // compressions up to the selected layer
+};
+
+__device__ __forceinline__ uint64_t shr64(uint64_t x, uint32_t s) { return s >= 64 ? 0 : x >> s; }
+__device__ __forceinline__ uint64_t low_bits(uint64_t x, uint32_t depth) { return depth >= 64 ? x : x & ((1ULL << depth) - 1); }
+__device__ __forceinline__ uint32_t clamp_sel(uint32_t ones, uint32_t depth) { return depth == 0 ? 0u : (ones < 1u ? 1u : (ones < depth ? ones : depth)); }
+
+// field equality (the circuit's ===): both sides as canonical words
+__device__ __forceinline__ bool fe_equal(const Fe& a, const Fe& b) {
+  uint32_t wa[8], wb[8];
+  fr::to_canonical_words(a, wa);
+  fr::to_canonical_words(b, wb);
+  uint32_t d = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) d |= wa[i] ^ wb[i];
+  return d == 0;
+}
+
+// One loop, one permutation per step, for every lane: a sample lane runs 2 index steps (sponge over [entropy, slotRoot, counter]),
+// ceil((nf+1)/2) leaf steps, then the bottom walk and the middle walk; a top lane runs the top walk only.  Whole batches share the
+// circuit parameters, so the step counts and the phase tests are uniform across a wave except where inputs state other nCellsPerSlot
+// or nSlotsPerDataSet.
+__global__ void __launch_bounds__(TPB) k_verify_samples(VerifyGeom g, const uint64_t* __restrict__ prm, const uint4* __restrict__ heads,
+                                                          const uint4* __restrict__ cells, const uint4* __restrict__ paths,
+                                                          uint8_t* __restrict__ ok) {
+  __shared__ fr::QTab qtab;
+  fr::qtab_fill(qtab, threadIdx.x, TPB);
+  __syncthreads();
+  const size_t t = (size_t)blockIdx.x * TPB + threadIdx.x;
+  const size_t nst = g.n * g.ns;
+  if (t >= nst + g.n) return;
+  const bool top = t >= nst;
+  const size_t item = top ? t - nst : t / g.ns;
+  const uint64_t* q = prm + 4 * item;
+  if (q[3] == 0) {                                                     // shape refused by witness generation
+    ok[t] = 0;
+    return;
+  }
+  const uint4* head = heads + 2 * (size_t)(3 + g.m) * item;          // dataSetRoot, entropy, slotRoot, slotProof[m]
+  const Fe slot_root = load_fe_canonical(head + 4);
+  const Fe one = fr::fe_const(fr::FR_R1);
+  const uint4* src = cells + 2 * t * g.nf;
+  const uint64_t n_cells = q[0], lastc = n_cells - 1;
+  const uint32_t k = (uint32_t)__builtin_ctzll(n_cells);              // Log2: nCells = 2^k, 1 <= k <= maxDepth (checked on the host)
+  const uint32_t dm = g.md - g.bd;
+  PathWalk wa, wb;                                                     // sample: bottom, middle (single_cell.circom:41-60); top: top, -
+  uint32_t n_pre, depth_last;
+  Fe cur;
+  State s;
+  if (top) {                                                           // sample_cells.circom:95-109
+    const uint64_t last = q[1] - 1;                                    // CeilingLog2: bits of nSlots - 1, mask = its bit length
+    const uint32_t bl = last ? 64u - (uint32_t)__builtin_clzll(last) : 0u;
+    wa = PathWalk{q[2], low_bits(q[2] ^ last, g.m), head + 6, clamp_sel(bl, g.m)};
+    wb = PathWalk{0, 0, head, 0};
+    n_pre = 0;
+    depth_last = g.m;
+    cur = slot_root;
+    s.x = s.y = s.z = fr::fe_zero();
+  } else {                                                             // CalculateCellIndexBits, sample_cells.circom:23-48
+    const uint4* path = paths + 2 * t * g.md;
+    wa = PathWalk{0, 0, path, k < g.bd ? k : g.bd};
+    wb = PathWalk{0, 0, path + 2 * g.bd, clamp_sel(k > g.bd ? k - g.bd : 0u, dm)};
+    n_pre = 2 + ((g.nf + 2) >> 1);
+    depth_last = dm;
+    cur = fr::fe_zero();
+    s.x = load_fe_canonical(head + 2);
+    s.y = slot_root;
+    s.z = fr::fe_const(fr::FR_CIV_RATE2_MONT);
+  }
+  const uint32_t total = n_pre + wa.sel + wb.sel;
+#pragma unroll 1
+  for (uint32_t step = 0; step < total; ++step) {
+    if (step < n_pre) {
+      if (step == 1) {                                                 // counter cnt + 1, then the sponge's "1" pad
+        const uint32_t counter = (uint32_t)(t - item * g.ns) + 1;
+        Fe c = fr::fe_zero();
+        c.l[0] = counter & fr::MASK;
+        c.l[1] = counter >> 29;
+        s.x = fr::norm(fr::add_lazy(s.x, fr::to_mont(c)));
+        s.y = fr::norm(fr::add_lazy(s.y, one));
+      } else if (step >= 2) {                                          // Poseidon2_hash_rate2(cellData), single_cell.circom:63-65
+        const uint32_t j = 2 * (step - 2);
+        Fe a = (j < g.nf) ? load_fe_canonical(src + 2 * j) : (j == g.nf ? one : fr::fe_zero());
+        Fe b = (j + 1 < g.nf) ? load_fe_canonical(src + 2 * (j + 1)) : (j + 1 == g.nf ? one : fr::fe_zero());
+        s.x = fr::norm(fr::add_lazy(s.x, a));
+        s.y = fr::norm(fr::add_lazy(s.y, b));
+      }
+    } else {
+      const uint32_t lvl = step - n_pre;
+      const bool in_a = lvl < wa.sel;
+      const uint32_t i = in_a ? lvl : lvl - wa.sel;
+      const uint64_t bits = in_a ? wa.bits : wb.bits, diff = in_a ? wa.diff : wb.diff;
+      const uint32_t b = (uint32_t)(bits >> i) & 1u;
+      const uint32_t key = (i == 0 ? 1u : 0u) + 2u * (((diff >> i) == 0 ? 1u : 0u) & (b ^ 1u));
+      const Fe sib = load_fe_canonical((in_a ? wa.path : wb.path) + 2 * i);
+      const uint32_t sw = 0u - b;
+#pragma unroll
+      for (int l = 0; l < fr::NL; ++l) {
+        s.x.l[l] = (cur.l[l] & ~sw) | (sib.l[l] & sw);
+        s.y.l[l] = (sib.l[l] & ~sw) | (cur.l[l] & sw);
+      }
+      s.z = key_fe(key);
+    }
+    p2::permute(s, qtab);
+    if (step == 1 && !top) {                                           // the index: low bits & (nCells - 1); the leaf sponge starts
+      uint32_t w[8];
+      fr::to_canonical_words(s.x, w);
+      const uint64_t idx = (((uint64_t)w[1] << 32) | w[0]) & lastc;
+      wa.bits = idx;                                                   // lastBits = the Log2 mask (sample_cells.circom:117-123)
+      wa.diff = low_bits(idx ^ lastc, g.bd);
+      wb.bits = shr64(idx, g.bd);
+      wb.diff = low_bits(shr64(idx ^ lastc, g.bd), dm);
+      s.x = fr::fe_zero();
+      s.y = fr::fe_zero();
+      s.z = fr::fe_const(fr::FR_CIV_RATE2_MONT);
+    } else if (step + 1 >= n_pre) {                                    // the leaf, then each reconstructed layer
+      cur = fr::norm(s.x);
+    }
+  }
+  const Fe want = top ? load_fe_canonical(head) : slot_root;           // dataSetRoot / slotRoot (single_cell.circom:71)
+  ok[t] = fe_equal(depth_last ? cur : fr::fe_zero(), want) ? 1 : 0;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Workgroups for n work items.  A grid holds at most 2^31 - 1 workgroups in x; the per-item kernels are launched in slices of
 // at most MAX_ITEMS items (every item is independent and addressed from a base pointer), the layer / sampling kernels, whose
 // item index is decomposed inside the kernel, refuse what does not fit one grid (2^38 nodes: far beyond any HBM).
@@ -578,6 +715,16 @@ hipError_t launch_gather_rows(const void* src, const uint64_t* index, size_t nro
   size_t work = nrows * (row_bytes / 4);
   unsigned grid = work > (size_t)4096 * TPB ? 4096u : grid_for(work);
   CP2K_LAUNCH(k_gather_rows, dim3(grid), dim3(TPB), 0, st, (const uint8_t*)src, index, nrows, row_bytes, (uint8_t*)out);
+  return hipGetLastError();
+}
+
+hipError_t launch_verify_samples(const VerifyGeom& g, const uint64_t* prm, const void* heads, const void* cells, const void* paths,
+                                 uint8_t* ok, hipStream_t st) {
+  const size_t lanes = g.n * g.ns + g.n;
+  if (lanes == 0) return hipSuccess;
+  if (!fits_one_grid(lanes)) return hipErrorInvalidValue;
+  CP2K_LAUNCH(k_verify_samples, dim3(grid_for(lanes)), dim3(TPB), 0, st, g, prm, (const uint4*)heads, (const uint4*)cells,
+              (const uint4*)paths, ok);
   return hipGetLastError();
 }
 

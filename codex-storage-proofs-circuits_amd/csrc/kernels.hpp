@@ -53,4 +53,15 @@ hipError_t launch_sample_paths(const TreeGeom& g, const void* nodes, const void*
 hipError_t launch_gather_rows(const void* src, const uint64_t* index, size_t nrows, size_t row_bytes, void* out,
                               hipStream_t st);
 
+// Proof-input verification (k_verify_samples, circuit/codex/sample_cells.circom:58-148) over n inputs that share the circuit
+// parameters.  Device arrays: prm n x 4 (nCellsPerSlot, nSlotsPerDataSet, slotIndex, shape ok), heads n x (3 + m) felts
+// (dataSetRoot, entropy, slotRoot, slotProof), cells n x ns x nf felts, paths n x ns x md felts; ok receives n x ns sample
+// bytes, then n dataset-root bytes.
+struct VerifyGeom {
+  size_t n;
+  uint32_t ns, nf, md, m, bd;   // nSamples, felts per cell, maxDepth, maxLog2NSlots, blockTreeDepth
+};
+hipError_t launch_verify_samples(const VerifyGeom& g, const uint64_t* prm, const void* heads, const void* cells, const void* paths,
+                                 uint8_t* ok, hipStream_t st);
+
 }  // namespace cp2k

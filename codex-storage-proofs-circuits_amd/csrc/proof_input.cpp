@@ -31,6 +31,7 @@
 
 #include "body_store.hpp"
 #include "json_text.hpp"
+#include "proof_input_obj.hpp"
 #include "trees.hpp"
 
 using namespace cp2i;
@@ -615,26 +616,7 @@ int enqueue_sampling(cp2_slot_trees* t, const cp2k::TreeGeom& g, SampleDev& d, S
 // ---------------------------------------------------------------------------------------------
 // proof input
 // ---------------------------------------------------------------------------------------------
-// cell bytes, Merkle paths and indices of a whole batch live in pinned blocks that every proof input of the batch
-// shares (one download each, no per-slot copies); the blocks return to the context's pool with the last reference
-struct BatchStore {
-  PinBuf idx, paths, leaves, cells;
-  std::vector<uint8_t> cells_heap;   // SlotFile / Host sources: sampled cells are read on the host
-  std::vector<uint8_t> heap;         // cp2_proof_input_create: everything copied from the caller
-};
-
-struct cp2_proof_input {
-  cp2_config cfg{};
-  uint64_t slot_idx = 0;
-  uint8_t entropy[32], dataset_root[32], slot_root[32];
-  size_t n_samples = 0;
-  std::vector<uint8_t> slot_proof;
-  std::shared_ptr<BatchStore> store;
-  const uint64_t* indices = nullptr;    // nSamples, inside store->idx
-  const uint8_t* cell_data = nullptr;   // nSamples x cellSize, inside store->cells / cells_heap
-  const uint8_t* paths = nullptr;       // nSamples x maxDepth x 32, inside store->paths
-  const uint8_t* leaves = nullptr;      // nSamples x 32: hash of each sampled cell (may be null for caller-made inputs)
-};
+// BatchStore and struct cp2_proof_input: proof_input_obj.hpp (shared with verify.cpp)
 
 // slotProof = padMerkleProof(merkleProof(dsetTree, slotIdx), maxLog2NSlots), gen_input/bn254.nim:51,72
 static void fill_slot_proof(const cp2_dataset* ds, uint64_t slot_idx, std::vector<uint8_t>& out) {
@@ -1080,7 +1062,8 @@ static void proof_input_text(const cp2_proof_input* p, std::string& s) {
   s.clear();
   s.reserve(body_bound(p->cfg, p->n_samples) + head_bound(p->cfg));
   text_head(s, p->cfg, p->slot_idx, p->dataset_root, p->entropy, p->slot_root, p->slot_proof.data());
-  text_body(s, p->cfg, p->n_samples, p->cell_data, p->paths);
+  if (p->cell_felts) text_body_felts(s, p->cfg, p->n_samples, p->cell_felts, p->paths);   // a parsed text: printed as read
+  else text_body(s, p->cfg, p->n_samples, p->cell_data, p->paths);
 }
 
 extern "C" int cp2_proof_input_json(const cp2_proof_input* p, char** text, size_t* len) try {

@@ -17,7 +17,7 @@ import std/os                  # getEnv: CODEX_P2_CACHE, as in the cli twin
 const libName = "libcodex_p2.so"
 const
   abiVersionMajor* = 1         ## CP2_ABI_VERSION_MAJOR / _MINOR of the include/codex_p2.h this binding was written against
-  abiVersionMinor* = 0         ## (tests/test_nim_binding.py keeps the two files equal)
+  abiVersionMinor* = 1         ## (tests/test_nim_binding.py keeps the two files equal)
 
 type
   F* = array[32, byte]          ## canonical little-endian field element (NOT constantine's Montgomery limbs)

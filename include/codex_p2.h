@@ -38,9 +38,10 @@ extern "C" {
  *          SONAME carries it: libcodex_p2.so.<MAJOR>.
  *   MINOR  grows with every release that only ADDS entry points; a caller needs library minor >= the minor it was written against.
  * cp2_abi_version() returns what the LIBRARY was built from: (MAJOR << 16) | MINOR.  It touches no device and needs no context.
- * History: 1.0 = the 105 entry points of round 5 + this function + cp2_set_ingest's two rings (round 6).                        */
+ * History: 1.0 = the 105 entry points of round 5 + this function + cp2_set_ingest's two rings (round 6).
+ *          1.1 = + cp2_proof_input_parse_json, _shape, _cell_felts and cp2_proof_inputs_verify (verification).                  */
 #define CP2_ABI_VERSION_MAJOR 1
-#define CP2_ABI_VERSION_MINOR 0
+#define CP2_ABI_VERSION_MINOR 1
 #define CP2_ABI_VERSION ((CP2_ABI_VERSION_MAJOR << 16) | CP2_ABI_VERSION_MINOR)
 int cp2_abi_version(void);
 
@@ -377,6 +378,42 @@ int cp2_dataset_build_streamed(cp2_ctx* ctx, const cp2_config* cfg, uint64_t fir
 int cp2_dataset_export_streamed(cp2_dataset* ds, const char* dir, int threads, uint64_t* total_bytes);
 /* the finished text of one prepared slot in a malloc'ed buffer (cp2_free_buffer) */
 int cp2_dataset_streamed_json(cp2_dataset* ds, uint64_t slot_idx, char** text, size_t* len);
+/* ---- verification: what SampleAndProve accepts (circuit/codex/sample_cells.circom:58-148) ----------------------------------
+ * The verifier accepts exactly the inputs for which SampleAndProve(maxDepth, maxLog2NSlots, blockTreeDepth, nFieldElemsPerCell,
+ * nSamples) has a satisfying witness, reading them as the field elements the circuit sees:
+ *   top      RootFromMerklePath(maxLog2NSlots) of slotRoot with path bits = slotIndex, last bits = nSlotsPerDataSet - 1,
+ *            mask = CeilingLog2(nSlotsPerDataSet).mask, path = slotProof, must give dataSetRoot (sample_cells.circom:95-109);
+ *   sample   counter cnt + 1: idx = lowbits(Poseidon2_hash_rate2([entropy, slotRoot, cnt + 1])) & (nCellsPerSlot - 1)
+ *            (:23-48), leaf = Poseidon2_hash_rate2(cellData[cnt]), then the bottom RootFromMerklePath(blockTreeDepth) and the
+ *            middle RootFromMerklePath(maxDepth - blockTreeDepth) over merklePaths[cnt], both with last bits = mask bits =
+ *            Log2(nCellsPerSlot).mask (:117-123), must give slotRoot (single_cell.circom:30-73);
+ *   RootFromMerklePath exactly as merkle.circom:44-114 (maskBitsCorrected[0] = 1, isLast from the top down, key = bottom + 2*odd,
+ *            the root is the layer the mask selects): a path entry above the selected layer is ignored, whatever its value.
+ * blockSize / cellSize must be a power of two >= 2 (the circuit has no blockTreeDepth 0): else CP2_ERR_INVALID. */
+#define CP2_VERIFY_DATASET_ROOT 1u   /* slotRoot + slotProof do not give dataSetRoot (sample_cells.circom:95-109)            */
+#define CP2_VERIFY_SAMPLE       2u   /* some sample's cell + path do not give slotRoot (single_cell.circom:63-71)            */
+#define CP2_VERIFY_SHAPE        4u   /* a witness-generation assertion fails: nCellsPerSlot not 2^k with 1 <= k <= maxDepth
+                                        (lib/log2.circom Log2_CircomWitnessCalc_Hack), nSlotsPerDataSet not in
+                                        [1, 2^maxLog2NSlots] (CeilingLog2), slotIndex >= 2^maxLog2NSlots (misc.circom ToBits) */
+/* input.json text (any JSON whitespace and key order; numbers as quoted decimal strings or bare integers) -> a proof input.
+ * cfg supplies the circuit parameters maxDepth, maxLog2NSlots, cellSize, blockSize and nSamples (0: as many rows as the text
+ * has); the text supplies the rest.  nCellsPerSlot, nSlotsPerDataSet and slotIndex are kept as read, shape failures included.
+ * Refused (CP2_ERR_INVALID, the key / row / column named in msg, which may be NULL): missing, unknown or repeated keys, wrong
+ * array lengths, a field element >= r, nCellsPerSlot / nSlotsPerDataSet / slotIndex >= 2^64, a sign, a non-digit, trailing text.
+ * The object holds the cells as field elements: cp2_proof_input_cell_data returns the bytes when every row is the 10*-padded
+ * encoding of cellSize bytes, else NULL; cell_indices and leaf_hashes are NULL; cp2_proof_input_json prints the field
+ * elements it holds (a producer's text comes back byte for byte).  Free with cp2_proof_input_free. */
+int cp2_proof_input_parse_json(const cp2_config* cfg, const char* text, size_t len, cp2_proof_input** out, char* msg, size_t msg_len);
+/* nCellsPerSlot, nSlotsPerDataSet and slotIndex as the object holds them (a parsed object: as the text states them) */
+int cp2_proof_input_shape(const cp2_proof_input* p, uint64_t* n_cells, uint64_t* n_slots, uint64_t* slot_idx);
+/* the sampled cells as the circuit sees them: nSamples x cp2_felts_per_bytes(cellSize) x 32 bytes (canonical LE) */
+int cp2_proof_input_cell_felts(const cp2_proof_input* p, uint8_t* out);
+/* status[i] = 0 (accepted) or CP2_VERIFY_* bits; sample_ok (may be NULL): n x nSamples bytes, 1 where that sample's equation
+ * holds.  All objects must share the circuit parameters (maxDepth, maxLog2NSlots, cellSize, blockSize, nSamples).
+ * CP2_VERIFY_SHAPE is reported alone, with every sample_ok byte 0.  One GPU launch per chunk of inputs (device memory bounded
+ * whatever n is); synchronous. */
+int cp2_proof_inputs_verify(cp2_ctx* ctx, const cp2_proof_input* const* ps, size_t n, uint32_t* status, uint8_t* sample_ok);
+
 /* replaces `writeCircomMainComponent`, reference/nim/proof_input/src/cli.nim:186-204 */
 int cp2_write_circom_main(const cp2_config* cfg, const char* path);
 
