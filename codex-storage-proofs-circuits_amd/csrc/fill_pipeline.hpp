@@ -15,11 +15,17 @@
 // O_DIRECT (cp2_set_ingest_direct / CP2_INGEST_DIRECT=1): slot files that are not in the page cache are read straight into the pinned
 // ring, whole 4 KiB blocks, without passing through (and evicting) the page cache; a piece whose file offset or buffer address is not
 // block aligned, the last partial block of a piece, and a file system that refuses O_DIRECT (tmpfs) are read buffered.
+// ONE READ RULE for every read of a slot file (these fills and read_file_cell, which the proof-input paths use): a read interrupted
+// (EINTR) is retried, a short read reads on, a read of 0 bytes is the end of the file -- zeros from there (slot.nim:61-66) -- and a
+// read that fails with any other errno is an ERROR naming the file, never zeros: the reference yields no data for a file it cannot
+// read.  The O_DIRECT attempt only ever reads ahead: whatever it fails on (EINVAL included), the buffered loop reads the rest of
+// the piece, and only that loop decides whether a read failed.
 #pragma once
 #include <fcntl.h>
 #include <unistd.h>
 
 #include <atomic>
+#include <cerrno>
 #include <condition_variable>
 #include <cstdint>
 #include <cstring>
@@ -34,6 +40,38 @@
 namespace cp2i {
 
 inline std::string fill_slot_file_name(const std::string& base, uint64_t slot) { return base + std::to_string(slot) + ".dat"; }   // dataset.nim:34
+
+// the largest cell a SlotFile source may have (slot.nim:60-61: assert(cellSize <= 16384)); larger is CP2_ERR_INVALID
+constexpr size_t SLOT_FILE_MAX_CELL = 16384;
+
+// The read every read of a slot file goes through.  ::pread in the product; only the CPU checks (tests/host_check) replace it, to
+// inject errors, interruptions and short reads.
+using SlotFileRead = ssize_t (*)(int fd, void* buf, size_t n, off_t off);
+inline SlotFileRead slot_file_read = ::pread;
+
+// Bytes [pos, n) of `out` from file offset off + pos onward, by the read rule above.  0, or the errno of the read that failed (the
+// bytes it did not read are zeros then, too: no caller may use them).
+inline int slot_file_read_rest(int fd, uint8_t* out, size_t n, uint64_t off, size_t pos = 0) {
+  int err = 0;
+  while (pos < n) {
+    const ssize_t r = slot_file_read(fd, out + pos, n - pos, (off_t)(off + pos));
+    if (r > 0) { pos += (size_t)r; continue; }
+    if (r == 0) break;                  // end of file
+    if (errno == EINTR) continue;
+    err = errno ? errno : EIO;
+    break;
+  }
+  if (pos < n) std::memset(out + pos, 0, n - pos);
+  return err;
+}
+
+// cell `cell` of an open slot file (slot.nim:57-68): 0, or the errno of a failed read
+inline int read_file_cell(int fd, size_t cell_size, uint64_t cell, uint8_t* out) { return slot_file_read_rest(fd, out, cell_size, cell * cell_size); }
+
+// what cp2_last_error says about a slot file: err == 0 it could not be opened, otherwise a read of it failed with errno `err`
+inline std::string slot_file_error(const std::string& fname, int err) {
+  return err == 0 ? "cannot open " + fname : "cannot read " + fname + ": " + std::strerror(err);
+}
 
 class FillPipeline {
  public:
@@ -62,8 +100,9 @@ class FillPipeline {
       for (size_t t = 1; t < (size_t)threads_ && t < job->n_grains; ++t) pool_->submit([job] { take_grains(job); });
   }
   // The OLDEST posted fill is complete (this thread takes grains of it too; the workers may already be on the next job).
-  // false: a slot file could not be opened -- *bad names the one of the LOWEST slot (whichever thread met it); its bytes read as zeros.
-  bool join(std::string* bad) {
+  // false: a slot file could not be opened or read -- *bad names the one of the LOWEST slot (whichever thread met it), *err is 0 when it
+  // could not be opened and the errno of the read that failed otherwise (slot_file_error); the turn's bytes must not be used.
+  bool join(std::string* bad, int* err = nullptr) {
     if (jobs_.empty()) return true;
     std::shared_ptr<Job> job = jobs_.front();
     jobs_.pop_front();
@@ -73,6 +112,7 @@ class FillPipeline {
       job->cv.wait(lk, [&] { return job->done == job->n_grains; });
       if (!job->first_bad.empty()) {
         if (bad) *bad = job->first_bad;
+        if (err) *err = job->first_bad_errno;
         return false;
       }
     }
@@ -96,7 +136,13 @@ class FillPipeline {
     size_t done = 0;                        // grains completed (under mu)
     std::string first_bad;                  // (under mu)
     uint64_t first_bad_slot = ~0ULL;
+    int first_bad_errno = 0;                // 0: could not be opened
   };
+
+  static void report(Job& job, uint64_t slot, const std::string& fname, int err) {
+    std::lock_guard<std::mutex> lk(job.mu);
+    if (slot < job.first_bad_slot) { job.first_bad_slot = slot; job.first_bad = fname; job.first_bad_errno = err; }
+  }
 
   static void fill_range(Job& job, size_t a, size_t b) {
     if (job.mem) { std::memcpy(job.buf + a, job.mem + a, b - a); return; }
@@ -107,10 +153,7 @@ class FillPipeline {
       const std::string fname = fill_slot_file_name(job.base, q.slot);
       const int fd = open(fname.c_str(), O_RDONLY);
       if (fd < 0) {
-        {
-          std::lock_guard<std::mutex> lk(job.mu);
-          if (q.slot < job.first_bad_slot) { job.first_bad_slot = q.slot; job.first_bad = fname; }
-        }
+        report(job, q.slot, fname, 0);
         std::memset(buf + p, 0, q.len);
         p += q.len;
         continue;
@@ -121,20 +164,16 @@ class FillPipeline {
         if (dfd >= 0) {
           const size_t whole = q.len / DIRECT_ALIGN * DIRECT_ALIGN;
           while (pos < whole) {
-            const ssize_t r = pread(dfd, buf + p + pos, whole - pos, (off_t)(q.file_off + pos));
-            if (r <= 0) break;
+            const ssize_t r = slot_file_read(dfd, buf + p + pos, whole - pos, (off_t)(q.file_off + pos));
+            if (r <= 0) break;                     // end of file or any failure: the buffered reads below go on from pos
             pos += (size_t)r;
             if ((size_t)r % DIRECT_ALIGN) break;   // short, unaligned: end of file (the buffered reads below see that too)
           }
           close(dfd);
         }
       }
-      while (pos < q.len) {
-        const ssize_t r = pread(fd, buf + p + pos, q.len - pos, (off_t)(q.file_off + pos));
-        if (r <= 0) break;
-        pos += (size_t)r;
-      }
-      if (pos < q.len) std::memset(buf + p + pos, 0, q.len - pos);
+      const int err = slot_file_read_rest(fd, buf + p, q.len, q.file_off, pos);
+      if (err) report(job, q.slot, fname, err);
       close(fd);
       p += q.len;
     }

@@ -720,6 +720,7 @@ int multi_build(cp2_multi* m, const cp2_config* cfg, BuildKind kind, const uint8
   *out = nullptr;
   m->err.clear();
   if (cfg->n_slots == 0 || cfg->max_depth < 0 || cfg->max_log2_nslots < 0) return CP2_ERR_INVALID;
+  if (cfg->file_base && cfg->cell_size > SLOT_FILE_MAX_CELL) { m->err = "slot files hold cells of at most 16384 bytes"; return CP2_ERR_INVALID; }   // slot.nim:60-61
   // whole slots or units -- the same plan for every kind of build.  A STREAMED build cut by units is two-phase: nothing of a proof
   // input can be made while later units hash (sampling needs the slot root, which exists only after the exchange of unit roots), so
   // it is the balanced unit build, the exchange, then every slot's input.json from the devices that hold its units -- batched per
@@ -934,9 +935,11 @@ int units_proof_inputs(cp2_multi_dataset* mds, const uint64_t* slots, size_t n, 
       for (size_t i = (size_t)t; i < n; i += (size_t)nt) {
         const std::string fname = slot_file_name(mds->file_base, slots[i]);
         const int fd = open(fname.c_str(), O_RDONLY);
-        if (fd < 0) { failed[t] = fname; return; }
-        for (size_t k = 0; k < ns; ++k) read_file_cell(fd, cs, idx[i * ns + k], &cells[(i * ns + k) * cs]);
+        if (fd < 0) { failed[t] = slot_file_error(fname, 0); return; }
+        int err = 0;
+        for (size_t k = 0; k < ns && !err; ++k) err = read_file_cell(fd, cs, idx[i * ns + k], &cells[(i * ns + k) * cs]);
         close(fd);
+        if (err) { failed[t] = slot_file_error(fname, err); return; }
       }
     };
     {
@@ -945,7 +948,7 @@ int units_proof_inputs(cp2_multi_dataset* mds, const uint64_t* slots, size_t n, 
       work(0);
       pool.wait_idle();
     }
-    for (auto& f : failed) if (!f.empty()) { m->err = "cannot open " + f; return CP2_ERR_IO; }
+    for (auto& f : failed) if (!f.empty()) { m->err = f; return CP2_ERR_IO; }
   } else if (total) {   // genFakeCell for every sampled index in one launch: the list form over "global cells" slot * nCells + cell, seed of slot 0
     DeviceRestore restore;
     CP2_HIP(ctx0, hipSetDevice(ctx0->device));

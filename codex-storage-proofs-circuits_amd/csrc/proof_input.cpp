@@ -95,6 +95,7 @@ static void canonical_felt(const uint8_t in[32], uint8_t out[32]) {
 static int dataset_check(const cp2_config* cfg, uint64_t first_slot, uint64_t n_local) {
   if (n_local == 0 || first_slot > cfg->n_slots || n_local > cfg->n_slots - first_slot) return CP2_ERR_INVALID;   // (no wrap-around)
   if (cfg->max_depth < 0 || cfg->max_log2_nslots < 0) return CP2_ERR_INVALID;
+  if (cfg->file_base && cfg->cell_size > SLOT_FILE_MAX_CELL) return CP2_ERR_INVALID;   // slot.nim:60-61
   return CP2_OK;
 }
 
@@ -644,20 +645,22 @@ static int host_cells_global(cp2_slot_trees* t, const uint64_t* g, size_t n, uin
     // a batch of proof inputs samples hundreds of thousands of cells (4096 slots x 100): the reads are spread over the
     // context's fill threads, each taking a contiguous range of the (slot-ordered) list and opening a slot file once per run
     const int threads = (int)std::min<size_t>(ctx->ingest_threads > 0 ? (size_t)ctx->ingest_threads : 8, std::max<size_t>(1, n / 256));
-    std::vector<std::string> failed(threads);
+    std::vector<std::string> failed(threads);   // per worker: slot_file_error of the file it could not open or read
     auto work = [&](int w) {
       int fd = -1;
       size_t open_slot = ~(size_t)0;
+      std::string fname;
       for (size_t i = n * w / threads; i < n * (w + 1) / threads; ++i) {
         size_t slot = g[i] / t->n_cells, cell = g[i] % t->n_cells;
         if (slot != open_slot) {
           if (fd >= 0) close(fd);
-          std::string fname = slot_file_name(t->file_base, (t->first_slot + slot) / t->units_per_slot);
+          fname = slot_file_name(t->file_base, (t->first_slot + slot) / t->units_per_slot);
           fd = open(fname.c_str(), O_RDONLY);
-          if (fd < 0) { failed[w] = fname; return; }
+          if (fd < 0) { failed[w] = slot_file_error(fname, 0); return; }
           open_slot = slot;
         }
-        read_file_cell(fd, cs, ((t->first_slot + slot) % t->units_per_slot) * t->n_cells + cell, out + i * cs);
+        const int err = read_file_cell(fd, cs, ((t->first_slot + slot) % t->units_per_slot) * t->n_cells + cell, out + i * cs);
+        if (err) { failed[w] = slot_file_error(fname, err); break; }
       }
       if (fd >= 0) close(fd);
     };
@@ -670,7 +673,7 @@ static int host_cells_global(cp2_slot_trees* t, const uint64_t* g, size_t n, uin
       pool.wait_idle();
     }
     for (const auto& f : failed)
-      if (!f.empty()) { ctx->err = "cannot open " + f; return CP2_ERR_IO; }
+      if (!f.empty()) { ctx->err = f; return CP2_ERR_IO; }
     return CP2_OK;
   }
   if (t->src == CellSrc::Dev) {   // cell sizes the row gather cannot take: plain copies
@@ -730,10 +733,12 @@ static int compact_proof_inputs(cp2_dataset* ds, const uint64_t* slots, size_t n
       for (size_t i = 0; i < n; ++i) {
         const std::string fname = slot_file_name(ds->file_base, slots[i]);
         const int fd = open(fname.c_str(), O_RDONLY);
-        if (fd < 0) { ctx->err = "cannot open " + fname; return CP2_ERR_IO; }
-        for (size_t k = 0; k < ns; ++k)
-          for (size_t j = 0; j < cpb; ++j) read_file_cell(fd, cs, (idx[i * ns + k] / cpb) * cpb + j, &h_blocks[((i * ns + k) * cpb + j) * cs]);
+        if (fd < 0) { ctx->err = slot_file_error(fname, 0); return CP2_ERR_IO; }
+        int err = 0;
+        for (size_t k = 0; k < ns && !err; ++k)
+          for (size_t j = 0; j < cpb && !err; ++j) err = read_file_cell(fd, cs, (idx[i * ns + k] / cpb) * cpb + j, &h_blocks[((i * ns + k) * cpb + j) * cs]);
         close(fd);
+        if (err) { ctx->err = slot_file_error(fname, err); return CP2_ERR_IO; }   // (before the block roots are checked: the read failed, not the data)
       }
       CP2_HIP(ctx, hipMemcpyAsync(d_cells.p, h_blocks.data(), h_blocks.size(), hipMemcpyHostToDevice, ctx->stream));
     } else {
@@ -1263,7 +1268,7 @@ static int build_streamed_in_mode(cp2_ctx* ctx, const cp2_config* cfg, uint64_t 
 
   std::atomic<int> task_status{CP2_OK};
   std::mutex io_mu;
-  std::string io_error;         // first slot file a formatting worker could not open
+  std::string io_error;         // first slot file a formatting worker could not open or read
   cp2_dataset* dsp = ds.get();
   size_t n_groups = 0;          // sampling passes enqueued so far
   size_t consumed = 0;          // passes whose body tasks have been handed to the workers
@@ -1293,14 +1298,17 @@ static int build_streamed_in_mode(cp2_ctx* ctx, const cp2_config* cfg, uint64_t 
               std::vector<uint8_t> cells(ns * cs);
               const std::string fname = slot_file_name(file_base, first_slot + s);
               int fd = open(fname.c_str(), O_RDONLY);
-              if (fd < 0) {       // reported like the classic path ("cannot open <file>"); no body for this slot
+              int err = 0;
+              if (fd >= 0) {
+                for (size_t c = 0; c < ns && !err; ++c) err = read_file_cell(fd, cs, idx[c], &cells[c * cs]);
+                close(fd);
+              }
+              if (fd < 0 || err) {   // reported like the classic path ("cannot open / cannot read <file>"); no body for this slot
                 task_status.store(CP2_ERR_IO);
                 std::lock_guard<std::mutex> lk(io_mu);
-                if (io_error.empty()) io_error = "cannot open " + fname;
+                if (io_error.empty()) io_error = slot_file_error(fname, fd < 0 ? 0 : err);
                 have = false;
               } else {
-                for (size_t c = 0; c < ns; ++c) read_file_cell(fd, cs, idx[c], &cells[c * cs]);
-                close(fd);
                 text_body(body, cfgv, ns, cells.data(), paths);
               }
             } else {

@@ -55,16 +55,6 @@ int aux_stream(cp2_ctx* ctx, hipStream_t* out, int which) {
 
 std::string slot_file_name(const std::string& base, uint64_t slot) { return fill_slot_file_name(base, slot); }   // dataset.nim:34
 
-void read_file_cell(int fd, size_t cell_size, uint64_t cell, uint8_t* out) {
-  size_t done = 0;
-  while (fd >= 0 && done < cell_size) {
-    ssize_t r = pread(fd, out + done, cell_size - done, (off_t)(cell * cell_size + done));
-    if (r <= 0) break;
-    done += (size_t)r;
-  }
-  if (done < cell_size) std::memset(out + done, 0, cell_size - done);
-}
-
 int trees_check_geometry(size_t cell_size, size_t block_size, size_t n_cells, size_t n_slots) {
   if (cell_size == 0 || block_size == 0 || n_cells == 0 || n_slots == 0) return CP2_ERR_INVALID;
   if (block_size % cell_size != 0) return CP2_ERR_INVALID;        // types.nim:104-107 cellsPerBlock assert
@@ -341,7 +331,7 @@ extern "C" int cp2_slot_trees_build_fake_units(cp2_ctx* ctx, uint64_t dataset_se
 extern "C" int cp2_slot_trees_build_file_units(cp2_ctx* ctx, const char* file_base, uint64_t units_per_slot, uint64_t first_unit,
                                                size_t n_units, size_t cell_size, size_t block_size, size_t cells_per_unit,
                                                cp2_slot_trees** out) try {
-  if (!ctx || !out || !file_base || units_per_slot == 0) return CP2_ERR_INVALID;
+  if (!ctx || !out || !file_base || units_per_slot == 0 || cell_size > SLOT_FILE_MAX_CELL) return CP2_ERR_INVALID;   // slot.nim:60-61
   CP2_TRY(trees_check_geometry(cell_size, block_size, cells_per_unit, n_units));
   if (units_per_slot > 1 && !unit_geometry_ok(units_per_slot, cell_size, block_size, cells_per_unit)) return CP2_ERR_INVALID;
   return trees_build_files(ctx, file_base, first_unit, n_units, cell_size, block_size, cells_per_unit, 0, nullptr, out, units_per_slot);
@@ -570,8 +560,9 @@ struct IngestPipe {
   }
   int fill_join() {
     std::string bad;
-    if (fill && !fill->join(&bad)) {
-      ctx->err = "cannot open " + bad;
+    int err = 0;
+    if (fill && !fill->join(&bad, &err)) {
+      ctx->err = slot_file_error(bad, err);
       return CP2_ERR_IO;
     }
     return CP2_OK;
@@ -833,7 +824,7 @@ int cp2i::trees_build_files(cp2_ctx* ctx, const std::string& base, uint64_t firs
                             size_t block_size, size_t n_cells, size_t group, const SlotsDone& done, cp2_slot_trees** out,
                             uint64_t units_per_slot, bool pooled_nodes, BuildScratch* scratch, int node_slot) {
   *out = nullptr;
-  if (units_per_slot == 0) return CP2_ERR_INVALID;
+  if (units_per_slot == 0 || cell_size > SLOT_FILE_MAX_CELL) return CP2_ERR_INVALID;   // slot.nim:60-61
   CP2_REFUSE_STUCK(ctx);
   CP2_TRY(trees_check_geometry(cell_size, block_size, n_cells, n_slots));
   CP2_HIP(ctx, hipSetDevice(ctx->device));

@@ -285,7 +285,13 @@ typedef struct cp2_config {
   uint64_t n_cells;         /* DataSetConfig.nCells (power of two)                   */
   uint64_t n_samples;       /* DataSetConfig.nSamples                                */
   uint64_t seed;            /* DataSource FakeData seed (used when file_base == NULL) */
-  const char* file_base;    /* DataSource SlotFile base name: slot k = "<base><k>.dat" (dataset.nim:34) */
+  const char* file_base;    /* DataSource SlotFile base name: slot k = "<base><k>.dat" (dataset.nim:34).  Cell i of a slot is
+                             * bytes [i x cell_size, (i + 1) x cell_size) of its file; what lies past the end of the file reads as
+                             * zeros (slot.nim:61-66).  A file that cannot be opened is CP2_ERR_IO with "cannot open <file>" in
+                             * cp2_last_error; a read of it that fails (EIO, EISDIR, ...: anything but the end of the file; an
+                             * interrupted read is retried) is CP2_ERR_IO with "cannot read <file>: <reason>", never zeros, and no
+                             * tree, proof input or input.json comes back from that call.  Cells over 16384 bytes are refused:
+                             * CP2_ERR_INVALID (slot.nim:60-61).  The same holds for cp2_slot_trees_build_file_units. */
 } cp2_config;
 
 /* A dataset whose slot trees are built: slot roots + dataset tree (gen_input/bn254.nim:41-51). */

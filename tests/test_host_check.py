@@ -50,8 +50,11 @@ def test_fill_pipeline_against_real_files_asan_ubsan_and_tsan(tmp_path):
     """The host side of the ingestion pipe (csrc/fill_pipeline.hpp, the class IngestPipe itself uses: grains from a shared counter,
     fills posted two turns deep, workers running on into the next turn while the building thread joins this one) against REAL slot
     files in a scratch directory -- short files, a missing file (named, lowest slot first), slots cut into units, O_DIRECT requested,
-    the host-array source -- every turn compared with the reference's own read of a cell (slot.nim:57-68).  Built with
-    AddressSanitizer + UBSan (ring buffers of exactly a turn's size) and again with ThreadSanitizer.  No GPU, no HIP."""
+    the host-array source -- every turn compared with the reference's own read of a cell (slot.nim:57-68).  Then the read rule through
+    an injected reader: EIO (first read of a piece, after a partial read, in a turn's last grain, in two slots at once: the lowest
+    named, with its errno), EIO / EINVAL from O_DIRECT (the buffered reads finish the piece), EINTR, 1-byte reads, a real directory
+    in place of a slot file -- through the pipe and through the per-cell reader.  Built with AddressSanitizer + UBSan (ring buffers
+    of exactly a turn's size) and again with ThreadSanitizer.  No GPU, no HIP."""
     src = os.path.join(ROOT, "tests", "host_check", "fill_pipeline_check.cpp")
     inc = "-I" + os.path.join(ROOT, "codex-storage-proofs-circuits_amd", "csrc")
     for name, flags, shapes in (("asan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], "150"), ("tsan", ["-fsanitize=thread"], "40")):
@@ -62,6 +65,7 @@ def test_fill_pipeline_against_real_files_asan_ubsan_and_tsan(tmp_path):
         r = subprocess.run([exe, str(scratch), shapes], capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, (name, r.stdout[-2000:], r.stderr[-4000:])
         assert "fill pipeline ok: %s shapes" % shapes in r.stdout and "ThreadSanitizer" not in r.stderr, (name, r.stdout, r.stderr[-2000:])
+        assert "read rule ok: 16 pipe cases" in r.stdout and "7 cell-reader cases" in r.stdout, (name, r.stdout)
 
 
 def _build_text_check(pkg, tmp_path, sanitize=("-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"), name="host_text_check"):
