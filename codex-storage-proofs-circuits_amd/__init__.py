@@ -15,7 +15,7 @@ import weakref
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION_MAJOR, ABI_VERSION_MINOR = 1, 1      # CP2_ABI_VERSION_* of the include/codex_p2.h this binding was written against (tests keep them equal)
+ABI_VERSION_MAJOR, ABI_VERSION_MINOR = 1, 2      # CP2_ABI_VERSION_* of the include/codex_p2.h this binding was written against (tests keep them equal)
 LIB_PATH = os.environ.get("CODEX_P2_LIB") or os.path.join(_HERE, "libcodex_p2.so")   # env override: kernel-variant A/B runs
 CLI_PATH = os.path.join(_HERE, "cli")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "codex_p2.h")
@@ -212,6 +212,8 @@ def load_library():
         "cp2_proof_input_shape": (i32, [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]),
         "cp2_proof_input_cell_felts": (i32, [vp, vp]),
         "cp2_proof_inputs_verify": (i32, [vp, vp, sz, vp, vp]),
+        "cp2_proof_inputs_generate_many": (i32, [vp, vp, vp, vp, sz, pvp]),
+        "cp2_proof_inputs_export_many": (i32, [vp, vp, vp, vp, sz, ctypes.POINTER(cp), i32, sz, ctypes.POINTER(u64)]),
     }
     for name, (res, args) in sigs.items():
         if v is None and name == "cp2_abi_version":
@@ -480,6 +482,45 @@ class Context:
         ok = np.zeros((n, ns), dtype=np.uint8)
         self._ck(self.L.cp2_proof_inputs_verify(self.h, hs, n, _p(status), _p(ok)), "cp2_proof_inputs_verify")
         return status, ok
+
+    @staticmethod
+    def _many_arrays(requests):
+        """(dataset handles, slot indices, entropies n x 32) of a sequence of (Dataset, slot, entropy) requests"""
+        n = len(requests)
+        hs = (ctypes.c_void_p * max(n, 1))(*[r[0].h for r in requests])
+        slots = np.ascontiguousarray(np.asarray([r[1] for r in requests], dtype=np.uint64).reshape(n))
+        ent = np.zeros((max(n, 1), 32), dtype=np.uint8)
+        for i, r in enumerate(requests):
+            e = r[2]
+            ent[i] = felt_bytes(e) if isinstance(e, int) else np.frombuffer(bytes(e), dtype=np.uint8) if isinstance(e, (bytes, bytearray)) else _u8(e)
+        return hs, slots, ent
+
+    def proof_inputs_many(self, requests):
+        """cp2_proof_inputs_generate_many: one proof input per (Dataset, slot, entropy) request, across datasets of one circuit
+        (entropy: an int or 32 bytes)."""
+        hs, slots, ent = self._many_arrays(requests)
+        n = len(requests)
+        out = (ctypes.c_void_p * max(n, 1))()
+        self._ck(self.L.cp2_proof_inputs_generate_many(self.h, hs, _p(slots), _p(ent), n, out), "cp2_proof_inputs_generate_many")
+        pis = []
+        for i, r in enumerate(requests):
+            pi = ProofInput(self, ctypes.c_void_p(out[i]), r[0].cfg)
+            pi.slot_idx = int(r[1])
+            pis.append(pi)
+        return pis
+
+    def export_proof_inputs_many(self, requests, paths=None, threads=1, batch=0):
+        """cp2_proof_inputs_export_many: generate + serialise (+ write paths[i] where it is not None) as a pipeline; returns the
+        total text bytes."""
+        hs, slots, ent = self._many_arrays(requests)
+        n = len(requests)
+        cpaths = None
+        if paths is not None:
+            cpaths = (ctypes.c_char_p * max(n, 1))(*[p.encode() if p else None for p in paths])
+        total = ctypes.c_uint64()
+        self._ck(self.L.cp2_proof_inputs_export_many(self.h, hs, _p(slots), _p(ent), n, cpaths, threads, batch, ctypes.byref(total)),
+                 "cp2_proof_inputs_export_many")
+        return total.value
 
     def dataset_streamed(self, cfg, entropy, first_slot=0, n_local=None, threads=1, group_slots=0):
         """cp2_dataset_build_streamed: trees + (overlapped) the proof-input bodies of every local slot for `entropy`."""

@@ -6,6 +6,7 @@
 //   k_sponge2_felts   a3  Sponge.hs:30-43 over field elements (sampling, generic byte strings)
 //   k_gen_fake_cells  a10 slot.nim:22-32
 //   k_gather_rows         path / cell gather for proof inputs (merkle.nim:21-42 does this on the host)
+//   k_sample_many, k_gather_addr, k_gen_fake_cells_many   the same across datasets (proof_many.cpp)
 //   k_verify_samples      what SampleAndProve accepts: sample_cells.circom:58-148, single_cell.circom:30-73, merkle.circom:44-114
 //
 // All global-memory field elements are 32-byte little-endian canonical integers (the ABI format).
@@ -438,6 +439,135 @@ __global__ void __launch_bounds__(TPB) k_gather_rows(const uint8_t* __restrict__
 }
 
 // ------------------------------------------------------------------------------------------------
+// Proof inputs across datasets (proof_many.cpp).  k_sample_many is k_sample_paths with the per-request inputs -- entropy, slot root,
+// slot geometry, node buffer -- read from a descriptor instead of kernel arguments, and ABSOLUTE node addresses written instead of
+// row indices, so that one launch serves the requests of every dataset and one k_gather_addr launch fetches all their paths.
+__global__ void __launch_bounds__(TPB) k_sample_many(const ManyReq* __restrict__ reqs, const TreeGeom* __restrict__ geoms, size_t n_req,
+                                                       uint32_t ns, uint32_t md, uint64_t* __restrict__ indices,
+                                                       uint64_t* __restrict__ blocks, uint64_t* __restrict__ addr) {
+  __shared__ fr::QTab qtab;
+  fr::qtab_fill(qtab, threadIdx.x, TPB);
+  __syncthreads();
+  const size_t total = n_req * ns;
+  size_t t = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (t >= total) return;
+  const size_t item = t / ns;
+  const uint32_t counter = (uint32_t)(t - item * ns) + 1;            // sample/bn254.nim:27
+  const ManyReq& q = reqs[item];
+  State s;
+  s.x = load_fe_canonical(reinterpret_cast<const uint4*>(q.entropy));
+  s.y = load_fe_canonical(reinterpret_cast<const uint4*>(q.slot_root));
+  s.z = fr::fe_const(fr::FR_CIV_RATE2_MONT);
+  p2::permute(s, qtab);
+  Fe c = fr::fe_zero();
+  c.l[0] = counter & fr::MASK;
+  c.l[1] = counter >> 29;
+  s.x = fr::norm(fr::add_lazy(s.x, fr::to_mont(c)));
+  s.y = fr::norm(fr::add_lazy(s.y, fr::fe_const(fr::FR_R1)));
+  p2::permute(s, qtab);
+  uint32_t w[8];
+  fr::to_canonical_words(s.x, w);
+  const uint64_t cell = (((uint64_t)w[1] << 32) | w[0]) & (q.n_cells - 1);   // extractLowBits, types/bn254.nim:47-59
+  indices[t] = cell;
+  const uint64_t b = cell / q.cpb;
+  if (!q.nodes) {                                                     // compact: the host rebuilds the touched block
+    blocks[t] = b;
+    return;
+  }
+  const TreeGeom& g = geoms[q.geom];
+  const uint64_t base = q.nodes, slot = q.slot;
+  addr[total * md + t] = base + (slot * g.n_cells + cell) * 32;      // the leaf: layer 0 row slot * nCells + cell
+  uint64_t* r = addr + t * md;
+  uint32_t d = 0;
+  uint64_t j = cell - b * g.cpb, m = g.cpb;
+  for (uint32_t k = 0; k + 1 < g.nb && d < md; ++k, ++d) {           // bottom proof inside the block tree
+    const uint64_t sib = j ^ 1;
+    r[d] = (sib < m) ? base + (g.boff[k] + (slot * g.nblocks + b) * g.bsz[k] + sib) * 32 : 0;
+    j >>= 1;
+    m = (m + 1) >> 1;
+  }
+  j = b;
+  m = g.nblocks;
+  for (uint32_t k = 0; k + 1 < g.nt && d < md; ++k, ++d) {           // top proof inside the slot's big tree
+    const uint64_t sib = j ^ 1;
+    r[d] = (sib < m) ? base + (g.toff[k] + slot * g.tsz[k] + sib) * 32 : 0;
+    j >>= 1;
+    m = (m + 1) >> 1;
+  }
+  for (; d < md; ++d) r[d] = 0;                                       // padMerkleProof
+}
+
+// Rows of row_bytes bytes from absolute device addresses (W: the widest word the row length allows); address 0 is a row of zeros.
+template <typename W>
+__global__ void __launch_bounds__(TPB) k_gather_addr(const uint64_t* __restrict__ addr, size_t nrows, size_t row_bytes,
+                                                       uint8_t* __restrict__ out) {
+  const size_t words_per_row = row_bytes / sizeof(W);
+  size_t t = (size_t)blockIdx.x * TPB + threadIdx.x;
+  const size_t stride = (size_t)gridDim.x * TPB;
+  for (; t < nrows * words_per_row; t += stride) {
+    const size_t r = t / words_per_row, w = t - r * words_per_row;
+    const uint64_t a = addr[r];
+    W v = 0;
+    if (a) v = reinterpret_cast<const W*>(a)[w];
+    reinterpret_cast<W*>(out + r * row_bytes)[w] = v;
+  }
+}
+
+// genFakeCell (slot.nim:22-32) with a seed per group of `per` rows: row i is cell firsts[i / per] + i % per of the slot seeded
+// seeds[i / per] (cp2_slot_seed).  The generator and the write-out through LDS are those of k_gen_fake_cells.
+__global__ void __launch_bounds__(TPB) k_gen_fake_cells_many(const uint64_t* __restrict__ seeds, const uint64_t* __restrict__ firsts,
+                                                               uint64_t per, size_t n_rows, size_t cell_size, uint8_t* __restrict__ out) {
+  __shared__ uint4 gen_stage[TPB / 64][64 * 9];
+  size_t t = (size_t)blockIdx.x * TPB + threadIdx.x;
+  const bool active = t < n_rows;
+  const bool wide = ((cell_size & 127) == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
+  if (!active && !wide) return;
+  const size_t grp = active ? t / per : 0;                           // idle tail lanes only take part in the write-out
+  const uint64_t seed1 = (active ? seeds[grp] : 0) + 0xdeadcafeULL;
+  const uint64_t seed2 = (active ? firsts[grp] + (t - grp * per) : 0) + 0x98765432ULL;
+  uint64_t state = 1;
+  if (wide) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    uint4* my = gen_stage[wave];
+    const size_t wave_row0 = (size_t)blockIdx.x * TPB + (size_t)wave * 64;
+#pragma unroll 1
+    for (size_t i = 0; i < cell_size; i += 128) {
+#pragma unroll 1
+      for (int piece = 0; piece < 8; ++piece) {
+        uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int b = 0; b < 16; ++b) {
+          state = state * (state + seed1) * (state + seed2) + state * (state ^ 0x5a5a5a5aULL) + seed1 * state + (seed2 + 17);
+          state = state % 1698428844001831ULL;
+          w[b >> 2] |= (uint32_t)(state & 0xff) << (8 * (b & 3));
+        }
+        my[lane * 9 + piece] = make_uint4(w[0], w[1], w[2], w[3]);   // row stride 9 x 16 B: conflict-free both ways
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int c = k * 8 + (lane >> 3), piece = lane & 7;
+        const size_t row = wave_row0 + c;
+        uint4 v = my[c * 9 + piece];
+        if (row < n_rows) *reinterpret_cast<uint4*>(out + row * cell_size + i + 16 * piece) = v;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+    }
+    return;
+  }
+  uint8_t* dst = out + t * cell_size;
+#pragma unroll 1
+  for (size_t i = 0; i < cell_size; ++i) {
+    state = state * (state + seed1) * (state + seed2) + state * (state ^ 0x5a5a5a5aULL) + seed1 * state + (seed2 + 17);
+    state = state % 1698428844001831ULL;
+    dst[i] = (uint8_t)state;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // What SampleAndProve accepts (circuit/codex/sample_cells.circom:58-148, single_cell.circom:30-73, merkle.circom:44-114), checked
 // in one launch: lane t < n*ns takes sample t % ns of input t / ns from its cell felts to the slot-root comparison (index sponge,
 // leaf sponge, bottom and middle reconstructions); lane n*ns + i checks input i's slot root against its dataset root.  One byte per
@@ -715,6 +845,32 @@ hipError_t launch_gather_rows(const void* src, const uint64_t* index, size_t nro
   size_t work = nrows * (row_bytes / 4);
   unsigned grid = work > (size_t)4096 * TPB ? 4096u : grid_for(work);
   CP2K_LAUNCH(k_gather_rows, dim3(grid), dim3(TPB), 0, st, (const uint8_t*)src, index, nrows, row_bytes, (uint8_t*)out);
+  return hipGetLastError();
+}
+
+hipError_t launch_sample_many(const ManyReq* reqs, const TreeGeom* geoms, size_t n_req, uint32_t ns, uint32_t md, uint64_t* indices,
+                              uint64_t* blocks, uint64_t* addr, hipStream_t st) {
+  if (n_req == 0 || ns == 0) return hipSuccess;
+  if (!fits_one_grid(n_req * ns)) return hipErrorInvalidValue;
+  CP2K_LAUNCH(k_sample_many, dim3(grid_for(n_req * ns)), dim3(TPB), 0, st, reqs, geoms, n_req, ns, md, indices, blocks, addr);
+  return hipGetLastError();
+}
+
+hipError_t launch_gather_addr(const uint64_t* addr, size_t nrows, size_t row_bytes, void* out, hipStream_t st) {
+  if (nrows == 0 || row_bytes == 0) return hipSuccess;
+  const bool words = (row_bytes & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0;   // (the callers' addresses are row multiples)
+  const size_t work = nrows * (words ? row_bytes / 4 : row_bytes);
+  const unsigned grid = work > (size_t)4096 * TPB ? 4096u : grid_for(work);
+  if (words) CP2K_LAUNCH(k_gather_addr<uint32_t>, dim3(grid), dim3(TPB), 0, st, addr, nrows, row_bytes, (uint8_t*)out);
+  else CP2K_LAUNCH(k_gather_addr<uint8_t>, dim3(grid), dim3(TPB), 0, st, addr, nrows, row_bytes, (uint8_t*)out);
+  return hipGetLastError();
+}
+
+hipError_t launch_gen_fake_cells_many(const uint64_t* seeds, const uint64_t* firsts, uint64_t per, size_t n_rows, size_t cell_size,
+                                      void* out, hipStream_t st) {
+  if (n_rows == 0 || cell_size == 0) return hipSuccess;
+  if (per == 0 || !fits_one_grid(n_rows)) return hipErrorInvalidValue;
+  CP2K_LAUNCH(k_gen_fake_cells_many, dim3(grid_for(n_rows)), dim3(TPB), 0, st, seeds, firsts, per, n_rows, cell_size, (uint8_t*)out);
   return hipGetLastError();
 }
 

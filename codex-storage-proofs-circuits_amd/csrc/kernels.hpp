@@ -64,4 +64,27 @@ struct VerifyGeom {
 hipError_t launch_verify_samples(const VerifyGeom& g, const uint64_t* prm, const void* heads, const void* cells, const void* paths,
                                  uint8_t* ok, hipStream_t st);
 
+// Proof inputs across datasets (proof_many.cpp).  One request = (dataset, slot, entropy); all requests share nSamples and maxDepth.
+struct alignas(16) ManyReq {
+  uint8_t entropy[32];     // canonical
+  uint8_t slot_root[32];   // the slot's root (layer 0 of its dataset tree)
+  uint64_t n_cells;        // cells of the slot (a power of two)
+  uint64_t cpb;            // cells per network block
+  uint64_t nodes;          // every node resident: device address of the node buffer of the dataset's trees; 0: compact
+  uint64_t slot;           // index of the slot inside that node buffer (resident only)
+  uint32_t geom, pad;      // resident only: index into the TreeGeom table
+};
+// k_sample_many: lane t = (request t / ns, counter t % ns + 1) of n_req * ns lanes.  indices[t] = cellIndex (sample/bn254.nim:16-27).
+// Resident requests: addr[t * md + d] = device address of path sibling d (merkle.nim:21-42,86-100), 0 where padMerkleProof pads with
+// zero (types.nim:27-37), and addr[n_req * ns * md + t] = the address of the sampled cell's own hash.  Compact requests: blocks[t] = the
+// touched network block; their addresses are left as they are.
+hipError_t launch_sample_many(const ManyReq* reqs, const TreeGeom* geoms, size_t n_req, uint32_t ns, uint32_t md, uint64_t* indices,
+                              uint64_t* blocks, uint64_t* addr, hipStream_t st);
+// out[r] = the row_bytes bytes at device address addr[r]; address 0 gives a row of zeros
+hipError_t launch_gather_addr(const uint64_t* addr, size_t nrows, size_t row_bytes, void* out, hipStream_t st);
+// genFakeCell (slot.nim:22-32), list form with a seed per group of `per` rows: row i is cell firsts[i / per] + i % per of the slot whose
+// seed (cp2_slot_seed) is seeds[i / per]
+hipError_t launch_gen_fake_cells_many(const uint64_t* seeds, const uint64_t* firsts, uint64_t per, size_t n_rows, size_t cell_size,
+                                      void* out, hipStream_t st);
+
 }  // namespace cp2k

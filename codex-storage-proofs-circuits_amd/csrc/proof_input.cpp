@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "body_store.hpp"
+#include "dataset_obj.hpp"
 #include "json_text.hpp"
 #include "proof_input_obj.hpp"
 #include "trees.hpp"
@@ -40,57 +41,7 @@ using namespace cp2text;
 // ---------------------------------------------------------------------------------------------
 // dataset
 // ---------------------------------------------------------------------------------------------
-struct cp2_dataset {
-  cp2_ctx* ctx = nullptr;
-  cp2_config cfg{};
-  std::string file_base;
-  bool from_file = false;
-  uint64_t first_slot = 0, n_local = 0;
-  cp2_slot_trees* trees = nullptr;            // every local slot tree (null for a roots-only dataset)
-  // Roots-only dataset: the slot trees of a dataset whose nodes do not fit the device (3.1 % of the data: 256 MiB per 8 GiB
-  // slot, 8 TiB for config 5's nominal 32 768 slots) are built batch by batch in pooled scratch and dropped again, only the
-  // 32-byte roots stay; the tree of a slot that is proved is rebuilt on demand (0.2 s per 8 GiB), which is what the reference
-  // does on EVERY run and once more per sample (gen_input/bn254.nim:42,57).
-  DevBuf local_roots;                         // roots-only: n_local x 32 bytes
-  // Compact dataset (between the two): of every local slot tree the part from the BLOCK ROOTS up stays (2 x nBlocks - 1 nodes:
-  // 8 MiB per 8 GiB slot, 1/32 of the full tree), layer-major over the local slots: layer k of slot s starts at element
-  // coff[k] + s * csizes[k].  The bottom of a path -- inside one network block -- is recomputed from the block's own cells
-  // (<= nSamples blocks of 64 KiB per proof input: SURVEY.md section 7, "keep only block roots + upper layers and re-hash the
-  // touched blocks"), checked against the stored block root.
-  DevBuf compact;
-  std::vector<size_t> csizes, coff;
-  int tree_mode = 1;                          // 1 every node resident, 2 compact, 0 roots only
-  bool have_roots = false;
-  std::vector<size_t> dsizes;                 // dataset-tree layer sizes
-  std::vector<uint8_t> dlayers;               // all dataset-tree layers, bottom first (host copy)
-  // streamed build: one JSON body (", \"cellData\": ... }") per local slot, made while later slots were hashing
-  bool prepared = false;
-  uint8_t prep_entropy[32] = {};
-  BodyStore bodies;
-  ~cp2_dataset() { cp2_slot_trees_free(trees); }
-};
-
-// The field modulus r as four little-endian 64-bit words (README.md:76 of the reference), and a 32-byte value reduced into [0, r):
-// `Entropy` is a field element in the reference (types/bn254.nim:21), so what is stored and printed is the canonical
-// representative even when the caller hands in 32 arbitrary bytes (at most five subtractions: 2^256 / r < 5.3).
-static const uint64_t FR_MODULUS_LE64[4] = {0x43e1f593f0000001ULL, 0x2833e84879b97091ULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL};
-static void canonical_felt(const uint8_t in[32], uint8_t out[32]) {
-  uint64_t w[4];
-  std::memcpy(w, in, 32);
-  for (;;) {
-    bool ge = true;
-    for (int i = 3; i >= 0; --i)
-      if (w[i] != FR_MODULUS_LE64[i]) { ge = w[i] > FR_MODULUS_LE64[i]; break; }
-    if (!ge) break;
-    unsigned __int128 borrow = 0;
-    for (int i = 0; i < 4; ++i) {
-      unsigned __int128 d = (unsigned __int128)w[i] - FR_MODULUS_LE64[i] - borrow;
-      w[i] = (uint64_t)d;
-      borrow = (d >> 64) & 1;
-    }
-  }
-  std::memcpy(out, w, 32);
-}
+// struct cp2_dataset and canonical_felt: dataset_obj.hpp (shared with proof_many.cpp)
 
 static int dataset_check(const cp2_config* cfg, uint64_t first_slot, uint64_t n_local) {
   if (n_local == 0 || first_slot > cfg->n_slots || n_local > cfg->n_slots - first_slot) return CP2_ERR_INVALID;   // (no wrap-around)
@@ -120,7 +71,7 @@ static int dataset_build_trees(cp2_dataset* ds, size_t group, const SlotsDone& d
 }
 
 // the device buffer holding the roots of the local slots (n_local x 32 bytes)
-static const void* dataset_roots_dev(const cp2_dataset* ds) {
+const void* dataset_roots_dev(const cp2_dataset* ds) {
   if (ds->trees) return cp2_slot_trees_roots_dev(ds->trees);
   if (ds->tree_mode == 2) return ds->compact.u8() + ds->coff.back() * 32;   // the last layer: one root per local slot
   return ds->local_roots.p;
@@ -620,7 +571,7 @@ int enqueue_sampling(cp2_slot_trees* t, const cp2k::TreeGeom& g, SampleDev& d, S
 // BatchStore and struct cp2_proof_input: proof_input_obj.hpp (shared with verify.cpp)
 
 // slotProof = padMerkleProof(merkleProof(dsetTree, slotIdx), maxLog2NSlots), gen_input/bn254.nim:51,72
-static void fill_slot_proof(const cp2_dataset* ds, uint64_t slot_idx, std::vector<uint8_t>& out) {
+void fill_slot_proof(const cp2_dataset* ds, uint64_t slot_idx, std::vector<uint8_t>& out) {
   out.assign((size_t)ds->cfg.max_log2_nslots * 32, 0);
   size_t k = slot_idx, m = ds->cfg.n_slots, off = 0;
   for (size_t i = 0; i + 1 < ds->dsizes.size(); ++i) {
@@ -686,7 +637,6 @@ static int host_cells_global(cp2_slot_trees* t, const uint64_t* g, size_t n, uin
   return CP2_ERR_INVALID;
 }
 
-static void fill_slot_proof(const cp2_dataset* ds, uint64_t slot_idx, std::vector<uint8_t>& out);
 
 // generateProofInput (gen_input/bn254.nim:53-74) on a COMPACT dataset, for `n` slots in one pass: the top of every path -- block
 // root to slot root -- is gathered from the stored layers; the bottom -- cell to block root (merkleProof on the block's tree,

@@ -17,7 +17,7 @@ import std/os                  # getEnv: CODEX_P2_CACHE, as in the cli twin
 const libName = "libcodex_p2.so"
 const
   abiVersionMajor* = 1         ## CP2_ABI_VERSION_MAJOR / _MINOR of the include/codex_p2.h this binding was written against
-  abiVersionMinor* = 1         ## (tests/test_nim_binding.py keeps the two files equal)
+  abiVersionMinor* = 2         ## (tests/test_nim_binding.py keeps the two files equal)
 
 type
   F* = array[32, byte]          ## canonical little-endian field element (NOT constantine's Montgomery limbs)
@@ -63,6 +63,11 @@ proc cp2_dataset_build_streamed(ctx: Cp2Ctx, cfg: ptr Cp2Config, firstSlot, nLoc
 proc cp2_dataset_export_streamed(ds: Cp2Dataset, dir: cstring, threads: cint, totalBytes: ptr uint64): cint {.importc.}
 proc cp2_proof_input_generate(ds: Cp2Dataset, slotIdx: uint64, entropy: ptr byte, p: ptr Cp2ProofInput): cint {.importc.}
 proc cp2_proof_input_free(p: Cp2ProofInput) {.importc.}
+# requests (ds[i], slotIdx[i], entropies[32*i ..]) across datasets of one circuit (generateProofInputBN254 per request, gen_input/bn254.nim:78)
+proc cp2_proof_inputs_generate_many(ctx: Cp2Ctx, ds: ptr Cp2Dataset, slotIdx: ptr uint64, entropies: ptr byte, n: csize_t,
+                                    outp: ptr Cp2ProofInput): cint {.importc.}
+proc cp2_proof_inputs_export_many(ctx: Cp2Ctx, ds: ptr Cp2Dataset, slotIdx: ptr uint64, entropies: ptr byte, n: csize_t,
+                                  paths: ptr cstring, threads: cint, batch: csize_t, totalBytes: ptr uint64): cint {.importc.}
 proc cp2_proof_input_write_json(p: Cp2ProofInput, path: cstring): cint {.importc.}
 proc cp2_proof_input_roots(p: Cp2ProofInput, datasetRoot, slotRoot, entropy: ptr byte): cint {.importc.}
 proc cp2_proof_input_nsamples(p: Cp2ProofInput): csize_t {.importc.}

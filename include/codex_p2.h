@@ -39,9 +39,10 @@ extern "C" {
  *   MINOR  grows with every release that only ADDS entry points; a caller needs library minor >= the minor it was written against.
  * cp2_abi_version() returns what the LIBRARY was built from: (MAJOR << 16) | MINOR.  It touches no device and needs no context.
  * History: 1.0 = the 105 entry points of round 5 + this function + cp2_set_ingest's two rings (round 6).
- *          1.1 = + cp2_proof_input_parse_json, _shape, _cell_felts and cp2_proof_inputs_verify (verification).                  */
+ *          1.1 = + cp2_proof_input_parse_json, _shape, _cell_felts and cp2_proof_inputs_verify (verification).
+ *          1.2 = + cp2_proof_inputs_generate_many and cp2_proof_inputs_export_many (proof inputs across datasets).               */
 #define CP2_ABI_VERSION_MAJOR 1
-#define CP2_ABI_VERSION_MINOR 1
+#define CP2_ABI_VERSION_MINOR 2
 #define CP2_ABI_VERSION ((CP2_ABI_VERSION_MAJOR << 16) | CP2_ABI_VERSION_MINOR)
 int cp2_abi_version(void);
 
@@ -384,6 +385,36 @@ int cp2_dataset_build_streamed(cp2_ctx* ctx, const cp2_config* cfg, uint64_t fir
 int cp2_dataset_export_streamed(cp2_dataset* ds, const char* dir, int threads, uint64_t* total_bytes);
 /* the finished text of one prepared slot in a malloc'ed buffer (cp2_free_buffer) */
 int cp2_dataset_streamed_json(cp2_dataset* ds, uint64_t slot_idx, char** text, size_t* len);
+/* ---- proof inputs across datasets ----------------------------------------------------------------------------------------
+ * generateProofInput (reference/nim/proof_input/src/gen_input/bn254.nim:35-79) takes a dataset, a slot and an entropy on every call
+ * (generateProofInputBN254, :78).  These take n such requests at once: request i is (ds[i], slot_idx[i], entropies[32*i .. 32*i+32)).
+ * A storage node holding one slot each of many datasets (cp2_dataset_build(_cached) with first_slot = k, n_local = 1, then
+ * cp2_dataset_set_roots with the manifest's slot roots) proves all of them each period in one call.
+ *   Same result   out[i] is the object cp2_proof_input_generate(ds[i], slot_idx[i], entropy i) returns, and its cp2_proof_input_json
+ *                 text is byte-identical.  Entropies are reduced to their canonical residue as there.  A dataset may appear in many
+ *                 requests, with the same or different slots and entropies.
+ *   One circuit   every dataset belongs to ctx and has the same SampleAndProve template arguments (sample_cells.circom:58-148):
+ *                 max_depth, max_log2_nslots, cell_size, block_size, n_samples (the rule of cp2_proof_inputs_verify).  n_cells,
+ *                 n_slots, the source (seed or file_base) and what the dataset keeps of its trees may differ.
+ *   Refusals      checked before any proof work on the device: CP2_ERR_INVALID, every out[i] NULL, and cp2_last_error names the
+ *                 request index.  A request is refused when ds[i] is NULL; its dataset belongs to another context; its circuit
+ *                 parameters differ from request 0's; its slot is not local to its dataset; its dataset has no dataset tree and not
+ *                 all of its slots are local (cp2_dataset_set_roots was never called); nCells or a tree depth breaks an assert of
+ *                 generateProofInput (sample/bn254.nim:19-20, types.nim:29); or the root the dataset tree holds for its slot (what
+ *                 cp2_dataset_set_roots was given) differs from the slot's built root (that input.json would be rejected by the circuit).
+ *   All or nothing  slot data that no longer hashes to what was built (a compact dataset's block-root check, a roots-only dataset's
+ *                 rebuild check) and slot-file reads that fail are CP2_ERR_IO, naming the request, the block and the slot where they
+ *                 apply, and no object comes back.  A context whose stream will not drain is refused (CP2_ERR_HIP).  n == 0: CP2_OK.
+ * Datasets that keep every node or the compact layers are sampled and gathered in one pass for all requests (the compact ones in
+ * chunks whose touched blocks fit the staging chunk, CODEX_P2_STAGE_MB); a roots-only dataset costs one slot rebuild per request.
+ * Datasets of a cp2_multi_dataset belong to the multi-device object's own contexts. */
+int cp2_proof_inputs_generate_many(cp2_ctx* ctx, cp2_dataset* const* ds, const uint64_t* slot_idx, const uint8_t* entropies /* n x 32 */,
+                                   size_t n, cp2_proof_input** out);
+/* The same, serialised on `threads` host threads and written to paths[i] (paths == NULL or paths[i] == NULL: serialise only), as a
+ * two-stage pipeline like cp2_dataset_export_proof_inputs (device work of chunk k+1 while chunk k is formatted); batch == 0: 512
+ * requests per chunk.  Every request is checked before the first chunk.  total_bytes (may be NULL) receives the summed text length. */
+int cp2_proof_inputs_export_many(cp2_ctx* ctx, cp2_dataset* const* ds, const uint64_t* slot_idx, const uint8_t* entropies, size_t n,
+                                 const char* const* paths, int threads, size_t batch, uint64_t* total_bytes);
 /* ---- verification: what SampleAndProve accepts (circuit/codex/sample_cells.circom:58-148) ----------------------------------
  * The verifier accepts exactly the inputs for which SampleAndProve(maxDepth, maxLog2NSlots, blockTreeDepth, nFieldElemsPerCell,
  * nSamples) has a satisfying witness, reading them as the field elements the circuit sees:
