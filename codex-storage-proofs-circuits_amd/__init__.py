@@ -214,6 +214,8 @@ def load_library():
         "cp2_proof_inputs_verify": (i32, [vp, vp, sz, vp, vp]),
         "cp2_proof_inputs_generate_many": (i32, [vp, vp, vp, vp, sz, pvp]),
         "cp2_proof_inputs_export_many": (i32, [vp, vp, vp, vp, sz, ctypes.POINTER(cp), i32, sz, ctypes.POINTER(u64)]),
+        "cp2_dataset_scrub": (i32, [vp, u64, u64, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_int)]),
+        "cp2_multi_dataset_scrub": (i32, [vp, u64, u64, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_int)]),
     }
     for name, (res, args) in sigs.items():
         if v is None and name == "cp2_abi_version":
@@ -585,6 +587,18 @@ class SlotTrees:
         return out, leaves
 
 
+SCRUB_SLOT, SCRUB_BLOCK, SCRUB_CELL = 0, 1, 2     # CP2_SCRUB_* (include/codex_p2.h): what a scrub's indices count
+
+
+def _scrub(fn, h, first_slot, n_slots, cap, ck, where):
+    """(granularity, bad: uint64[k, 2] of (slot, index), n_bad) of cp2_dataset_scrub / cp2_multi_dataset_scrub"""
+    cap = int(cap)
+    bad = np.empty((cap, 2), dtype=np.uint64)
+    n, g = ctypes.c_size_t(), ctypes.c_int()
+    ck(fn(h, first_slot, n_slots, _p(bad) if cap else None, cap, ctypes.byref(n), ctypes.byref(g)), where)
+    return g.value, bad[:min(cap, n.value)].copy(), n.value
+
+
 class Dataset:
     def __init__(self, ctx, cfg, first_slot, n_local, cache=None, streamed=None):
         self.ctx, self.cfg = ctx, cfg
@@ -685,6 +699,12 @@ class Dataset:
         s = ctypes.string_at(text, ln.value).decode()
         self.ctx.L.cp2_free_buffer(text)
         return s
+
+    def scrub(self, first_slot=None, n_slots=0, cap=1 << 20):
+        """cp2_dataset_scrub: re-read slots first_slot .. + n_slots (0: every local slot) from the source and compare them with what the
+        dataset keeps.  Returns (granularity SCRUB_*, bad: uint64[k, 2] of (slot, index), the lowest k = min(cap, n_bad), n_bad)."""
+        first = self.first_slot if first_slot is None else first_slot
+        return _scrub(self.ctx.L.cp2_dataset_scrub, self.h, first, n_slots, cap, self.ctx._ck, "cp2_dataset_scrub")
 
     def proof_inputs(self, slot_indices, entropy):
         """Batched generateProofInput for many slots of this dataset (one sampling / gather / fetch)."""
@@ -880,6 +900,11 @@ class MultiDataset:
         self.multi._ck(self.multi.L.cp2_multi_dataset_export_streamed(self.h, directory.encode() if directory else None, threads,
                                                                       ctypes.byref(total)), "cp2_multi_dataset_export_streamed")
         return total.value
+
+    def scrub(self, first_slot=None, n_slots=0, cap=1 << 20):
+        """cp2_multi_dataset_scrub: Dataset.scrub over every shard (cut by units: cell indices of the slot)."""
+        first = 0 if first_slot is None else first_slot
+        return _scrub(self.multi.L.cp2_multi_dataset_scrub, self.h, first, n_slots, cap, self.multi._ck, "cp2_multi_dataset_scrub")
 
     def streamed_json(self, slot_idx):
         text, ln = ctypes.c_void_p(), ctypes.c_size_t()

@@ -8,6 +8,7 @@
 //   k_gather_rows         path / cell gather for proof inputs (merkle.nim:21-42 does this on the host)
 //   k_sample_many, k_gather_addr, k_gen_fake_cells_many   the same across datasets (proof_many.cpp)
 //   k_verify_samples      what SampleAndProve accepts: sample_cells.circom:58-148, single_cell.circom:30-73, merkle.circom:44-114
+//   k_scrub_compare       a rebuilt layer against the kept one, mismatch bitmap + per-workgroup counts (scrub.cpp)
 //
 // All global-memory field elements are 32-byte little-endian canonical integers (the ABI format).
 #include "kernels.hpp"
@@ -568,6 +569,48 @@ __global__ void __launch_bounds__(TPB) k_gen_fake_cells_many(const uint64_t* __r
 }
 
 // ------------------------------------------------------------------------------------------------
+// Scrub (scrub.cpp): a batch's freshly built layer -- cell hashes, block roots or slot roots -- against the layer the dataset keeps for
+// the same slots, 32-byte rows, two 16-byte loads a side.  A wave covers 64 consecutive rows per step and writes their mismatch bitmap
+// (__ballot) as one plain 64-bit store; the workgroup's tile of SCRUB_TILE rows ends with one count, summed in LDS: no atomics, and
+// the host reads the counts of a clean batch (4 bytes per 4096 rows) and bitmap words only where a count is non-zero.  Every word of the
+// tile is written (zeros past the last row), so the host never reads a word the kernel did not write.
+constexpr int SCRUB_STEPS = (int)(SCRUB_TILE / TPB);
+static_assert(SCRUB_TILE % TPB == 0 && TPB % 64 == 0, "a tile is whole workgroup steps of whole waves");
+__global__ void __launch_bounds__(TPB) k_scrub_compare(const uint4* __restrict__ fresh, size_t fstride, const uint4* __restrict__ kept,
+                                                         size_t kstride, size_t rows, size_t total, unsigned long long* __restrict__ bits,
+                                                         uint32_t* __restrict__ counts) {
+  __shared__ uint32_t wave_count[TPB / 64];
+  const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const size_t tile0 = (size_t)blockIdx.x * SCRUB_TILE;
+  const bool dense = fstride == rows && kstride == rows;            // layer-major layouts: the batch's rows are one contiguous run on both sides
+  uint32_t n = 0;
+  for (int j = 0; j < SCRUB_STEPS; ++j) {
+    const size_t g = tile0 + (size_t)j * TPB + threadIdx.x;
+    bool diff = false;
+    if (g < total) {
+      size_t fo = g, ko = g;
+      if (!dense) {
+        const size_t item = g / rows, r = g - item * rows;
+        fo = item * fstride + r;
+        ko = item * kstride + r;
+      }
+      const uint4 a0 = fresh[2 * fo], a1 = fresh[2 * fo + 1], b0 = kept[2 * ko], b1 = kept[2 * ko + 1];
+      diff = ((a0.x ^ b0.x) | (a0.y ^ b0.y) | (a0.z ^ b0.z) | (a0.w ^ b0.w) | (a1.x ^ b1.x) | (a1.y ^ b1.y) | (a1.z ^ b1.z) | (a1.w ^ b1.w)) != 0;
+    }
+    const unsigned long long m = __ballot(diff);
+    if (lane == 0) bits[(tile0 + (size_t)j * TPB) / 64 + wave] = m;
+    n += (uint32_t)__popcll(m);
+  }
+  if (lane == 0) wave_count[wave] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t s = 0;
+    for (int w = 0; w < TPB / 64; ++w) s += wave_count[w];
+    counts[blockIdx.x] = s;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // What SampleAndProve accepts (circuit/codex/sample_cells.circom:58-148, single_cell.circom:30-73, merkle.circom:44-114), checked
 // in one launch: lane t < n*ns takes sample t % ns of input t / ns from its cell felts to the slot-root comparison (index sponge,
 // leaf sponge, bottom and middle reconstructions); lane n*ns + i checks input i's slot root against its dataset root.  One byte per
@@ -871,6 +914,17 @@ hipError_t launch_gen_fake_cells_many(const uint64_t* seeds, const uint64_t* fir
   if (n_rows == 0 || cell_size == 0) return hipSuccess;
   if (per == 0 || !fits_one_grid(n_rows)) return hipErrorInvalidValue;
   CP2K_LAUNCH(k_gen_fake_cells_many, dim3(grid_for(n_rows)), dim3(TPB), 0, st, seeds, firsts, per, n_rows, cell_size, (uint8_t*)out);
+  return hipGetLastError();
+}
+
+hipError_t launch_scrub_compare(const void* fresh, size_t fstride, const void* kept, size_t kstride, size_t rows, size_t n_items,
+                                uint64_t* bits, uint32_t* counts, hipStream_t st) {
+  if (n_items == 0 || rows == 0) return hipSuccess;
+  if (!fresh || !kept || !bits || !counts || fstride < rows || kstride < rows) return hipErrorInvalidValue;
+  const size_t total = n_items * rows, groups = scrub_groups(total);
+  if (groups > MAX_BLOCKS) return hipErrorInvalidValue;
+  CP2K_LAUNCH(k_scrub_compare, dim3((unsigned)groups), dim3(TPB), 0, st, (const uint4*)fresh, fstride, (const uint4*)kept, kstride, rows, total,
+              (unsigned long long*)bits, counts);
   return hipGetLastError();
 }
 

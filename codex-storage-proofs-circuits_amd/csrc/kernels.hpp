@@ -53,6 +53,15 @@ hipError_t launch_sample_paths(const TreeGeom& g, const void* nodes, const void*
 hipError_t launch_gather_rows(const void* src, const uint64_t* index, size_t nrows, size_t row_bytes, void* out,
                               hipStream_t st);
 
+// Scrub (scrub.cpp): row g < n_items * rows (item g / rows, row g % rows) of the fresh layer (fresh + (item * fstride + row) * 32) against
+// the kept one (kept + (item * kstride + row) * 32), 32-byte rows.  Workgroup w covers rows [w * SCRUB_TILE, + SCRUB_TILE): bits[g / 64]
+// bit g % 64 is set where the rows differ (every word of the tile is written, zeros past the end) and counts[w] holds the tile's number
+// of set bits.  bits: scrub_groups(n) * SCRUB_TILE / 64 words, counts: scrub_groups(n) words.
+constexpr size_t SCRUB_TILE = 4096;
+inline size_t scrub_groups(size_t n_rows) { return (n_rows + SCRUB_TILE - 1) / SCRUB_TILE; }
+hipError_t launch_scrub_compare(const void* fresh, size_t fstride, const void* kept, size_t kstride, size_t rows, size_t n_items,
+                                uint64_t* bits, uint32_t* counts, hipStream_t st);
+
 // Proof-input verification (k_verify_samples, circuit/codex/sample_cells.circom:58-148) over n inputs that share the circuit
 // parameters.  Device arrays: prm n x 4 (nCellsPerSlot, nSlotsPerDataSet, slotIndex, shape ok), heads n x (3 + m) felts
 // (dataSetRoot, entropy, slotRoot, slotProof), cells n x ns x nf felts, paths n x ns x md felts; ok receives n x ns sample

@@ -1192,3 +1192,86 @@ extern "C" int cp2_multi_dataset_streamed_json(cp2_multi_dataset* mds, uint64_t 
 } catch (...) {
   return CP2_ERR_INVALID;
 }
+
+// cp2_dataset_scrub over the shards, each on its own host thread and context (scrub.cpp), nothing exchanged between devices.  Shard
+// ranges are contiguous and in slot (or unit) order, so concatenating the shards' reports in shard order keeps them sorted.
+extern "C" int cp2_multi_dataset_scrub(cp2_multi_dataset* mds, uint64_t first_slot, uint64_t n_slots, uint64_t* bad, size_t cap, size_t* n_bad,
+                                       int* granularity) try {
+  if (!mds || !n_bad || (cap && !bad)) return CP2_ERR_INVALID;
+  cp2_multi* m = mds->m;
+  m->err.clear();
+  const uint64_t n_all = mds->cfg.n_slots, S = mds->units_per_slot;
+  if (n_slots == 0) {
+    first_slot = 0;
+    n_slots = n_all;
+  }
+  if (first_slot >= n_all || n_slots > n_all - first_slot) {
+    m->err = "scrub: slots " + std::to_string(first_slot) + " + " + std::to_string(n_slots) + " are not inside the dataset's " + std::to_string(n_all);
+    return CP2_ERR_INVALID;
+  }
+  // by units every node of every unit tree is resident: cells.  By slots: the finest level every shard keeps (each chose its own mode)
+  int level = CP2_SCRUB_CELL;
+  if (!mds->by_units())
+    for (auto& s : mds->shards) level = std::min(level, dataset_scrub_level(s.ds));
+  const auto t0 = std::chrono::steady_clock::now();
+  const size_t world = mds->shards.size();
+  std::vector<std::vector<uint64_t>> got(world);
+  std::vector<uint64_t> count(world, 0);
+  std::vector<std::string> errs(world);
+  DeviceRestore restore;
+  const int st = for_each_shard(world, [&](size_t i) -> int {
+    auto& s = mds->shards[i];
+    const uint64_t a = std::max(first_slot * S, s.first), z = std::min((first_slot + n_slots) * S, s.first + s.count);   // slots or units
+    if (a >= z) return CP2_OK;
+    cp2_ctx* ctx = s.ds ? cp2_dataset_ctx(s.ds) : s.units->ctx;
+    int r = CP2_OK;
+    if (s.ds) {
+      r = dataset_scrub(s.ds, a, z - a, level, cap, got[i], &count[i]);
+    } else {
+      const cp2_slot_trees* t = s.units;
+      ScrubSrc src;
+      src.from_file = t->src == CellSrc::File;
+      src.file_base = t->file_base;
+      src.seed = t->dataset_seed;
+      src.cell_size = t->cell_size;
+      src.block_size = t->block_size;
+      src.n_cells = t->n_cells;
+      src.units_per_slot = S;
+      r = scrub_items(ctx, src, a, z - a, CP2_SCRUB_CELL, t->nodes.u8() + (t->boff[0] + (a - s.first) * t->n_cells) * 32, t->n_cells, cap,
+                      got[i], &count[i]);
+      for (size_t j = 0; r == CP2_OK && j < got[i].size(); j += 2) {   // (unit, cell of the unit) -> (slot, cell of the slot)
+        const uint64_t u = got[i][j];
+        got[i][j] = u / S;
+        got[i][j + 1] += (u % S) * t->n_cells;
+      }
+    }
+    if (r != CP2_OK)
+      errs[i] = "device " + std::to_string(m->devices[s.dev]) + (S > 1 ? ", units " : ", slots ") + std::to_string(a) + ".." + std::to_string(z) +
+                ": " + (*cp2_last_error(ctx) ? cp2_last_error(ctx) : cp2_strerror(r));
+    return r;
+  });
+  if (st != CP2_OK) {
+    for (auto& e : errs) if (!e.empty()) { m->err = e; break; }
+    return st;
+  }
+  uint64_t total = 0;
+  size_t k = 0;
+  for (size_t i = 0; i < world; ++i) {
+    total += count[i];
+    for (size_t j = 0; j < got[i].size() && k < 2 * cap; ++j) bad[k++] = got[i][j];
+  }
+  *n_bad = (size_t)total;
+  if (granularity) *granularity = level;
+  if (std::getenv("CP2_TRACE")) {
+    const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    const double bytes = (double)n_slots * (double)mds->cfg.n_cells * (double)mds->cfg.cell_size;
+    std::fprintf(stderr, "[cp2 trace] multi scrub: slots %llu..%llu (%llu) on %zu shard(s), %.0f bytes, %.3f s (%.2f GB/s), %llu mismatch(es) at %s level\n",
+                 (unsigned long long)first_slot, (unsigned long long)(first_slot + n_slots - 1), (unsigned long long)n_slots, world, bytes, s,
+                 s > 0 ? bytes / s / 1e9 : 0.0, (unsigned long long)total, level == CP2_SCRUB_CELL ? "cell" : (level == CP2_SCRUB_BLOCK ? "block" : "slot"));
+  }
+  return CP2_OK;
+} catch (const std::bad_alloc&) {
+  return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
+} catch (...) {
+  return CP2_ERR_INVALID;
+}

@@ -1,0 +1,195 @@
+// Scrub behind the C ABI: cp2_dataset_scrub (include/codex_p2.h); cp2_multi_dataset_scrub (multi_gpu.cpp) runs scrub_items per shard.
+//
+// A storage node keeps a slot's trees -- every node, the compact layers or the roots -- and proves every period from the touched blocks
+// alone; nothing on that path reads the rest of the slot.  A scrub re-reads the selected slots from the dataset's source and hashes them
+// exactly as the compact / roots-only builds do (dataset_build_transient, proof_input.cpp): batches of about half a staging chunk of nodes
+// in a BuildScratch, two node buffers used alternately, nothing synchronised per batch.  Where the build copies out what it keeps, the
+// scrub compares instead: the builder's SlotsDone hook -- on the stream the batch's layer passes ran on -- launches k_scrub_compare over the
+// fresh layer and the kept one (the fresh layer never leaves the device) and downloads one count per 4096 rows into pinned memory.  When
+// batch k's node buffer is handed to batch k + 2 the host reads batch k's counts and downloads bitmap words only for tiles with a
+// mismatch; batches are decoded in order, so the report comes out sorted by (item, row) with no sort anywhere.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "dataset_obj.hpp"
+#include "trees.hpp"
+
+using namespace cp2i;
+
+int cp2i::scrub_items(cp2_ctx* ctx, const ScrubSrc& src, uint64_t item0, uint64_t n_items, int level, const uint8_t* kept, size_t kstride,
+                      size_t cap, std::vector<uint64_t>& bad, uint64_t* n_bad) {
+  *n_bad = 0;
+  if (n_items == 0) return CP2_OK;
+  if (!kept || src.cell_size == 0 || src.block_size < src.cell_size) return CP2_ERR_INVALID;
+  CP2_REFUSE_STUCK(ctx);
+  CP2_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t nblocks = src.n_cells / (src.block_size / src.cell_size);
+  const size_t rows = level == CP2_SCRUB_CELL ? src.n_cells : (level == CP2_SCRUB_BLOCK ? nblocks : 1);
+  if (rows == 0 || kstride < rows) return CP2_ERR_INVALID;
+  // batches as the compact build cuts them (transient_batch_slots, proof_input.cpp): half a staging chunk of nodes, at least one item
+  const size_t per_item = std::max<size_t>(1, trees_node_bytes(1, src.cell_size, src.block_size, src.n_cells));
+  const size_t batch = std::max<size_t>(1, std::min<size_t>(n_items, (ctx->stage_bytes / 2) / per_item));
+  const size_t groups = cp2k::scrub_groups(batch * rows);
+  const int n_bufs = n_items > batch ? 2 : 1;
+  DevBuf d_bits[2], d_counts[2];               // (declared before the scratch: they go after it has drained the streams)
+  PinBuf h_counts[2];
+  for (int b = 0; b < n_bufs; ++b) {
+    CP2_TRY(d_bits[b].scratch(ctx, groups * cp2k::SCRUB_TILE / 8));
+    CP2_TRY(d_counts[b].scratch(ctx, groups * 4));
+    CP2_TRY(h_counts[b].alloc(ctx, groups * 4));
+  }
+  struct Pending { bool live = false; uint64_t s0 = 0; size_t n = 0; } pending[2];
+  std::vector<uint64_t> words(cp2k::SCRUB_TILE / 64);
+  uint64_t total = 0;
+  // batch in buffer b has landed (its event completed): its counts are in h_counts[b], its bitmap in d_bits[b]
+  auto collect = [&](int b) -> int {
+    Pending& p = pending[b];
+    if (!p.live) return CP2_OK;
+    p.live = false;
+    const size_t ng = cp2k::scrub_groups(p.n * rows);
+    const uint32_t* c = static_cast<const uint32_t*>(h_counts[b].p);
+    for (size_t w = 0; w < ng; ++w) {
+      if (!c[w]) continue;
+      total += c[w];
+      if (bad.size() / 2 >= cap) continue;      // the report is full: only counting from here on
+      CP2_HIP(ctx, hipMemcpy(words.data(), d_bits[b].u8() + w * (cp2k::SCRUB_TILE / 8), cp2k::SCRUB_TILE / 8, hipMemcpyDeviceToHost));
+      for (size_t k = 0; k < words.size() && bad.size() / 2 < cap; ++k)
+        for (uint64_t m = words[k]; m && bad.size() / 2 < cap; m &= m - 1) {
+          const uint64_t g = w * cp2k::SCRUB_TILE + k * 64 + (uint64_t)__builtin_ctzll(m);
+          if (g >= p.n * rows) break;             // (never: the kernel leaves the words past the last row zero)
+          bad.push_back(item0 + p.s0 + g / rows);
+          bad.push_back(g % rows);
+        }
+    }
+    return CP2_OK;
+  };
+  int st = CP2_OK;
+  {
+    BuildScratch scratch;                       // drains the context's streams before its buffers go, whatever path leaves this scope
+    hipEvent_t landed[2] = {nullptr, nullptr};
+    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 2; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } ev_guard{landed};
+    for (int i = 0; i < 2; ++i) CP2_HIP(ctx, hipEventCreateWithFlags(&landed[i], hipEventDisableTiming));
+    size_t k = 0;
+    for (uint64_t s0 = 0; st == CP2_OK && s0 < n_items; s0 += batch, ++k) {
+      const size_t n = (size_t)std::min<uint64_t>(batch, n_items - s0);
+      const int b = (int)(k & 1);
+      if (k >= 2) {
+        if (hipEventSynchronize(landed[b]) != hipSuccess) { (void)hipGetLastError(); ctx->err = "scrub: a batch failed on the device"; st = CP2_ERR_HIP; break; }
+        st = collect(b);
+        if (st != CP2_OK) break;
+      }
+      const uint8_t* kept_b = kept + s0 * kstride * 32;
+      // the builder calls this once, with every slot of the batch, on the stream its layer passes ran on (group 0: one pass at the end)
+      SlotsDone compare = [&, b, n, kept_b](cp2_slot_trees* t, size_t a, size_t z, hipStream_t ls) -> int {
+        if (a != 0 || z != n) { ctx->err = "scrub: a batch's layers were built in parts"; return CP2_ERR_INVALID; }
+        const size_t off = level == CP2_SCRUB_CELL ? t->boff[0] : (level == CP2_SCRUB_BLOCK ? t->toff[0] : t->toff.back());
+        const size_t fstride = level == CP2_SCRUB_CELL ? t->n_cells : (level == CP2_SCRUB_BLOCK ? t->tsizes[0] : 1);
+        CP2_HIP(ctx, cp2k::launch_scrub_compare(t->nodes.u8() + off * 32, fstride, kept_b, kstride, rows, n, static_cast<uint64_t*>(d_bits[b].p),
+                                                static_cast<uint32_t*>(d_counts[b].p), ls));
+        CP2_HIP(ctx, hipMemcpyAsync(h_counts[b].p, d_counts[b].p, cp2k::scrub_groups(n * rows) * 4, hipMemcpyDeviceToHost, ls));
+        return CP2_OK;
+      };
+      cp2_slot_trees* t = nullptr;
+      st = src.from_file ? trees_build_files(ctx, src.file_base, item0 + s0, n, src.cell_size, src.block_size, src.n_cells, 0, compare, &t,
+                                             src.units_per_slot, true, &scratch, b)
+                         : trees_build_fake(ctx, src.seed, item0 + s0, n, src.cell_size, src.block_size, src.n_cells, 0, compare, &t,
+                                            src.units_per_slot, true, &scratch, b);
+      hipStream_t tail = scratch.tail_stream ? scratch.tail_stream : ctx->stream;
+      if (st == CP2_OK && hipEventRecord(landed[b], tail) != hipSuccess) { ctx->err = "hipEventRecord failed"; st = CP2_ERR_HIP; }
+      cp2_slot_trees_free(t);                   // (the batch's nodes are the scratch's: nothing is waited for here)
+      if (st == CP2_OK) { pending[b].live = true; pending[b].s0 = s0; pending[b].n = n; }
+    }
+    if (st == CP2_OK) {                         // everything landed (a failed launch or copy shows up here)
+      if (hipStreamSynchronize(ctx->stream) != hipSuccess || (ctx->aux_stream && hipStreamSynchronize(ctx->aux_stream) != hipSuccess) ||
+          (ctx->aux2_stream && hipStreamSynchronize(ctx->aux2_stream) != hipSuccess)) {
+        (void)hipGetLastError();
+        ctx->err = "scrub: a batch failed on the device";
+        st = CP2_ERR_HIP;
+      }
+    }
+    if (st == CP2_OK) st = collect((int)(k & 1));          // the older of the two batches still pending first
+    if (st == CP2_OK) st = collect((int)((k + 1) & 1));
+  }
+  if (st != CP2_OK) return st;
+  *n_bad = total;
+  return CP2_OK;
+}
+
+int cp2i::dataset_scrub_level(const cp2_dataset* ds) {
+  return ds->trees ? CP2_SCRUB_CELL : (ds->tree_mode == 2 ? CP2_SCRUB_BLOCK : CP2_SCRUB_SLOT);
+}
+
+int cp2i::dataset_scrub(cp2_dataset* ds, uint64_t first_slot, uint64_t n, int level, size_t cap, std::vector<uint64_t>& bad, uint64_t* n_bad) {
+  *n_bad = 0;
+  if (level > dataset_scrub_level(ds) || first_slot < ds->first_slot || first_slot - ds->first_slot > ds->n_local ||
+      n > ds->n_local - (first_slot - ds->first_slot))
+    return CP2_ERR_INVALID;
+  const cp2_config& c = ds->cfg;
+  ScrubSrc src;
+  src.from_file = ds->from_file;
+  src.file_base = ds->file_base;
+  src.seed = c.seed;
+  src.cell_size = c.cell_size;
+  src.block_size = c.block_size;
+  src.n_cells = c.n_cells;
+  const uint64_t local = first_slot - ds->first_slot;
+  // the kept layer of the first slot scrubbed: the dataset's layer-major `trees`, its `compact` layers (coff / csizes) or its roots
+  const uint8_t* kept = nullptr;
+  size_t kstride = 1;
+  if (level == CP2_SCRUB_CELL) {
+    kept = ds->trees->nodes.u8() + (ds->trees->boff[0] + local * ds->trees->n_cells) * 32;
+    kstride = ds->trees->n_cells;
+  } else if (level == CP2_SCRUB_BLOCK && ds->trees) {
+    kept = ds->trees->nodes.u8() + (ds->trees->toff[0] + local * ds->trees->tsizes[0]) * 32;
+    kstride = ds->trees->tsizes[0];
+  } else if (level == CP2_SCRUB_BLOCK) {
+    kept = ds->compact.u8() + (ds->coff[0] + local * ds->csizes[0]) * 32;
+    kstride = ds->csizes[0];
+  } else {
+    kept = static_cast<const uint8_t*>(dataset_roots_dev(ds)) + local * 32;
+  }
+  return scrub_items(ds->ctx, src, first_slot, n, level, kept, kstride, cap, bad, n_bad);
+}
+
+extern "C" int cp2_dataset_scrub(cp2_dataset* ds, uint64_t first_slot, uint64_t n_slots, uint64_t* bad, size_t cap, size_t* n_bad,
+                                 int* granularity) try {
+  if (!ds || !n_bad || (cap && !bad)) return CP2_ERR_INVALID;
+  cp2_ctx* ctx = ds->ctx;
+  if (n_slots == 0) {
+    first_slot = ds->first_slot;
+    n_slots = ds->n_local;
+  }
+  if (first_slot < ds->first_slot || first_slot - ds->first_slot >= ds->n_local || n_slots > ds->n_local - (first_slot - ds->first_slot)) {
+    ctx->err = "scrub: slots " + std::to_string(first_slot) + " + " + std::to_string(n_slots) + " are not inside the local range " +
+               std::to_string(ds->first_slot) + " + " + std::to_string(ds->n_local);
+    return CP2_ERR_INVALID;
+  }
+  CP2_REFUSE_STUCK(ctx);
+  const auto t0 = std::chrono::steady_clock::now();
+  const int level = dataset_scrub_level(ds);
+  std::vector<uint64_t> got;
+  uint64_t count = 0;
+  CP2_TRY(dataset_scrub(ds, first_slot, n_slots, level, cap, got, &count));
+  std::copy(got.begin(), got.end(), bad);      // (got holds min(cap, count) pairs)
+  *n_bad = (size_t)count;
+  if (granularity) *granularity = level;
+  if (std::getenv("CP2_TRACE")) {
+    const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    const double bytes = (double)n_slots * (double)ds->cfg.n_cells * (double)ds->cfg.cell_size;
+    std::fprintf(stderr, "[cp2 trace] scrub: slots %llu..%llu (%llu), %.0f bytes, %.3f s (%.2f GB/s), %llu mismatch(es) at %s level\n",
+                 (unsigned long long)first_slot, (unsigned long long)(first_slot + n_slots - 1), (unsigned long long)n_slots, bytes, s,
+                 s > 0 ? bytes / s / 1e9 : 0.0, (unsigned long long)count, level == CP2_SCRUB_CELL ? "cell" : (level == CP2_SCRUB_BLOCK ? "block" : "slot"));
+  }
+  return CP2_OK;
+} catch (const std::bad_alloc&) {
+  return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
+} catch (...) {
+  return CP2_ERR_INVALID;
+}

@@ -88,6 +88,25 @@ int kept_load(cp2_ctx* ctx, const char* path, const KeptMeta& want, void* d_buf,
 // slot roots?  One small download.  The multi-device exchange is verified with it (multi_gpu.cpp).
 int dataset_own_roots_in_place(cp2_dataset* ds, bool* ok);
 
+// Scrub (scrub.cpp): items (whole slots, or units of a slot cut by units_per_slot) rebuilt batch by batch in a BuildScratch from their
+// source, and the fresh layer of `level` (CP2_SCRUB_CELL: cell hashes, _BLOCK: block roots, _SLOT: item roots) compared on the device
+// with the kept one.  The kept layer of items [item0, item0 + n) starts at `kept` (32-byte rows) with `kstride` rows per item.
+// Mismatches are appended to `bad` as (item, row) pairs in that order, at most `cap` of them; *n_bad counts all.  Reads the kept
+// layer only.
+struct ScrubSrc {
+  bool from_file = false;
+  std::string file_base;
+  uint64_t seed = 0;                   // dataset seed (fake source)
+  size_t cell_size = 0, block_size = 0, n_cells = 0;   // n_cells: per item
+  uint64_t units_per_slot = 1;
+};
+int scrub_items(cp2_ctx* ctx, const ScrubSrc& src, uint64_t item0, uint64_t n, int level, const uint8_t* kept, size_t kstride, size_t cap,
+                std::vector<uint64_t>& bad, uint64_t* n_bad);
+// the finest level a dataset keeps: CP2_SCRUB_CELL (every node), _BLOCK (compact) or _SLOT (roots only)
+int dataset_scrub_level(const cp2_dataset* ds);
+// slots [first_slot, first_slot + n) of the dataset's local range at `level` (at most dataset_scrub_level): (slot, index) pairs
+int dataset_scrub(cp2_dataset* ds, uint64_t first_slot, uint64_t n, int level, size_t cap, std::vector<uint64_t>& bad, uint64_t* n_bad);
+
 // stage timings on stderr when CP2_TRACE is set (the reference's only tracing is shell `time`, workflow/prove.sh:30-37)
 bool stream_serial();   // CP2_STREAM_SERIAL=1 (A/B tooling): the streamed build hashes its groups one launch after the other, as rounds 2-4 did
 

@@ -68,6 +68,11 @@ proc cp2_proof_inputs_generate_many(ctx: Cp2Ctx, ds: ptr Cp2Dataset, slotIdx: pt
                                     outp: ptr Cp2ProofInput): cint {.importc.}
 proc cp2_proof_inputs_export_many(ctx: Cp2Ctx, ds: ptr Cp2Dataset, slotIdx: ptr uint64, entropies: ptr byte, n: csize_t,
                                   paths: ptr cstring, threads: cint, batch: csize_t, totalBytes: ptr uint64): cint {.importc.}
+# scrub: the slots re-read from their source against what the dataset keeps; bad = cap x (slot, index), granularity CP2_SCRUB_*
+proc cp2_dataset_scrub(ds: Cp2Dataset, firstSlot, nSlots: uint64, bad: ptr uint64, cap: csize_t, nBad: ptr csize_t,
+                       granularity: ptr cint): cint {.importc.}
+proc cp2_multi_dataset_scrub(ds: Cp2MultiDataset, firstSlot, nSlots: uint64, bad: ptr uint64, cap: csize_t, nBad: ptr csize_t,
+                             granularity: ptr cint): cint {.importc.}
 proc cp2_proof_input_write_json(p: Cp2ProofInput, path: cstring): cint {.importc.}
 proc cp2_proof_input_roots(p: Cp2ProofInput, datasetRoot, slotRoot, entropy: ptr byte): cint {.importc.}
 proc cp2_proof_input_nsamples(p: Cp2ProofInput): csize_t {.importc.}

@@ -40,7 +40,9 @@ extern "C" {
  * cp2_abi_version() returns what the LIBRARY was built from: (MAJOR << 16) | MINOR.  It touches no device and needs no context.
  * History: 1.0 = the 105 entry points of round 5 + this function + cp2_set_ingest's two rings (round 6).
  *          1.1 = + cp2_proof_input_parse_json, _shape, _cell_felts and cp2_proof_inputs_verify (verification).
- *          1.2 = + cp2_proof_inputs_generate_many and cp2_proof_inputs_export_many (proof inputs across datasets).               */
+ *          1.2 = + cp2_proof_inputs_generate_many and cp2_proof_inputs_export_many (proof inputs across datasets).
+ *          next: + cp2_dataset_scrub and cp2_multi_dataset_scrub (scrub).  MINOR stays 2 until the release that carries them: the
+ *                bump to 1.3 goes in its own commit with that release.                                                               */
 #define CP2_ABI_VERSION_MAJOR 1
 #define CP2_ABI_VERSION_MINOR 2
 #define CP2_ABI_VERSION ((CP2_ABI_VERSION_MAJOR << 16) | CP2_ABI_VERSION_MINOR)
@@ -451,6 +453,31 @@ int cp2_proof_input_cell_felts(const cp2_proof_input* p, uint8_t* out);
  * whatever n is); synchronous. */
 int cp2_proof_inputs_verify(cp2_ctx* ctx, const cp2_proof_input* const* ps, size_t n, uint32_t* status, uint8_t* sample_ok);
 
+/* ---- scrub: the stored slot data against what the dataset keeps ----------------------------------------------------------
+ * cp2_dataset_build_cached trusts a slot file of unchanged size and mtime, and a compact proof input reads only the blocks its samples
+ * touch: bytes that changed underneath (bit rot, a bad sector, a partial restore) surface as CP2_ERR_IO when a challenge lands on them.
+ * A scrub reads the selected slots again from the dataset's source (slot files, or the fake source: regenerated, always clean), hashes
+ * them in the context's build scratch as the compact / roots-only builds do (the same ingestion settings: cp2_set_ingest, O_DIRECT,
+ * mapped) and compares, on the device, at the finest level the dataset keeps:
+ *   CP2_SCRUB_CELL   every node kept (and every unit build of a cp2_multi_dataset): index = the cell of the slot whose hash differs;
+ *   CP2_SCRUB_BLOCK  compact: index = the network block of the slot whose root differs -- the unit a storage node repairs;
+ *   CP2_SCRUB_SLOT   roots only: index = 0, the slot root differs.
+ *   Slots    first_slot .. first_slot + n_slots - 1, dataset slot numbers inside the local range; n_slots == 0: every local slot
+ *            (first_slot is not read).  Outside the range: CP2_ERR_INVALID.
+ *   Result   *n_bad = the number of mismatches; bad (cap x 2 uint64: slot, index) receives the lowest min(cap, *n_bad) of them in
+ *            (slot, index) order; cap == 0 with bad == NULL only counts; *granularity = CP2_SCRUB_* (granularity may be NULL).
+ *            Changed data is not an error: CP2_OK with *n_bad > 0.  A file now shorter reads as zeros past its end (slot.nim:61-66),
+ *            so its changed tail blocks are reported.  A file that cannot be opened or read is CP2_ERR_IO with the builders' messages
+ *            (cp2_config), and nothing is written to the outputs; neither on any other error.  A context whose stream will not drain
+ *            is refused (CP2_ERR_HIP).
+ *   Read-only  the kept nodes, the dataset tree, the mode and any cache file stay as they are: every proof input and input.json is
+ *            byte-identical before and after a scrub.  CP2_TRACE prints one line per scrub (slots, bytes, seconds, mismatches). */
+#define CP2_SCRUB_SLOT  0
+#define CP2_SCRUB_BLOCK 1
+#define CP2_SCRUB_CELL  2
+int cp2_dataset_scrub(cp2_dataset* ds, uint64_t first_slot, uint64_t n_slots, uint64_t* bad /* cap x 2: (slot, index) */, size_t cap,
+                      size_t* n_bad, int* granularity);
+
 /* replaces `writeCircomMainComponent`, reference/nim/proof_input/src/cli.nim:186-204 */
 int cp2_write_circom_main(const cp2_config* cfg, const char* path);
 
@@ -545,6 +572,11 @@ int cp2_multi_dataset_export_proof_inputs(cp2_multi_dataset* mds, const uint64_t
                                           const char* dir, int threads, size_t batch, uint64_t* total_bytes);
 int cp2_multi_dataset_export_streamed(cp2_multi_dataset* mds, const char* dir, int threads, uint64_t* total_bytes);
 int cp2_multi_dataset_streamed_json(cp2_multi_dataset* mds, uint64_t slot_idx, char** text, size_t* len);
+/* cp2_dataset_scrub over the shards: any range of the dataset's n_slots slots, each shard's part on its own host thread and context,
+ * nothing exchanged between devices; the reports merged in slot order.  Cut by units, the comparison is on the cells of every unit
+ * and the indices are cells of the SLOT (not of the unit).  Cut by slots, the granularity is the finest level every shard keeps. */
+int cp2_multi_dataset_scrub(cp2_multi_dataset* mds, uint64_t first_slot, uint64_t n_slots, uint64_t* bad, size_t cap, size_t* n_bad,
+                            int* granularity);
 
 #ifdef __cplusplus
 }
