@@ -216,6 +216,8 @@ def load_library():
         "cp2_proof_inputs_export_many": (i32, [vp, vp, vp, vp, sz, ctypes.POINTER(cp), i32, sz, ctypes.POINTER(u64)]),
         "cp2_dataset_scrub": (i32, [vp, u64, u64, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_int)]),
         "cp2_multi_dataset_scrub": (i32, [vp, u64, u64, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_int)]),
+        "cp2_dataset_repair_blocks": (i32, [vp, vp, vp, sz, i32, cp, vp, ctypes.POINTER(sz)]),
+        "cp2_multi_dataset_repair_blocks": (i32, [vp, vp, vp, sz, i32, cp, vp, ctypes.POINTER(sz)]),
     }
     for name, (res, args) in sigs.items():
         if v is None and name == "cp2_abi_version":
@@ -599,6 +601,26 @@ def _scrub(fn, h, first_slot, n_slots, cap, ck, where):
     return g.value, bad[:min(cap, n.value)].copy(), n.value
 
 
+# CP2_REPAIR_* (include/codex_p2.h): the flag that makes a repair check only, and the per-request verdicts
+REPAIR_CHECK_ONLY = 1
+REPAIR_MATCH, REPAIR_MISMATCH, REPAIR_UNWRITTEN = 0, 1, 2
+
+
+def _repair(fn, h, block_size, slot_block, data, check_only, cache_path, ck, where):
+    """(status: uint32[n], n_written) of cp2_dataset_repair_blocks / cp2_multi_dataset_repair_blocks.  `data` may be any buffer of
+    n x block_size bytes that numpy can view without a copy (bytes, a numpy array, a pinned torch tensor's .numpy())."""
+    sb = np.ascontiguousarray(np.asarray(slot_block, dtype=np.uint64).reshape(-1, 2))
+    n = sb.shape[0]
+    d = np.ascontiguousarray(data) if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)   # (no copy of a contiguous array)
+    if d.nbytes != n * block_size:
+        raise ValueError("repair: %d request(s) need %d bytes of candidates, got %d" % (n, n * block_size, d.nbytes))
+    status = np.empty(n, dtype=np.uint32)
+    written = ctypes.c_size_t()
+    ck(fn(h, _p(sb) if n else None, _p(d) if n else None, n, REPAIR_CHECK_ONLY if check_only else 0,
+          cache_path.encode() if cache_path else None, _p(status) if n else None, ctypes.byref(written)), where)
+    return status, written.value
+
+
 class Dataset:
     def __init__(self, ctx, cfg, first_slot, n_local, cache=None, streamed=None):
         self.ctx, self.cfg = ctx, cfg
@@ -705,6 +727,13 @@ class Dataset:
         dataset keeps.  Returns (granularity SCRUB_*, bad: uint64[k, 2] of (slot, index), the lowest k = min(cap, n_bad), n_bad)."""
         first = self.first_slot if first_slot is None else first_slot
         return _scrub(self.ctx.L.cp2_dataset_scrub, self.h, first, n_slots, cap, self.ctx._ck, "cp2_dataset_scrub")
+
+    def repair_blocks(self, slot_block, data, check_only=False, cache_path=None):
+        """cp2_dataset_repair_blocks: candidate blocks (n x blockSize bytes) for (slot, block) pairs checked on the device against the
+        kept block roots; the matching ones written back into the slot files (unless check_only) and, with cache_path, the cache's
+        stamps of those files kept valid.  Returns (status: uint32[n] of REPAIR_*, n_written)."""
+        return _repair(self.ctx.L.cp2_dataset_repair_blocks, self.h, self.cfg.block_size, slot_block, data, check_only, cache_path, self.ctx._ck,
+                       "cp2_dataset_repair_blocks")
 
     def proof_inputs(self, slot_indices, entropy):
         """Batched generateProofInput for many slots of this dataset (one sampling / gather / fetch)."""
@@ -905,6 +934,11 @@ class MultiDataset:
         """cp2_multi_dataset_scrub: Dataset.scrub over every shard (cut by units: cell indices of the slot)."""
         first = 0 if first_slot is None else first_slot
         return _scrub(self.multi.L.cp2_multi_dataset_scrub, self.h, first, n_slots, cap, self.multi._ck, "cp2_multi_dataset_scrub")
+
+    def repair_blocks(self, slot_block, data, check_only=False, cache_path=None):
+        """cp2_multi_dataset_repair_blocks: Dataset.repair_blocks over every shard (slots of the whole dataset)."""
+        return _repair(self.multi.L.cp2_multi_dataset_repair_blocks, self.h, self.cfg.block_size, slot_block, data, check_only, cache_path,
+                       self.multi._ck, "cp2_multi_dataset_repair_blocks")
 
     def streamed_json(self, slot_idx):
         text, ln = ctypes.c_void_p(), ctypes.c_size_t()

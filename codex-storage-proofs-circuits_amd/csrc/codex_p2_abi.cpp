@@ -484,6 +484,8 @@ int stream_map(cp2_ctx* ctx, const uint8_t* in, size_t in_item, uint8_t* out, si
 }
 }  // namespace
 
+bool cp2i::host_array_pinned(const uint8_t* p, size_t bytes, size_t step) { return host_range_pinned(p, bytes, step); }
+
 extern "C" int cp2_permute_batch(cp2_ctx* ctx, const uint8_t* in, uint8_t* out, size_t n) try {
   if (!ctx || (n && (!in || !out))) return CP2_ERR_INVALID;
   if (n == 0) return CP2_OK;

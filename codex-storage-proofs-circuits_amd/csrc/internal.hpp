@@ -301,6 +301,9 @@ inline std::vector<size_t> layer_sizes_of(size_t n) {
 int merkle_trees_dev(cp2_ctx* ctx, const void* d_leaves, size_t n, size_t nseg, void* d_layers_out, bool leaves_in_place);
 // hash n host-resident cells into d_leaves (device, n x 32 bytes) through the pinned ingestion pipe
 int hash_host_cells_pipelined(cp2_ctx* ctx, const uint8_t* cells, size_t cell_size, size_t n, uint8_t* d_leaves);
+// is the host range [p, p + bytes) memory the copy engines read in place (hipHostMalloc'ed or hipHostRegister'ed by the caller)?  Probed
+// every `step` bytes and at the last byte, as the host-array entry points do (codex_p2_abi.cpp)
+bool host_array_pinned(const uint8_t* p, size_t bytes, size_t step);
 // the context's second (which = 1) or third (which = 2) stream, created on first use
 int aux_stream(cp2_ctx* ctx, hipStream_t* out, int which = 1);
 

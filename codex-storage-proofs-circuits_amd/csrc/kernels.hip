@@ -9,6 +9,7 @@
 //   k_sample_many, k_gather_addr, k_gen_fake_cells_many   the same across datasets (proof_many.cpp)
 //   k_verify_samples      what SampleAndProve accepts: sample_cells.circom:58-148, single_cell.circom:30-73, merkle.circom:44-114
 //   k_scrub_compare       a rebuilt layer against the kept one, mismatch bitmap + per-workgroup counts (scrub.cpp)
+//   k_repair_compare      candidate block roots against the kept rows they would replace, one verdict per request (repair.cpp)
 //
 // All global-memory field elements are 32-byte little-endian canonical integers (the ABI format).
 #include "kernels.hpp"
@@ -611,6 +612,24 @@ __global__ void __launch_bounds__(TPB) k_scrub_compare(const uint4* __restrict__
 }
 
 // ------------------------------------------------------------------------------------------------
+// Block repair (repair.cpp): lane i takes request i's freshly built block root (fresh row i, the roots of a chunk are one contiguous
+// layer) and the kept row the dataset holds for that block (row rows[i] of the kept node buffer, computed on the host from the
+// dataset's layout), two 16-byte loads a side, and writes one verdict word: 0 the roots are equal, 1 they differ.  A row at or past
+// kept_rows (never: the host validated every request) is a mismatch and is not read.
+__global__ void __launch_bounds__(TPB) k_repair_compare(const uint4* __restrict__ fresh, const uint4* __restrict__ kept, size_t kept_rows,
+                                                          const uint64_t* __restrict__ rows, size_t n, uint32_t* __restrict__ verdict) {
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t r = rows[i];
+  uint32_t v = 1;
+  if (r < kept_rows) {
+    const uint4 a0 = fresh[2 * i], a1 = fresh[2 * i + 1], b0 = kept[2 * r], b1 = kept[2 * r + 1];
+    v = ((a0.x ^ b0.x) | (a0.y ^ b0.y) | (a0.z ^ b0.z) | (a0.w ^ b0.w) | (a1.x ^ b1.x) | (a1.y ^ b1.y) | (a1.z ^ b1.z) | (a1.w ^ b1.w)) != 0;
+  }
+  verdict[i] = v;
+}
+
+// ------------------------------------------------------------------------------------------------
 // What SampleAndProve accepts (circuit/codex/sample_cells.circom:58-148, single_cell.circom:30-73, merkle.circom:44-114), checked
 // in one launch: lane t < n*ns takes sample t % ns of input t / ns from its cell felts to the slot-root comparison (index sponge,
 // leaf sponge, bottom and middle reconstructions); lane n*ns + i checks input i's slot root against its dataset root.  One byte per
@@ -925,6 +944,15 @@ hipError_t launch_scrub_compare(const void* fresh, size_t fstride, const void* k
   if (groups > MAX_BLOCKS) return hipErrorInvalidValue;
   CP2K_LAUNCH(k_scrub_compare, dim3((unsigned)groups), dim3(TPB), 0, st, (const uint4*)fresh, fstride, (const uint4*)kept, kstride, rows, total,
               (unsigned long long*)bits, counts);
+  return hipGetLastError();
+}
+
+hipError_t launch_repair_compare(const void* fresh, const void* kept, size_t kept_rows, const uint64_t* rows, size_t n, uint32_t* verdict,
+                                 hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  if (!fresh || !kept || !rows || !verdict || !fits_one_grid(n)) return hipErrorInvalidValue;
+  CP2K_LAUNCH(k_repair_compare, dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, st, (const uint4*)fresh, (const uint4*)kept, kept_rows, rows, n,
+              verdict);
   return hipGetLastError();
 }
 

@@ -62,6 +62,10 @@ inline size_t scrub_groups(size_t n_rows) { return (n_rows + SCRUB_TILE - 1) / S
 hipError_t launch_scrub_compare(const void* fresh, size_t fstride, const void* kept, size_t kstride, size_t rows, size_t n_items,
                                 uint64_t* bits, uint32_t* counts, hipStream_t st);
 
+// Block repair (repair.cpp): verdict[i] = 0 when the 32-byte row i of `fresh` equals row rows[i] of `kept` (kept_rows rows), else 1.
+hipError_t launch_repair_compare(const void* fresh, const void* kept, size_t kept_rows, const uint64_t* rows, size_t n, uint32_t* verdict,
+                                 hipStream_t st);
+
 // Proof-input verification (k_verify_samples, circuit/codex/sample_cells.circom:58-148) over n inputs that share the circuit
 // parameters.  Device arrays: prm n x 4 (nCellsPerSlot, nSlotsPerDataSet, slotIndex, shape ok), heads n x (3 + m) felts
 // (dataSetRoot, entropy, slotRoot, slotProof), cells n x ns x nf felts, paths n x ns x md felts; ok receives n x ns sample

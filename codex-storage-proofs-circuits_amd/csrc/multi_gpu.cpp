@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "trees.hpp"
+#include "repair.hpp"
 #include "exchange_policy.hpp"
 
 using namespace cp2i;
@@ -1270,6 +1271,110 @@ extern "C" int cp2_multi_dataset_scrub(cp2_multi_dataset* mds, uint64_t first_sl
                  s > 0 ? bytes / s / 1e9 : 0.0, (unsigned long long)total, level == CP2_SCRUB_CELL ? "cell" : (level == CP2_SCRUB_BLOCK ? "block" : "slot"));
   }
   return CP2_OK;
+} catch (const std::bad_alloc&) {
+  return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
+} catch (...) {
+  return CP2_ERR_INVALID;
+}
+
+// cp2_dataset_repair_blocks over the shards: every request routed to the shard that holds its block (cut by units: the unit of the block,
+// the block index unit-local), each shard's candidates checked on its own host thread and context; then the matched blocks written once
+// for all shards (two shards can hold units of one slot file: one group, one sync per file), and only then each shard's cache restamped.
+extern "C" int cp2_multi_dataset_repair_blocks(cp2_multi_dataset* mds, const uint64_t* slot_block, const uint8_t* data, size_t n, int flags,
+                                               const char* cache_path, uint32_t* status, size_t* n_written) try {
+  if (!mds) return CP2_ERR_INVALID;
+  cp2_multi* m = mds->m;
+  m->err.clear();
+  const cp2_config& c = mds->cfg;
+  const uint64_t S = mds->units_per_slot;
+  const size_t world = mds->shards.size();
+  int mode = 1;                                           // by units every node of every unit tree is resident
+  for (auto& s : mds->shards)
+    if (s.ds && repair_dataset_mode(s.ds) == 0) mode = 0;
+  std::string err;
+  if (repair_refuse(c, c.file_base != nullptr, mode, slot_block, data, n, flags, status, 0, c.n_slots, &err) != CP2_OK) {
+    m->err = err;
+    return CP2_ERR_INVALID;
+  }
+  if (n == 0) {
+    if (n_written) *n_written = 0;
+    return CP2_OK;
+  }
+  auto ctx_of = [&](size_t k) { return mds->shards[k].ds ? cp2_dataset_ctx(mds->shards[k].ds) : mds->shards[k].units->ctx; };
+  for (size_t k = 0; k < world; ++k)
+    if (ctx_of(k)->stuck) {
+      m->err = "device " + std::to_string(m->devices[mds->shards[k].dev]) + ": this context takes no further work: a multi-device exchange timed out";
+      return CP2_ERR_HIP;
+    }
+  const auto t0 = std::chrono::steady_clock::now();
+  const uint64_t per_unit = c.n_cells / (c.block_size / c.cell_size) / S;   // blocks of a unit (of the slot when S == 1)
+  std::vector<uint64_t> firsts(world), counts(world);
+  for (size_t k = 0; k < world; ++k) { firsts[k] = mds->shards[k].first; counts[k] = mds->shards[k].count; }
+  std::vector<std::vector<size_t>> reqs(world);
+  std::vector<std::vector<uint64_t>> rows(world);
+  for (size_t i = 0; i < n; ++i) {
+    const UnitBlock u = repair_unit_of(slot_block[2 * i], slot_block[2 * i + 1], S, per_unit);   // S == 1: (slot, block)
+    const size_t k = repair_shard_of(firsts, counts, u.unit);
+    if (k == world) { m->err = "repair: request " + std::to_string(i) + " lies in no shard"; return CP2_ERR_INVALID; }
+    auto& s = mds->shards[k];
+    reqs[k].push_back(i);
+    rows[k].push_back(s.ds ? repair_dataset_row(s.ds, u.unit, u.block)
+                           : repair_row_full(s.units->boff.back(), s.units->bsizes.back(), s.units->nblocks, u.unit - s.first, u.block));
+  }
+  std::vector<uint32_t> st(n);
+  std::vector<std::string> errs(world);
+  DeviceRestore restore;
+  const int rc = for_each_shard(world, [&](size_t k) -> int {
+    const std::vector<size_t>& q = reqs[k];
+    if (q.empty()) return CP2_OK;
+    auto& s = mds->shards[k];
+    cp2_ctx* ctx = ctx_of(k);
+    RepairKept kept = s.ds ? repair_dataset_kept(s.ds) : RepairKept{s.units->nodes.u8(), s.units->nodes.bytes / 32};
+    // the shard's candidates: read where they are when its requests are one run of the caller's array (q ascends), else gathered
+    const uint8_t* p = data + q.front() * c.block_size;
+    std::vector<uint8_t> gathered;
+    if (q.back() - q.front() + 1 != q.size()) {
+      gathered.resize(q.size() * c.block_size);
+      for (size_t j = 0; j < q.size(); ++j) std::memcpy(&gathered[j * c.block_size], data + q[j] * c.block_size, c.block_size);
+      p = gathered.data();
+    }
+    std::vector<uint32_t> v(q.size());
+    const int r = repair_check(ctx, kept, c.cell_size, c.block_size, p, rows[k].data(), q.size(), v.data());
+    if (r != CP2_OK) {
+      errs[k] = "device " + std::to_string(m->devices[s.dev]) + (S > 1 ? ", units " : ", slots ") + std::to_string(s.first) + ".." +
+                std::to_string(s.first + s.count) + ": " + (*cp2_last_error(ctx) ? cp2_last_error(ctx) : cp2_strerror(r));
+      return r;
+    }
+    for (size_t j = 0; j < q.size(); ++j) st[q[j]] = v[j];
+    return CP2_OK;
+  });
+  if (rc != CP2_OK) {
+    for (auto& e : errs) if (!e.empty()) { m->err = e; break; }
+    return rc;
+  }
+  size_t written_n = 0, restamped = 0;
+  int r = CP2_OK;
+  if (!(flags & CP2_REPAIR_CHECK_ONLY)) {
+    std::vector<FileStamp> written;
+    r = repair_write(mds->file_base, c.block_size, slot_block, data, n, st.data(), &written_n, &written, &err);
+    for (size_t k = 0; cache_path && !written.empty() && k < world; ++k) {   // the names cp2_multi_dataset_build_cached gives the shards' caches
+      const auto& s = mds->shards[k];
+      const std::string of = ".shard" + std::to_string(k) + "of" + std::to_string(world);
+      std::vector<std::string> paths;
+      if (S > 1) paths = {std::string(cache_path) + ".units" + std::to_string(S) + of};
+      else if (world == 1) paths = {std::string(cache_path), std::string(cache_path) + ".kept"};
+      else paths = {std::string(cache_path) + of, std::string(cache_path) + of + ".kept"};
+      std::string rerr;
+      const int rs = repair_restamp_caches(paths, c, s.count, c.n_cells / S, s.first, S, mds->file_base, written, &restamped, &rerr);
+      if (r == CP2_OK && rs != CP2_OK) { r = rs; err = rerr; }
+    }
+  }
+  std::copy(st.begin(), st.end(), status);
+  if (n_written) *n_written = written_n;
+  if (r != CP2_OK) m->err = err;
+  repair_trace("multi repair", n, status, written_n, c.block_size, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(),
+               restamped, cache_path != nullptr);
+  return r;
 } catch (const std::bad_alloc&) {
   return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
 } catch (...) {

@@ -1,0 +1,42 @@
+// Block repair shared by repair.cpp (cp2_dataset_repair_blocks) and multi_gpu.cpp (cp2_multi_dataset_repair_blocks).  Not installed.
+#pragma once
+#include <string>
+#include <vector>
+
+#include "repair_plan.hpp"
+#include "trees.hpp"
+
+namespace cp2i {
+
+// the device node buffer that holds the kept block roots (32-byte rows)
+struct RepairKept {
+  const uint8_t* nodes = nullptr;
+  size_t rows = 0;
+};
+// what a dataset keeps of its block roots: every node (its trees) or the compact layers; tree mode 1, 2, or 0 (roots only: none)
+int repair_dataset_mode(const cp2_dataset* ds);
+RepairKept repair_dataset_kept(const cp2_dataset* ds);
+// the kept row of block `block` of dataset slot `slot` (inside the local range) of a dataset of mode 1 or 2
+uint64_t repair_dataset_row(const cp2_dataset* ds, uint64_t slot, uint64_t block);
+// the checks of cp2_dataset_repair_blocks before any device or file work (validation, roots-only, fake source without CHECK_ONLY):
+// CP2_OK, or CP2_ERR_INVALID with *err naming the rule and, for a request, its index.  tree_mode 0: roots only.
+int repair_refuse(const cp2_config& cfg, bool from_file, int tree_mode, const uint64_t* slot_block, const uint8_t* data, size_t n, int flags,
+                  const uint32_t* status, uint64_t first_slot, uint64_t n_local, std::string* err);
+// n candidate blocks (host, n x block_size) hashed and reduced to their block roots on the context's device, chunk by chunk (half the
+// context's staging each), and compared with row rows[i] of `k` by k_repair_compare: status[i] = CP2_REPAIR_MATCH or _MISMATCH
+int repair_check(cp2_ctx* ctx, const RepairKept& k, size_t cell_size, size_t block_size, const uint8_t* data, const uint64_t* rows, size_t n,
+                 uint32_t* status);
+// the requests whose status is CP2_REPAIR_MATCH written into "<base><slot>.dat", grouped by file in ascending offset order, each file synced
+// once.  The first file that cannot be opened, written or synced: CP2_ERR_IO, *err "cannot write <file>: <reason>", its matched requests and
+// those of every later file CP2_REPAIR_UNWRITTEN.  *n_written counts the blocks of the files written and synced, `written` their stamps.
+int repair_write(const std::string& base, size_t block_size, const uint64_t* slot_block, const uint8_t* data, size_t n, uint32_t* status,
+                 size_t* n_written, std::vector<FileStamp>* written, std::string* err);
+// cache_restamp (trees.hpp) over each of `paths`; *restamped accumulates
+int repair_restamp_caches(const std::vector<std::string>& paths, const cp2_config& cfg, uint64_t n_items, size_t n_cells, uint64_t first_item,
+                          uint64_t units_per_slot, const std::string& base, const std::vector<FileStamp>& written, size_t* restamped,
+                          std::string* err);
+// the CP2_TRACE line of one call
+void repair_trace(const char* what, size_t n, const uint32_t* status, size_t n_written, size_t block_size, double seconds, size_t restamped,
+                  bool cache);
+
+}  // namespace cp2i

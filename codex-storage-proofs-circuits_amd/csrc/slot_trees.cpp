@@ -28,6 +28,7 @@
 #include "fake_turns.hpp"
 #include "ingest_turns.hpp"
 #include "fill_pipeline.hpp"
+#include "repair_plan.hpp"
 
 using namespace cp2i;
 
@@ -1361,6 +1362,58 @@ int cp2i::kept_load(cp2_ctx* ctx, const char* path, const KeptMeta& w, void* d_b
     CP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   return sum.finish() == h.checksum ? CP2_OK : CP2_ERR_IO;
+}
+
+// ---- stamps of a cache after a block repair (repair.cpp) ---------------------------------------------------------------------------
+int cp2i::cache_restamp(const char* path, uint64_t n_items, size_t cell_size, size_t block_size, size_t n_cells, uint64_t first_item,
+                        uint64_t units_per_slot, const std::string& base, const std::vector<FileStamp>& written, size_t* restamped,
+                        std::string* err) {
+  *restamped = 0;
+  const int fd = open(path, O_RDWR | O_NOFOLLOW | O_CLOEXEC);
+  if (fd < 0) return CP2_OK;                                      // no cache there: nothing to keep valid
+  struct Closer { int fd; ~Closer() { close(fd); } } closer{fd};
+  char magic[8] = {};
+  if (!pread_all(fd, reinterpret_cast<uint8_t*>(magic), 8, 0)) return CP2_OK;
+  uint64_t stamps_at = 0, n_stamps = 0, base_len = 0;
+  if (std::memcmp(magic, "CP2TREE3", 8) == 0) {
+    TreeFileHeader h{};
+    if (!pread_all(fd, reinterpret_cast<uint8_t*>(&h), sizeof h, 0)) return CP2_OK;
+    if (h.n_slots != n_items || h.cell_size != cell_size || h.block_size != block_size || h.n_cells != n_cells || h.src != (uint64_t)CellSrc::File ||
+        h.first_slot != first_item || h.units_per_slot != units_per_slot || h.file_base_len != base.size() || h.n_stamps != n_items)
+      return CP2_OK;
+    stamps_at = sizeof h + h.file_base_len;
+    n_stamps = h.n_stamps;
+    base_len = h.file_base_len;
+  } else if (std::memcmp(magic, "CP2KEPT1", 8) == 0) {
+    KeptFileHeader h{};
+    if (!pread_all(fd, reinterpret_cast<uint8_t*>(&h), sizeof h, 0)) return CP2_OK;
+    if (units_per_slot != 1 || h.n_slots != n_items || h.cell_size != cell_size || h.block_size != block_size || h.n_cells != n_cells ||
+        h.src != (uint64_t)CellSrc::File || h.first_slot != first_item || h.file_base_len != base.size() || h.n_stamps != n_items)
+      return CP2_OK;
+    stamps_at = sizeof h + h.file_base_len;
+    n_stamps = h.n_stamps;
+    base_len = h.file_base_len;
+  } else {
+    return CP2_OK;
+  }
+  std::string got(base_len, '\0');
+  if (base_len && !pread_all(fd, reinterpret_cast<uint8_t*>(&got[0]), base_len, (off_t)(stamps_at - base_len))) return CP2_OK;
+  if (got != base) return CP2_OK;
+  std::vector<uint64_t> stamps(2 * n_stamps);
+  if (!pread_all(fd, reinterpret_cast<uint8_t*>(stamps.data()), stamps.size() * 8, (off_t)stamps_at)) return CP2_OK;
+  const std::vector<size_t> changed = repair_restamp(stamps, first_item, units_per_slot, written);
+  if (changed.empty()) return CP2_OK;
+  for (size_t i : changed)
+    if (!pwrite_all(fd, reinterpret_cast<const uint8_t*>(&stamps[2 * i]), 16, (off_t)(stamps_at + 16 * i))) {
+      *err = std::string("cannot restamp ") + path + ": " + std::strerror(errno);
+      return CP2_ERR_IO;
+    }
+  if (fdatasync(fd) != 0) {
+    *err = std::string("cannot sync ") + path + ": " + std::strerror(errno);
+    return CP2_ERR_IO;
+  }
+  *restamped = changed.size();
+  return CP2_OK;
 }
 
 // trees loaded from a cache that were built from caller memory have no cell source until one is attached

@@ -84,6 +84,16 @@ struct KeptMeta {
 int kept_save(cp2_ctx* ctx, const char* path, const KeptMeta& meta, const void* d_buf, size_t bytes);
 int kept_load(cp2_ctx* ctx, const char* path, const KeptMeta& want, void* d_buf, size_t bytes);
 
+// Block repair (repair.cpp): the per-item (size, mtime_ns) stamps of the cache file at `path` -- a tree cache ("CP2TREE3") or a kept
+// file ("CP2KEPT1") -- that describes exactly these items of slot-file data (magic, geometry, SlotFile source, first item, units per
+// slot, base name): the stamps of items whose file this call wrote are set to the file's stat after the writes, where they equalled its
+// stat before the first write (repair_restamp, repair_plan.hpp), with pwrite and fdatasync in place.  Stamps sit outside the checksum.
+// *restamped = how many stamps changed; a file that does not describe these items is left alone (CP2_OK, 0).  CP2_ERR_IO when a file
+// that does describe them cannot be rewritten.
+struct FileStamp;
+int cache_restamp(const char* path, uint64_t n_items, size_t cell_size, size_t block_size, size_t n_cells, uint64_t first_item,
+                  uint64_t units_per_slot, const std::string& base, const std::vector<FileStamp>& written, size_t* restamped, std::string* err);
+
 // After cp2_dataset_set_roots*: do rows [first_slot, first_slot + n_local) of the dataset tree's bottom layer hold THIS dataset's own
 // slot roots?  One small download.  The multi-device exchange is verified with it (multi_gpu.cpp).
 int dataset_own_roots_in_place(cp2_dataset* ds, bool* ok);

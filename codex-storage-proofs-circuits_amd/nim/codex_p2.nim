@@ -73,6 +73,12 @@ proc cp2_dataset_scrub(ds: Cp2Dataset, firstSlot, nSlots: uint64, bad: ptr uint6
                        granularity: ptr cint): cint {.importc.}
 proc cp2_multi_dataset_scrub(ds: Cp2MultiDataset, firstSlot, nSlots: uint64, bad: ptr uint64, cap: csize_t, nBad: ptr csize_t,
                              granularity: ptr cint): cint {.importc.}
+# repair: candidate blocks checked against the kept block roots, the matching ones written back; slotBlock = n x (slot, block),
+# data = n x blockSize bytes, flags CP2_REPAIR_CHECK_ONLY, status = n x CP2_REPAIR_*
+proc cp2_dataset_repair_blocks(ds: Cp2Dataset, slotBlock: ptr uint64, data: ptr byte, n: csize_t, flags: cint, cachePath: cstring,
+                               status: ptr uint32, nWritten: ptr csize_t): cint {.importc.}
+proc cp2_multi_dataset_repair_blocks(ds: Cp2MultiDataset, slotBlock: ptr uint64, data: ptr byte, n: csize_t, flags: cint,
+                                     cachePath: cstring, status: ptr uint32, nWritten: ptr csize_t): cint {.importc.}
 proc cp2_proof_input_write_json(p: Cp2ProofInput, path: cstring): cint {.importc.}
 proc cp2_proof_input_roots(p: Cp2ProofInput, datasetRoot, slotRoot, entropy: ptr byte): cint {.importc.}
 proc cp2_proof_input_nsamples(p: Cp2ProofInput): csize_t {.importc.}

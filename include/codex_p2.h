@@ -41,8 +41,9 @@ extern "C" {
  * History: 1.0 = the 105 entry points of round 5 + this function + cp2_set_ingest's two rings (round 6).
  *          1.1 = + cp2_proof_input_parse_json, _shape, _cell_felts and cp2_proof_inputs_verify (verification).
  *          1.2 = + cp2_proof_inputs_generate_many and cp2_proof_inputs_export_many (proof inputs across datasets).
- *          next: + cp2_dataset_scrub and cp2_multi_dataset_scrub (scrub).  MINOR stays 2 until the release that carries them: the
- *                bump to 1.3 goes in its own commit with that release.                                                               */
+ *          next: + cp2_dataset_scrub and cp2_multi_dataset_scrub (scrub), cp2_dataset_repair_blocks and
+ *                cp2_multi_dataset_repair_blocks (repair).  MINOR stays 2 until the release that carries them: the bump to 1.3 goes in
+ *                its own commit with that release.                                                                                   */
 #define CP2_ABI_VERSION_MAJOR 1
 #define CP2_ABI_VERSION_MINOR 2
 #define CP2_ABI_VERSION ((CP2_ABI_VERSION_MAJOR << 16) | CP2_ABI_VERSION_MINOR)
@@ -478,6 +479,48 @@ int cp2_proof_inputs_verify(cp2_ctx* ctx, const cp2_proof_input* const* ps, size
 int cp2_dataset_scrub(cp2_dataset* ds, uint64_t first_slot, uint64_t n_slots, uint64_t* bad /* cap x 2: (slot, index) */, size_t cap,
                       size_t* n_bad, int* granularity);
 
+/* ---- repair: replacement blocks checked against the kept block roots, then written back ----------------------------------------
+ * A scrub names the network blocks whose data no longer hashes to what the dataset keeps; the node fetches or re-decodes them (erasure
+ * decoding is the caller's) and hands the candidates in here.  Each candidate is checked ALONE, on the device, against the block root the
+ * dataset keeps for that block (every node kept: the block-tree root layer; compact: layer 0 of the compact layers): its cells are hashed
+ * and reduced to a block root exactly as the builders do, one verdict per request.  Only candidates that match are written.
+ *   Requests   slot_block (n x 2 uint64: dataset slot inside the local range, block of the slot < nBlocks), data (n x blockSize bytes,
+ *              request i at i x blockSize).  Pageable or large buffers go through the context's pinned ring in chunks, upload and
+ *              hashing overlapped; caller-pinned buffers (hipHostMalloc / hipHostRegister) are read in place.  A batch larger than half
+ *              the context's staging (CODEX_P2_STAGE_MB) runs in several chunks.
+ *   Refused    before any device or file work, CP2_ERR_INVALID with the request index (where there is one) in cp2_last_error: a NULL
+ *              handle; NULL slot_block, data or status when n > 0; a slot outside the local range; a block >= nBlocks; the same (slot,
+ *              block) twice; an unknown flag; a roots-only dataset (it keeps no block roots: write the slot whole, then rebuild or
+ *              scrub it); a fake-source dataset without CP2_REPAIR_CHECK_ONLY (it has no files).  A refused call leaves status,
+ *              *n_written, the files and the cache untouched.  n == 0: CP2_OK.  A context whose stream will not drain is refused
+ *              (CP2_ERR_HIP).
+ *   Result     status[i] = CP2_REPAIR_MATCH (hashes to the kept block root; written unless CP2_REPAIR_CHECK_ONLY), _MISMATCH (differs;
+ *              never written) or _UNWRITTEN (matched, but its file could not be written or synced); *n_written = the blocks written
+ *              and synced (n_written may be NULL).  A wrong candidate is not an error: CP2_OK.
+ *   Write      each matching block with pwrite to "<base><slot>.dat" at block x blockSize, grouped by file in ascending offset order,
+ *              every file fdatasync'ed once after its last write.  A missing file is created (mode 0644 before umask); a write past
+ *              the end extends the file, and a hole left before it reads as zeros, which the next scrub reports.  The first file that
+ *              cannot be opened, written or synced stops the writing: CP2_ERR_IO, "cannot write <file>: <reason>"; the blocks of
+ *              earlier files stay written (and counted), the matched blocks of that file and of every later one are _UNWRITTEN.  A
+ *              write is not atomic: a block torn by a crash shows up in the next scrub.
+ *   Cache      cache_path (may be NULL): after every write and sync, the (size, mtime) stamps in whichever of <cache_path> and
+ *              <cache_path>.kept describe this dataset (magic, geometry, source, first slot, base name) are set, in place (pwrite +
+ *              fdatasync), for the files this call wrote -- only where the stamp equalled that file's stat before the call's first
+ *              write: when the damage itself changed the mtime the cache was stale and stays stale.  The next
+ *              cp2_dataset_build_cached then loads the cache instead of rebuilding.  Stamps lie outside the node checksum: a torn
+ *              restamp costs a rebuild, nothing more.
+ *   Unchanged  the kept nodes, the dataset tree, the mode and the bodies of a streamed build: the proof inputs and input.json files of
+ *              clean slots stay byte-identical, and one that failed with CP2_ERR_IO on a damaged block is, after a matching repair,
+ *              the one from before the damage.  CP2_TRACE prints one line per call (requests, matched, written, bytes, seconds,
+ *              whether the cache was restamped). */
+#define CP2_REPAIR_CHECK_ONLY 1      /* flag: verdicts only, nothing written */
+#define CP2_REPAIR_MATCH      0      /* status: hashes to the kept block root; written unless CHECK_ONLY */
+#define CP2_REPAIR_MISMATCH   1      /* status: differs from the kept block root; not written */
+#define CP2_REPAIR_UNWRITTEN  2      /* status: matched, but its file could not be written or synced (call returns CP2_ERR_IO) */
+int cp2_dataset_repair_blocks(cp2_dataset* ds, const uint64_t* slot_block /* n x 2: dataset slot, block of the slot */,
+                              const uint8_t* data /* n x block_size */, size_t n, int flags, const char* cache_path,
+                              uint32_t* status /* n */, size_t* n_written);
+
 /* replaces `writeCircomMainComponent`, reference/nim/proof_input/src/cli.nim:186-204 */
 int cp2_write_circom_main(const cp2_config* cfg, const char* path);
 
@@ -578,6 +621,13 @@ int cp2_multi_dataset_streamed_json(cp2_multi_dataset* mds, uint64_t slot_idx, c
 int cp2_multi_dataset_scrub(cp2_multi_dataset* mds, uint64_t first_slot, uint64_t n_slots, uint64_t* bad, size_t cap, size_t* n_bad,
                             int* granularity);
 
+/* cp2_dataset_repair_blocks over the shards: slots of the whole dataset (0 .. n_slots - 1); each request goes to the shard that holds
+ * its block (cut by units: the unit holding the block), each shard checks its candidates on its own host thread and context, and the
+ * statuses come back in request order.  The matched blocks are written once all shards have checked (units of one slot share its file:
+ * one sync per file), and only then is every shard's cache restamped under the names cp2_multi_dataset_build_cached gives them
+ * ("<cache_path>.shardIofW", "<cache_path>.unitsS.shardIofW"; one shard: <cache_path> and <cache_path>.kept). */
+int cp2_multi_dataset_repair_blocks(cp2_multi_dataset* mds, const uint64_t* slot_block, const uint8_t* data, size_t n, int flags,
+                                    const char* cache_path, uint32_t* status, size_t* n_written);
 #ifdef __cplusplus
 }
 #endif
