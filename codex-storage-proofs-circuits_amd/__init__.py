@@ -365,6 +365,9 @@ class Context:
         self._ck(self.L.cp2_sponge2_felts_batch(self.h, _p(f), nf, nitems, _p(out)), "cp2_sponge2_felts_batch")
         return out
 
+    def sponge2_felts_batch_dev(self, d_felts, nf, nitems, d_out):
+        self._ck(self.L.cp2_sponge2_felts_batch_dev(self.h, ctypes.c_void_p(d_felts), nf, nitems, ctypes.c_void_p(d_out)), "cp2_sponge2_felts_batch_dev")
+
     # -- a4
     def bytes_to_felts(self, data):
         d = _u8(np.frombuffer(bytes(data), dtype=np.uint8))
