@@ -218,6 +218,10 @@ def load_library():
         "cp2_multi_dataset_scrub": (i32, [vp, u64, u64, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_int)]),
         "cp2_dataset_repair_blocks": (i32, [vp, vp, vp, sz, i32, cp, vp, ctypes.POINTER(sz)]),
         "cp2_multi_dataset_repair_blocks": (i32, [vp, vp, vp, sz, i32, cp, vp, ctypes.POINTER(sz)]),
+        "cp2_block_proof_depth": (sz, [sz, sz, sz]),
+        "cp2_dataset_block_proofs": (i32, [vp, vp, sz, vp, vp]),
+        "cp2_blocks_verify": (i32, [vp, sz, sz, sz, vp, sz, vp, vp, vp, sz, vp, vp]),
+        "cp2_dataset_repair_blocks_proved": (i32, [vp, vp, vp, vp, sz, i32, cp, vp, ctypes.POINTER(sz)]),
     }
     for name, (res, args) in sigs.items():
         if v is None and name == "cp2_abi_version":
@@ -331,6 +335,21 @@ class Context:
 
     def set_body_budget(self, max_resident_bytes=0, spill_dir=None):
         self._ck(self.L.cp2_set_body_budget(self.h, max_resident_bytes, spill_dir.encode() if spill_dir else None), "cp2_set_body_budget")
+
+    def blocks_verify(self, cell_size, block_size, n_cells, slot_roots, root_block, data, paths, want_roots=True):
+        """cp2_blocks_verify: candidate blocks (n x block_size bytes) with their Merkle paths (uint8[n, depth, 32]) checked against the
+        stated slot roots; root_block = (index into slot_roots, block of the slot) pairs.  Returns (status: uint32[n] of BLOCK_*,
+        block_roots: uint8[n, 32] or None)."""
+        r = _u8(slot_roots).reshape(-1, 32)
+        rb = np.ascontiguousarray(np.asarray(root_block, dtype=np.uint64).reshape(-1, 2))
+        n = rb.shape[0]
+        d, p = _candidates("block verify", data, n, block_size, paths, block_proof_depth(cell_size, block_size, n_cells))
+        status = np.empty(n, dtype=np.uint32)
+        roots = np.empty((n, 32), dtype=np.uint8) if want_roots else None
+        self._ck(self.L.cp2_blocks_verify(self.h, cell_size, block_size, n_cells, _p(r) if r.size else None, r.shape[0], _p(rb) if n else None,
+                                          _p(d) if n else None, _p(p) if n else None, n, _p(status) if n else None,
+                                          _p(roots) if want_roots and n else None), "cp2_blocks_verify")
+        return status, roots
 
     # -- a1
     def permute_batch(self, states, out=None):
@@ -624,6 +643,25 @@ def _repair(fn, h, block_size, slot_block, data, check_only, cache_path, ck, whe
     return status, written.value
 
 
+BLOCK_MATCH, BLOCK_MISMATCH = 0, 1                # CP2_BLOCK_* (include/codex_p2.h): the verdicts of cp2_blocks_verify
+
+
+def block_proof_depth(cell_size, block_size, n_cells):
+    """cp2_block_proof_depth: siblings in the proof of one network block (0: a geometry the tree builders refuse); host only"""
+    return load_library().cp2_block_proof_depth(cell_size, block_size, n_cells)
+
+
+def _candidates(what, data, n, block_size, paths, depth):
+    """the candidate bytes without a copy (see _repair) and the paths as uint8[n, depth, 32]"""
+    d = np.ascontiguousarray(data) if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
+    if d.nbytes != n * block_size:
+        raise ValueError("%s: %d request(s) need %d bytes of candidates, got %d" % (what, n, n * block_size, d.nbytes))
+    p = _u8(paths)
+    if p.size != n * depth * 32:
+        raise ValueError("%s: %d request(s) need %d bytes of paths (depth %d), got %d" % (what, n, n * depth * 32, depth, p.size))
+    return d, p
+
+
 class Dataset:
     def __init__(self, ctx, cfg, first_slot, n_local, cache=None, streamed=None):
         self.ctx, self.cfg = ctx, cfg
@@ -737,6 +775,35 @@ class Dataset:
         stamps of those files kept valid.  Returns (status: uint32[n] of REPAIR_*, n_written)."""
         return _repair(self.ctx.L.cp2_dataset_repair_blocks, self.h, self.cfg.block_size, slot_block, data, check_only, cache_path, self.ctx._ck,
                        "cp2_dataset_repair_blocks")
+
+    @property
+    def block_proof_depth(self):
+        return block_proof_depth(self.cfg.cell_size, self.cfg.block_size, self.cfg.n_cells)
+
+    def block_proofs(self, slot_block):
+        """cp2_dataset_block_proofs: (block_roots: uint8[n, 32], paths: uint8[n, depth, 32]) of (slot, block) pairs, from what the dataset
+        keeps (every node or the compact layers; a roots-only dataset refuses)."""
+        sb = np.ascontiguousarray(np.asarray(slot_block, dtype=np.uint64).reshape(-1, 2))
+        n, depth = sb.shape[0], self.block_proof_depth
+        roots = np.empty((n, 32), dtype=np.uint8)
+        paths = np.empty((n, depth, 32), dtype=np.uint8)
+        self.ctx._ck(self.ctx.L.cp2_dataset_block_proofs(self.h, _p(sb) if n else None, n, _p(roots) if n else None, _p(paths) if n else None),
+                     "cp2_dataset_block_proofs")
+        return roots, paths
+
+    def repair_blocks_proved(self, slot_block, data, paths, check_only=False, cache_path=None):
+        """cp2_dataset_repair_blocks_proved: repair_blocks with the Merkle path (uint8[n, depth, 32]) of every candidate, checked against the
+        dataset's slot roots: works in every residency mode.  Returns (status: uint32[n] of REPAIR_*, n_written)."""
+        sb = np.ascontiguousarray(np.asarray(slot_block, dtype=np.uint64).reshape(-1, 2))
+        n = sb.shape[0]
+        d, p = _candidates("repair", data, n, self.cfg.block_size, paths, self.block_proof_depth)
+        status = np.empty(n, dtype=np.uint32)
+        written = ctypes.c_size_t()
+        self.ctx._ck(self.ctx.L.cp2_dataset_repair_blocks_proved(self.h, _p(sb) if n else None, _p(d) if n else None, _p(p) if n else None, n,
+                                                                 REPAIR_CHECK_ONLY if check_only else 0, cache_path.encode() if cache_path else None,
+                                                                 _p(status) if n else None, ctypes.byref(written)),
+                     "cp2_dataset_repair_blocks_proved")
+        return status, written.value
 
     def proof_inputs(self, slot_indices, entropy):
         """Batched generateProofInput for many slots of this dataset (one sampling / gather / fetch)."""

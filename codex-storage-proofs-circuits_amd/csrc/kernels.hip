@@ -10,6 +10,7 @@
 //   k_verify_samples      what SampleAndProve accepts: sample_cells.circom:58-148, single_cell.circom:30-73, merkle.circom:44-114
 //   k_scrub_compare       a rebuilt layer against the kept one, mismatch bitmap + per-workgroup counts (scrub.cpp)
 //   k_repair_compare      candidate block roots against the kept rows they would replace, one verdict per request (repair.cpp)
+//   k_block_path_roots    a13 candidate block roots walked up their Merkle paths to the slot root, merkle.nim:51-74 (block_proofs.cpp)
 //
 // All global-memory field elements are 32-byte little-endian canonical integers (the ABI format).
 #include "kernels.hpp"
@@ -766,6 +767,54 @@ __global__ void __launch_bounds__(TPB) k_verify_samples(VerifyGeom g, const uint
 }
 
 // ------------------------------------------------------------------------------------------------
+// Block proofs (block_proofs.cpp): lane i takes request i's freshly built block root (fresh row i, where k_repair_compare reads it), its
+// (slot root index, block) pair and its path of `depth` siblings, and runs reconstructRoot (merkle.nim:51-74) up to the slot root: the
+// schedule of block_proof_schedule (block_proof_plan.hpp) -- running index j, layer size m; the node goes right where j is odd, the key
+// is (level 0 ? 1 : 0) + 2 where j is the even last node of its layer -- with left / right by limb masks and the key by arithmetic, one
+// permutation per level.  The result is compared with slot_roots[root] as canonical words; one verdict word: 0 equal, 1 not.  depth is
+// uniform over the launch, j and m are per lane.  The host validated every request (root < n_roots, block < n_blocks).  roots_out (may be
+// NULL) receives the block root each candidate hashed to.
+__global__ void __launch_bounds__(TPB) k_block_path_roots(const uint4* __restrict__ fresh, const uint4* __restrict__ paths,
+                                                            const uint64_t* __restrict__ root_block, const uint4* __restrict__ slot_roots,
+                                                            uint64_t n_blocks, uint32_t depth, size_t n, uint32_t* __restrict__ verdict,
+                                                            uint4* __restrict__ roots_out) {
+  __shared__ fr::QTab qtab;
+  fr::qtab_fill(qtab, threadIdx.x, TPB);
+  __syncthreads();
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  const uint4 f0 = fresh[2 * i], f1 = fresh[2 * i + 1];
+  if (roots_out) {
+    roots_out[2 * i] = f0;
+    roots_out[2 * i + 1] = f1;
+  }
+  const uint32_t fw[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
+  Fe cur = fr::to_mont(fr::from_words(fw));
+  const uint4* path = paths + 2 * i * depth;
+  uint64_t j = root_block[2 * i + 1], m = n_blocks;
+  State s;
+#pragma unroll 1
+  for (uint32_t lvl = 0; lvl < depth; ++lvl) {
+    const Fe sib = load_fe_canonical(path + 2 * lvl);
+    const uint32_t b = (uint32_t)j & 1u;
+    const uint32_t key = (lvl == 0 ? 1u : 0u) + 2u * ((j == m - 1 ? 1u : 0u) & (b ^ 1u));
+    const uint32_t sw = 0u - b;
+#pragma unroll
+    for (int l = 0; l < fr::NL; ++l) {
+      s.x.l[l] = (cur.l[l] & ~sw) | (sib.l[l] & sw);
+      s.y.l[l] = (sib.l[l] & ~sw) | (cur.l[l] & sw);
+    }
+    s.z = key_fe(key);
+    p2::permute(s, qtab);
+    cur = fr::norm(s.x);
+    j >>= 1;
+    m = (m + 1) >> 1;
+  }
+  const Fe want = load_fe_canonical(slot_roots + 2 * root_block[2 * i]);
+  verdict[i] = fe_equal(cur, want) ? 0u : 1u;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Workgroups for n work items.  A grid holds at most 2^31 - 1 workgroups in x; the per-item kernels are launched in slices of
 // at most MAX_ITEMS items (every item is independent and addressed from a base pointer), the layer / sampling kernels, whose
 // item index is decomposed inside the kernel, refuse what does not fit one grid (2^38 nodes: far beyond any HBM).
@@ -954,6 +1003,20 @@ hipError_t launch_repair_compare(const void* fresh, const void* kept, size_t kep
   CP2K_LAUNCH(k_repair_compare, dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, st, (const uint4*)fresh, (const uint4*)kept, kept_rows, rows, n,
               verdict);
   return hipGetLastError();
+}
+
+hipError_t launch_block_path_roots(const void* fresh, const void* paths, const uint64_t* root_block, const void* slot_roots, uint64_t n_blocks,
+                                   uint32_t depth, size_t n, uint32_t* verdict, void* roots_out, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  if (!fresh || !paths || !root_block || !slot_roots || !verdict || depth == 0 || n_blocks == 0) return hipErrorInvalidValue;
+  for (size_t i0 = 0; i0 < n; i0 += MAX_ITEMS) {
+    const size_t m = n - i0 < MAX_ITEMS ? n - i0 : MAX_ITEMS;
+    CP2K_LAUNCH(k_block_path_roots, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)fresh + 2 * i0, (const uint4*)paths + 2 * i0 * depth,
+                root_block + 2 * i0, (const uint4*)slot_roots, n_blocks, depth, m, verdict + i0, roots_out ? (uint4*)roots_out + 2 * i0 : nullptr);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 hipError_t launch_verify_samples(const VerifyGeom& g, const uint64_t* prm, const void* heads, const void* cells, const void* paths,

@@ -66,6 +66,13 @@ hipError_t launch_scrub_compare(const void* fresh, size_t fstride, const void* k
 hipError_t launch_repair_compare(const void* fresh, const void* kept, size_t kept_rows, const uint64_t* rows, size_t n, uint32_t* verdict,
                                  hipStream_t st);
 
+// Block proofs (block_proofs.cpp, k_block_path_roots): request i < n = the 32-byte row i of `fresh` (a candidate's block root), the pair
+// root_block[2 i], root_block[2 i + 1] (index into slot_roots, block of the slot; validated by the host) and `depth` canonical siblings
+// at paths + i * depth * 32.  reconstructRoot (merkle.nim:51-74) over n_blocks leaves; verdict[i] = 0 when the result equals
+// slot_roots[root] as a field element, else 1; roots_out (may be NULL) receives n x 32 bytes, the rows of `fresh`.
+hipError_t launch_block_path_roots(const void* fresh, const void* paths, const uint64_t* root_block, const void* slot_roots, uint64_t n_blocks,
+                                   uint32_t depth, size_t n, uint32_t* verdict, void* roots_out, hipStream_t st);
+
 // Proof-input verification (k_verify_samples, circuit/codex/sample_cells.circom:58-148) over n inputs that share the circuit
 // parameters.  Device arrays: prm n x 4 (nCellsPerSlot, nSlotsPerDataSet, slotIndex, shape ok), heads n x (3 + m) felts
 // (dataSetRoot, entropy, slotRoot, slotProof), cells n x ns x nf felts, paths n x ns x md felts; ok receives n x ns sample

@@ -44,6 +44,24 @@ bool stat_stamp(const std::string& path, uint64_t out[2]) {
 int cp2i::repair_check(cp2_ctx* ctx, const RepairKept& k, size_t cell_size, size_t block_size, const uint8_t* data, const uint64_t* rows,
                        size_t n, uint32_t* status) {
   if (n == 0) return CP2_OK;
+  DevBuf d_rows;                                     // (goes after the streams have drained: DevBuf::release)
+  RepairJudge judge;
+  judge.begin = [&](size_t) -> int {
+    CP2_TRY(d_rows.scratch(ctx, n * 8));
+    CP2_HIP(ctx, hipMemcpyAsync(d_rows.p, rows, n * 8, hipMemcpyHostToDevice, ctx->stream));
+    return CP2_OK;
+  };
+  // each root against the kept row of its request
+  judge.verdicts = [&](const uint8_t* fresh, size_t c0, size_t m, uint32_t* verdict, hipStream_t st) -> int {
+    CP2_HIP(ctx, cp2k::launch_repair_compare(fresh, k.nodes, k.rows, static_cast<const uint64_t*>(d_rows.p) + c0, m, verdict, st));
+    return CP2_OK;
+  };
+  return repair_check_with(ctx, cell_size, block_size, data, n, status, judge);
+}
+
+int cp2i::repair_check_with(cp2_ctx* ctx, size_t cell_size, size_t block_size, const uint8_t* data, size_t n, uint32_t* status,
+                            const RepairJudge& judge) {
+  if (n == 0) return CP2_OK;
   CP2_REFUSE_STUCK(ctx);
   CP2_HIP(ctx, hipSetDevice(ctx->device));
   const size_t cpb = block_size / cell_size;
@@ -56,13 +74,12 @@ int cp2i::repair_check(cp2_ctx* ctx, const RepairKept& k, size_t cell_size, size
   // requests per chunk: half the context's staging in candidate bytes (the node buffer of a chunk holds about as much again)
   const size_t chunk = std::max<size_t>(1, std::min<size_t>(n, (ctx->stage_bytes / 2) / block_size));
   const bool pinned = host_array_pinned(data, n * block_size, PIECE_BYTES);
-  DevBuf d_rows, d_verdict, d_nodes, d_cells;        // (device buffers go after every stream has drained: DevBuf::release)
-  CP2_TRY(d_rows.scratch(ctx, n * 8));
+  DevBuf d_verdict, d_nodes, d_cells;                // (device buffers go after every stream has drained: DevBuf::release)
+  if (judge.begin) CP2_TRY(judge.begin(chunk));
   CP2_TRY(d_verdict.scratch(ctx, n * 4));
   CP2_TRY(d_nodes.scratch(ctx, chunk * per_block * 32));
   const size_t last = n - (n - 1) / chunk * chunk;   // requests of the last chunk
   if (pinned || chunk * block_size <= SMALL_BYTES || last * block_size <= SMALL_BYTES) CP2_TRY(d_cells.scratch(ctx, chunk * block_size));
-  CP2_HIP(ctx, hipMemcpyAsync(d_rows.p, rows, n * 8, hipMemcpyHostToDevice, ctx->stream));
   hipStream_t aux = nullptr, copy = nullptr;
   hipEvent_t ready = nullptr, up = nullptr, aux_done = nullptr;
   struct Guard {
@@ -109,10 +126,11 @@ int cp2i::repair_check(cp2_ctx* ctx, const RepairKept& k, size_t cell_size, size
       CP2_HIP(ctx, hipMemcpyAsync(d_cells.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
       CP2_HIP(ctx, cp2k::launch_hash_cells(d_cells.p, cell_size, m * cpb, d_nodes.p, ctx->stream));
     }
-    // the block trees of the chunk (segment = block, layer-major), then each root against the kept row of its request
+    // what the verdicts of this chunk read beside its roots, queued behind the hashing; the block trees of the chunk (segment = block,
+    // layer-major); then the verdicts of its requests from the root layer
+    if (judge.stage) CP2_TRY(judge.stage(c0, m, ctx->stream));
     CP2_TRY(merkle_trees_dev(ctx, d_nodes.p, cpb, m, d_nodes.p, true));
-    CP2_HIP(ctx, cp2k::launch_repair_compare(d_nodes.u8() + below_root * m * 32, k.nodes, k.rows, static_cast<const uint64_t*>(d_rows.p) + c0, m,
-                                             static_cast<uint32_t*>(d_verdict.p) + c0, ctx->stream));
+    CP2_TRY(judge.verdicts(d_nodes.u8() + below_root * m * 32, c0, m, static_cast<uint32_t*>(d_verdict.p) + c0, ctx->stream));
   }
   std::vector<uint32_t> v(n);
   CP2_HIP(ctx, hipMemcpyAsync(v.data(), d_verdict.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));

@@ -1,5 +1,6 @@
 // Block repair shared by repair.cpp (cp2_dataset_repair_blocks) and multi_gpu.cpp (cp2_multi_dataset_repair_blocks).  Not installed.
 #pragma once
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -26,6 +27,18 @@ int repair_refuse(const cp2_config& cfg, bool from_file, int tree_mode, const ui
 // context's staging each), and compared with row rows[i] of `k` by k_repair_compare: status[i] = CP2_REPAIR_MATCH or _MISMATCH
 int repair_check(cp2_ctx* ctx, const RepairKept& k, size_t cell_size, size_t block_size, const uint8_t* data, const uint64_t* rows, size_t n,
                  uint32_t* status);
+// The same data path with the last step given by the caller (block_proofs.cpp walks each root up its Merkle path instead of comparing
+// it with a kept row).  begin (may be empty): once, before any chunk, with the number of requests a chunk holds at most, for what the call needs on the
+// device (queued on the context's stream).  stage (may be empty): per chunk of requests [c0, c0 + m), queued on `st` behind the chunk's hashing and before its
+// block trees: what the verdicts of that chunk read beside the roots.  verdicts: queued on `st` behind the chunk's block trees; `fresh`
+// holds the chunk's m block roots (32-byte rows, request c0 + i at row i), verdict[i] receives 0 for a match, anything else for a
+// mismatch.  Everything the callbacks allocate must outlive the call (it ends with the stream drained).
+struct RepairJudge {
+  std::function<int(size_t chunk)> begin;
+  std::function<int(size_t c0, size_t m, hipStream_t st)> stage;
+  std::function<int(const uint8_t* fresh, size_t c0, size_t m, uint32_t* verdict, hipStream_t st)> verdicts;
+};
+int repair_check_with(cp2_ctx* ctx, size_t cell_size, size_t block_size, const uint8_t* data, size_t n, uint32_t* status, const RepairJudge& judge);
 // the requests whose status is CP2_REPAIR_MATCH written into "<base><slot>.dat", grouped by file in ascending offset order, each file synced
 // once.  The first file that cannot be opened, written or synced: CP2_ERR_IO, *err "cannot write <file>: <reason>", its matched requests and
 // those of every later file CP2_REPAIR_UNWRITTEN.  *n_written counts the blocks of the files written and synced, `written` their stamps.

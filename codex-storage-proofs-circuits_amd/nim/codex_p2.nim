@@ -79,6 +79,14 @@ proc cp2_dataset_repair_blocks(ds: Cp2Dataset, slotBlock: ptr uint64, data: ptr 
                                status: ptr uint32, nWritten: ptr csize_t): cint {.importc.}
 proc cp2_multi_dataset_repair_blocks(ds: Cp2MultiDataset, slotBlock: ptr uint64, data: ptr byte, n: csize_t, flags: cint,
                                      cachePath: cstring, status: ptr uint32, nWritten: ptr csize_t): cint {.importc.}
+# block proofs: merkleProof(bigTree, block) served from what a dataset keeps, candidates + paths checked against bare slot roots
+# (rootBlock = n x (index into slotRoots, block), status = n x CP2_BLOCK_*), and repair with a path beside every candidate
+proc cp2_block_proof_depth(cellSize, blockSize, nCells: csize_t): csize_t {.importc.}
+proc cp2_dataset_block_proofs(ds: Cp2Dataset, slotBlock: ptr uint64, n: csize_t, blockRoots, paths: ptr byte): cint {.importc.}
+proc cp2_blocks_verify(ctx: Cp2Ctx, cellSize, blockSize, nCells: csize_t, slotRoots: ptr byte, nRoots: csize_t, rootBlock: ptr uint64,
+                       data, paths: ptr byte, n: csize_t, status: ptr uint32, blockRoots: ptr byte): cint {.importc.}
+proc cp2_dataset_repair_blocks_proved(ds: Cp2Dataset, slotBlock: ptr uint64, data, paths: ptr byte, n: csize_t, flags: cint,
+                                      cachePath: cstring, status: ptr uint32, nWritten: ptr csize_t): cint {.importc.}
 proc cp2_proof_input_write_json(p: Cp2ProofInput, path: cstring): cint {.importc.}
 proc cp2_proof_input_roots(p: Cp2ProofInput, datasetRoot, slotRoot, entropy: ptr byte): cint {.importc.}
 proc cp2_proof_input_nsamples(p: Cp2ProofInput): csize_t {.importc.}

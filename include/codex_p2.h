@@ -42,8 +42,9 @@ extern "C" {
  *          1.1 = + cp2_proof_input_parse_json, _shape, _cell_felts and cp2_proof_inputs_verify (verification).
  *          1.2 = + cp2_proof_inputs_generate_many and cp2_proof_inputs_export_many (proof inputs across datasets).
  *          next: + cp2_dataset_scrub and cp2_multi_dataset_scrub (scrub), cp2_dataset_repair_blocks and
- *                cp2_multi_dataset_repair_blocks (repair).  MINOR stays 2 until the release that carries them: the bump to 1.3 goes in
- *                its own commit with that release.                                                                                   */
+ *                cp2_multi_dataset_repair_blocks (repair), cp2_block_proof_depth, cp2_dataset_block_proofs, cp2_blocks_verify and
+ *                cp2_dataset_repair_blocks_proved (block proofs).  MINOR stays 2 until the release that carries them: the bump to 1.3
+ *                goes in its own commit with that release.                                                                           */
 #define CP2_ABI_VERSION_MAJOR 1
 #define CP2_ABI_VERSION_MINOR 2
 #define CP2_ABI_VERSION ((CP2_ABI_VERSION_MAJOR << 16) | CP2_ABI_VERSION_MINOR)
@@ -520,6 +521,66 @@ int cp2_dataset_scrub(cp2_dataset* ds, uint64_t first_slot, uint64_t n_slots, ui
 int cp2_dataset_repair_blocks(cp2_dataset* ds, const uint64_t* slot_block /* n x 2: dataset slot, block of the slot */,
                               const uint8_t* data /* n x block_size */, size_t n, int flags, const char* cache_path,
                               uint32_t* status /* n */, size_t* n_written);
+
+/* ---- block proofs: network blocks proved and checked against slot roots with Merkle paths ----------------------------------------
+ * Scrub and repair rest on the block roots a dataset keeps.  A node that receives blocks of a slot it has no tree for knows only the slot
+ * root (from the manifest); what a peer can send with a 64 KiB block is the block's Merkle path to that root.  The proof of block b of a
+ * slot of nBlocks = nCells / (blockSize / cellSize) blocks is merkleProof(bigTree, b) (reference/nim/proof_input/src/merkle.nim:21-42):
+ * leaf = the block root (the root of the block tree over the block's cell hashes), numberOfLeaves = nBlocks, path = one sibling per
+ * layer of the tree over the slot's block roots, bottom first, ZERO where the sibling is out of range (an odd layer's last node, the
+ * singleton).  Its length is cp2_block_proof_depth = cp2_merkle_num_layers(nBlocks) - 1: ceil(log2(nBlocks)), and 1 for nBlocks == 1.
+ * It is never padded to maxDepth: this proof is not circuit input.  Checking is reconstructRoot (merkle.nim:51-74): on level i with
+ * running index j and layer size m, j odd -> compress(sibling, h, key); j == m - 1 (even, last) -> compress(h, sibling, key + 2); else
+ * compress(h, sibling, key); key = 1 on level 0, else 0; then j >>= 1, m = (m + 1) >> 1.  Siblings and roots are 32-byte little-endian
+ * field elements, inputs >= r taken mod r.
+ *
+ * cp2_block_proof_depth: host only; 0 for a geometry the tree builders refuse (a zero size, a block that is not whole cells, nCells that
+ * is not whole blocks, the size caps).
+ *
+ * cp2_dataset_block_proofs serves proofs from what a dataset keeps: every node, or the compact layers (which ARE that tree).
+ *   Requests   slot_block (n x 2 uint64: dataset slot inside the local range, block of the slot < nBlocks); the same pair may repeat.
+ *   Result     block_roots (n x 32 bytes, may be NULL) and paths (n x depth x 32 bytes, request i at i x depth x 32, bottom first).  One
+ *              upload of the row list, one gather on the device, one download.
+ *   Refused    CP2_ERR_INVALID, the request index (where there is one) in cp2_last_error, outputs untouched: a NULL handle; NULL
+ *              slot_block or paths when n > 0; a slot outside the local range; a block >= nBlocks; a roots-only dataset (it keeps
+ *              only its slot roots: no layers to take a path from).  n == 0: CP2_OK.  A context whose stream will not drain is refused
+ *              (CP2_ERR_HIP).  The unit builds inside a cp2_multi_dataset are not served (a shard by slots is a plain cp2_dataset).
+ *   Read-only  nothing of the dataset changes.
+ *
+ * cp2_blocks_verify checks n candidate blocks, each with its path, against slot roots the caller states: no dataset, no tree.
+ *   Requests   slot_roots (n_roots x 32 bytes); root_block (n x 2 uint64: index into slot_roots, block of the slot); data (n x blockSize
+ *              bytes); paths (n x depth x 32 bytes).  nBlocks need not be a power of two.  The same (root, block) twice is allowed (two
+ *              peers may send the same block): each gets its own verdict.  The data path is repair's: chunks of half the context's
+ *              staging (CODEX_P2_STAGE_MB), caller-pinned buffers read in place, large pageable chunks through the pinned ring; each
+ *              chunk's paths are uploaded with the chunk, the slot roots once.  Every candidate's cells are hashed and reduced to its
+ *              block root exactly as the builders do, then walked up its path on the device.
+ *   Refused    before any device work, CP2_ERR_INVALID, outputs untouched: a NULL context; a geometry the tree builders refuse; a NULL
+ *              array (block_roots excepted) when n > 0; a root index >= n_roots or a block >= nBlocks, with the request index in
+ *              cp2_last_error.  n == 0: CP2_OK.  A context whose stream will not drain is refused (CP2_ERR_HIP).
+ *   Result     status[i] = CP2_BLOCK_MATCH (the candidate and its path reconstruct slot_roots[root]) or CP2_BLOCK_MISMATCH; block_roots
+ *              (n x 32 bytes, may be NULL) = what each candidate hashed to.  A wrong block or a wrong path is not an error: CP2_OK.
+ *              CP2_TRACE prints one line per call (requests, matched, bytes, seconds, GB/s).
+ *
+ * cp2_dataset_repair_blocks_proved is cp2_dataset_repair_blocks with a path beside every candidate, in EVERY residency mode: the
+ * verdicts come from the path check against the dataset's own slot roots (cp2_dataset_local_roots), also when block roots are kept, so
+ * the call means the same for a dataset that keeps every node, the compact layers or only its roots.
+ *   Requests   as cp2_dataset_repair_blocks, plus paths (n x depth x 32 bytes).
+ *   Refused    as there, without the roots-only refusal and with NULL paths when n > 0 (the same (slot, block) twice stays refused: two
+ *              writes to one offset; a fake-source dataset takes CP2_REPAIR_CHECK_ONLY only).
+ *   Result, Write, Cache, Unchanged   as cp2_dataset_repair_blocks; status values are CP2_REPAIR_*.  A roots-only dataset's next scrub of
+ *              a repaired slot is clean, and its proof inputs are those from before the damage. */
+#define CP2_BLOCK_MATCH    0         /* status: the candidate and its path reconstruct the stated slot root */
+#define CP2_BLOCK_MISMATCH 1         /* status: they do not */
+size_t cp2_block_proof_depth(size_t cell_size, size_t block_size, size_t n_cells);
+int cp2_dataset_block_proofs(cp2_dataset* ds, const uint64_t* slot_block /* n x 2: dataset slot, block of the slot */, size_t n,
+                             uint8_t* block_roots /* n x 32, may be NULL */, uint8_t* paths /* n x depth x 32 */);
+int cp2_blocks_verify(cp2_ctx* ctx, size_t cell_size, size_t block_size, size_t n_cells, const uint8_t* slot_roots /* n_roots x 32 */,
+                      size_t n_roots, const uint64_t* root_block /* n x 2: index into slot_roots, block of the slot */,
+                      const uint8_t* data /* n x block_size */, const uint8_t* paths /* n x depth x 32 */, size_t n,
+                      uint32_t* status /* n */, uint8_t* block_roots /* n x 32, may be NULL */);
+int cp2_dataset_repair_blocks_proved(cp2_dataset* ds, const uint64_t* slot_block /* n x 2: dataset slot, block of the slot */,
+                                     const uint8_t* data /* n x block_size */, const uint8_t* paths /* n x depth x 32 */, size_t n,
+                                     int flags, const char* cache_path, uint32_t* status /* n */, size_t* n_written);
 
 /* replaces `writeCircomMainComponent`, reference/nim/proof_input/src/cli.nim:186-204 */
 int cp2_write_circom_main(const cp2_config* cfg, const char* path);
