@@ -222,6 +222,11 @@ def load_library():
         "cp2_dataset_block_proofs": (i32, [vp, vp, sz, vp, vp]),
         "cp2_blocks_verify": (i32, [vp, sz, sz, sz, vp, sz, vp, vp, vp, sz, vp, vp]),
         "cp2_dataset_repair_blocks_proved": (i32, [vp, vp, vp, vp, sz, i32, cp, vp, ctypes.POINTER(sz)]),
+        "cp2_fill_begin": (i32, [vp, ctypes.POINTER(Config), u64, u64, vp, pvp]),
+        "cp2_fill_add": (i32, [vp, vp, vp, vp, sz, vp, ctypes.POINTER(sz)]),
+        "cp2_fill_missing": (i32, [vp, vp, sz, ctypes.POINTER(u64)]),
+        "cp2_fill_finish": (i32, [vp, cp, pvp]),
+        "cp2_fill_free": (None, [vp]),
     }
     for name, (res, args) in sigs.items():
         if v is None and name == "cp2_abi_version":
@@ -495,6 +500,10 @@ class Context:
         return SlotTrees(self, h)
 
     # -- dataset / proof input
+    def fill(self, cfg, slot_roots, first_slot=0, n_local=None):
+        """cp2_fill_begin: a session that fills local slots [first_slot, + n_local) from proved network blocks (FillSession)"""
+        return FillSession(self, cfg, slot_roots, first_slot, cfg.n_slots - first_slot if n_local is None else n_local)
+
     def dataset(self, cfg, first_slot=0, n_local=None, cache=None):
         return Dataset(self, cfg, first_slot, cfg.n_slots if n_local is None else n_local, cache)
 
@@ -676,8 +685,19 @@ class Dataset:
                     "cp2_dataset_build_cached")
         else:
             ctx._ck(ctx.L.cp2_dataset_build(ctx.h, ctypes.byref(cfg), first_slot, n_local, ctypes.byref(h)), "cp2_dataset_build")
+        self._own(h, first_slot, n_local)
+
+    def _own(self, h, first_slot, n_local):
         self.h, self.first_slot, self.n_local = h, first_slot, n_local
-        ctx._children.add(self)
+        self.ctx._children.add(self)
+
+    @classmethod
+    def adopt(cls, ctx, cfg, h, first_slot, n_local):
+        """a Dataset around a cp2_dataset handle made elsewhere (cp2_fill_finish); it owns the handle like a built one"""
+        ds = cls.__new__(cls)
+        ds.ctx, ds.cfg = ctx, cfg
+        ds._own(h, first_slot, n_local)
+        return ds
 
     def free(self):
         if self.h:
@@ -812,6 +832,74 @@ class Dataset:
         hs = (ctypes.c_void_p * idx.size)()
         self.ctx._ck(self.ctx.L.cp2_proof_inputs_generate_batch(self.h, _p(idx), idx.size, _p(e), hs), "cp2_proof_inputs_generate_batch")
         return [ProofInput(self.ctx, ctypes.c_void_p(h), self.cfg) for h in hs]
+
+
+FILL_NEW, FILL_MISMATCH, FILL_DUPLICATE, FILL_UNWRITTEN = 0, 1, 2, 3   # CP2_FILL_* (include/codex_p2.h): the per-request results of cp2_fill_add
+
+
+class FillSession:
+    """One cp2_fill: slots filled from proved network blocks in any order, then handed over as a compact Dataset.  Owns the handle; a
+    failing add (CP2_ERR_IO: a slot file could not be written) raises with the statuses in the error's `fill_status`."""
+
+    def __init__(self, ctx, cfg, slot_roots, first_slot, n_local):
+        self.ctx, self.cfg, self.first_slot, self.n_local = ctx, cfg, first_slot, n_local
+        r = _u8(slot_roots).reshape(-1, 32)
+        if r.shape[0] != n_local:
+            raise ValueError("fill: %d local slot(s) need %d roots, got %d" % (n_local, n_local, r.shape[0]))
+        h = ctypes.c_void_p()
+        ctx._ck(ctx.L.cp2_fill_begin(ctx.h, ctypes.byref(cfg), first_slot, n_local, _p(r) if r.size else None, ctypes.byref(h)), "cp2_fill_begin")
+        self.h = h
+        ctx._children.add(self)
+
+    def free(self):
+        if self.h:
+            self.ctx.L.cp2_fill_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if _finalizing():
+                return
+            self.free()
+        except Exception:
+            pass
+
+    @property
+    def block_proof_depth(self):
+        return block_proof_depth(self.cfg.cell_size, self.cfg.block_size, self.cfg.n_cells)
+
+    def add(self, slot_block, data, paths, status=None):
+        """cp2_fill_add: blocks (n x blockSize bytes, any buffer numpy views without a copy) with their paths (uint8[n, depth, 32]) for
+        (slot, block) pairs.  Returns (status: uint32[n] of FILL_*, n_new); `status` may be a caller's uint32[n] array to fill."""
+        sb = np.ascontiguousarray(np.asarray(slot_block, dtype=np.uint64).reshape(-1, 2))
+        n = sb.shape[0]
+        d, p = _candidates("fill", data, n, self.cfg.block_size, paths, self.block_proof_depth)
+        if status is None:
+            status = np.empty(n, dtype=np.uint32)
+        assert status.dtype == np.uint32 and status.flags["C_CONTIGUOUS"] and status.size == n
+        new = ctypes.c_size_t()
+        st = self.ctx.L.cp2_fill_add(self.h, _p(sb) if n else None, _p(d) if n else None, _p(p) if n else None, n, _p(status) if n else None,
+                                     ctypes.byref(new))
+        try:
+            self.ctx._ck(st, "cp2_fill_add")
+        except CodexP2Error as e:
+            e.fill_status, e.n_new = status, new.value
+            raise
+        return status, new.value
+
+    def missing(self, cap=1 << 20):
+        """cp2_fill_missing: (missing: uint64[k, 2] of (slot, block), ascending, the lowest k = min(cap, n_missing), n_missing); cap = 0 counts"""
+        cap = int(cap)
+        out = np.empty((cap, 2), dtype=np.uint64)
+        n = ctypes.c_uint64()
+        self.ctx._ck(self.ctx.L.cp2_fill_missing(self.h, _p(out) if cap else None, cap, ctypes.byref(n)), "cp2_fill_missing")
+        return out[:min(cap, n.value)].copy(), n.value
+
+    def finish(self, cache_path=None):
+        """cp2_fill_finish: the compact Dataset of the filled slots (it takes the session's device buffer; the session then only frees)"""
+        h = ctypes.c_void_p()
+        self.ctx._ck(self.ctx.L.cp2_fill_finish(self.h, cache_path.encode() if cache_path else None, ctypes.byref(h)), "cp2_fill_finish")
+        return Dataset.adopt(self.ctx, self.cfg, h, self.first_slot, self.n_local)
 
 
 GATHER_AUTO, GATHER_RCCL, GATHER_HOST, GATHER_COPY = 0, 1, 2, 3

@@ -1,0 +1,287 @@
+// Fill sessions behind the C ABI (include/codex_p2.h): cp2_fill_begin, cp2_fill_add, cp2_fill_missing, cp2_fill_finish, cp2_fill_free.
+//
+// A node that takes on a slot holds the manifest's slot root and receives the slot's network blocks from peers, in any order, each with
+// its Merkle path.  cp2_blocks_verify checks such blocks and forgets the block roots it computed; a session KEEPS them.  It owns the compact
+// layout of its slots (cp2_dataset, dataset_obj.hpp: the tree over the block roots, layer-major over the local slots) from the start;
+// every add runs verify's data path (repair_check_with, repair.cpp) and ends in k_block_path_commit, which walks each candidate's root up
+// its path and, where the slot root comes out, stores the block root into layer 0.  The host's bitmap (fill_plan.hpp) says what is
+// present; the proved blocks are written into the slot files by repair's writer.  When nothing is missing, finish builds the upper
+// layers with the layer kernel (one launch per layer over all slots), compares the top layer with the stated roots and hands the buffer
+// to a new compact dataset: no slot byte is read or hashed a second time.
+#include <hip/hip_runtime.h>
+
+#include <fcntl.h>
+#include <unistd.h>
+
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "block_proof_plan.hpp"
+#include "dataset_obj.hpp"
+#include "fill_plan.hpp"
+#include "repair.hpp"
+
+using namespace cp2i;
+
+static_assert(FILL_NEW == CP2_FILL_NEW && FILL_MISMATCH == CP2_FILL_MISMATCH && FILL_DUPLICATE == CP2_FILL_DUPLICATE &&
+              FILL_UNWRITTEN == CP2_FILL_UNWRITTEN, "fill_plan.hpp restates the header's statuses");
+static_assert(FILL_WRITE == CP2_REPAIR_MATCH && FILL_SKIP == CP2_REPAIR_MISMATCH && FILL_WRITE_FAILED == CP2_REPAIR_UNWRITTEN,
+              "repair_write takes and leaves repair's statuses");
+
+// the session behind the header's opaque cp2_fill
+struct cp2_fill_session {
+  cp2_ctx* ctx = nullptr;
+  cp2_config cfg{};                     // file_base cleared: the name lives in `file_base`
+  std::string file_base;
+  bool from_file = false;
+  FillPlan plan;
+  DevBuf compact;                       // the compact layout of the local slots; becomes the dataset's buffer in finish
+  DevBuf slot_roots;                    // the stated roots, canonical: n_local x 32 bytes
+};
+
+namespace {
+
+cp2_fill_session* session(void* f) { return static_cast<cp2_fill_session*>(f); }
+const cp2_fill_session* session(const void* f) { return static_cast<const cp2_fill_session*>(f); }
+
+bool file_has_magic(const char* path, const char* magic8) {
+  char m[8] = {};
+  const int fd = open(path, O_RDONLY | O_CLOEXEC);
+  if (fd < 0) return false;
+  const bool ok = pread(fd, m, 8, 0) == 8 && std::memcmp(m, magic8, 8) == 0;
+  close(fd);
+  return ok;
+}
+
+// the kept form of the session's layers, under the name and with the contents cp2_dataset_build_cached writes for a compact dataset: a
+// tree cache at the path stays, the kept form goes beside it
+int save_kept(const cp2_fill_session* f, const char* cache_path) {
+  const cp2_config& c = f->cfg;
+  KeptMeta meta;
+  meta.n_slots = f->plan.n_local; meta.cell_size = c.cell_size; meta.block_size = c.block_size; meta.n_cells = c.n_cells;
+  meta.src = (uint64_t)(f->from_file ? CellSrc::File : CellSrc::Fake); meta.dataset_seed = c.seed; meta.first_slot = f->plan.first_slot;
+  meta.mode = 2; meta.file_base = f->file_base;
+  const std::string path = file_has_magic(cache_path, "CP2TREE3") ? std::string(cache_path) + ".kept" : std::string(cache_path);
+  return kept_save(f->ctx, path.c_str(), meta, f->compact.p, f->plan.rows * 32);
+}
+
+// the session's buffer handed over without a copy
+void hand_over(DevBuf& from, DevBuf& to) {
+  to.release();
+  to.p = from.p; to.bytes = from.bytes; to.owner = from.owner; to.home = from.home; to.borrowed = from.borrowed;
+  from.p = nullptr; from.bytes = 0; from.owner = nullptr; from.home = nullptr; from.borrowed = false;
+}
+
+void fill_trace(size_t n, const uint32_t* status, size_t n_new, size_t block_size, uint64_t missing, double seconds) {
+  if (!std::getenv("CP2_TRACE")) return;
+  size_t proved = 0;
+  for (size_t i = 0; i < n; ++i) proved += status[i] != FILL_MISMATCH;
+  const double bytes = (double)n * (double)block_size;
+  std::fprintf(stderr, "[cp2 trace] fill add: %zu request(s), %zu proved, %zu new, %llu still missing, %.0f bytes, %.3f s (%.2f GB/s)\n", n, proved,
+               n_new, (unsigned long long)missing, bytes, seconds, seconds > 0 ? bytes / seconds / 1e9 : 0.0);
+}
+
+}  // namespace
+
+extern "C" int cp2_fill_begin(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local, const uint8_t* slot_roots, void** out) try {
+  if (!ctx || !cfg || !out) return CP2_ERR_INVALID;
+  *out = nullptr;
+  CP2_REFUSE_STUCK(ctx);
+  std::string err;
+  if (!fill_check_range(cfg->n_slots, first_slot, n_local, cfg->max_depth, cfg->max_log2_nslots, cfg->n_cells, cfg->cell_size,
+                        cfg->file_base ? SLOT_FILE_MAX_CELL : 0, &err)) {
+    ctx->err = err;
+    return CP2_ERR_INVALID;
+  }
+  if (trees_check_geometry(cfg->cell_size, cfg->block_size, cfg->n_cells, n_local) != CP2_OK) {
+    ctx->err = "fill: cell_size " + std::to_string(cfg->cell_size) + ", block_size " + std::to_string(cfg->block_size) + ", n_cells " +
+               std::to_string(cfg->n_cells) + " is a geometry the tree builders refuse";
+    return CP2_ERR_INVALID;
+  }
+  if (!slot_roots) {
+    ctx->err = "fill: slot_roots must not be NULL";
+    return CP2_ERR_INVALID;
+  }
+  CP2_HIP(ctx, hipSetDevice(ctx->device));
+  std::unique_ptr<cp2_fill_session> f(new (std::nothrow) cp2_fill_session());
+  if (!f) return CP2_ERR_ALLOC;
+  f->ctx = ctx;
+  f->cfg = *cfg;
+  f->from_file = cfg->file_base != nullptr;
+  if (f->from_file) f->file_base = cfg->file_base;
+  f->cfg.file_base = nullptr;
+  f->plan.init(first_slot, n_local, cfg->n_cells / (cfg->block_size / cfg->cell_size));
+  CP2_TRY(f->compact.alloc(ctx, f->plan.rows * 32));            // what a compact dataset of these slots holds, once
+  CP2_TRY(f->slot_roots.alloc(ctx, n_local * 32));
+  std::vector<uint8_t> roots(n_local * 32);                      // values of at least r are reduced, as everywhere else
+  for (uint64_t s = 0; s < n_local; ++s) canonical_felt(slot_roots + s * 32, &roots[s * 32]);
+  CP2_HIP(ctx, hipMemcpyAsync(f->slot_roots.p, roots.data(), roots.size(), hipMemcpyHostToDevice, ctx->stream));
+  CP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  *out = f.release();
+  return CP2_OK;
+} catch (const std::bad_alloc&) {
+  return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
+} catch (...) {
+  return CP2_ERR_INVALID;
+}
+
+extern "C" int cp2_fill_add(void* fill, const uint64_t* slot_block, const uint8_t* data, const uint8_t* paths, size_t n, uint32_t* status,
+                            size_t* n_new) try {
+  cp2_fill_session* f = session(fill);
+  if (!f) return CP2_ERR_INVALID;
+  cp2_ctx* ctx = f->ctx;
+  const cp2_config& c = f->cfg;
+  FillPlan& plan = f->plan;
+  if (n && (!slot_block || !data || !paths || !status)) {
+    ctx->err = "fill: slot_block, data, paths and status must not be NULL when n > 0";
+    return CP2_ERR_INVALID;
+  }
+  std::string err;
+  if (!plan.validate(slot_block, n, &err)) {
+    ctx->err = err;
+    return CP2_ERR_INVALID;
+  }
+  if (n == 0) {
+    if (n_new) *n_new = 0;
+    return CP2_OK;
+  }
+  CP2_REFUSE_STUCK(ctx);
+  CP2_HIP(ctx, hipSetDevice(ctx->device));
+  const auto t0 = std::chrono::steady_clock::now();
+  // cp2_blocks_verify's data path; its last step also keeps the block roots that were proved
+  const size_t depth = block_proof_depth(plan.n_blocks), path_bytes = depth * 32;
+  std::vector<uint64_t> local_block, dest;
+  plan.device_requests(slot_block, n, &local_block, &dest);
+  DevBuf d_req, d_dest, d_paths;                     // (go after the streams have drained: DevBuf::release)
+  RepairJudge judge;
+  judge.begin = [&](size_t chunk) -> int {
+    CP2_TRY(d_req.scratch(ctx, n * 16));
+    CP2_TRY(d_dest.scratch(ctx, n * 8));
+    CP2_TRY(d_paths.scratch(ctx, chunk * path_bytes));
+    CP2_HIP(ctx, hipMemcpyAsync(d_req.p, local_block.data(), n * 16, hipMemcpyHostToDevice, ctx->stream));
+    CP2_HIP(ctx, hipMemcpyAsync(d_dest.p, dest.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
+    return CP2_OK;
+  };
+  // the chunk's paths travel with the chunk (the previous chunk's walk, earlier on this stream, has read its own)
+  judge.stage = [&](size_t c0, size_t m, hipStream_t st) -> int {
+    CP2_HIP(ctx, hipMemcpyAsync(d_paths.p, paths + c0 * path_bytes, m * path_bytes, hipMemcpyHostToDevice, st));
+    return CP2_OK;
+  };
+  judge.verdicts = [&](const uint8_t* fresh, size_t c0, size_t m, uint32_t* verdict, hipStream_t st) -> int {
+    CP2_HIP(ctx, cp2k::launch_block_path_commit(fresh, d_paths.p, static_cast<const uint64_t*>(d_req.p) + 2 * c0, f->slot_roots.p,
+                                                static_cast<const uint64_t*>(d_dest.p) + c0, plan.n_blocks, (uint32_t)depth, m, verdict,
+                                                f->compact.p, plan.rows, st));
+    return CP2_OK;
+  };
+  std::vector<uint32_t> verdict(n), st(n);
+  CP2_TRY(repair_check_with(ctx, c.cell_size, c.block_size, data, n, verdict.data(), judge));
+  plan.resolve(slot_block, verdict.data(), n, st.data());
+  int r = CP2_OK;
+  if (f->from_file) {                                // the NEW blocks into "<file_base><slot>.dat": repair's writer and its rules
+    std::vector<uint32_t> w = FillPlan::write_mask(st.data(), n);
+    size_t written_n = 0;
+    std::vector<FileStamp> written;
+    r = repair_write(f->file_base, c.block_size, slot_block, data, n, w.data(), &written_n, &written, &err);
+    FillPlan::roll_back(slot_block, w, st.data());
+  }
+  const size_t set = plan.commit(slot_block, st.data(), n);   // present only now: an UNWRITTEN block stays missing and can be sent again
+  std::copy(st.begin(), st.end(), status);
+  if (n_new) *n_new = set;
+  if (r != CP2_OK) ctx->err = err;
+  fill_trace(n, status, set, c.block_size, plan.n_missing(), std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+  return r;
+} catch (const std::bad_alloc&) {
+  return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
+} catch (...) {
+  return CP2_ERR_INVALID;
+}
+
+extern "C" int cp2_fill_missing(const void* fill, uint64_t* missing, size_t cap, uint64_t* n_missing) try {
+  const cp2_fill_session* f = session(fill);
+  if (!f || !n_missing) return CP2_ERR_INVALID;
+  if (cap && !missing) {
+    f->ctx->err = "fill: missing must not be NULL when cap > 0";
+    return CP2_ERR_INVALID;
+  }
+  *n_missing = f->plan.missing(missing, cap);
+  return CP2_OK;
+} catch (...) {
+  return CP2_ERR_INVALID;
+}
+
+extern "C" int cp2_fill_finish(void* fill, const char* cache_path, cp2_dataset** out) try {
+  cp2_fill_session* f = session(fill);
+  if (!f || !out) return CP2_ERR_INVALID;
+  *out = nullptr;
+  cp2_ctx* ctx = f->ctx;
+  FillPlan& plan = f->plan;
+  std::string err;
+  if (!plan.may_finish(&err)) {
+    ctx->err = err;
+    return CP2_ERR_INVALID;
+  }
+  CP2_REFUSE_STUCK(ctx);
+  CP2_HIP(ctx, hipSetDevice(ctx->device));
+  const auto t0 = std::chrono::steady_clock::now();
+  // the upper layers of all local trees from layer 0, layer-major, one launch per layer over all slots: the compact layout is exactly
+  // what merkle_trees_dev writes for n_local trees of n_blocks leaves each
+  CP2_TRY(merkle_trees_dev(ctx, f->compact.p, plan.n_blocks, plan.n_local, f->compact.p, true));
+  // the top layer against the stated roots, on the device
+  const size_t nl = (size_t)plan.n_local;
+  DevBuf d_rows, d_verdict;
+  CP2_TRY(d_rows.scratch(ctx, nl * 8));
+  CP2_TRY(d_verdict.scratch(ctx, nl * 4));
+  std::vector<uint64_t> rows(nl);
+  for (size_t s = 0; s < nl; ++s) rows[s] = s;
+  std::vector<uint32_t> verdict(nl);
+  CP2_HIP(ctx, hipMemcpyAsync(d_rows.p, rows.data(), nl * 8, hipMemcpyHostToDevice, ctx->stream));
+  CP2_HIP(ctx, cp2k::launch_repair_compare(f->compact.u8() + plan.coff.back() * 32, f->slot_roots.p, nl, static_cast<const uint64_t*>(d_rows.p), nl,
+                                           static_cast<uint32_t*>(d_verdict.p), ctx->stream));
+  CP2_HIP(ctx, hipMemcpyAsync(verdict.data(), d_verdict.p, nl * 4, hipMemcpyDeviceToHost, ctx->stream));
+  CP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (size_t s = 0; s < nl; ++s)
+    if (verdict[s] != 0) {
+      ctx->err = "fill: the tree over the kept block roots of slot " + std::to_string(plan.first_slot + s) + " does not end in the stated slot root";
+      return CP2_ERR_IO;
+    }
+  // the kept form, with the stamps of the slot files as they stand: cp2_dataset_build_cached loads it instead of rebuilding
+  if (cache_path) {
+    const int st = save_kept(f, cache_path);
+    if (st != CP2_OK) {
+      if (ctx->err.empty()) ctx->err = std::string("fill: cannot write the kept layers to ") + cache_path;
+      return st;
+    }
+  }
+  // the session's buffer becomes the compact buffer of an ordinary dataset (dataset_alloc_kept's layout), source as begun
+  std::unique_ptr<cp2_dataset> ds(new (std::nothrow) cp2_dataset());
+  if (!ds) return CP2_ERR_ALLOC;
+  ds->ctx = ctx;
+  ds->cfg = f->cfg;
+  ds->from_file = f->from_file;
+  ds->file_base = f->file_base;
+  ds->first_slot = plan.first_slot;
+  ds->n_local = plan.n_local;
+  ds->tree_mode = 2;
+  ds->csizes = plan.csizes;
+  ds->coff = plan.coff;
+  hand_over(f->compact, ds->compact);
+  plan.finished = true;
+  if (std::getenv("CP2_TRACE"))
+    std::fprintf(stderr, "[cp2 trace] fill finish: %llu slot(s) of %llu block(s), %zu layer(s) built, %.3f ms%s\n", (unsigned long long)plan.n_local,
+                 (unsigned long long)plan.n_blocks, plan.csizes.size() - 1,
+                 std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3, cache_path ? ", kept form saved" : "");
+  *out = ds.release();
+  return CP2_OK;
+} catch (const std::bad_alloc&) {
+  return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
+} catch (...) {
+  return CP2_ERR_INVALID;
+}
+
+extern "C" void cp2_fill_free(void* fill) { delete session(fill); }

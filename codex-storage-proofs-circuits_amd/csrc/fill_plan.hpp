@@ -1,0 +1,220 @@
+// The host side of a fill session (csrc/fill.cpp: cp2_fill_begin / _add / _missing / _finish): which sessions and requests are accepted,
+// where a proved block root goes in the compact layout, which blocks are present, how the device's verdicts become NEW / DUPLICATE, how a
+// failed write takes its blocks back, the ordered list of what is missing, and when a session may finish.  No HIP in here:
+// tests/host_check/fill_plan_check.cpp walks it over random geometries and request sets on the CPU, under AddressSanitizer + UBSan.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "repair_plan.hpp"
+
+namespace cp2i {
+
+// the per-request results of cp2_fill_add: the values of CP2_FILL_* (include/codex_p2.h)
+constexpr uint32_t FILL_NEW = 0, FILL_MISMATCH = 1, FILL_DUPLICATE = 2, FILL_UNWRITTEN = 3;
+// what the writer (repair_write) takes and leaves: the values of CP2_REPAIR_MATCH / _MISMATCH / _UNWRITTEN
+constexpr uint32_t FILL_WRITE = 0, FILL_SKIP = 1, FILL_WRITE_FAILED = 2;
+
+// ---- the session's range -----------------------------------------------------------------------------------------------------------
+// What cp2_dataset_build asks of (cfg, first_slot, n_local) before it looks at the geometry, and the power of two proof inputs need
+// (sample/bn254.nim:19-20).  max_cell: the largest cell a slot file holds (0: fake source, no limit).
+inline bool fill_check_range(uint64_t n_slots, uint64_t first_slot, uint64_t n_local, int max_depth, int max_log2_nslots, uint64_t n_cells,
+                             uint64_t cell_size, uint64_t max_cell, std::string* err) {
+  if (n_local == 0 || first_slot > n_slots || n_local > n_slots - first_slot) {   // (no wrap-around)
+    *err = "fill: slots " + std::to_string(first_slot) + " + " + std::to_string(n_local) + " are not a range inside the dataset's " +
+           std::to_string(n_slots);
+    return false;
+  }
+  if (max_depth < 0 || max_log2_nslots < 0) {
+    *err = "fill: negative maxDepth or maxLog2NSlots";
+    return false;
+  }
+  if (n_cells == 0 || (n_cells & (n_cells - 1))) {
+    *err = "fill: nCells = " + std::to_string(n_cells) + " is not a power of two";
+    return false;
+  }
+  if (max_cell && cell_size > max_cell) {
+    *err = "fill: slot files hold cells of at most " + std::to_string(max_cell) + " bytes";
+    return false;
+  }
+  return true;
+}
+
+// ---- the session ------------------------------------------------------------------------------------------------------------------
+struct FillPlan {
+  uint64_t first_slot = 0, n_local = 0, n_blocks = 0;
+  // the compact layout of n_local slot trees (cp2_dataset: csizes / coff): layer k of local slot s starts at row coff[k] + s * csizes[k];
+  // layer 0 holds the block roots, the last layer the slot roots
+  std::vector<size_t> csizes, coff;
+  size_t rows = 0;                       // rows of all layers
+  std::vector<uint64_t> bits;            // bit (local * n_blocks + block): the block is proved AND written; the authority on presence
+  uint64_t n_present = 0;
+  bool finished = false;
+
+  // layer sizes n, ceil(n / 2), ... 1 with at least one round of compression (merkle/bn254.nim:29-58, layer_sizes_of)
+  void init(uint64_t first, uint64_t local, uint64_t blocks) {
+    first_slot = first; n_local = local; n_blocks = blocks;
+    csizes.clear(); coff.clear();
+    rows = 0;
+    bool bottom = true;
+    for (size_t m = (size_t)blocks; blocks;) {
+      csizes.push_back(m);
+      coff.push_back(rows);
+      rows += (size_t)local * m;
+      if (m == 1 && !bottom) break;
+      m = (m + 1) / 2;
+      bottom = false;
+    }
+    bits.assign((size_t)((total() + 63) / 64), 0);
+    n_present = 0;
+    finished = false;
+  }
+  uint64_t total() const { return n_local * n_blocks; }
+  uint64_t n_missing() const { return total() - n_present; }
+  bool present(uint64_t local, uint64_t block) const {
+    const uint64_t g = local * n_blocks + block;
+    return (bits[(size_t)(g >> 6)] >> (g & 63)) & 1;
+  }
+  // the row of layer 0 that keeps the root of `block` of dataset slot `slot` (the row repair compares with in a compact dataset)
+  uint64_t dest_row(uint64_t slot, uint64_t block) const { return repair_row_compact(coff[0], csizes[0], slot - first_slot, block); }
+
+  // ---- validation ----------------------------------------------------------------------------------------------------------------
+  // Requests are (dataset slot, block) pairs.  A finished session takes none; every slot inside the local range, every block below
+  // n_blocks; the same pair twice is allowed (two peers may answer).  false with *err naming the lowest request index that breaks a rule.
+  bool validate(const uint64_t* slot_block, size_t n, std::string* err) const {
+    if (finished) {
+      *err = "fill: the session is finished: it accepts only cp2_fill_free";
+      return false;
+    }
+    for (size_t i = 0; i < n; ++i) {
+      const uint64_t s = slot_block[2 * i], b = slot_block[2 * i + 1];
+      if (s < first_slot || s - first_slot >= n_local) {
+        *err = "fill: request " + std::to_string(i) + ": slot " + std::to_string(s) + " is not inside the local range " +
+               std::to_string(first_slot) + " + " + std::to_string(n_local);
+        return false;
+      }
+      if (b >= n_blocks) {
+        *err = "fill: request " + std::to_string(i) + ": block " + std::to_string(b) + " of slot " + std::to_string(s) + " is not below nBlocks = " +
+               std::to_string(n_blocks);
+        return false;
+      }
+    }
+    return true;
+  }
+
+  // ---- what the device reads -------------------------------------------------------------------------------------------------------
+  // per request the (local slot, block) pair the walk indexes the slot roots and starts from, and the destination row
+  void device_requests(const uint64_t* slot_block, size_t n, std::vector<uint64_t>* local_block, std::vector<uint64_t>* dest) const {
+    local_block->resize(2 * n);
+    dest->resize(n);
+    for (size_t i = 0; i < n; ++i) {
+      (*local_block)[2 * i] = slot_block[2 * i] - first_slot;
+      (*local_block)[2 * i + 1] = slot_block[2 * i + 1];
+      (*dest)[i] = dest_row(slot_block[2 * i], slot_block[2 * i + 1]);
+    }
+  }
+
+  // ---- NEW / DUPLICATE ---------------------------------------------------------------------------------------------------------------
+  // verdict[i] == 0: the device proved request i.  A proved block that is present already, or that a LOWER proved index of this call
+  // names, is a DUPLICATE; the first is NEW.  Changes nothing of the session.
+  void resolve(const uint64_t* slot_block, const uint32_t* verdict, size_t n, uint32_t* status) const {
+    std::vector<size_t> proved;
+    for (size_t i = 0; i < n; ++i) {
+      status[i] = FILL_MISMATCH;
+      if (verdict[i] == 0) proved.push_back(i);
+    }
+    // by (slot, block), the lowest index first: repair's write order, whose groups put equal pairs side by side
+    for (const WriteGroup& g : repair_write_groups(slot_block, proved)) {
+      std::vector<size_t> reqs(g.reqs);
+      std::stable_sort(reqs.begin(), reqs.end(), [&](size_t a, size_t b) {
+        if (slot_block[2 * a + 1] != slot_block[2 * b + 1]) return slot_block[2 * a + 1] < slot_block[2 * b + 1];
+        return a < b;
+      });
+      for (size_t k = 0; k < reqs.size(); ++k) {
+        const size_t i = reqs[k];
+        const bool again = k > 0 && slot_block[2 * reqs[k - 1] + 1] == slot_block[2 * i + 1];
+        status[i] = again || present(g.slot - first_slot, slot_block[2 * i + 1]) ? FILL_DUPLICATE : FILL_NEW;
+      }
+    }
+  }
+
+  // ---- writing -------------------------------------------------------------------------------------------------------------------
+  // what the writer is handed: the NEW blocks to write, everything else to skip
+  static std::vector<uint32_t> write_mask(const uint32_t* status, size_t n) {
+    std::vector<uint32_t> w(n);
+    for (size_t i = 0; i < n; ++i) w[i] = status[i] == FILL_NEW ? FILL_WRITE : FILL_SKIP;
+    return w;
+  }
+  // ... and the roll-back: a NEW block whose file failed (or came after the failing one) is UNWRITTEN and stays missing, and so is every
+  // DUPLICATE of it in this call: "already present" would be untrue of a block that is still missing
+  static void roll_back(const uint64_t* slot_block, const std::vector<uint32_t>& written, uint32_t* status) {
+    std::vector<size_t> failed;
+    for (size_t i = 0; i < written.size(); ++i)
+      if (status[i] == FILL_NEW && written[i] == FILL_WRITE_FAILED) {
+        status[i] = FILL_UNWRITTEN;
+        failed.push_back(i);
+      }
+    if (failed.empty()) return;
+    for (size_t i = 0; i < written.size(); ++i) {
+      if (status[i] != FILL_DUPLICATE) continue;
+      for (size_t k : failed)
+        if (slot_block[2 * k] == slot_block[2 * i] && slot_block[2 * k + 1] == slot_block[2 * i + 1]) { status[i] = FILL_UNWRITTEN; break; }
+    }
+  }
+  // the presence bits of the blocks that are still NEW (after the files were synced; at once for the fake source): returns how many
+  size_t commit(const uint64_t* slot_block, const uint32_t* status, size_t n) {
+    size_t set = 0;
+    for (size_t i = 0; i < n; ++i) {
+      if (status[i] != FILL_NEW) continue;
+      const uint64_t g = (slot_block[2 * i] - first_slot) * n_blocks + slot_block[2 * i + 1];
+      uint64_t& w = bits[(size_t)(g >> 6)];
+      if (!((w >> (g & 63)) & 1)) {
+        w |= 1ULL << (g & 63);
+        ++set;
+      }
+    }
+    n_present += set;
+    return set;
+  }
+
+  // ---- what is missing ----------------------------------------------------------------------------------------------------------------
+  // the lowest min(cap, n_missing) absent (dataset slot, block) pairs in ascending order into `out` (may be NULL when cap == 0); returns
+  // the number of all absent blocks
+  uint64_t missing(uint64_t* out, size_t cap) const {
+    size_t k = 0;
+    const uint64_t all = total();
+    for (size_t w = 0; k < cap && w < bits.size(); ++w) {
+      uint64_t absent = ~bits[w];
+      while (absent && k < cap) {
+        const uint64_t g = (uint64_t)w * 64 + (uint64_t)__builtin_ctzll(absent);
+        absent &= absent - 1;
+        if (g >= all) break;
+        out[2 * k] = first_slot + g / n_blocks;
+        out[2 * k + 1] = g % n_blocks;
+        ++k;
+      }
+    }
+    return n_missing();
+  }
+
+  // ---- finishing -----------------------------------------------------------------------------------------------------------------------
+  // every block present and the session not finished yet; else false with *err naming the count and the first missing pair
+  bool may_finish(std::string* err) const {
+    if (finished) {
+      *err = "fill: the session is finished: it accepts only cp2_fill_free";
+      return false;
+    }
+    if (n_missing()) {
+      uint64_t first[2] = {0, 0};
+      (void)missing(first, 1);
+      *err = "fill: " + std::to_string(n_missing()) + " block(s) are missing, the first is (slot " + std::to_string(first[0]) + ", block " +
+             std::to_string(first[1]) + ")";
+      return false;
+    }
+    return true;
+  }
+};
+
+}  // namespace cp2i

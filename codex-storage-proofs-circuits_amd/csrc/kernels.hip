@@ -11,6 +11,7 @@
 //   k_scrub_compare       a rebuilt layer against the kept one, mismatch bitmap + per-workgroup counts (scrub.cpp)
 //   k_repair_compare      candidate block roots against the kept rows they would replace, one verdict per request (repair.cpp)
 //   k_block_path_roots    a13 candidate block roots walked up their Merkle paths to the slot root, merkle.nim:51-74 (block_proofs.cpp)
+//   k_block_path_commit   the same walk; a proved block root is also stored into layer 0 of a fill session's compact buffer (fill.cpp)
 //
 // All global-memory field elements are 32-byte little-endian canonical integers (the ABI format).
 #include "kernels.hpp"
@@ -815,6 +816,61 @@ __global__ void __launch_bounds__(TPB) k_block_path_roots(const uint4* __restric
 }
 
 // ------------------------------------------------------------------------------------------------
+// Slot filling (fill.cpp): k_block_path_roots' walk, with what a fill session keeps of a proved block.  Lane i takes request i's freshly
+// built block root, its (local slot, block) pair and its path, runs reconstructRoot (merkle.nim:51-74, the schedule of block_proof_schedule:
+// key, odd and last rules) and compares the result with slot_roots[slot] as canonical words.  Where they are equal it also copies the
+// canonical block root (row i of `fresh`, as the layer kernel wrote it) to row dest[i] of `layer0`, the session's compact buffer: the host
+// computed dest[i] = coff[0] + local_slot * csizes[0] + block, a row of layer 0.  Two 16-byte vector stores; the row is read again from
+// `fresh` after the walk instead of being held in registers across it.  No atomics and no device bitmap: the host's bitmap is the authority
+// on presence.  Two matching requests for the same (slot, block) in one launch store identical bytes to one row, which is benign: a block
+// root that reconstructs the slot root at that position is the one block root the tree has there.  A row at or past n_rows (never: the
+// host validated every request) is a mismatch and nothing is stored.
+__global__ void __launch_bounds__(TPB) k_block_path_commit(const uint4* __restrict__ fresh, const uint4* __restrict__ paths,
+                                                             const uint64_t* __restrict__ slot_block, const uint4* __restrict__ slot_roots,
+                                                             const uint64_t* __restrict__ dest, uint64_t n_blocks, uint32_t depth, size_t n,
+                                                             uint32_t* __restrict__ verdict, uint4* __restrict__ layer0, uint64_t n_rows) {
+  __shared__ fr::QTab qtab;
+  fr::qtab_fill(qtab, threadIdx.x, TPB);
+  __syncthreads();
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  Fe cur;
+  {
+    const uint4 f0 = fresh[2 * i], f1 = fresh[2 * i + 1];
+    const uint32_t fw[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
+    cur = fr::to_mont(fr::from_words(fw));
+  }
+  const uint4* path = paths + 2 * i * depth;
+  uint64_t j = slot_block[2 * i + 1], m = n_blocks;
+  State s;
+#pragma unroll 1
+  for (uint32_t lvl = 0; lvl < depth; ++lvl) {
+    const Fe sib = load_fe_canonical(path + 2 * lvl);
+    const uint32_t b = (uint32_t)j & 1u;
+    const uint32_t key = (lvl == 0 ? 1u : 0u) + 2u * ((j == m - 1 ? 1u : 0u) & (b ^ 1u));
+    const uint32_t sw = 0u - b;
+#pragma unroll
+    for (int l = 0; l < fr::NL; ++l) {
+      s.x.l[l] = (cur.l[l] & ~sw) | (sib.l[l] & sw);
+      s.y.l[l] = (sib.l[l] & ~sw) | (cur.l[l] & sw);
+    }
+    s.z = key_fe(key);
+    p2::permute(s, qtab);
+    cur = fr::norm(s.x);
+    j >>= 1;
+    m = (m + 1) >> 1;
+  }
+  const Fe want = load_fe_canonical(slot_roots + 2 * slot_block[2 * i]);
+  const uint64_t r = dest[i];
+  const bool keep = fe_equal(cur, want) && r < n_rows;
+  verdict[i] = keep ? 0u : 1u;
+  if (keep) {
+    layer0[2 * r] = fresh[2 * i];
+    layer0[2 * r + 1] = fresh[2 * i + 1];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Workgroups for n work items.  A grid holds at most 2^31 - 1 workgroups in x; the per-item kernels are launched in slices of
 // at most MAX_ITEMS items (every item is independent and addressed from a base pointer), the layer / sampling kernels, whose
 // item index is decomposed inside the kernel, refuse what does not fit one grid (2^38 nodes: far beyond any HBM).
@@ -1013,6 +1069,20 @@ hipError_t launch_block_path_roots(const void* fresh, const void* paths, const u
     const size_t m = n - i0 < MAX_ITEMS ? n - i0 : MAX_ITEMS;
     CP2K_LAUNCH(k_block_path_roots, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)fresh + 2 * i0, (const uint4*)paths + 2 * i0 * depth,
                 root_block + 2 * i0, (const uint4*)slot_roots, n_blocks, depth, m, verdict + i0, roots_out ? (uint4*)roots_out + 2 * i0 : nullptr);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+hipError_t launch_block_path_commit(const void* fresh, const void* paths, const uint64_t* slot_block, const void* slot_roots, const uint64_t* dest,
+                                    uint64_t n_blocks, uint32_t depth, size_t n, uint32_t* verdict, void* layer0, uint64_t n_rows, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  if (!fresh || !paths || !slot_block || !slot_roots || !dest || !verdict || !layer0 || depth == 0 || n_blocks == 0) return hipErrorInvalidValue;
+  for (size_t i0 = 0; i0 < n; i0 += MAX_ITEMS) {
+    const size_t m = n - i0 < MAX_ITEMS ? n - i0 : MAX_ITEMS;
+    CP2K_LAUNCH(k_block_path_commit, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)fresh + 2 * i0, (const uint4*)paths + 2 * i0 * depth,
+                slot_block + 2 * i0, (const uint4*)slot_roots, dest + i0, n_blocks, depth, m, verdict + i0, (uint4*)layer0, n_rows);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }

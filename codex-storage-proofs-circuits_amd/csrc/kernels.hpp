@@ -73,6 +73,12 @@ hipError_t launch_repair_compare(const void* fresh, const void* kept, size_t kep
 hipError_t launch_block_path_roots(const void* fresh, const void* paths, const uint64_t* root_block, const void* slot_roots, uint64_t n_blocks,
                                    uint32_t depth, size_t n, uint32_t* verdict, void* roots_out, hipStream_t st);
 
+// Slot filling (fill.cpp, k_block_path_commit): launch_block_path_roots' walk over (local slot, block) pairs, slot_roots indexed by the
+// local slot.  Where request i is a match (verdict[i] = 0) the 32-byte row i of `fresh` is also stored to row dest[i] of `layer0` (n_rows
+// rows; the host computed dest[i] inside layer 0 of the compact layout); a mismatch stores nothing.
+hipError_t launch_block_path_commit(const void* fresh, const void* paths, const uint64_t* slot_block, const void* slot_roots, const uint64_t* dest,
+                                    uint64_t n_blocks, uint32_t depth, size_t n, uint32_t* verdict, void* layer0, uint64_t n_rows, hipStream_t st);
+
 // Proof-input verification (k_verify_samples, circuit/codex/sample_cells.circom:58-148) over n inputs that share the circuit
 // parameters.  Device arrays: prm n x 4 (nCellsPerSlot, nSlotsPerDataSet, slotIndex, shape ok), heads n x (3 + m) felts
 // (dataSetRoot, entropy, slotRoot, slotProof), cells n x ns x nf felts, paths n x ns x md felts; ok receives n x ns sample

@@ -87,6 +87,15 @@ proc cp2_blocks_verify(ctx: Cp2Ctx, cellSize, blockSize, nCells: csize_t, slotRo
                        data, paths: ptr byte, n: csize_t, status: ptr uint32, blockRoots: ptr byte): cint {.importc.}
 proc cp2_dataset_repair_blocks_proved(ds: Cp2Dataset, slotBlock: ptr uint64, data, paths: ptr byte, n: csize_t, flags: cint,
                                       cachePath: cstring, status: ptr uint32, nWritten: ptr csize_t): cint {.importc.}
+# fill sessions: a slot filled from proved blocks in any order, then handed over as a compact dataset without a second pass.  The
+# session handle is a plain `pointer` (cp2_fill is void in the header); slotBlock = n x (slot, block), status = n x CP2_FILL_*,
+# missing = cap x (slot, block) ascending
+proc cp2_fill_begin(ctx: Cp2Ctx, cfg: ptr Cp2Config, firstSlot, nLocal: uint64, slotRoots: ptr byte, fill: ptr pointer): cint {.importc.}
+proc cp2_fill_add(fill: pointer, slotBlock: ptr uint64, data, paths: ptr byte, n: csize_t, status: ptr uint32,
+                  nNew: ptr csize_t): cint {.importc.}
+proc cp2_fill_missing(fill: pointer, missing: ptr uint64, cap: csize_t, nMissing: ptr uint64): cint {.importc.}
+proc cp2_fill_finish(fill: pointer, cachePath: cstring, ds: ptr Cp2Dataset): cint {.importc.}
+proc cp2_fill_free(fill: pointer) {.importc.}
 proc cp2_proof_input_write_json(p: Cp2ProofInput, path: cstring): cint {.importc.}
 proc cp2_proof_input_roots(p: Cp2ProofInput, datasetRoot, slotRoot, entropy: ptr byte): cint {.importc.}
 proc cp2_proof_input_nsamples(p: Cp2ProofInput): csize_t {.importc.}

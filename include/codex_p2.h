@@ -43,8 +43,9 @@ extern "C" {
  *          1.2 = + cp2_proof_inputs_generate_many and cp2_proof_inputs_export_many (proof inputs across datasets).
  *          next: + cp2_dataset_scrub and cp2_multi_dataset_scrub (scrub), cp2_dataset_repair_blocks and
  *                cp2_multi_dataset_repair_blocks (repair), cp2_block_proof_depth, cp2_dataset_block_proofs, cp2_blocks_verify and
- *                cp2_dataset_repair_blocks_proved (block proofs).  MINOR stays 2 until the release that carries them: the bump to 1.3
- *                goes in its own commit with that release.                                                                           */
+ *                cp2_dataset_repair_blocks_proved (block proofs), cp2_fill_begin, cp2_fill_add, cp2_fill_missing, cp2_fill_finish and
+ *                cp2_fill_free (fill sessions).  MINOR stays 2 until the release that carries them: the bump to 1.3 goes in its own
+ *                commit with that release.                                                                                           */
 #define CP2_ABI_VERSION_MAJOR 1
 #define CP2_ABI_VERSION_MINOR 2
 #define CP2_ABI_VERSION ((CP2_ABI_VERSION_MAJOR << 16) | CP2_ABI_VERSION_MINOR)
@@ -581,6 +582,77 @@ int cp2_blocks_verify(cp2_ctx* ctx, size_t cell_size, size_t block_size, size_t 
 int cp2_dataset_repair_blocks_proved(cp2_dataset* ds, const uint64_t* slot_block /* n x 2: dataset slot, block of the slot */,
                                      const uint8_t* data /* n x block_size */, const uint8_t* paths /* n x depth x 32 */, size_t n,
                                      int flags, const char* cache_path, uint32_t* status /* n */, size_t* n_written);
+
+/* ---- fill sessions: slots filled from proved blocks in any order into a compact dataset ----------------------------------------------
+ * A node that takes on a slot holds only the manifest's slot root.  It receives the slot's network blocks from peers, in any order and
+ * over many round trips, each with its path.  cp2_blocks_verify can check them, but forgets the block roots it computed, and building
+ * the dataset afterwards (cp2_dataset_build) reads and hashes every byte a second time.  A compact dataset IS the tree over the block
+ * roots, so a session keeps each proved root where that tree has it and turns into a dataset when the last block has arrived.
+ *
+ * The handle: cp2_fill names the session in a caller's source; the entry points spell it `void*` (cp2_fill is void, so `cp2_fill* f;
+ * cp2_fill_begin(..., &f)` is exact), because the mechanical comparison of this header with the Nim binding knows a fixed set of
+ * handle types.  One context, whole sessions: free a session before its context.
+ *
+ * cp2_fill_begin opens a session for local slots [first_slot, first_slot + n_local) whose roots the caller states.
+ *   Checked    cfg, first_slot and n_local exactly as cp2_dataset_build checks them, nCells a power of two; CP2_ERR_INVALID otherwise, and
+ *              for a NULL argument.  A context whose stream will not drain is refused (CP2_ERR_HIP).
+ *   Source     cfg->file_base != NULL (SlotFile): proved blocks are written to "<file_base><slot>.dat".  file_base == NULL (fake source):
+ *              nothing is written and the finished dataset has the fake source of cfg->seed -- the analogue of CP2_REPAIR_CHECK_ONLY.
+ *   Memory     the compact layout of n_local slots (2 x nBlocks - 1 nodes of 32 bytes per slot), allocated once, plus the roots.  A host
+ *              bitmap of n_local x nBlocks bits is the authority on which blocks are present.
+ *   Roots      slot_roots: n_local x 32 bytes from the manifest; values >= r are reduced, as everywhere else.
+ *
+ * cp2_fill_add checks n blocks with their paths and keeps those that prove.
+ *   Data path  cp2_blocks_verify's, unchanged: chunks of half the context's staging, caller-pinned buffers read in place, the pinned ring
+ *              otherwise, each chunk's paths uploaded with it.  The last device step (k_block_path_commit) also stores the block root of
+ *              every candidate that reconstructs its slot root into layer 0 of the session's compact buffer.
+ *   Refused    before any device or file work, CP2_ERR_INVALID, the request index (where there is one) in cp2_last_error, outputs
+ *              untouched: a NULL session; a NULL array when n > 0 (n_new may be NULL); a slot outside the local range; a block >=
+ *              nBlocks; a session that has been finished.  n == 0: CP2_OK.
+ *   Result     status[i] = CP2_FILL_NEW, _MISMATCH, _DUPLICATE or _UNWRITTEN.  The same (slot, block) may appear twice in one call or
+ *              across calls (two peers may answer): the lowest proved index of the first call that proves it is NEW, every later proved
+ *              one is DUPLICATE and is not written again.  A wrong block or path is not an error: CP2_OK.
+ *   Write      repair's rules: the NEW blocks grouped by file in ascending offset order, missing files created, one fdatasync per file
+ *              and call.  The first file that cannot be opened, written or synced stops the writing: CP2_ERR_IO, its NEW blocks and
+ *              those of later files become CP2_FILL_UNWRITTEN, and so do their duplicates in the same call (never DUPLICATE for a block
+ *              that is still missing).
+ *   Presence   a block's bit is set only after its file has been synced (at once for the fake source), so an UNWRITTEN block stays
+ *              missing and can be sent again.  *n_new = the bits this call set.  CP2_TRACE prints one line per call.
+ *
+ * cp2_fill_missing: host only.  The lowest min(cap, *n_missing) absent (dataset slot, block) pairs in ascending order into `missing`;
+ * *n_missing = the number of all absent blocks.  cap == 0 with a NULL `missing` only counts.
+ *
+ * cp2_fill_finish turns a complete session into a dataset.
+ *   Refused    CP2_ERR_INVALID while any block is absent, cp2_last_error naming the count and the first missing pair; the session stays
+ *              usable.  Also for a session already finished.
+ *   Work       the upper layers of all n_local trees are built from layer 0 with the builders' layer kernel, one launch per layer over all
+ *              slots, and the top layer is compared on the device with the stated roots (a difference: CP2_ERR_IO naming the slot, no
+ *              dataset).  No slot byte is read or hashed.
+ *   Result     *out = a new cp2_dataset that owns the session's buffer (no copy): compact (cp2_dataset_keeps_trees == 2), source as begun.
+ *              It is an ordinary dataset: cp2_dataset_set_roots, proof inputs, cp2_proof_inputs_generate_many, scrub, repair and block
+ *              proofs work on it; free it with cp2_dataset_free.
+ *   Cache      with cache_path the kept form is saved first, under the name rule of cp2_dataset_build_cached (beside a tree cache, as
+ *              "<cache_path>.kept") and with the (size, mtime) stamps of the slot files as they stand: a later cp2_dataset_build_cached
+ *              of the same configuration, in any process, loads it instead of rebuilding.  A save that fails returns its status, no
+ *              dataset, and the session stays complete and usable.
+ *   After      a successful finish the session accepts only cp2_fill_free.
+ *
+ * Out of scope: cp2_multi_* (a session lives in one context); persisting or resuming a half-filled session; adopting blocks that are
+ * already on disk; fetching and erasure decoding, which stay with the caller. */
+typedef void cp2_fill;
+#define CP2_FILL_NEW        0  /* proved against the slot root, first time seen: root kept, block written            */
+#define CP2_FILL_MISMATCH   1  /* block + path do not reconstruct the slot root: nothing kept, nothing written       */
+#define CP2_FILL_DUPLICATE  2  /* proved, but the block is already present (earlier call, or a lower request index   */
+                               /* of this call): not written again                                                   */
+#define CP2_FILL_UNWRITTEN  3  /* proved and new, but its file could not be written or synced (call: CP2_ERR_IO)     */
+int cp2_fill_begin(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local,
+                   const uint8_t* slot_roots /* n_local x 32, from the manifest */, void** out /* cp2_fill** */);
+int cp2_fill_add(void* f /* cp2_fill* */, const uint64_t* slot_block /* n x 2: dataset slot, block */, const uint8_t* data /* n x blockSize */,
+                 const uint8_t* paths /* n x depth x 32 */, size_t n, uint32_t* status /* n */, size_t* n_new);
+int cp2_fill_missing(const void* f /* const cp2_fill* */, uint64_t* missing /* cap x 2: (slot, block), ascending */, size_t cap,
+                     uint64_t* n_missing);
+int cp2_fill_finish(void* f /* cp2_fill* */, const char* cache_path /* may be NULL */, cp2_dataset** out);
+void cp2_fill_free(void* f /* cp2_fill* */);
 
 /* replaces `writeCircomMainComponent`, reference/nim/proof_input/src/cli.nim:186-204 */
 int cp2_write_circom_main(const cp2_config* cfg, const char* path);
