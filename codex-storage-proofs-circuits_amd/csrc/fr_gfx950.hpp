@@ -13,7 +13,8 @@
 //   * mont_mul / mont_sqr with masked quotient digits accept limbs up to 2.47 U on either operand (column sum
 //       2^35 + 9*La*Lb + 9*U*U < 2^64 needs La*Lb < 6.1 U^2) and produce limbs 0..7 < U; value bound out < A*B/R + N;
 //   * with UNMASKED quotient digits (the S-box): the m*N part of a column is below 2^32 * 3.4005 U, operands up to
-//       2.02 U on a squaring, La*Lb < 4.09 U^2 on a product; value bound out < A*B/R + 8.01 N;
+//       2.02 U on a squaring, La*Lb < 4.088 U^2 on a product (the exact budget is 4.0884 U^2: (2^64 - 2^35 - (2^32 - 1) * 3.4005 U) / 9);
+//       value bound out < A*B/R + 8.01 N;
 //   * either way no conditional subtraction is ever needed inside a chain (lazy Montgomery): R = 169 N contracts
 //     x -> x^2/R + 8 N for everything below 160 N, and the S-box sees inputs below 60 N (poseidon2_dev.hpp);
 //   * y and z of the internal rounds are held in five 58-bit limbs (struct Wide) with 6 spare bits each.
@@ -160,7 +161,7 @@ __device__ __forceinline__ void tie_cols(acc_t& acc, uint32_t (&a)[NL], uint32_t
 // They are still correct modulo 2^29 (the column still clears), the extra bits only add multiples of N further up, so
 // the result is congruent and every output limb is still exact; what changes is its SIZE, out < A*B/R + 8.01 N instead of
 // + N, and the column budget: sum_j m_k N_j < 2^32 * (N_0 + .. + N_8) = 2^32 * 3.4005 U = 2^62.77, which leaves
-// 2^63.2 for the a*b products: limbs up to 2.02 U on a squaring, La * Lb < 4.09 U^2 on a product.  One v_and_b32 less
+// 2^63.2 for the a*b products: limbs up to 2.02 U on a squaring, La * Lb < 4.088 U^2 on a product.  One v_and_b32 less
 // per low column: 27 instructions per S-box, the only user (its values are re-bounded in poseidon2_dev.hpp).
 template <bool MASKM = true>
 __device__ __forceinline__ Fe mont_mul(const Fe& a_in, const Fe& b) {

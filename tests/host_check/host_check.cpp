@@ -1,6 +1,8 @@
 // Host build of the DEVICE arithmetic (csrc/fr_gfx950.hpp + csrc/poseidon2_dev.hpp with CP2_HOST_CHECK):
 // runs the very same source on the CPU with a 128-bit shadow accumulator and asserted limb bounds, under
 // -fsanitize=address,undefined, on random and adversarial states, and compares every result with the C oracle.
+// Whole permutations only: their intermediates are pseudorandom, so the documented extremes of the single primitives are met
+// by tests/device_check (fr_unit_ops.hpp: one function at a time on raw limbs), not here.
 // Usage: host_check <n_random> ; exits non-zero on any mismatch or bound violation.
 #define CP2_HOST_CHECK 1
 #include <cstdint>
