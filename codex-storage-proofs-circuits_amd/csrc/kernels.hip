@@ -1009,6 +1009,8 @@ hipError_t launch_sample_paths(const TreeGeom& g, const void* nodes, const void*
 
 hipError_t launch_gather_rows(const void* src, const uint64_t* index, size_t nrows, size_t row_bytes, void* out, hipStream_t st) {
   if (nrows == 0) return hipSuccess;
+  // the kernel moves whole 32-bit words: a row length or a pointer that is no multiple of four is refused, not truncated
+  if ((row_bytes & 3) != 0 || ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(out)) & 3) != 0) return hipErrorInvalidValue;
   size_t work = nrows * (row_bytes / 4);
   unsigned grid = work > (size_t)4096 * TPB ? 4096u : grid_for(work);
   CP2K_LAUNCH(k_gather_rows, dim3(grid), dim3(TPB), 0, st, (const uint8_t*)src, index, nrows, row_bytes, (uint8_t*)out);

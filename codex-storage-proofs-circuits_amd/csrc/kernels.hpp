@@ -50,6 +50,8 @@ hipError_t launch_gen_fake_cells(uint64_t seed0, uint64_t cells_per_slot, uint64
 hipError_t launch_sample_paths(const TreeGeom& g, const void* nodes, const void* d_entropy, const uint64_t* slots, uint64_t slot0,
                                size_t n_items, uint32_t ns, uint32_t md, uint64_t* indices, uint64_t* gcell, uint64_t* rows,
                                hipStream_t st);
+// out[r] = row index[r] of src (row_bytes bytes each), zeros where index[r] is ~0.  Whole 32-bit words: hipErrorInvalidValue, and
+// nothing launched, when row_bytes is no multiple of 4 or src / out are not 4-byte aligned.
 hipError_t launch_gather_rows(const void* src, const uint64_t* index, size_t nrows, size_t row_bytes, void* out,
                               hipStream_t st);
 

@@ -1,0 +1,250 @@
+"""CPU suite: the models of tests/kernel_models.py against oracle/poseidon2_ref.py, the case plans of tests/test_gpu_kernel_units.py
+against what that module says it covers, and the build of tests/device_check/libkernel_unit.so."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import kernel_models as K
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG_DIR = os.path.join(ROOT, "codex-storage-proofs-circuits_amd")
+
+
+# ---- the models --------------------------------------------------------------------------------------------------------------------
+SMALL_TREES = [(cpb, nblocks) for cpb in (1, 2, 3, 4, 5) for nblocks in (1, 2, 3, 5, 8)]
+
+
+def small_slot_trees(P, cpb, nblocks, n_slots):
+    """Per slot (mini trees, big tree) over small distinct leaves, and the node table laid out as TreeGeom documents it."""
+    g = K.tree_geom(cpb, nblocks, cpb * nblocks, n_slots)
+    nodes, trees = {}, []
+    for s in range(n_slots):
+        mini = [P.merkle_tree([1000003 * s + 1009 * b + i + 1 for i in range(cpb)]) for b in range(nblocks)]
+        big = P.merkle_tree([t[-1][0] for t in mini])
+        trees.append((mini, big))
+        for b, t in enumerate(mini):
+            for k, layer in enumerate(t[:-1]):
+                for i, v in enumerate(layer):
+                    nodes[g.boff[k] + (s * nblocks + b) * g.bsz[k] + i] = v
+        for k, layer in enumerate(big):
+            for i, v in enumerate(layer):
+                nodes[g.toff[k] + s * g.tsz[k] + i] = v
+    assert sorted(nodes) == list(range(g.total_rows))                 # the layout has no hole and no overlap
+    assert len(set(nodes.values())) == len(nodes)                       # a value names its node
+    return g, nodes, trees
+
+
+@pytest.mark.parametrize("cpb,nblocks", SMALL_TREES)
+def test_path_rows_model_picks_the_nodes_of_the_merged_padded_proof(oracle, cpb, nblocks):
+    _, P = oracle
+    g, nodes, trees = small_slot_trees(P, cpb, nblocks, 2)
+    depth = K.path_depth(g)
+    for s, (mini, big) in enumerate(trees):
+        assert nodes[K.root_row(g, s)] == big[-1][0]
+        for cell in range(cpb * nblocks):
+            bot = P.merkle_proof(mini[cell // cpb], cell % cpb)
+            top = P.merkle_proof(big, cell // cpb)
+            merged = P.merge_merkle_proofs(bot, top)
+            assert merged["leafIndex"] == cell
+            want = P.pad_merkle_proof(merged, depth + 3)["merklePath"]
+            for md in (depth - 1, depth, depth + 3):
+                rows = K.path_rows_model(g, s, cell, md)
+                assert [0 if r == K.PAD_ROW else nodes[r] for r in rows] == want[:md], (s, cell, md)
+                addr, leaf = K.path_addr_model(g, 4096, s, cell, md)
+                assert addr == [0 if r == K.PAD_ROW else 4096 + 32 * r for r in rows]
+                assert leaf == 4096 + 32 * (s * g.n_cells + cell)
+
+
+@pytest.mark.parametrize("n_blocks", (1, 2, 3, 5, 6, 7, 8, 9))
+def test_walk_model_is_reconstruct_root(oracle, n_blocks):
+    _, P = oracle
+    layers = P.merkle_tree([77 * i + 5 for i in range(n_blocks)])
+    for b in range(n_blocks):
+        proof = P.merkle_proof(layers, b)
+        assert K.walk_model(proof["leafValue"], b, n_blocks, proof["merklePath"], P.compress) == P.reconstruct_root(proof) == layers[-1][0]
+        for wrong in (b - 1, b + 1):
+            if 0 <= wrong < n_blocks:
+                assert K.walk_model(proof["leafValue"], wrong, n_blocks, proof["merklePath"], P.compress) == P.reconstruct_root(dict(proof, leafIndex=wrong))
+
+
+def test_tree_geom_layer_sizes():
+    assert K.layer_sizes(1) == [1, 1] and K.layer_sizes(2) == [2, 1] and K.layer_sizes(5) == [5, 3, 2, 1]
+    g = K.tree_geom(4, 3, 12, 2)
+    assert (g.nb, g.nt, g.bsz, g.tsz) == (3, 3, [4, 2, 1], [3, 2, 1])
+    assert g.boff == [0, 24, 36] and g.toff == [36, 42, 46] and g.total_rows == 48       # the block roots are layer 0 of the big trees
+
+
+def test_scrub_model_by_hand():
+    rng = np.random.default_rng(5)
+    fresh = rng.integers(0, 256, size=(5 * 3, 32), dtype=np.uint8)
+    kept = rng.integers(0, 256, size=(7 * 3, 32), dtype=np.uint8)
+    for item in range(3):
+        kept[7 * item:7 * item + 3] = fresh[5 * item:5 * item + 3]
+    kept[7 * 1 + 2, 31] ^= 0x80              # item 1 row 2: g = 5
+    fresh[5 * 2 + 0, 0] ^= 1                 # item 2 row 0: g = 6
+    bits, counts = K.scrub_model(fresh, kept, 3, 5, 7, 3)
+    assert bits.size == K.SCRUB_TILE // 64 and bits[0] == (1 << 5) | (1 << 6) and not bits[1:].any() and counts.tolist() == [2]
+    bits, counts = K.scrub_model(fresh[:4097].repeat(300, axis=0)[:4097], np.zeros((4097, 32), np.uint8), 4097, 4097, 4097, 1)
+    assert bits.size == 2 * K.SCRUB_TILE // 64 and counts.tolist() == [4096, 1] and bits[64] == 1 and not bits[65:].any()
+
+
+def test_batched_compress_is_the_oracles_compress(oracle):
+    """The layer test takes its expected rows from the C oracle's permutation over (x, y, key) states, many at a time; that is its compress."""
+    C, P = oracle
+    rng = np.random.default_rng(11)
+    xy = rng.integers(0, 256, size=(8, 2, 32), dtype=np.uint8)
+    xy[:, :, 31] &= 0x1F
+    for i in range(8):
+        key = i % 4
+        state = np.concatenate([xy[i, 0], xy[i, 1], C.felt_bytes(key)])
+        got = C.permute_batch(state.reshape(1, 96))[0, :32]
+        assert np.array_equal(got, C.compress(xy[i, 0], xy[i, 1], key))
+        x, y = (int.from_bytes(xy[i, j].tobytes(), "little") for j in (0, 1))
+        assert int.from_bytes(got.tobytes(), "little") == P.compress(x, y, key)
+
+
+# ---- the plans ---------------------------------------------------------------------------------------------------------------------
+def test_scrub_plan():
+    cases = K.scrub_plan()
+    dense = [c for c in cases if c.fstride == c.rows == c.kstride]
+    assert {c.rows * c.n_items for c in dense if c.n_items == 1} == set(K.SCRUB_TOTALS)
+    assert {c.rows * c.n_items for c in dense if c.n_items > 1} >= {63, 64, 65, 255, 256, 4095, 4096, 4097, 8192}
+    assert {(c.rows, c.fstride, c.kstride) for c in cases if not (c.fstride == c.rows == c.kstride)} == {(1, 1, 2), (3, 5, 7), (4097, 4100, 4097), (64, 64, 65)}
+    assert {c.n_items for c in cases if (c.rows, c.kstride) == (1, 2)} == set(K.SCRUB_TOTALS)
+    tile = K.SCRUB_TILE
+    for layout in K.SCRUB_STRIDED:                                      # each strided layout crosses a tile seam, three of them end in a partial wave
+        totals = {c.rows * c.n_items for c in cases if (c.rows, c.fstride, c.kstride) == layout}
+        assert any(t > tile for t in totals) and (layout[0] == 64 or any(t % 64 for t in totals)), layout
+    by_layout = {}
+    for c in cases:
+        by_layout.setdefault((c.rows, c.fstride, c.kstride, c.n_items), set()).add(c.planted)
+    for (rows, fs, ks, n), planted in by_layout.items():
+        want = {"none", "all", "row0", "last", "1%"} | ({"63/64"} if rows * n > 63 else set()) | ({"4095/4096"} if rows * n > 4095 else set())
+        assert planted == want, (rows, fs, ks, n)
+    used, small, sides = set(), set(), set()
+    for c in cases:
+        rows = K.scrub_planted_rows(c)
+        bit, side = K.scrub_planted_bits(c)
+        assert rows.size == bit.size == side.size and np.unique(rows).size == rows.size and (rows.size == 0 or rows.max() < c.rows * c.n_items)
+        used |= set(bit.tolist())
+        if c.planted in ("row0", "last", "63/64", "4095/4096"):         # one or two rows: a dropped XOR term cannot hide behind another row
+            small |= set(bit.tolist())
+        sides |= set(side.tolist())
+    assert used == set(range(256)) and sides == {0, 1}
+    assert {b // 32 for b in small} == set(range(8)) and len(small) >= 128
+    assert [c.no for c in cases] == list(range(len(cases)))
+
+
+def test_repair_plan():
+    cases = K.repair_plan()
+    assert {(c.n, c.kind, c.tail) for c in cases} == {(n, k, t) for n in (1, 63, 64, 65, 257, 1000) for k in ("permutation", "repeats") for t in ("plain", "last", "bound")}
+    words = set()
+    for c in cases:
+        flips = K.repair_flips(c)
+        assert all(0 <= i < c.n for i, _ in flips) and not (c.tail == "bound" and any(i == c.n - 1 for i, _ in flips))
+        words |= {bit // 32 for _, bit in flips}
+    assert words == set(range(8))
+    assert {bit for c in cases for _, bit in K.repair_flips(c)} == set(range(256))
+    assert any(K.repair_flips(c) for c in cases if c.n == 1) and any(not K.repair_flips(c) for c in cases if c.n == 1)
+
+
+def test_sample_plan():
+    cases = K.sample_plan()
+    assert {(c.cpb, c.nblocks) for c in cases if c.n_cells == c.cpb * c.nblocks} == {(a, b) for a in (1, 2, 4, 32) for b in (1, 2, 64, 1 << 15)}
+    odd = {(c.cpb, c.nblocks, c.n_cells) for c in cases if c.n_cells != c.cpb * c.nblocks}
+    assert odd and all(n & (n - 1) == 0 and n < a * b for a, b, n in odd)
+    assert any(any(m % 2 for m in K.layer_sizes(b)[:-1]) for a, b, n in odd) and any(any(m % 2 and m > 1 for m in K.layer_sizes(a)[:-1]) for a, b, n in odd)
+    assert {c.ns for c in cases} == {1, 5, 100} and {c.ns * c.n_items for c in cases} >= {1, 255, 256, 257}
+    assert all(c.n_slots == 3 for c in cases if c.form == "list" or c.n_items <= 3)
+    depth = {(c.cpb, c.nblocks): K.path_depth(K.tree_geom(c.cpb, c.nblocks, c.cpb * c.nblocks, 3)) for c in cases}
+    assert min(depth.values()) > 1
+    for geo in depth:
+        mine = [c for c in cases if (c.cpb, c.nblocks) == geo]
+        assert {c.md - depth[geo] for c in mine} == {-1, 0, 3} and {c.form for c in mine} == {"list", "range"}
+        assert {(c.ns, c.n_items) for c in mine} >= set(K.SAMPLE_LANES)
+    for lanes in K.SAMPLE_LANES:
+        mine = [c for c in cases if (c.ns, c.n_items) == lanes]
+        assert {c.md - depth[(c.cpb, c.nblocks)] for c in mine} == {-1, 0, 3}
+        assert {c.form for c in mine if c.n_slots == 3} == ({"list", "range"} if lanes[1] <= 3 else {"list"})
+    big_range = [c for c in cases if c.form == "range" and c.n_items > 3]
+    assert {c.n_items for c in big_range} == {255, 256, 257} and all(c.nblocks <= 64 and c.slot0 + c.n_items == c.n_slots for c in big_range)
+    assert all(c.slot0 + c.n_items <= c.n_slots for c in cases if c.form == "range")
+    assert max(K.tree_geom(c.cpb, c.nblocks, c.n_cells, c.n_slots).total_rows for c in cases) * 32 <= 256 << 20     # what the node buffer takes
+    cp = K.compact_plan()
+    assert {n for n, _ in cp} == {1 << 31, 1 << 32, 1 << 33, 1 << 40, 1 << 63}
+    for n in K.COMPACT_N_CELLS:
+        cpbs = {c for m, c in cp if m == n}
+        assert any(c % 2 == 1 and c > 1 for c in cpbs) and any(c > 1 and c & (c - 1) == 0 for c in cpbs)
+    assert K.reaches_high(1 << 32, 1 << 33) and not K.reaches_high((1 << 32) - 1, 1 << 33)
+    assert K.reaches_high(1 << 31, 1 << 32) and not K.reaches_high((1 << 31) - 1, 1 << 32) and K.reaches_high(1 << 30, 1 << 31)
+
+
+def test_gather_plans():
+    rows = K.gather_rows_plan()
+    assert {w for w, _ in rows} == {4, 32, 36, 2048}
+    for w in K.GATHER_ROWS_WIDTHS:
+        assert any(n * (w // 4) > K.GRID_WORDS for ww, n in rows if ww == w) and any(n * (w // 4) <= 512 for ww, n in rows if ww == w)
+    assert (32, 131073) in rows
+    addr = K.gather_addr_plan()
+    assert {(w, a) for w, a, _ in addr} >= {(w, a) for w in (1, 3, 31, 32, 33, 100, 2048, 2050) for a in (0, 1, 2)}
+    over = {K.gather_addr_wordwise(w, a) for w, a, n in addr if n * (w // 4 if K.gather_addr_wordwise(w, a) else w) > K.GRID_WORDS}
+    assert over == {True, False}
+    assert max(n * w for w, a, n in addr) <= 8 << 20 and max(n * w for w, n in rows) <= 8 << 20
+
+
+def test_layer_plan():
+    plan = K.layer_plan()
+    assert {(m, s, b) for m, s, b, _, _ in plan} == {(m, s, b) for m in (1, 2, 3, 4, 5, 255, 256, 257, 511, 513) for s in (1, 3, 257) for b in (0, 1)}
+    for (m, s, b) in {(m, s, b) for m, s, b, _, _ in plan}:
+        gaps = {(i - m, o - (m + 1) // 2) for mm, ss, bb, i, o in plan if (mm, ss, bb) == (m, s, b)}
+        assert gaps >= {(0, 0), (1, 1), (5, 5)}
+    assert any(s == 257 and m % 2 == 1 and i > m and o > (m + 1) // 2 for m, s, b, i, o in plan)        # many segments, an odd tail in each, gaps
+
+
+def test_fake_many_plan():
+    plan = K.fake_many_plan()
+    assert set(plan) == {(p, n, c, a) for p in (1, 3, 100) for n in (1, 63, 64, 65, 257, 301) for c in (1, 127, 128, 2048, 2049) for a in (0, 4, 1)}
+    assert any(n % p for p, n, _, _ in plan if p > 1)                                                      # a partial last group
+    groups = [K.fake_group(g) for g in range(301)]
+    assert len(set(groups)) == 301 and len({s for s, _ in groups}) == 301
+    assert any(f < (1 << 32) <= f + 99 for _, f in groups) and any(f < (1 << 32) <= f + 2 for _, f in groups)
+    assert all(0 <= s < (1 << 64) and f + 100 < (1 << 64) for s, f in groups)
+
+
+def test_walk_plan():
+    assert K.WALK_N_BLOCKS == tuple(range(1, 18)) + (31, 32, 33)
+    for n in K.WALK_N_BLOCKS:
+        depth = len(K.layer_sizes(n)) - 1
+        reqs = K.walk_plan(n)
+        for b in range(n):
+            mine = [r for r in reqs if r.block == b]
+            assert {r.root for r in mine if r.kind == "true"} == {0, 1}
+            assert sorted(r.level for r in mine if r.kind == "sibling") == list(range(depth))
+            assert sum(r.kind == "fresh" for r in mine) == 1 and sum(r.kind == "other root" for r in mine) == 1
+            assert {r.index for r in mine if r.kind == "neighbour"} == {x for x in (b - 1, b + 1) if 0 <= x < n}
+            assert all(r.index == b for r in mine if r.kind != "neighbour")
+
+
+# ---- the check library -------------------------------------------------------------------------------------------------------------
+def dynamic_symbols(path, defined):
+    out = subprocess.check_output(["nm", "-D", "--defined-only" if defined else "--undefined-only", path], text=True)
+    return {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
+
+
+def test_check_library_builds_and_forwards_to_the_product(pkg):
+    """make builds it (hipcc for gfx950, the product's flags); it defines the ku_ forwarders and takes every launcher from
+    libcodex_p2.so, whose code objects are therefore the ones that run."""
+    subprocess.check_call(["make", "-C", PKG_DIR, "../tests/device_check/libkernel_unit.so"], stdout=subprocess.DEVNULL)
+    lib = os.path.join(ROOT, "tests", "device_check", "libkernel_unit.so")
+    launchers = ("scrub_compare", "repair_compare", "sample_paths", "sample_many", "gather_rows", "gather_addr", "gen_fake_cells_many",
+                 "compress_layer", "block_path_roots", "block_path_commit")
+    mine, wanted, product = dynamic_symbols(lib, True), dynamic_symbols(lib, False), dynamic_symbols(pkg.LIB_PATH, True)
+    assert {"ku_" + n for n in launchers} | {"ku_sizeof_tree_geom", "ku_sizeof_many_req", "ku_scrub_tile"} <= mine
+    for n in launchers:
+        sym = [s for s in wanted if s.startswith("_ZN4cp2k%d%s" % (len("launch_" + n), "launch_" + n))]
+        assert len(sym) == 1 and sym[0] in product, n
+    assert not [s for s in mine if "cp2k" in s or s.startswith("cp2_")]
+    needed = subprocess.check_output(["readelf", "-d", lib], text=True)
+    assert "libcodex_p2.so." in needed and "$ORIGIN/../../codex-storage-proofs-circuits_amd" in needed
