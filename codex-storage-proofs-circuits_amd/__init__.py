@@ -227,6 +227,8 @@ def load_library():
         "cp2_fill_missing": (i32, [vp, vp, sz, ctypes.POINTER(u64)]),
         "cp2_fill_finish": (i32, [vp, cp, pvp]),
         "cp2_fill_free": (None, [vp]),
+        "cp2_fill_save": (i32, [vp, cp]),
+        "cp2_fill_resume": (i32, [vp, ctypes.POINTER(Config), u64, u64, vp, cp, i32, pvp, ctypes.POINTER(u64)]),
     }
     for name, (res, args) in sigs.items():
         if v is None and name == "cp2_abi_version":
@@ -503,6 +505,11 @@ class Context:
     def fill(self, cfg, slot_roots, first_slot=0, n_local=None):
         """cp2_fill_begin: a session that fills local slots [first_slot, + n_local) from proved network blocks (FillSession)"""
         return FillSession(self, cfg, slot_roots, first_slot, cfg.n_slots - first_slot if n_local is None else n_local)
+
+    def fill_resume(self, cfg, slot_roots, path, first_slot=0, n_local=None, trust_files=False):
+        """cp2_fill_resume: the session saved at `path` (FillSession.save), every block it calls present re-checked on the device against what
+        the source holds now unless trust_files; the session's `n_dropped` says how many blocks the disk no longer backs"""
+        return FillSession.resume(self, cfg, slot_roots, path, first_slot, cfg.n_slots - first_slot if n_local is None else n_local, trust_files)
 
     def dataset(self, cfg, first_slot=0, n_local=None, cache=None):
         return Dataset(self, cfg, first_slot, cfg.n_slots if n_local is None else n_local, cache)
@@ -835,6 +842,7 @@ class Dataset:
 
 
 FILL_NEW, FILL_MISMATCH, FILL_DUPLICATE, FILL_UNWRITTEN = 0, 1, 2, 3   # CP2_FILL_* (include/codex_p2.h): the per-request results of cp2_fill_add
+RESUME_TRUST_FILES = 1                                                 # CP2_RESUME_TRUST_FILES: cp2_fill_resume reads no slot byte
 
 
 class FillSession:
@@ -849,7 +857,27 @@ class FillSession:
         h = ctypes.c_void_p()
         ctx._ck(ctx.L.cp2_fill_begin(ctx.h, ctypes.byref(cfg), first_slot, n_local, _p(r) if r.size else None, ctypes.byref(h)), "cp2_fill_begin")
         self.h = h
+        self.n_dropped = 0
         ctx._children.add(self)
+
+    @classmethod
+    def resume(cls, ctx, cfg, slot_roots, path, first_slot, n_local, trust_files=False):
+        """cp2_fill_resume: a session around the checkpoint at `path`; n_dropped = the blocks the re-check took back"""
+        r = _u8(slot_roots).reshape(-1, 32)
+        if r.shape[0] != n_local:
+            raise ValueError("fill: %d local slot(s) need %d roots, got %d" % (n_local, n_local, r.shape[0]))
+        f = cls.__new__(cls)
+        f.ctx, f.cfg, f.first_slot, f.n_local, f.h = ctx, cfg, first_slot, n_local, None
+        h, dropped = ctypes.c_void_p(), ctypes.c_uint64()
+        ctx._ck(ctx.L.cp2_fill_resume(ctx.h, ctypes.byref(cfg), first_slot, n_local, _p(r) if r.size else None, os.fsencode(path),
+                                      RESUME_TRUST_FILES if trust_files else 0, ctypes.byref(h), ctypes.byref(dropped)), "cp2_fill_resume")
+        f.h, f.n_dropped = h, dropped.value
+        ctx._children.add(f)
+        return f
+
+    def save(self, path):
+        """cp2_fill_save: a checkpoint of this unfinished session at `path` (written beside it and renamed)"""
+        self.ctx._ck(self.ctx.L.cp2_fill_save(self.h, os.fsencode(path)), "cp2_fill_save")
 
     def free(self):
         if self.h:

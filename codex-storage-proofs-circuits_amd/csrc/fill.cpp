@@ -1,4 +1,5 @@
-// Fill sessions behind the C ABI (include/codex_p2.h): cp2_fill_begin, cp2_fill_add, cp2_fill_missing, cp2_fill_finish, cp2_fill_free.
+// Fill sessions behind the C ABI (include/codex_p2.h): cp2_fill_begin, cp2_fill_add, cp2_fill_missing, cp2_fill_finish, cp2_fill_free, and
+// their checkpoints: cp2_fill_save, cp2_fill_resume.
 //
 // A node that takes on a slot holds the manifest's slot root and receives the slot's network blocks from peers, in any order, each with
 // its Merkle path.  cp2_blocks_verify checks such blocks and forgets the block roots it computed; a session KEEPS them.  It owns the compact
@@ -8,11 +9,20 @@
 // present; the proved blocks are written into the slot files by repair's writer.  When nothing is missing, finish builds the upper
 // layers with the layer kernel (one launch per layer over all slots), compares the top layer with the stated roots and hands the buffer
 // to a new compact dataset: no slot byte is read or hashed a second time.
+//
+// A session lives for as long as its blocks take to arrive, so it can be saved at any point (cp2_fill_save: geometry, source, stated roots,
+// bitmap and layer 0 under a checksum, fill_checkpoint.hpp) and resumed by a later process (cp2_fill_resume).  Resume trusts the disk only as
+// far as the device has re-checked it: every block the checkpoint calls present is read back (or, fake source, regenerated), hashed and
+// reduced to its block root by the builders' kernels on repair's data path, and k_block_root_recheck compares that root with the row of
+// layer 0 the checkpoint kept, zeroing the row where they differ; the host clears those blocks' bits, and they are missing again.
 #include <hip/hip_runtime.h>
 
 #include <fcntl.h>
+#include <sys/stat.h>
 #include <unistd.h>
 
+#include <algorithm>
+#include <cerrno>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -24,6 +34,7 @@
 
 #include "block_proof_plan.hpp"
 #include "dataset_obj.hpp"
+#include "fill_checkpoint.hpp"
 #include "fill_plan.hpp"
 #include "repair.hpp"
 
@@ -43,6 +54,7 @@ struct cp2_fill_session {
   FillPlan plan;
   DevBuf compact;                       // the compact layout of the local slots; becomes the dataset's buffer in finish
   DevBuf slot_roots;                    // the stated roots, canonical: n_local x 32 bytes
+  std::vector<uint8_t> roots;           // ... and on the host, for a checkpoint
 };
 
 namespace {
@@ -89,9 +101,8 @@ void fill_trace(size_t n, const uint32_t* status, size_t n_new, size_t block_siz
 
 }  // namespace
 
-extern "C" int cp2_fill_begin(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local, const uint8_t* slot_roots, void** out) try {
-  if (!ctx || !cfg || !out) return CP2_ERR_INVALID;
-  *out = nullptr;
+// what cp2_fill_begin and cp2_fill_resume ask of (cfg, first_slot, n_local, slot_roots) before anything is allocated
+static int session_check(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local, const uint8_t* slot_roots) {
   CP2_REFUSE_STUCK(ctx);
   std::string err;
   if (!fill_check_range(cfg->n_slots, first_slot, n_local, cfg->max_depth, cfg->max_log2_nslots, cfg->n_cells, cfg->cell_size,
@@ -108,6 +119,12 @@ extern "C" int cp2_fill_begin(cp2_ctx* ctx, const cp2_config* cfg, uint64_t firs
     ctx->err = "fill: slot_roots must not be NULL";
     return CP2_ERR_INVALID;
   }
+  return CP2_OK;
+}
+
+// the session of a checked (cfg, first_slot, n_local, slot_roots): the plan, the compact buffer (as allocated) and the roots on the device
+static int session_open(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local, const uint8_t* slot_roots,
+                        std::unique_ptr<cp2_fill_session>* out) {
   CP2_HIP(ctx, hipSetDevice(ctx->device));
   std::unique_ptr<cp2_fill_session> f(new (std::nothrow) cp2_fill_session());
   if (!f) return CP2_ERR_ALLOC;
@@ -119,10 +136,20 @@ extern "C" int cp2_fill_begin(cp2_ctx* ctx, const cp2_config* cfg, uint64_t firs
   f->plan.init(first_slot, n_local, cfg->n_cells / (cfg->block_size / cfg->cell_size));
   CP2_TRY(f->compact.alloc(ctx, f->plan.rows * 32));            // what a compact dataset of these slots holds, once
   CP2_TRY(f->slot_roots.alloc(ctx, n_local * 32));
-  std::vector<uint8_t> roots(n_local * 32);                      // values of at least r are reduced, as everywhere else
-  for (uint64_t s = 0; s < n_local; ++s) canonical_felt(slot_roots + s * 32, &roots[s * 32]);
-  CP2_HIP(ctx, hipMemcpyAsync(f->slot_roots.p, roots.data(), roots.size(), hipMemcpyHostToDevice, ctx->stream));
+  f->roots.resize(n_local * 32);                                 // values of at least r are reduced, as everywhere else
+  for (uint64_t s = 0; s < n_local; ++s) canonical_felt(slot_roots + s * 32, &f->roots[s * 32]);
+  CP2_HIP(ctx, hipMemcpyAsync(f->slot_roots.p, f->roots.data(), f->roots.size(), hipMemcpyHostToDevice, ctx->stream));
   CP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  *out = std::move(f);
+  return CP2_OK;
+}
+
+extern "C" int cp2_fill_begin(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local, const uint8_t* slot_roots, void** out) try {
+  if (!ctx || !cfg || !out) return CP2_ERR_INVALID;
+  *out = nullptr;
+  CP2_TRY(session_check(ctx, cfg, first_slot, n_local, slot_roots));
+  std::unique_ptr<cp2_fill_session> f;
+  CP2_TRY(session_open(ctx, cfg, first_slot, n_local, slot_roots, &f));
   *out = f.release();
   return CP2_OK;
 } catch (const std::bad_alloc&) {
@@ -277,6 +304,296 @@ extern "C" int cp2_fill_finish(void* fill, const char* cache_path, cp2_dataset**
                  (unsigned long long)plan.n_blocks, plan.csizes.size() - 1,
                  std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3, cache_path ? ", kept form saved" : "");
   *out = ds.release();
+  return CP2_OK;
+} catch (const std::bad_alloc&) {
+  return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
+} catch (...) {
+  return CP2_ERR_INVALID;
+}
+
+// ---- checkpoints ------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+FillCkptMeta session_meta(const cp2_fill_session* f) {
+  FillCkptMeta m;
+  const cp2_config& c = f->cfg;
+  m.cell_size = c.cell_size; m.block_size = c.block_size; m.n_cells = c.n_cells; m.n_slots = c.n_slots;
+  m.first_slot = f->plan.first_slot; m.n_local = f->plan.n_local;
+  m.src = f->from_file ? FILL_SRC_FILE : FILL_SRC_FAKE;
+  m.seed = c.seed;
+  m.file_base = f->file_base;
+  m.roots = f->roots;
+  return m;
+}
+
+bool write_all(int fd, const uint8_t* p, size_t n) {
+  while (n) {
+    const ssize_t w = write(fd, p, n);
+    if (w < 0 && errno == EINTR) continue;
+    if (w <= 0) return false;
+    p += w; n -= (size_t)w;
+  }
+  return true;
+}
+
+// the whole checkpoint file in memory, its size checked against what its header states before the buffer is sized
+int read_checkpoint(cp2_ctx* ctx, const char* path, FillCheckpoint* ck) {
+  const std::string name(path);
+  const int fd = open(path, O_RDONLY | O_CLOEXEC);
+  if (fd < 0) {
+    ctx->err = "fill: cannot open checkpoint " + name + ": " + std::strerror(errno);
+    return CP2_ERR_IO;
+  }
+  struct Closer { int fd; ~Closer() { close(fd); } } closer{fd};
+  struct stat sb;
+  if (fstat(fd, &sb) != 0) {
+    ctx->err = "fill: cannot stat checkpoint " + name + ": " + std::strerror(errno);
+    return CP2_ERR_IO;
+  }
+  const size_t size = (size_t)sb.st_size;
+  uint8_t fixed[FILL_CKPT_FIXED] = {};
+  std::string why;
+  FillCkptMeta m;
+  FillCkptLayout l;
+  const size_t head = std::min(size, sizeof fixed);
+  const int eh = head ? slot_file_read_rest(fd, fixed, head, 0) : 0;
+  if (eh) {
+    ctx->err = "fill: cannot read checkpoint " + name + ": " + std::strerror(eh);
+    return CP2_ERR_IO;
+  }
+  bool ok = fill_ckpt_fixed(fixed, size, &m, &l, &why);
+  if (ok && size != l.size) {
+    why = size < l.size ? "is truncated: " + std::to_string(size) + " bytes of " + std::to_string(l.size) : "is corrupt: longer than its header states";
+    ok = false;
+  }
+  if (!ok) {
+    ctx->err = "fill: checkpoint " + name + " " + why;
+    return CP2_ERR_IO;
+  }
+  std::vector<uint8_t> buf(size);
+  const int e = slot_file_read_rest(fd, buf.data(), size, 0);
+  if (e) {
+    ctx->err = "fill: cannot read checkpoint " + name + ": " + std::strerror(e);
+    return CP2_ERR_IO;
+  }
+  if (!fill_ckpt_parse(buf.data(), size, ck, &why)) {
+    ctx->err = "fill: checkpoint " + name + " " + why;
+    return CP2_ERR_IO;
+  }
+  return CP2_OK;
+}
+
+// The blocks of plan entries [i0, i0 + m) of a fake-source session regenerated on the device and reduced to their block roots as
+// repair_check_with reduces candidate blocks (cells hashed, one tree segment per block), verdicts by k_block_root_recheck.  Everything is
+// queued on the context's stream; d_seeds / d_firsts / d_dest hold the whole plan.
+int recheck_fake_chunk(cp2_fill_session* f, size_t i0, size_t m, const uint64_t* d_seeds, const uint64_t* d_firsts, const uint64_t* d_dest,
+                       DevBuf& d_cells, DevBuf& d_nodes, uint32_t* d_verdict, size_t below_root) {
+  cp2_ctx* ctx = f->ctx;
+  const cp2_config& c = f->cfg;
+  const size_t cpb = c.block_size / c.cell_size;
+  CP2_HIP(ctx, cp2k::launch_gen_fake_cells_many(d_seeds + i0, d_firsts + i0, cpb, m * cpb, c.cell_size, d_cells.p, ctx->stream));
+  CP2_HIP(ctx, cp2k::launch_hash_cells(d_cells.p, c.cell_size, m * cpb, d_nodes.p, ctx->stream));
+  CP2_TRY(merkle_trees_dev(ctx, d_nodes.p, cpb, m, d_nodes.p, true));
+  CP2_HIP(ctx, cp2k::launch_block_root_recheck(d_nodes.u8() + below_root * m * 32, d_dest + i0, m, d_verdict + i0, f->compact.p, f->plan.total(), ctx->stream));
+  return CP2_OK;
+}
+
+// Every block the session calls present against what its source holds now; the global indices of those that no longer hash to their kept
+// root are appended to `dropped` (their rows of layer 0 are zeros by then).  *bytes = what was read or regenerated.
+int recheck_present(cp2_fill_session* f, std::vector<uint64_t>* dropped, uint64_t* n_read, double* bytes) {
+  cp2_ctx* ctx = f->ctx;
+  const cp2_config& c = f->cfg;
+  const FillPlan& plan = f->plan;
+  const size_t bs = c.block_size, cpb = bs / c.cell_size;
+  const size_t chunk = std::max<size_t>(1, (ctx->stage_bytes / 2) / bs);          // repair_check_with's chunks
+  const FillReadPlan rp = fill_read_plan(plan.bits, plan.total(), plan.n_blocks, chunk);
+  const size_t n = rp.g.size();
+  *n_read = n;
+  *bytes = (double)n * (double)bs;
+  if (n == 0) return CP2_OK;
+  std::vector<uint32_t> verdict(n);
+  if (!f->from_file) {
+    std::vector<uint64_t> seeds(n), firsts(n);
+    for (size_t i = 0; i < n; ++i) {
+      seeds[i] = cp2_slot_seed(c.seed, plan.first_slot + rp.g[i] / plan.n_blocks);
+      firsts[i] = (rp.g[i] % plan.n_blocks) * cpb;
+    }
+    const std::vector<size_t> sizes = layer_sizes_of(cpb);
+    size_t below_root = 0, per_block = 0;
+    for (size_t j = 0; j < sizes.size(); ++j) {
+      per_block += sizes[j];
+      if (j + 1 < sizes.size()) below_root += sizes[j];
+    }
+    const size_t most = std::min(n, chunk);
+    DevBuf d_seeds, d_firsts, d_dest, d_verdict, d_cells, d_nodes;     // (go after the streams have drained: DevBuf::release)
+    CP2_TRY(d_seeds.scratch(ctx, n * 8));
+    CP2_TRY(d_firsts.scratch(ctx, n * 8));
+    CP2_TRY(d_dest.scratch(ctx, n * 8));
+    CP2_TRY(d_verdict.scratch(ctx, n * 4));
+    CP2_TRY(d_cells.scratch(ctx, most * bs));
+    CP2_TRY(d_nodes.scratch(ctx, most * per_block * 32));
+    CP2_HIP(ctx, hipMemcpyAsync(d_seeds.p, seeds.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
+    CP2_HIP(ctx, hipMemcpyAsync(d_firsts.p, firsts.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
+    CP2_HIP(ctx, hipMemcpyAsync(d_dest.p, rp.g.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));   // (coff[0] == 0: a global index is its row)
+    for (size_t k = 0; k < rp.n_chunks(); ++k)
+      CP2_TRY(recheck_fake_chunk(f, rp.chunk_begin(k), rp.chunk_end(k) - rp.chunk_begin(k), static_cast<const uint64_t*>(d_seeds.p),
+                                 static_cast<const uint64_t*>(d_firsts.p), static_cast<const uint64_t*>(d_dest.p), d_cells, d_nodes,
+                                 static_cast<uint32_t*>(d_verdict.p), below_root));
+    CP2_HIP(ctx, hipMemcpyAsync(verdict.data(), d_verdict.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) {
+      (void)hipGetLastError();
+      ctx->err = "fill: the re-check failed on the device";
+      return CP2_ERR_HIP;
+    }
+  } else {
+    // slot files: a chunk's blocks read file by file in ascending offset order into one host buffer, then repair's data path, unchanged
+    std::unique_ptr<uint8_t[]> host(new uint8_t[std::min(n, chunk) * bs]);
+    DevBuf d_dest;
+    for (size_t k = 0; k < rp.n_chunks(); ++k) {
+      const size_t i0 = rp.chunk_begin(k), m = rp.chunk_end(k) - i0;
+      for (const FillReadPlan::Run& run : rp.runs(k)) {
+        const std::string fname = slot_file_name(f->file_base, plan.first_slot + run.local);
+        const int fd = open(fname.c_str(), O_RDONLY | O_CLOEXEC);
+        if (fd < 0) { ctx->err = slot_file_error(fname, 0); return CP2_ERR_IO; }
+        int err = 0;
+        for (size_t i = run.i0; i < run.i1 && !err; ++i)
+          err = slot_file_read_rest(fd, host.get() + (i - i0) * bs, bs, (rp.g[i] % plan.n_blocks) * bs);
+        close(fd);
+        if (err) { ctx->err = slot_file_error(fname, err); return CP2_ERR_IO; }   // a read that fails is an error, never a dropped block
+      }
+      RepairJudge judge;
+      judge.begin = [&](size_t) -> int {
+        CP2_TRY(d_dest.scratch(ctx, m * 8));
+        CP2_HIP(ctx, hipMemcpyAsync(d_dest.p, rp.g.data() + i0, m * 8, hipMemcpyHostToDevice, ctx->stream));
+        return CP2_OK;
+      };
+      judge.verdicts = [&](const uint8_t* fresh, size_t c0, size_t mm, uint32_t* v, hipStream_t st) -> int {
+        CP2_HIP(ctx, cp2k::launch_block_root_recheck(fresh, static_cast<const uint64_t*>(d_dest.p) + c0, mm, v, f->compact.p, plan.total(), st));
+        return CP2_OK;
+      };
+      CP2_TRY(repair_check_with(ctx, c.cell_size, bs, host.get(), m, verdict.data() + i0, judge));
+    }
+  }
+  for (size_t i = 0; i < n; ++i)
+    if (verdict[i] != 0) dropped->push_back(rp.g[i]);
+  return CP2_OK;
+}
+
+}  // namespace
+
+extern "C" int cp2_fill_save(const void* fill, const char* path) try {
+  const cp2_fill_session* f = session(fill);
+  if (!f || !path) return CP2_ERR_INVALID;
+  cp2_ctx* ctx = f->ctx;
+  if (f->plan.finished) {
+    ctx->err = "fill: the session is finished: its durable form is the kept cache of cp2_fill_finish, not a checkpoint";
+    return CP2_ERR_INVALID;
+  }
+  CP2_REFUSE_STUCK(ctx);
+  CP2_HIP(ctx, hipSetDevice(ctx->device));
+  std::vector<uint8_t> buf;
+  FillCkptLayout l;
+  if (!fill_ckpt_begin(session_meta(f), f->plan.bits, &buf, &l)) {
+    ctx->err = "fill: the session is larger than a checkpoint describes";
+    return CP2_ERR_INVALID;
+  }
+  // layer 0 in one download; rows of absent blocks hold whatever the allocation held and are zeroed on the host before anything is written
+  CP2_HIP(ctx, hipMemcpyAsync(buf.data() + l.layer0_at, f->compact.p, (size_t)l.total * 32, hipMemcpyDeviceToHost, ctx->stream));
+  CP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  fill_ckpt_seal(&buf, l);
+  const std::string tmp = std::string(path) + ".tmp." + std::to_string((long)getpid());
+  const int fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_NOFOLLOW | O_CLOEXEC, 0644);
+  if (fd < 0) {
+    ctx->err = "fill: cannot create checkpoint " + tmp + ": " + std::strerror(errno);
+    return CP2_ERR_IO;
+  }
+  const char* what = nullptr;
+  if (!write_all(fd, buf.data(), buf.size()) || fsync(fd) != 0) what = std::strerror(errno);
+  if (close(fd) != 0 && !what) what = std::strerror(errno);
+  if (!what && std::rename(tmp.c_str(), path) != 0) what = std::strerror(errno);
+  if (what) {                                         // an older checkpoint at `path` stays as it is
+    ctx->err = "fill: cannot write checkpoint " + std::string(path) + " (through " + tmp + "): " + what;
+    std::remove(tmp.c_str());
+    return CP2_ERR_IO;
+  }
+  if (std::getenv("CP2_TRACE"))
+    std::fprintf(stderr, "[cp2 trace] fill save: %llu of %llu block(s) present, %zu bytes\n", (unsigned long long)f->plan.n_present,
+                 (unsigned long long)f->plan.total(), buf.size());
+  return CP2_OK;
+} catch (const std::bad_alloc&) {
+  return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
+} catch (...) {
+  return CP2_ERR_INVALID;
+}
+
+extern "C" int cp2_fill_resume(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local, const uint8_t* slot_roots, const char* path,
+                               int flags, void** out, uint64_t* n_dropped) try {
+  if (!ctx || !cfg || !out || !path) return CP2_ERR_INVALID;
+  *out = nullptr;
+  if (flags & ~CP2_RESUME_TRUST_FILES) {
+    ctx->err = "fill: unknown resume flag bits";
+    return CP2_ERR_INVALID;
+  }
+  CP2_TRY(session_check(ctx, cfg, first_slot, n_local, slot_roots));
+  const auto t0 = std::chrono::steady_clock::now();
+  // the checkpoint: intact, then a description of exactly this session
+  FillCheckpoint ck;
+  CP2_TRY(read_checkpoint(ctx, path, &ck));
+  FillCkptMeta want;
+  want.cell_size = cfg->cell_size; want.block_size = cfg->block_size; want.n_cells = cfg->n_cells; want.n_slots = cfg->n_slots;
+  want.first_slot = first_slot; want.n_local = n_local;
+  want.src = cfg->file_base ? FILL_SRC_FILE : FILL_SRC_FAKE;
+  want.seed = cfg->seed;
+  if (cfg->file_base) want.file_base = cfg->file_base;
+  want.roots.resize(n_local * 32);
+  for (uint64_t s = 0; s < n_local; ++s) canonical_felt(slot_roots + s * 32, &want.roots[s * 32]);
+  const std::string differs = fill_ckpt_differs(ck.meta, want);
+  if (!differs.empty()) {
+    ctx->err = "fill: checkpoint " + std::string(path) + " describes another session: " + differs;
+    return CP2_ERR_INVALID;
+  }
+  const bool recheck = !(flags & CP2_RESUME_TRUST_FILES);
+  const uint64_t n_blocks = ck.meta.n_blocks();
+  uint64_t present = 0;
+  for (uint64_t w : ck.bits) present += (uint64_t)__builtin_popcountll(w);
+  // slot files first: what a file is too short to back (or no file at all) is dropped without a read; absence is a state, not an error
+  std::vector<uint64_t> dropped;
+  if (recheck && cfg->file_base) {
+    std::vector<uint64_t> whole(n_local, 0);
+    for (uint64_t s = 0; s < n_local; ++s) {
+      const std::string fname = slot_file_name(want.file_base, first_slot + s);
+      struct stat sb;
+      if (stat(fname.c_str(), &sb) == 0) whole[s] = (uint64_t)sb.st_size / cfg->block_size;
+      else if (errno != ENOENT && errno != ENOTDIR) {
+        ctx->err = slot_file_error(fname, 0);
+        return CP2_ERR_IO;
+      }
+    }
+    fill_ckpt_drop_short(whole, n_blocks, &ck.bits, &ck.layer0, &dropped);
+  }
+  std::unique_ptr<cp2_fill_session> f;
+  CP2_TRY(session_open(ctx, cfg, first_slot, n_local, slot_roots, &f));
+  if (!f->plan.restore(ck.bits)) {
+    ctx->err = "fill: checkpoint " + std::string(path) + " is corrupt: its bitmap is not one of this session";
+    return CP2_ERR_IO;
+  }
+  CP2_HIP(ctx, hipMemcpyAsync(f->compact.p, ck.layer0.data(), ck.layer0.size(), hipMemcpyHostToDevice, ctx->stream));
+  CP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  uint64_t n_read = 0;
+  double bytes = 0;
+  if (recheck) {
+    std::vector<uint64_t> changed;
+    CP2_TRY(recheck_present(f.get(), &changed, &n_read, &bytes));
+    (void)f->plan.drop(changed.data(), changed.size());
+    dropped.insert(dropped.end(), changed.begin(), changed.end());
+  }
+  if (std::getenv("CP2_TRACE")) {
+    const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    std::fprintf(stderr, "[cp2 trace] fill resume: %llu block(s) present in the checkpoint, %llu re-read, %zu dropped, %.0f bytes, %.3f s (%.2f GB/s)\n",
+                 (unsigned long long)present, (unsigned long long)n_read, dropped.size(), bytes, seconds, seconds > 0 ? bytes / seconds / 1e9 : 0.0);
+  }
+  if (n_dropped) *n_dropped = dropped.size();
+  *out = f.release();
   return CP2_OK;
 } catch (const std::bad_alloc&) {
   return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI

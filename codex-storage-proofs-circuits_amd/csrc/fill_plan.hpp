@@ -178,6 +178,30 @@ struct FillPlan {
     n_present += set;
     return set;
   }
+  // ... and its reverse (cp2_fill_resume): the presence bits of blocks the disk no longer backs, as global indices local * n_blocks + block;
+  // returns how many were set.  A dropped block is missing like one that never arrived.
+  size_t drop(const uint64_t* global, size_t n) {
+    size_t cleared = 0;
+    for (size_t i = 0; i < n; ++i) {
+      if (global[i] >= total()) continue;
+      uint64_t& w = bits[(size_t)(global[i] >> 6)];
+      if ((w >> (global[i] & 63)) & 1) {
+        w &= ~(1ULL << (global[i] & 63));
+        ++cleared;
+      }
+    }
+    n_present -= cleared;
+    return cleared;
+  }
+  // a saved bitmap taken over (cp2_fill_resume): false when it is not a bitmap of this session (its size, or a bit past the last block)
+  bool restore(const std::vector<uint64_t>& saved) {
+    if (saved.size() != bits.size()) return false;
+    if ((total() & 63) && (saved.back() >> (total() & 63))) return false;
+    bits = saved;
+    n_present = 0;
+    for (uint64_t w : bits) n_present += (uint64_t)__builtin_popcountll(w);
+    return true;
+  }
 
   // ---- what is missing ----------------------------------------------------------------------------------------------------------------
   // the lowest min(cap, n_missing) absent (dataset slot, block) pairs in ascending order into `out` (may be NULL when cap == 0); returns

@@ -12,6 +12,7 @@
 //   k_repair_compare      candidate block roots against the kept rows they would replace, one verdict per request (repair.cpp)
 //   k_block_path_roots    a13 candidate block roots walked up their Merkle paths to the slot root, merkle.nim:51-74 (block_proofs.cpp)
 //   k_block_path_commit   the same walk; a proved block root is also stored into layer 0 of a fill session's compact buffer (fill.cpp)
+//   k_block_root_recheck  re-read block roots against layer 0 of a resumed fill session; a row the disk no longer backs is zeroed (fill.cpp)
 //
 // All global-memory field elements are 32-byte little-endian canonical integers (the ABI format).
 #include "kernels.hpp"
@@ -871,6 +872,32 @@ __global__ void __launch_bounds__(TPB) k_block_path_commit(const uint4* __restri
 }
 
 // ------------------------------------------------------------------------------------------------
+// Resuming a fill session (fill.cpp): k_repair_compare's comparison, with what a resumed session does about a block whose bytes on disk no
+// longer hash to the root the checkpoint kept -- as k_block_path_commit is k_block_path_roots' walk with what a session keeps of a proved
+// block.  Lane i takes the freshly built block root of re-read block i (fresh row i) and row dest[i] of `layer0`, the session's compact
+// buffer (the host computed dest[i] inside layer 0), two 16-byte loads a side, and writes one verdict word: 0 equal, 1 not.  Where they
+// differ it overwrites the row of layer 0 with zeros, two 16-byte vector stores, so that the buffer never keeps a root the disk does not
+// back; the host clears the block's presence bit from the verdict.  The rows of one launch are distinct (the read plan names every present
+// block once), so no lane reads a row another lane zeroes.  A row at or past n_rows (never: the host computed every row) is a mismatch
+// and is neither read nor written.  No atomics, no LDS, no permutation.
+__global__ void __launch_bounds__(TPB) k_block_root_recheck(const uint4* __restrict__ fresh, const uint64_t* __restrict__ dest, size_t n,
+                                                              uint32_t* __restrict__ verdict, uint4* __restrict__ layer0, uint64_t n_rows) {
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t r = dest[i];
+  uint32_t v = 1;
+  if (r < n_rows) {
+    const uint4 a0 = fresh[2 * i], a1 = fresh[2 * i + 1], b0 = layer0[2 * r], b1 = layer0[2 * r + 1];
+    v = ((a0.x ^ b0.x) | (a0.y ^ b0.y) | (a0.z ^ b0.z) | (a0.w ^ b0.w) | (a1.x ^ b1.x) | (a1.y ^ b1.y) | (a1.z ^ b1.z) | (a1.w ^ b1.w)) != 0;
+    if (v) {
+      layer0[2 * r] = make_uint4(0, 0, 0, 0);
+      layer0[2 * r + 1] = make_uint4(0, 0, 0, 0);
+    }
+  }
+  verdict[i] = v;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Workgroups for n work items.  A grid holds at most 2^31 - 1 workgroups in x; the per-item kernels are launched in slices of
 // at most MAX_ITEMS items (every item is independent and addressed from a base pointer), the layer / sampling kernels, whose
 // item index is decomposed inside the kernel, refuse what does not fit one grid (2^38 nodes: far beyond any HBM).
@@ -1085,6 +1112,20 @@ hipError_t launch_block_path_commit(const void* fresh, const void* paths, const 
     const size_t m = n - i0 < MAX_ITEMS ? n - i0 : MAX_ITEMS;
     CP2K_LAUNCH(k_block_path_commit, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)fresh + 2 * i0, (const uint4*)paths + 2 * i0 * depth,
                 slot_block + 2 * i0, (const uint4*)slot_roots, dest + i0, n_blocks, depth, m, verdict + i0, (uint4*)layer0, n_rows);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+hipError_t launch_block_root_recheck(const void* fresh, const uint64_t* dest, size_t n, uint32_t* verdict, void* layer0, uint64_t n_rows,
+                                     hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  if (!fresh || !dest || !verdict || !layer0) return hipErrorInvalidValue;
+  for (size_t i0 = 0; i0 < n; i0 += MAX_ITEMS) {
+    const size_t m = n - i0 < MAX_ITEMS ? n - i0 : MAX_ITEMS;
+    CP2K_LAUNCH(k_block_root_recheck, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)fresh + 2 * i0, dest + i0, m, verdict + i0, (uint4*)layer0,
+                n_rows);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }

@@ -96,6 +96,12 @@ proc cp2_fill_add(fill: pointer, slotBlock: ptr uint64, data, paths: ptr byte, n
 proc cp2_fill_missing(fill: pointer, missing: ptr uint64, cap: csize_t, nMissing: ptr uint64): cint {.importc.}
 proc cp2_fill_finish(fill: pointer, cachePath: cstring, ds: ptr Cp2Dataset): cint {.importc.}
 proc cp2_fill_free(fill: pointer) {.importc.}
+# fill checkpoints: a session saved at any point (cp2_fill_save) and resumed by a later process (cp2_fill_resume), which re-checks on the
+# device every block the checkpoint calls present unless flags = CP2_RESUME_TRUST_FILES; nDropped may be nil
+const CP2_RESUME_TRUST_FILES* = 1.cint
+proc cp2_fill_save(fill: pointer, path: cstring): cint {.importc.}
+proc cp2_fill_resume(ctx: Cp2Ctx, cfg: ptr Cp2Config, firstSlot, nLocal: uint64, slotRoots: ptr byte, path: cstring, flags: cint,
+                     fill: ptr pointer, nDropped: ptr uint64): cint {.importc.}
 proc cp2_proof_input_write_json(p: Cp2ProofInput, path: cstring): cint {.importc.}
 proc cp2_proof_input_roots(p: Cp2ProofInput, datasetRoot, slotRoot, entropy: ptr byte): cint {.importc.}
 proc cp2_proof_input_nsamples(p: Cp2ProofInput): csize_t {.importc.}

@@ -44,8 +44,8 @@ extern "C" {
  *          next: + cp2_dataset_scrub and cp2_multi_dataset_scrub (scrub), cp2_dataset_repair_blocks and
  *                cp2_multi_dataset_repair_blocks (repair), cp2_block_proof_depth, cp2_dataset_block_proofs, cp2_blocks_verify and
  *                cp2_dataset_repair_blocks_proved (block proofs), cp2_fill_begin, cp2_fill_add, cp2_fill_missing, cp2_fill_finish and
- *                cp2_fill_free (fill sessions).  MINOR stays 2 until the release that carries them: the bump to 1.3 goes in its own
- *                commit with that release.                                                                                           */
+ *                cp2_fill_free (fill sessions), cp2_fill_save and cp2_fill_resume (fill checkpoints).  MINOR stays 2 until the release
+ *                that carries them: the bump to 1.3 goes in its own commit with that release.                                         */
 #define CP2_ABI_VERSION_MAJOR 1
 #define CP2_ABI_VERSION_MINOR 2
 #define CP2_ABI_VERSION ((CP2_ABI_VERSION_MAJOR << 16) | CP2_ABI_VERSION_MINOR)
@@ -637,8 +637,8 @@ int cp2_dataset_repair_blocks_proved(cp2_dataset* ds, const uint64_t* slot_block
  *              dataset, and the session stays complete and usable.
  *   After      a successful finish the session accepts only cp2_fill_free.
  *
- * Out of scope: cp2_multi_* (a session lives in one context); persisting or resuming a half-filled session; adopting blocks that are
- * already on disk; fetching and erasure decoding, which stay with the caller. */
+ * Out of scope: cp2_multi_* (a session lives in one context); fetching and erasure decoding, which stay with the caller.  Saving and
+ * resuming a half-filled session, and re-checking the blocks already on disk that its checkpoint covers: the checkpoint section below. */
 typedef void cp2_fill;
 #define CP2_FILL_NEW        0  /* proved against the slot root, first time seen: root kept, block written            */
 #define CP2_FILL_MISMATCH   1  /* block + path do not reconstruct the slot root: nothing kept, nothing written       */
@@ -653,6 +653,51 @@ int cp2_fill_missing(const void* f /* const cp2_fill* */, uint64_t* missing /* c
                      uint64_t* n_missing);
 int cp2_fill_finish(void* f /* cp2_fill* */, const char* cache_path /* may be NULL */, cp2_dataset** out);
 void cp2_fill_free(void* f /* cp2_fill* */);
+
+/* ---- fill checkpoints: a session saved at any point and resumed against what is on disk ----------------------------------------------
+ * A session lives for as long as its blocks take to arrive.  What it has proved so far exists in its host bitmap and in layer 0 of its
+ * compact buffer only: were the process to die, the blocks already in the slot files could not be proved again without their paths, and
+ * the slot would have to be fetched whole.  cp2_fill_save writes both down; cp2_fill_resume, in any later process, opens a session from
+ * them and trusts the disk only as far as the device has re-checked it.
+ *
+ * cp2_fill_save writes a checkpoint of an unfinished session to `path`.
+ *   Contents   "CP2FILL1", the geometry (cell_size, block_size, n_cells, n_slots, first_slot, n_local), the source kind, the seed and the
+ *              file base name, the stated slot roots (canonical), the presence bitmap, layer 0 of the compact buffer (n_local x nBlocks
+ *              rows of 32 bytes; rows of absent blocks are written as zeros, so two saves of one state are byte-identical), and the
+ *              checksum of the kept form over all of it (csrc/fill_checkpoint.hpp has the layout).
+ *   Work       one download on the context's stream; written to "<path>.tmp.<pid>", synced, then renamed.  Nothing of the session changes.
+ *   Refused    CP2_ERR_INVALID: a NULL session or path; a finished session (its durable form is the kept cache of cp2_fill_finish).
+ *              CP2_ERR_HIP: a context whose stream will not drain.
+ *   Failure    CP2_ERR_IO naming the file; an older checkpoint at `path` stays intact.
+ *   Durable    a block's bit is set only after its slot file has been synced, so every block a checkpoint calls present was durable when
+ *              the checkpoint was written.  Blocks added after the last save are simply missing again after a resume: there is no
+ *              journal per add.
+ *
+ * cp2_fill_resume opens a session from the checkpoint at `path`.
+ *   Checked    cfg, first_slot, n_local and slot_roots exactly as cp2_fill_begin checks them.  The checkpoint must be intact (magic,
+ *              sizes, checksum): a missing, truncated or corrupt file is CP2_ERR_IO naming the path.  It must describe THIS session --
+ *              geometry, range, source kind, the seed (fake source), the file base name (slot files), the stated roots after reduction
+ *              mod r: otherwise CP2_ERR_INVALID naming the first field that differs.  In every failing case no session is created and
+ *              *out = NULL.
+ *   Re-check   every block the checkpoint calls present is checked against what the source holds now.  Slot files: a file that does not
+ *              exist, or ends before the block does, drops that block without a read (absence is a state, not an error); the others are
+ *              read from "<file_base><slot>.dat", file by file in ascending offset order, in chunks of half the context's staging, and
+ *              go through cp2_dataset_repair_blocks' data path unchanged; a read that fails is CP2_ERR_IO with the builders' message and
+ *              no session.  Fake source: the blocks are regenerated on the device and hashed the same way.  The last device step
+ *              (k_block_root_recheck) compares each fresh block root with the row of layer 0 the checkpoint kept and zeroes the row
+ *              where they differ; the host clears that block's bit.  *n_dropped (may be NULL) = the blocks dropped either way.
+ *   Flags      CP2_RESUME_TRUST_FILES: the checkpoint's presence bits are taken as they are, no slot byte is read, *n_dropped = 0.  What
+ *              remains is cp2_fill_finish's comparison of the top layer with the stated roots (CP2_ERR_IO naming the slot).
+ *   Result     *out = a session indistinguishable from one begun fresh that has received exactly the surviving blocks: cp2_fill_missing
+ *              lists the dropped blocks among the absent ones, cp2_fill_add takes them again as CP2_FILL_NEW, and the finished dataset is
+ *              the one cp2_dataset_build makes.  CP2_TRACE prints one line (blocks present, re-read, dropped, bytes, seconds, GB/s).
+ *
+ * Out of scope: cp2_multi_*; a journal per add; adopting blocks the checkpoint does not cover. */
+#define CP2_RESUME_TRUST_FILES 1   /* flag: take the checkpoint's presence bits as they are, read no slot byte */
+int cp2_fill_save(const void* f /* const cp2_fill* */, const char* path);
+int cp2_fill_resume(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local,
+                    const uint8_t* slot_roots /* n_local x 32, from the manifest */, const char* path, int flags, void** out /* cp2_fill** */,
+                    uint64_t* n_dropped /* may be NULL */);
 
 /* replaces `writeCircomMainComponent`, reference/nim/proof_input/src/cli.nim:186-204 */
 int cp2_write_circom_main(const cp2_config* cfg, const char* path);
