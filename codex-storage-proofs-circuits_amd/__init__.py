@@ -229,6 +229,8 @@ def load_library():
         "cp2_fill_free": (None, [vp]),
         "cp2_fill_save": (i32, [vp, cp]),
         "cp2_fill_resume": (i32, [vp, ctypes.POINTER(Config), u64, u64, vp, cp, i32, pvp, ctypes.POINTER(u64)]),
+        "cp2_fill_keep_nodes": (i32, [vp]),
+        "cp2_fill_block_proofs": (i32, [vp, vp, sz, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         if v is None and name == "cp2_abi_version":
@@ -843,6 +845,7 @@ class Dataset:
 
 FILL_NEW, FILL_MISMATCH, FILL_DUPLICATE, FILL_UNWRITTEN = 0, 1, 2, 3   # CP2_FILL_* (include/codex_p2.h): the per-request results of cp2_fill_add
 RESUME_TRUST_FILES = 1                                                 # CP2_RESUME_TRUST_FILES: cp2_fill_resume reads no slot byte
+FILL_PROOF_OK, FILL_PROOF_ABSENT, FILL_PROOF_PARTIAL = 0, 1, 2         # CP2_FILL_PROOF_*: the per-request results of cp2_fill_block_proofs
 
 
 class FillSession:
@@ -914,6 +917,24 @@ class FillSession:
             e.fill_status, e.n_new = status, new.value
             raise
         return status, new.value
+
+    def keep_nodes(self):
+        """cp2_fill_keep_nodes: from here on every proved path leaves all its nodes in the session's buffer, and block_proofs serves"""
+        self.ctx._ck(self.ctx.L.cp2_fill_keep_nodes(self.h), "cp2_fill_keep_nodes")
+
+    def block_proofs(self, slot_block, statuses_only=False):
+        """cp2_fill_block_proofs: (status: uint32[n] of FILL_PROOF_*, block_roots: uint8[n, 32], paths: uint8[n, depth, 32]) of (slot, block)
+        pairs from the session's own buffer; the rows of a request that is not served are zeros.  statuses_only: just the statuses, from the
+        host bitmaps, no device work."""
+        sb = np.ascontiguousarray(np.asarray(slot_block, dtype=np.uint64).reshape(-1, 2))
+        n, depth = sb.shape[0], self.block_proof_depth
+        status = np.empty(n, dtype=np.uint32)
+        roots = None if statuses_only else np.empty((n, 32), dtype=np.uint8)
+        paths = None if statuses_only else np.empty((n, depth, 32), dtype=np.uint8)
+        self.ctx._ck(self.ctx.L.cp2_fill_block_proofs(self.h, _p(sb) if n else None, n, _p(status) if n else None,
+                                                      _p(roots) if n and not statuses_only else None,
+                                                      _p(paths) if n and not statuses_only else None), "cp2_fill_block_proofs")
+        return status if statuses_only else (status, roots, paths)
 
     def missing(self, cap=1 << 20):
         """cp2_fill_missing: (missing: uint64[k, 2] of (slot, block), ascending, the lowest k = min(cap, n_missing), n_missing); cap = 0 counts"""

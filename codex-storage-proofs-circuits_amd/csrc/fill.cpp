@@ -1,5 +1,5 @@
-// Fill sessions behind the C ABI (include/codex_p2.h): cp2_fill_begin, cp2_fill_add, cp2_fill_missing, cp2_fill_finish, cp2_fill_free, and
-// their checkpoints: cp2_fill_save, cp2_fill_resume.
+// Fill sessions behind the C ABI (include/codex_p2.h): cp2_fill_begin, cp2_fill_add, cp2_fill_missing, cp2_fill_finish, cp2_fill_free,
+// their checkpoints: cp2_fill_save, cp2_fill_resume, and the sessions that serve while they fill: cp2_fill_keep_nodes, cp2_fill_block_proofs.
 //
 // A node that takes on a slot holds the manifest's slot root and receives the slot's network blocks from peers, in any order, each with
 // its Merkle path.  cp2_blocks_verify checks such blocks and forgets the block roots it computed; a session KEEPS them.  It owns the compact
@@ -15,6 +15,11 @@
 // far as the device has re-checked it: every block the checkpoint calls present is read back (or, fake source, regenerated), hashed and
 // reduced to its block root by the builders' kernels on repair's data path, and k_block_root_recheck compares that root with the row of
 // layer 0 the checkpoint kept, zeroing the row where they differ; the host clears those blocks' bits, and they are missing again.
+//
+// A session that is still filling can vouch for the blocks it holds.  A path that ends in the stated slot root proves every node on it, and
+// the compact buffer has a row for each, unused until finish.  After cp2_fill_keep_nodes every add ends in k_block_path_commit_nodes, which
+// stores the proved siblings and ancestors where the tree has them; the host's second bitmap (FillPlan::known) says which rows hold
+// authentic nodes, and cp2_fill_block_proofs serves a present block's proof with the gather cp2_dataset_block_proofs does on a dataset.
 #include <hip/hip_runtime.h>
 
 #include <fcntl.h>
@@ -42,6 +47,9 @@ using namespace cp2i;
 
 static_assert(FILL_NEW == CP2_FILL_NEW && FILL_MISMATCH == CP2_FILL_MISMATCH && FILL_DUPLICATE == CP2_FILL_DUPLICATE &&
               FILL_UNWRITTEN == CP2_FILL_UNWRITTEN, "fill_plan.hpp restates the header's statuses");
+static_assert(FILL_PROOF_OK == CP2_FILL_PROOF_OK && FILL_PROOF_ABSENT == CP2_FILL_PROOF_ABSENT && FILL_PROOF_PARTIAL == CP2_FILL_PROOF_PARTIAL,
+              "fill_plan.hpp restates the header's proof statuses");
+static_assert(BLOCK_PROOF_NO_ROW == NO_ROW, "k_gather_rows zero-fills the rows the plan marks as absent");
 static_assert(FILL_WRITE == CP2_REPAIR_MATCH && FILL_SKIP == CP2_REPAIR_MISMATCH && FILL_WRITE_FAILED == CP2_REPAIR_UNWRITTEN,
               "repair_write takes and leaves repair's statuses");
 
@@ -55,6 +63,7 @@ struct cp2_fill_session {
   DevBuf compact;                       // the compact layout of the local slots; becomes the dataset's buffer in finish
   DevBuf slot_roots;                    // the stated roots, canonical: n_local x 32 bytes
   std::vector<uint8_t> roots;           // ... and on the host, for a checkpoint
+  DevBuf layer_tab;                     // a session that keeps nodes: coff then csizes as uint64, depth + 1 entries each, uploaded once
 };
 
 namespace {
@@ -185,12 +194,14 @@ extern "C" int cp2_fill_add(void* fill, const uint64_t* slot_block, const uint8_
   const size_t depth = block_proof_depth(plan.n_blocks), path_bytes = depth * 32;
   std::vector<uint64_t> local_block, dest;
   plan.device_requests(slot_block, n, &local_block, &dest);
-  DevBuf d_req, d_dest, d_paths;                     // (go after the streams have drained: DevBuf::release)
+  const bool keeps = plan.keeps_nodes;
+  DevBuf d_req, d_dest, d_paths, d_walk;             // (go after the streams have drained: DevBuf::release)
   RepairJudge judge;
   judge.begin = [&](size_t chunk) -> int {
     CP2_TRY(d_req.scratch(ctx, n * 16));
     CP2_TRY(d_dest.scratch(ctx, n * 8));
     CP2_TRY(d_paths.scratch(ctx, chunk * path_bytes));
+    if (keeps) CP2_TRY(d_walk.scratch(ctx, chunk * 2 * path_bytes));   // the chunk's siblings and ancestors as the walk meets them
     CP2_HIP(ctx, hipMemcpyAsync(d_req.p, local_block.data(), n * 16, hipMemcpyHostToDevice, ctx->stream));
     CP2_HIP(ctx, hipMemcpyAsync(d_dest.p, dest.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
     return CP2_OK;
@@ -201,6 +212,13 @@ extern "C" int cp2_fill_add(void* fill, const uint64_t* slot_block, const uint8_
     return CP2_OK;
   };
   judge.verdicts = [&](const uint8_t* fresh, size_t c0, size_t m, uint32_t* verdict, hipStream_t st) -> int {
+    if (keeps) {                                     // the same walk; a proved path leaves all its nodes where the tree has them
+      const uint64_t* tab = static_cast<const uint64_t*>(f->layer_tab.p);
+      CP2_HIP(ctx, cp2k::launch_block_path_commit_nodes(fresh, d_paths.p, static_cast<const uint64_t*>(d_req.p) + 2 * c0, f->slot_roots.p,
+                                                        static_cast<const uint64_t*>(d_dest.p) + c0, tab, tab + depth + 1, plan.n_blocks,
+                                                        (uint32_t)depth, m, verdict, f->compact.p, plan.rows, d_walk.p, st));
+      return CP2_OK;
+    }
     CP2_HIP(ctx, cp2k::launch_block_path_commit(fresh, d_paths.p, static_cast<const uint64_t*>(d_req.p) + 2 * c0, f->slot_roots.p,
                                                 static_cast<const uint64_t*>(d_dest.p) + c0, plan.n_blocks, (uint32_t)depth, m, verdict,
                                                 f->compact.p, plan.rows, st));
@@ -208,6 +226,7 @@ extern "C" int cp2_fill_add(void* fill, const uint64_t* slot_block, const uint8_
   };
   std::vector<uint32_t> verdict(n), st(n);
   CP2_TRY(repair_check_with(ctx, c.cell_size, c.block_size, data, n, verdict.data(), judge));
+  if (keeps) plan.mark_proved(slot_block, verdict.data(), n);   // written or not: the nodes of a proved path are authentic and stored
   plan.resolve(slot_block, verdict.data(), n, st.data());
   int r = CP2_OK;
   if (f->from_file) {                                // the NEW blocks into "<file_base><slot>.dat": repair's writer and its rules
@@ -594,6 +613,140 @@ extern "C" int cp2_fill_resume(cp2_ctx* ctx, const cp2_config* cfg, uint64_t fir
   }
   if (n_dropped) *n_dropped = dropped.size();
   *out = f.release();
+  return CP2_OK;
+} catch (const std::bad_alloc&) {
+  return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
+} catch (...) {
+  return CP2_ERR_INVALID;
+}
+
+// ---- sessions that serve ------------------------------------------------------------------------------------------------------------------
+extern "C" int cp2_fill_keep_nodes(void* fill) try {
+  cp2_fill_session* f = session(fill);
+  if (!f) return CP2_ERR_INVALID;
+  cp2_ctx* ctx = f->ctx;
+  FillPlan& plan = f->plan;
+  if (plan.finished) {
+    ctx->err = "fill: the session is finished: its proofs come from the dataset (cp2_dataset_block_proofs)";
+    return CP2_ERR_INVALID;
+  }
+  if (plan.keeps_nodes) return CP2_OK;               // one-way, and once
+  CP2_REFUSE_STUCK(ctx);
+  CP2_HIP(ctx, hipSetDevice(ctx->device));
+  const auto t0 = std::chrono::steady_clock::now();
+  // the two tables the kernel takes a row from: layer_off, then layer_size
+  const size_t layers = plan.csizes.size();
+  std::vector<uint64_t> tab(2 * layers);
+  for (size_t l = 0; l < layers; ++l) {
+    tab[l] = plan.coff[l];
+    tab[layers + l] = plan.csizes[l];
+  }
+  DevBuf d_tab;
+  CP2_TRY(d_tab.alloc(ctx, tab.size() * 8));
+  CP2_HIP(ctx, hipMemcpyAsync(d_tab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+  // layer 0: the rows of absent blocks hold whatever the allocation held, and no kernel may read a row that was never written
+  const size_t total = (size_t)plan.total();
+  std::vector<uint8_t> layer0;
+  if (plan.n_present == 0) {
+    CP2_HIP(ctx, hipMemsetAsync(f->compact.p, 0, total * 32, ctx->stream));
+  } else if (plan.n_missing()) {
+    layer0.resize(total * 32);
+    CP2_HIP(ctx, hipMemcpyAsync(layer0.data(), f->compact.p, total * 32, hipMemcpyDeviceToHost, ctx->stream));
+    CP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t g = 0; g < total; ++g)
+      if (!((plan.bits[g >> 6] >> (g & 63)) & 1)) std::memset(&layer0[g * 32], 0, 32);
+    CP2_HIP(ctx, hipMemcpyAsync(f->compact.p, layer0.data(), total * 32, hipMemcpyHostToDevice, ctx->stream));
+  }
+  // every upper layer once, exactly as finish builds them; a parent of an unknown child comes out as a value nobody reads
+  CP2_TRY(merkle_trees_dev(ctx, f->compact.p, plan.n_blocks, plan.n_local, f->compact.p, true));
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess) {
+    (void)hipGetLastError();
+    ctx->err = "fill: building the upper layers failed on the device";
+    return CP2_ERR_HIP;
+  }
+  hand_over(d_tab, f->layer_tab);
+  plan.derive_from_presence();
+  plan.keeps_nodes = true;
+  if (std::getenv("CP2_TRACE")) {
+    uint64_t servable = 0;
+    for (uint64_t s = 0; s < plan.n_local; ++s)
+      for (uint64_t b = 0; b < plan.n_blocks; ++b) servable += plan.servable(s, b);
+    std::fprintf(stderr, "[cp2 trace] fill keep nodes: %llu of %llu block(s) present, %llu servable, %zu layer(s) built, %.3f ms\n",
+                 (unsigned long long)plan.n_present, (unsigned long long)plan.total(), (unsigned long long)servable, layers - 1,
+                 std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3);
+  }
+  return CP2_OK;
+} catch (const std::bad_alloc&) {
+  return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
+} catch (...) {
+  return CP2_ERR_INVALID;
+}
+
+extern "C" int cp2_fill_block_proofs(void* fill, const uint64_t* slot_block, size_t n, uint32_t* status, uint8_t* block_roots, uint8_t* paths) try {
+  cp2_fill_session* f = session(fill);
+  if (!f) return CP2_ERR_INVALID;
+  cp2_ctx* ctx = f->ctx;
+  const FillPlan& plan = f->plan;
+  if (n && (!slot_block || !status)) {
+    ctx->err = "fill proofs: slot_block and status must not be NULL when n > 0";
+    return CP2_ERR_INVALID;
+  }
+  if (plan.finished) {
+    ctx->err = "fill proofs: the session is finished: its proofs come from the dataset (cp2_dataset_block_proofs)";
+    return CP2_ERR_INVALID;
+  }
+  if (!plan.keeps_nodes) {
+    ctx->err = "fill proofs: this session does not keep the nodes of the paths it proves: call cp2_fill_keep_nodes first";
+    return CP2_ERR_INVALID;
+  }
+  std::string err;
+  if (!block_proofs_validate(slot_block, n, plan.first_slot, plan.n_local, plan.n_blocks, &err)) {
+    ctx->err = "fill proofs:" + err.substr(err.find(':') + 1);
+    return CP2_ERR_INVALID;
+  }
+  if (n == 0) return CP2_OK;
+  const auto t0 = std::chrono::steady_clock::now();
+  // the statuses, from the host's two bitmaps
+  std::vector<uint32_t> st(n);
+  size_t count[3] = {0, 0, 0};
+  for (size_t i = 0; i < n; ++i) {
+    st[i] = plan.proof_status(slot_block[2 * i] - plan.first_slot, slot_block[2 * i + 1]);
+    ++count[st[i]];
+  }
+  if (block_roots || paths) {
+    CP2_REFUSE_STUCK(ctx);
+    CP2_HIP(ctx, hipSetDevice(ctx->device));
+    // the rows of every request: its block root, then its siblings bottom first; a request that is not served names no row at all
+    const size_t depth = plan.depth(), per = depth + 1;
+    std::vector<uint64_t> rows(n * per, BLOCK_PROOF_NO_ROW);
+    for (size_t i = 0; i < n; ++i) {
+      if (st[i] != FILL_PROOF_OK) continue;
+      const uint64_t s = slot_block[2 * i], b = slot_block[2 * i + 1];
+      rows[i * per] = plan.dest_row(s, b);
+      block_proof_rows(plan.coff, plan.csizes, s - plan.first_slot, b, depth, &rows[i * per + 1]);
+    }
+    for (uint64_t r : rows)
+      if (r != BLOCK_PROOF_NO_ROW && r >= plan.rows) {
+        ctx->err = "fill proofs: a row lies outside the session's buffer";
+        return CP2_ERR_INVALID;
+      }
+    DevBuf d_rows, d_out;
+    CP2_TRY(d_rows.scratch(ctx, rows.size() * 8));
+    CP2_TRY(d_out.scratch(ctx, rows.size() * 32));
+    std::vector<uint8_t> out(rows.size() * 32);
+    CP2_HIP(ctx, hipMemcpyAsync(d_rows.p, rows.data(), rows.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    CP2_HIP(ctx, cp2k::launch_gather_rows(f->compact.p, static_cast<const uint64_t*>(d_rows.p), rows.size(), 32, d_out.p, ctx->stream));
+    CP2_HIP(ctx, hipMemcpyAsync(out.data(), d_out.p, out.size(), hipMemcpyDeviceToHost, ctx->stream));
+    CP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < n; ++i) {
+      if (block_roots) std::memcpy(block_roots + i * 32, &out[i * per * 32], 32);
+      if (paths) std::memcpy(paths + i * depth * 32, &out[(i * per + 1) * 32], depth * 32);
+    }
+  }
+  std::copy(st.begin(), st.end(), status);
+  if (std::getenv("CP2_TRACE"))
+    std::fprintf(stderr, "[cp2 trace] fill proofs: %zu request(s), %zu served, %zu absent, %zu partial, %.6f s\n", n, count[FILL_PROOF_OK],
+                 count[FILL_PROOF_ABSENT], count[FILL_PROOF_PARTIAL], std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
   return CP2_OK;
 } catch (const std::bad_alloc&) {
   return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI

@@ -1,13 +1,17 @@
 // The host side of a fill session (csrc/fill.cpp: cp2_fill_begin / _add / _missing / _finish): which sessions and requests are accepted,
 // where a proved block root goes in the compact layout, which blocks are present, how the device's verdicts become NEW / DUPLICATE, how a
-// failed write takes its blocks back, the ordered list of what is missing, and when a session may finish.  No HIP in here:
-// tests/host_check/fill_plan_check.cpp walks it over random geometries and request sets on the CPU, under AddressSanitizer + UBSan.
+// failed write takes its blocks back, the ordered list of what is missing, and when a session may finish; for a session that serves
+// (cp2_fill_keep_nodes, cp2_fill_block_proofs): which rows of the compact layout hold authentic nodes, and which proofs can be served.  No
+// HIP in here: tests/host_check/fill_plan_check.cpp and fill_nodes_check.cpp walk it over random geometries and request sets on the CPU,
+// under AddressSanitizer + UBSan.
 #pragma once
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <string>
 #include <vector>
 
+#include "block_proof_plan.hpp"
 #include "repair_plan.hpp"
 
 namespace cp2i {
@@ -16,6 +20,8 @@ namespace cp2i {
 constexpr uint32_t FILL_NEW = 0, FILL_MISMATCH = 1, FILL_DUPLICATE = 2, FILL_UNWRITTEN = 3;
 // what the writer (repair_write) takes and leaves: the values of CP2_REPAIR_MATCH / _MISMATCH / _UNWRITTEN
 constexpr uint32_t FILL_WRITE = 0, FILL_SKIP = 1, FILL_WRITE_FAILED = 2;
+// the per-request results of cp2_fill_block_proofs: the values of CP2_FILL_PROOF_* (include/codex_p2.h)
+constexpr uint32_t FILL_PROOF_OK = 0, FILL_PROOF_ABSENT = 1, FILL_PROOF_PARTIAL = 2;
 
 // ---- the session's range -----------------------------------------------------------------------------------------------------------
 // What cp2_dataset_build asks of (cfg, first_slot, n_local) before it looks at the geometry, and the power of two proof inputs need
@@ -52,6 +58,10 @@ struct FillPlan {
   std::vector<uint64_t> bits;            // bit (local * n_blocks + block): the block is proved AND written; the authority on presence
   uint64_t n_present = 0;
   bool finished = false;
+  // a session that serves (cp2_fill_keep_nodes): bit r: row r of the compact layout holds the authentic node of its place in the tree,
+  // stored by a proved path (mark_proved) or built from children that were (derive_from_presence).  All clear until nodes are kept.
+  std::vector<uint64_t> known;
+  bool keeps_nodes = false;
 
   // layer sizes n, ceil(n / 2), ... 1 with at least one round of compression (merkle/bn254.nim:29-58, layer_sizes_of)
   void init(uint64_t first, uint64_t local, uint64_t blocks) {
@@ -68,9 +78,12 @@ struct FillPlan {
       bottom = false;
     }
     bits.assign((size_t)((total() + 63) / 64), 0);
+    known.assign((rows + 63) / 64, 0);
+    keeps_nodes = false;
     n_present = 0;
     finished = false;
   }
+  size_t depth() const { return csizes.size() - 1; }     // siblings of a block's path: block_proof_depth(n_blocks)
   uint64_t total() const { return n_local * n_blocks; }
   uint64_t n_missing() const { return total() - n_present; }
   bool present(uint64_t local, uint64_t block) const {
@@ -201,6 +214,56 @@ struct FillPlan {
     n_present = 0;
     for (uint64_t w : bits) n_present += (uint64_t)__builtin_popcountll(w);
     return true;
+  }
+
+  // ---- the nodes a serving session keeps ---------------------------------------------------------------------------------------------
+  // the row of node `index` of layer `level` of local slot `local`: what k_block_path_commit_nodes computes from its two device tables
+  // (layer_off = coff, layer_size = csizes), and block_proof_sibling_row's row for an in-range sibling
+  uint64_t node_row(size_t level, uint64_t local, uint64_t index) const { return coff[level] + local * csizes[level] + index; }
+  bool is_known(uint64_t row) const { return (known[(size_t)(row >> 6)] >> (row & 63)) & 1; }
+  void set_known(uint64_t row) { known[(size_t)(row >> 6)] |= 1ULL << (row & 63); }
+  // The rows the kernel stored for the requests it proved (verdict[i] == 0): the block root, and per level the sibling (unless its index
+  // lies past its layer: the zero of an odd layer's last node or of the one-block slot, which has no row) and the ancestor.  Whether the
+  // block was then written does not matter: an UNWRITTEN block is still missing, but its nodes are authentic and stored.
+  void mark_proved(const uint64_t* slot_block, const uint32_t* verdict, size_t n) {
+    for (size_t i = 0; i < n; ++i) {
+      if (verdict[i] != 0) continue;
+      const uint64_t local = slot_block[2 * i] - first_slot, b = slot_block[2 * i + 1];
+      set_known(node_row(0, local, b));
+      for (size_t l = 0; l < depth(); ++l) {
+        const uint64_t sib = (b >> l) ^ 1;
+        if (sib < csizes[l]) set_known(node_row(l, local, sib));
+        set_known(node_row(l + 1, local, b >> (l + 1)));
+      }
+    }
+  }
+  // What a session knows when node keeping is turned on, after every upper layer was built once from layer 0 (absent rows zeroed): a
+  // block root is known where the block is present, and a parent where both children are; the last node of an odd layer (and the
+  // singleton) has one child.  Parents of unknown children hold values nobody reads: their bits stay clear until a proved path stores them.
+  void derive_from_presence() {
+    std::fill(known.begin(), known.end(), 0);
+    for (uint64_t s = 0; s < n_local; ++s)
+      for (uint64_t b = 0; b < n_blocks; ++b)
+        if (present(s, b)) set_known(node_row(0, s, b));
+    for (size_t l = 0; l < depth(); ++l)
+      for (uint64_t s = 0; s < n_local; ++s)
+        for (uint64_t k = 0; k < csizes[l + 1]; ++k) {
+          const bool left = is_known(node_row(l, s, 2 * k));
+          const bool right = 2 * k + 1 < csizes[l] ? is_known(node_row(l, s, 2 * k + 1)) : true;
+          if (left && right) set_known(node_row(l + 1, s, k));
+        }
+  }
+  // can the proof of (local, block) be served: the block present, and every sibling of its path that has a row (block_proof_rows) known
+  bool servable(uint64_t local, uint64_t block) const {
+    if (!present(local, block)) return false;
+    for (size_t l = 0; l < depth(); ++l) {
+      const uint64_t r = block_proof_sibling_row(coff[l], csizes[l], local, block, l);
+      if (r != BLOCK_PROOF_NO_ROW && !is_known(r)) return false;
+    }
+    return true;
+  }
+  uint32_t proof_status(uint64_t local, uint64_t block) const {
+    return !present(local, block) ? FILL_PROOF_ABSENT : servable(local, block) ? FILL_PROOF_OK : FILL_PROOF_PARTIAL;
   }
 
   // ---- what is missing ----------------------------------------------------------------------------------------------------------------

@@ -12,6 +12,7 @@
 //   k_repair_compare      candidate block roots against the kept rows they would replace, one verdict per request (repair.cpp)
 //   k_block_path_roots    a13 candidate block roots walked up their Merkle paths to the slot root, merkle.nim:51-74 (block_proofs.cpp)
 //   k_block_path_commit   the same walk; a proved block root is also stored into layer 0 of a fill session's compact buffer (fill.cpp)
+//   k_block_path_commit_nodes   the same walk; a proved path's 2 x depth + 1 nodes are stored where the session's tree has them (fill.cpp)
 //   k_block_root_recheck  re-read block roots against layer 0 of a resumed fill session; a row the disk no longer backs is zeroed (fill.cpp)
 //
 // All global-memory field elements are 32-byte little-endian canonical integers (the ABI format).
@@ -872,6 +873,87 @@ __global__ void __launch_bounds__(TPB) k_block_path_commit(const uint4* __restri
 }
 
 // ------------------------------------------------------------------------------------------------
+// Slot filling with the nodes kept (fill.cpp, a session after cp2_fill_keep_nodes): k_block_path_commit's walk -- same schedule, keys, odd /
+// last rules and comparison with slot_roots[slot] -- with what a serving session keeps of a proved path: all of it.  A path that ends in
+// the stated slot root proves every node on it, the `depth` siblings the peer sent and the `depth` ancestors the walk computed (were one
+// of them wrong, another root would have come out), and the session's compact buffer has a row for each.
+//   During the walk lane i writes, for every level l, the canonical sibling (a value of at least r lands as its residue) and the canonical
+//   ancestor (`cur` after level l) into rows 2 l and 2 l + 1 of its own `depth` x 2 rows of `scratch`: staging memory, never the tree, so
+//   unproved data goes nowhere else, and the walk holds none of the 2 x depth rows in registers.
+//   After the verdict, on a match only, a second loop over the levels with no permutation in it copies rows, two 16-byte loads and two
+//   16-byte stores each: the block root to layer 0, row dest[i] (as k_block_path_commit); sibling l to layer l, index (b >> l) ^ 1;
+//   ancestor l to layer l + 1, index b >> (l + 1).  The row of (layer l, index) is layer_off[l] + local_slot * layer_size[l] + index
+//   (FillPlan::node_row, fill_plan.hpp), from two device tables of depth + 1 entries.  An index at or past layer_size[l] -- the ZERO sibling
+//   of an odd layer's last node, or of the one-block slot -- is skipped, and so is a row at or past n_rows (never: the host validated every
+//   request and made the tables).  On a mismatch nothing outside the lane's scratch rows and its verdict word is written.
+// No atomics: two proved requests that name the same node store identical bytes, the argument k_block_path_commit makes for layer 0, which
+// holds for every authentic node.  LDS is the QTab only.
+__device__ __forceinline__ void copy_row(uint4* __restrict__ to, const uint4* from) {
+  const uint4 a = from[0], b = from[1];
+  to[0] = a;
+  to[1] = b;
+}
+
+__global__ void __launch_bounds__(TPB) k_block_path_commit_nodes(const uint4* __restrict__ fresh, const uint4* __restrict__ paths,
+                                                                   const uint64_t* __restrict__ slot_block, const uint4* __restrict__ slot_roots,
+                                                                   const uint64_t* __restrict__ dest, const uint64_t* __restrict__ layer_off,
+                                                                   const uint64_t* __restrict__ layer_size, uint64_t n_blocks, uint32_t depth,
+                                                                   size_t n, uint32_t* __restrict__ verdict, uint4* __restrict__ tree,
+                                                                   uint64_t n_rows, uint4* scratch) {
+  __shared__ fr::QTab qtab;
+  fr::qtab_fill(qtab, threadIdx.x, TPB);
+  __syncthreads();
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  Fe cur;
+  {
+    const uint4 f0 = fresh[2 * i], f1 = fresh[2 * i + 1];
+    const uint32_t fw[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
+    cur = fr::to_mont(fr::from_words(fw));
+  }
+  const uint4* path = paths + 2 * i * depth;
+  uint4* mine = scratch + 4 * i * depth;               // rows 2 l (sibling l) and 2 l + 1 (ancestor l), two uint4 a row
+  uint64_t j = slot_block[2 * i + 1], m = n_blocks;
+  State s;
+#pragma unroll 1
+  for (uint32_t lvl = 0; lvl < depth; ++lvl) {
+    const Fe sib = load_fe_canonical(path + 2 * lvl);
+    store_fe_canonical(mine + 4 * lvl, sib);
+    const uint32_t b = (uint32_t)j & 1u;
+    const uint32_t key = (lvl == 0 ? 1u : 0u) + 2u * ((j == m - 1 ? 1u : 0u) & (b ^ 1u));
+    const uint32_t sw = 0u - b;
+#pragma unroll
+    for (int l = 0; l < fr::NL; ++l) {
+      s.x.l[l] = (cur.l[l] & ~sw) | (sib.l[l] & sw);
+      s.y.l[l] = (sib.l[l] & ~sw) | (cur.l[l] & sw);
+    }
+    s.z = key_fe(key);
+    p2::permute(s, qtab);
+    cur = fr::norm(s.x);
+    store_fe_canonical(mine + 4 * lvl + 2, cur);
+    j >>= 1;
+    m = (m + 1) >> 1;
+  }
+  const uint64_t slot = slot_block[2 * i];
+  const Fe want = load_fe_canonical(slot_roots + 2 * slot);
+  const uint64_t r = dest[i];
+  const bool keep = fe_equal(cur, want) && r < n_rows;
+  verdict[i] = keep ? 0u : 1u;
+  if (!keep) return;
+  copy_row(tree + 2 * r, fresh + 2 * i);
+  const uint64_t blk = slot_block[2 * i + 1];
+#pragma unroll 1
+  for (uint32_t lvl = 0; lvl < depth; ++lvl) {
+    const uint64_t size = layer_size[lvl], sib = (blk >> lvl) ^ 1;
+    const uint64_t rs = layer_off[lvl] + slot * size + sib;
+    if (sib < size && rs < n_rows) copy_row(tree + 2 * rs, mine + 4 * lvl);
+    const uint64_t up = layer_size[lvl + 1], anc = blk >> (lvl + 1);
+    const uint64_t ra = layer_off[lvl + 1] + slot * up + anc;
+    if (anc < up && ra < n_rows) copy_row(tree + 2 * ra, mine + 4 * lvl + 2);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Resuming a fill session (fill.cpp): k_repair_compare's comparison, with what a resumed session does about a block whose bytes on disk no
 // longer hash to the root the checkpoint kept -- as k_block_path_commit is k_block_path_roots' walk with what a session keeps of a proved
 // block.  Lane i takes the freshly built block root of re-read block i (fresh row i) and row dest[i] of `layer0`, the session's compact
@@ -1112,6 +1194,24 @@ hipError_t launch_block_path_commit(const void* fresh, const void* paths, const 
     const size_t m = n - i0 < MAX_ITEMS ? n - i0 : MAX_ITEMS;
     CP2K_LAUNCH(k_block_path_commit, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)fresh + 2 * i0, (const uint4*)paths + 2 * i0 * depth,
                 slot_block + 2 * i0, (const uint4*)slot_roots, dest + i0, n_blocks, depth, m, verdict + i0, (uint4*)layer0, n_rows);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+hipError_t launch_block_path_commit_nodes(const void* fresh, const void* paths, const uint64_t* slot_block, const void* slot_roots,
+                                          const uint64_t* dest, const uint64_t* layer_off, const uint64_t* layer_size, uint64_t n_blocks,
+                                          uint32_t depth, size_t n, uint32_t* verdict, void* tree, uint64_t n_rows, void* scratch, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  if (!fresh || !paths || !slot_block || !slot_roots || !dest || !layer_off || !layer_size || !verdict || !tree || !scratch || depth == 0 ||
+      n_blocks == 0)
+    return hipErrorInvalidValue;
+  for (size_t i0 = 0; i0 < n; i0 += MAX_ITEMS) {
+    const size_t m = n - i0 < MAX_ITEMS ? n - i0 : MAX_ITEMS;
+    CP2K_LAUNCH(k_block_path_commit_nodes, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)fresh + 2 * i0, (const uint4*)paths + 2 * i0 * depth,
+                slot_block + 2 * i0, (const uint4*)slot_roots, dest + i0, layer_off, layer_size, n_blocks, depth, m, verdict + i0, (uint4*)tree,
+                n_rows, (uint4*)scratch + 4 * i0 * depth);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }

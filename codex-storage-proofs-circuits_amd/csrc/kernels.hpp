@@ -81,6 +81,16 @@ hipError_t launch_block_path_roots(const void* fresh, const void* paths, const u
 hipError_t launch_block_path_commit(const void* fresh, const void* paths, const uint64_t* slot_block, const void* slot_roots, const uint64_t* dest,
                                     uint64_t n_blocks, uint32_t depth, size_t n, uint32_t* verdict, void* layer0, uint64_t n_rows, hipStream_t st);
 
+// Slot filling with the nodes kept (fill.cpp, k_block_path_commit_nodes): launch_block_path_commit's walk and verdicts.  Where request i is
+// a match, the block root goes to row dest[i] as there, and every node its path proves goes where the compact layout has it: sibling l to
+// row layer_off[l] + local_slot * layer_size[l] + ((block >> l) ^ 1) unless that index is at or past layer_size[l], ancestor l to row
+// layer_off[l + 1] + local_slot * layer_size[l + 1] + (block >> (l + 1)); layer_off / layer_size are device tables of depth + 1 entries,
+// `tree` has n_rows rows.  `scratch` (device, n x depth x 64 bytes, 16-byte aligned) receives every request's canonical siblings and
+// ancestors during the walk; a mismatch writes nothing else.
+hipError_t launch_block_path_commit_nodes(const void* fresh, const void* paths, const uint64_t* slot_block, const void* slot_roots,
+                                          const uint64_t* dest, const uint64_t* layer_off, const uint64_t* layer_size, uint64_t n_blocks,
+                                          uint32_t depth, size_t n, uint32_t* verdict, void* tree, uint64_t n_rows, void* scratch, hipStream_t st);
+
 // Resuming a fill session (fill.cpp, k_block_root_recheck): verdict[i] = 0 when the 32-byte row i of `fresh` (the root a re-read block
 // hashed to) equals row dest[i] of `layer0` (n_rows rows), else 1 -- and then that row of layer0 is overwritten with zeros.  dest[i] >=
 // n_rows: verdict 1, nothing read or written.  The rows of one call are distinct.

@@ -102,6 +102,10 @@ const CP2_RESUME_TRUST_FILES* = 1.cint
 proc cp2_fill_save(fill: pointer, path: cstring): cint {.importc.}
 proc cp2_fill_resume(ctx: Cp2Ctx, cfg: ptr Cp2Config, firstSlot, nLocal: uint64, slotRoots: ptr byte, path: cstring, flags: cint,
                      fill: ptr pointer, nDropped: ptr uint64): cint {.importc.}
+# fill sessions that serve: after cp2_fill_keep_nodes a session stores every node of the paths it proves, and cp2_fill_block_proofs serves
+# the proofs of present blocks from its buffer; status = n x CP2_FILL_PROOF_* (0 served, 1 absent, 2 partial), blockRoots and paths may be nil
+proc cp2_fill_keep_nodes(fill: pointer): cint {.importc.}
+proc cp2_fill_block_proofs(fill: pointer, slotBlock: ptr uint64, n: csize_t, status: ptr uint32, blockRoots, paths: ptr byte): cint {.importc.}
 proc cp2_proof_input_write_json(p: Cp2ProofInput, path: cstring): cint {.importc.}
 proc cp2_proof_input_roots(p: Cp2ProofInput, datasetRoot, slotRoot, entropy: ptr byte): cint {.importc.}
 proc cp2_proof_input_nsamples(p: Cp2ProofInput): csize_t {.importc.}

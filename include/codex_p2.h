@@ -44,8 +44,9 @@ extern "C" {
  *          next: + cp2_dataset_scrub and cp2_multi_dataset_scrub (scrub), cp2_dataset_repair_blocks and
  *                cp2_multi_dataset_repair_blocks (repair), cp2_block_proof_depth, cp2_dataset_block_proofs, cp2_blocks_verify and
  *                cp2_dataset_repair_blocks_proved (block proofs), cp2_fill_begin, cp2_fill_add, cp2_fill_missing, cp2_fill_finish and
- *                cp2_fill_free (fill sessions), cp2_fill_save and cp2_fill_resume (fill checkpoints).  MINOR stays 2 until the release
- *                that carries them: the bump to 1.3 goes in its own commit with that release.                                         */
+ *                cp2_fill_free (fill sessions), cp2_fill_save and cp2_fill_resume (fill checkpoints), cp2_fill_keep_nodes and
+ *                cp2_fill_block_proofs (fill sessions that serve).  MINOR stays 2 until the release that carries them: the bump to 1.3
+ *                goes in its own commit with that release.                                                                            */
 #define CP2_ABI_VERSION_MAJOR 1
 #define CP2_ABI_VERSION_MINOR 2
 #define CP2_ABI_VERSION ((CP2_ABI_VERSION_MAJOR << 16) | CP2_ABI_VERSION_MINOR)
@@ -698,6 +699,50 @@ int cp2_fill_save(const void* f /* const cp2_fill* */, const char* path);
 int cp2_fill_resume(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local,
                     const uint8_t* slot_roots /* n_local x 32, from the manifest */, const char* path, int flags, void** out /* cp2_fill** */,
                     uint64_t* n_dropped /* may be NULL */);
+
+/* ---- fill sessions that serve: block proofs from a session while it is still filling ---------------------------------------------------
+ * A session becomes a dataset only when its last block has arrived, which takes minutes to hours at network speed; until then it holds
+ * thousands of blocks it has proved and written, and cp2_dataset_block_proofs serves none of them.  Nothing new has to be learned to
+ * serve them: a path that ends in the stated slot root proves every node on it -- the `depth` siblings the peer sent and the `depth`
+ * ancestors the walk computed -- and the session's compact buffer, the whole tree over the block roots, has a row for each.  A session
+ * that keeps nodes stores them there, and a present block's proof is a gather from the session's own buffer.
+ *
+ * cp2_fill_keep_nodes turns node keeping on, at any point of an unfinished session.  One-way; a second call is a no-op (CP2_OK).
+ *   Work       the rows of layer 0 whose block is absent are zeroed, every upper layer is built once with the builders' layer kernel as
+ *              cp2_fill_finish does, and a host bitmap with one bit per row of the compact layout records what is known: a block root
+ *              where the block is present, a parent where both children are known (one child for the last node of an odd layer).  So a
+ *              resumed session, or one that was half full before the call, serves the blocks whose whole neighbourhood it already holds.
+ *   Afterwards cp2_fill_add ends in k_block_path_commit_nodes: the same walk and verdicts, and for every request that proves, the block
+ *              root, the in-range siblings and the ancestors of its path are stored where the tree has them and their bits set (whether
+ *              or not the block is then written: a CP2_FILL_UNWRITTEN block stays missing, its nodes are authentic).  A request that
+ *              does not prove leaves nothing in the buffer.  Statuses, writes, presence and the trace line of cp2_fill_add are unchanged.
+ *   Refused    CP2_ERR_INVALID: a NULL session; a finished session.  CP2_ERR_HIP: a context whose stream will not drain.
+ *
+ * cp2_fill_block_proofs serves proofs from the session's buffer, in cp2_dataset_block_proofs' layout.
+ *   Requests   slot_block (n x 2 uint64: dataset slot inside the local range, block of the slot < nBlocks); the same pair may repeat.
+ *   Result     status[i] = CP2_FILL_PROOF_OK (served), _ABSENT (the block is not present) or _PARTIAL (present, but a sibling of its path
+ *              is not known yet: only blocks that arrived before keeping was turned on can be, until later adds bring their
+ *              neighbourhood).  block_roots (n x 32 bytes, may be NULL) and paths (n x depth x 32 bytes, bottom first, zero for a sibling
+ *              past its layer's end, may be NULL); the rows of a request that is not OK are zeros.  One upload of the row list, one gather
+ *              on the device, one download; with both outputs NULL the statuses come from the host bitmaps with no device work.  A block
+ *              added after keeping was turned on is served from the moment it is present.  CP2_TRACE prints one line (requests, served,
+ *              absent, partial, seconds).
+ *   Refused    CP2_ERR_INVALID, the request index (where there is one) in cp2_last_error, outputs untouched: a NULL session; NULL
+ *              slot_block or status when n > 0; a slot outside the local range; a block >= nBlocks; a session that does not keep nodes;
+ *              a finished session (its proofs come from the dataset).  n == 0: CP2_OK.
+ *   Read-only  nothing of the session changes.
+ *
+ * Checkpoints stay as they are (layer 0 and the presence bitmap): a resumed session keeps no nodes until cp2_fill_keep_nodes is called.
+ * cp2_fill_finish is unchanged: it rebuilds every layer, which overwrites the kept nodes with equal values.
+ * Out of scope: cp2_multi_*; accepting a block without its whole path on the strength of kept nodes; deriving nodes a second time.
+ * The three values are written in parentheses: the per-request results of cp2_fill_add above stay the only bare CP2_FILL_* numbers. */
+#define CP2_FILL_PROOF_OK      (0)  /* status: the proof is served                                                      */
+#define CP2_FILL_PROOF_ABSENT  (1)  /* status: the block is not present                                                 */
+#define CP2_FILL_PROOF_PARTIAL (2)  /* status: the block is present, but a sibling of its path is not known yet         */
+int cp2_fill_keep_nodes(void* f /* cp2_fill* */);
+int cp2_fill_block_proofs(void* f /* cp2_fill* */, const uint64_t* slot_block /* n x 2: dataset slot, block */, size_t n,
+                          uint32_t* status /* n */, uint8_t* block_roots /* n x 32, may be NULL */,
+                          uint8_t* paths /* n x depth x 32, may be NULL */);
 
 /* replaces `writeCircomMainComponent`, reference/nim/proof_input/src/cli.nim:186-204 */
 int cp2_write_circom_main(const cp2_config* cfg, const char* path);
