@@ -231,6 +231,8 @@ def load_library():
         "cp2_fill_resume": (i32, [vp, ctypes.POINTER(Config), u64, u64, vp, cp, i32, pvp, ctypes.POINTER(u64)]),
         "cp2_fill_keep_nodes": (i32, [vp]),
         "cp2_fill_block_proofs": (i32, [vp, vp, sz, vp, vp, vp]),
+        "cp2_fill_anchors": (i32, [vp, vp, sz, vp]),
+        "cp2_fill_add_anchored": (i32, [vp, vp, vp, vp, vp, sz, vp, ctypes.POINTER(sz)]),
     }
     for name, (res, args) in sigs.items():
         if v is None and name == "cp2_abi_version":
@@ -935,6 +937,43 @@ class FillSession:
                                                       _p(roots) if n and not statuses_only else None,
                                                       _p(paths) if n and not statuses_only else None), "cp2_fill_block_proofs")
         return status if statuses_only else (status, roots, paths)
+
+    def anchors(self, slot_block):
+        """cp2_fill_anchors: uint32[n], per (slot, block) pair the lowest level at which the session knows the node above the block (0: its
+        block root ... depth: only the stated slot root); host only.  A session that keeps no nodes answers depth throughout."""
+        sb = np.ascontiguousarray(np.asarray(slot_block, dtype=np.uint64).reshape(-1, 2))
+        n = sb.shape[0]
+        levels = np.empty(n, dtype=np.uint32)
+        self.ctx._ck(self.ctx.L.cp2_fill_anchors(self.h, _p(sb) if n else None, n, _p(levels) if n else None), "cp2_fill_anchors")
+        return levels
+
+    def add_anchored(self, slot_block, data, levels, paths, status=None):
+        """cp2_fill_add_anchored: add() for blocks that bring only their levels[i] lowest siblings; `paths` holds them packed in request
+        order (sum(levels) x 32 bytes; None when every level is 0).  Returns (status: uint32[n] of FILL_*, n_new)."""
+        sb = np.ascontiguousarray(np.asarray(slot_block, dtype=np.uint64).reshape(-1, 2))
+        n = sb.shape[0]
+        d = np.ascontiguousarray(data) if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)   # (no copy: see _candidates)
+        if d.nbytes != n * self.cfg.block_size:
+            raise ValueError("fill: %d request(s) need %d bytes of candidates, got %d" % (n, n * self.cfg.block_size, d.nbytes))
+        lv = np.ascontiguousarray(np.asarray(levels, dtype=np.uint32).reshape(-1))
+        if lv.size != n:
+            raise ValueError("fill: %d level(s) expected, got %d" % (n, lv.size))
+        total = int(lv.astype(np.uint64).sum())
+        p = _u8(paths) if paths is not None else np.empty(0, dtype=np.uint8)
+        if p.size != total * 32:
+            raise ValueError("fill: the levels ask for %d sibling(s) of 32 bytes, got %d bytes" % (total, p.size))
+        if status is None:
+            status = np.empty(n, dtype=np.uint32)
+        assert status.dtype == np.uint32 and status.flags["C_CONTIGUOUS"] and status.size == n
+        new = ctypes.c_size_t()
+        st = self.ctx.L.cp2_fill_add_anchored(self.h, _p(sb) if n else None, _p(d) if n else None, _p(lv) if n else None, _p(p) if p.size else None,
+                                              n, _p(status) if n else None, ctypes.byref(new))
+        try:
+            self.ctx._ck(st, "cp2_fill_add_anchored")
+        except CodexP2Error as e:
+            e.fill_status, e.n_new = status, new.value
+            raise
+        return status, new.value
 
     def missing(self, cap=1 << 20):
         """cp2_fill_missing: (missing: uint64[k, 2] of (slot, block), ascending, the lowest k = min(cap, n_missing), n_missing); cap = 0 counts"""

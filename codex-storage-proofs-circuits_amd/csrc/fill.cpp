@@ -1,5 +1,6 @@
 // Fill sessions behind the C ABI (include/codex_p2.h): cp2_fill_begin, cp2_fill_add, cp2_fill_missing, cp2_fill_finish, cp2_fill_free,
-// their checkpoints: cp2_fill_save, cp2_fill_resume, and the sessions that serve while they fill: cp2_fill_keep_nodes, cp2_fill_block_proofs.
+// their checkpoints: cp2_fill_save, cp2_fill_resume, the sessions that serve while they fill: cp2_fill_keep_nodes, cp2_fill_block_proofs, and
+// the adds whose paths stop at a node the session holds: cp2_fill_anchors, cp2_fill_add_anchored.
 //
 // A node that takes on a slot holds the manifest's slot root and receives the slot's network blocks from peers, in any order, each with
 // its Merkle path.  cp2_blocks_verify checks such blocks and forgets the block roots it computed; a session KEEPS them.  It owns the compact
@@ -20,6 +21,11 @@
 // the compact buffer has a row for each, unused until finish.  After cp2_fill_keep_nodes every add ends in k_block_path_commit_nodes, which
 // stores the proved siblings and ancestors where the tree has them; the host's second bitmap (FillPlan::known) says which rows hold
 // authentic nodes, and cp2_fill_block_proofs serves a present block's proof with the gather cp2_dataset_block_proofs does on a dataset.
+//
+// The kept nodes also shorten what a peer has to send.  A computed node that equals an authentic node proves everything below it, so a
+// block whose ancestor at level a is known needs its a lowest siblings only: cp2_fill_anchors names that level per block, and
+// cp2_fill_add_anchored is cp2_fill_add with packed paths of those lengths, ending in k_block_path_commit_anchored, which compares each
+// walk's result with the kept row instead of the slot root.  With the lowest anchors throughout a slot takes nBlocks - 1 siblings in all.
 #include <hip/hip_runtime.h>
 
 #include <fcntl.h>
@@ -99,13 +105,20 @@ void hand_over(DevBuf& from, DevBuf& to) {
   from.p = nullptr; from.bytes = 0; from.owner = nullptr; from.home = nullptr; from.borrowed = false;
 }
 
-void fill_trace(size_t n, const uint32_t* status, size_t n_new, size_t block_size, uint64_t missing, double seconds) {
+constexpr uint64_t WHOLE_PATHS = ~(uint64_t)0;
+
+// siblings: what an anchored add received (of n x depth a plain add would have); WHOLE_PATHS: a plain add, whose line says nothing of it
+void fill_trace(size_t n, const uint32_t* status, size_t n_new, size_t block_size, uint64_t missing, double seconds, uint64_t siblings, size_t depth) {
   if (!std::getenv("CP2_TRACE")) return;
   size_t proved = 0;
   for (size_t i = 0; i < n; ++i) proved += status[i] != FILL_MISMATCH;
   const double bytes = (double)n * (double)block_size;
-  std::fprintf(stderr, "[cp2 trace] fill add: %zu request(s), %zu proved, %zu new, %llu still missing, %.0f bytes, %.3f s (%.2f GB/s)\n", n, proved,
-               n_new, (unsigned long long)missing, bytes, seconds, seconds > 0 ? bytes / seconds / 1e9 : 0.0);
+  char anchored[96] = "";
+  if (siblings != WHOLE_PATHS)
+    std::snprintf(anchored, sizeof anchored, ", anchored: %llu sibling(s) received of %llu", (unsigned long long)siblings,
+                  (unsigned long long)n * (unsigned long long)depth);
+  std::fprintf(stderr, "[cp2 trace] fill add: %zu request(s), %zu proved, %zu new, %llu still missing, %.0f bytes, %.3f s (%.2f GB/s)%s\n", n, proved,
+               n_new, (unsigned long long)missing, bytes, seconds, seconds > 0 ? bytes / seconds / 1e9 : 0.0, anchored);
 }
 
 }  // namespace
@@ -167,53 +180,71 @@ extern "C" int cp2_fill_begin(cp2_ctx* ctx, const cp2_config* cfg, uint64_t firs
   return CP2_ERR_INVALID;
 }
 
-extern "C" int cp2_fill_add(void* fill, const uint64_t* slot_block, const uint8_t* data, const uint8_t* paths, size_t n, uint32_t* status,
-                            size_t* n_new) try {
-  cp2_fill_session* f = session(fill);
-  if (!f) return CP2_ERR_INVALID;
+// What cp2_fill_add and cp2_fill_add_anchored do with n > 0 requests they have checked.  levels == NULL: every request brings its whole
+// path, `paths` is n x depth rows and the walk ends at the stated slot root; otherwise request i brings levels[i] siblings, `paths` is
+// packed in request order and the walk ends at the node the plan names.  Everything else is one body: the data path, the chunks,
+// NEW / DUPLICATE, the writer and its roll-back, presence after the sync, the trace line.
+static int fill_add_checked(cp2_fill_session* f, const uint64_t* slot_block, const uint8_t* data, const uint8_t* paths, const uint32_t* levels,
+                            size_t n, uint32_t* status, size_t* n_new) {
   cp2_ctx* ctx = f->ctx;
   const cp2_config& c = f->cfg;
   FillPlan& plan = f->plan;
-  if (n && (!slot_block || !data || !paths || !status)) {
-    ctx->err = "fill: slot_block, data, paths and status must not be NULL when n > 0";
-    return CP2_ERR_INVALID;
-  }
   std::string err;
-  if (!plan.validate(slot_block, n, &err)) {
-    ctx->err = err;
-    return CP2_ERR_INVALID;
-  }
-  if (n == 0) {
-    if (n_new) *n_new = 0;
-    return CP2_OK;
-  }
   CP2_REFUSE_STUCK(ctx);
   CP2_HIP(ctx, hipSetDevice(ctx->device));
   const auto t0 = std::chrono::steady_clock::now();
   // cp2_blocks_verify's data path; its last step also keeps the block roots that were proved
   const size_t depth = block_proof_depth(plan.n_blocks), path_bytes = depth * 32;
-  std::vector<uint64_t> local_block, dest;
-  plan.device_requests(slot_block, n, &local_block, &dest);
+  std::vector<uint64_t> local_block, dest, path_off, anchor_row;
+  if (levels) plan.device_requests_anchored(slot_block, levels, n, &local_block, &dest, &path_off, &anchor_row);
+  else plan.device_requests(slot_block, n, &local_block, &dest);
   const bool keeps = plan.keeps_nodes;
-  DevBuf d_req, d_dest, d_paths, d_walk;             // (go after the streams have drained: DevBuf::release)
+  DevBuf d_req, d_dest, d_paths, d_walk, d_levels, d_off, d_anchor;   // (go after the streams have drained: DevBuf::release)
   RepairJudge judge;
   judge.begin = [&](size_t chunk) -> int {
     CP2_TRY(d_req.scratch(ctx, n * 16));
     CP2_TRY(d_dest.scratch(ctx, n * 8));
-    CP2_TRY(d_paths.scratch(ctx, chunk * path_bytes));
-    if (keeps) CP2_TRY(d_walk.scratch(ctx, chunk * 2 * path_bytes));   // the chunk's siblings and ancestors as the walk meets them
     CP2_HIP(ctx, hipMemcpyAsync(d_req.p, local_block.data(), n * 16, hipMemcpyHostToDevice, ctx->stream));
     CP2_HIP(ctx, hipMemcpyAsync(d_dest.p, dest.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (levels) {                                    // a chunk's packed paths are one contiguous range: rows [path_off[c0], path_off[c0 + m])
+      uint64_t most = 1;
+      for (size_t c0 = 0; c0 < n; c0 += chunk) most = std::max(most, path_off[std::min(n, c0 + chunk)] - path_off[c0]);
+      CP2_TRY(d_paths.scratch(ctx, (size_t)most * 32));
+      CP2_TRY(d_walk.scratch(ctx, (size_t)most * 64));
+      CP2_TRY(d_levels.scratch(ctx, n * 4));
+      CP2_TRY(d_off.scratch(ctx, n * 8));
+      CP2_TRY(d_anchor.scratch(ctx, n * 8));
+      CP2_HIP(ctx, hipMemcpyAsync(d_levels.p, levels, n * 4, hipMemcpyHostToDevice, ctx->stream));
+      CP2_HIP(ctx, hipMemcpyAsync(d_off.p, path_off.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
+      CP2_HIP(ctx, hipMemcpyAsync(d_anchor.p, anchor_row.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
+      return CP2_OK;
+    }
+    CP2_TRY(d_paths.scratch(ctx, chunk * path_bytes));
+    if (keeps) CP2_TRY(d_walk.scratch(ctx, chunk * 2 * path_bytes));   // the chunk's siblings and ancestors as the walk meets them
     return CP2_OK;
   };
   // the chunk's paths travel with the chunk (the previous chunk's walk, earlier on this stream, has read its own)
   judge.stage = [&](size_t c0, size_t m, hipStream_t st) -> int {
+    if (levels) {
+      const size_t rows = (size_t)(path_off[c0 + m] - path_off[c0]);
+      if (rows) CP2_HIP(ctx, hipMemcpyAsync(d_paths.p, paths + (size_t)path_off[c0] * 32, rows * 32, hipMemcpyHostToDevice, st));
+      return CP2_OK;
+    }
     CP2_HIP(ctx, hipMemcpyAsync(d_paths.p, paths + c0 * path_bytes, m * path_bytes, hipMemcpyHostToDevice, st));
     return CP2_OK;
   };
   judge.verdicts = [&](const uint8_t* fresh, size_t c0, size_t m, uint32_t* verdict, hipStream_t st) -> int {
+    const uint64_t* tab = static_cast<const uint64_t*>(f->layer_tab.p);
+    if (levels) {                                    // the same walk, each lane up to the kept node the plan named
+      CP2_HIP(ctx, cp2k::launch_block_path_commit_anchored(fresh, d_paths.p, static_cast<const uint32_t*>(d_levels.p) + c0,
+                                                           static_cast<const uint64_t*>(d_off.p) + c0, path_off[c0],
+                                                           static_cast<const uint64_t*>(d_req.p) + 2 * c0, f->slot_roots.p,
+                                                           static_cast<const uint64_t*>(d_dest.p) + c0, static_cast<const uint64_t*>(d_anchor.p) + c0,
+                                                           tab, tab + depth + 1, plan.n_blocks, (uint32_t)depth, m, verdict, f->compact.p, plan.rows,
+                                                           d_walk.p, st));
+      return CP2_OK;
+    }
     if (keeps) {                                     // the same walk; a proved path leaves all its nodes where the tree has them
-      const uint64_t* tab = static_cast<const uint64_t*>(f->layer_tab.p);
       CP2_HIP(ctx, cp2k::launch_block_path_commit_nodes(fresh, d_paths.p, static_cast<const uint64_t*>(d_req.p) + 2 * c0, f->slot_roots.p,
                                                         static_cast<const uint64_t*>(d_dest.p) + c0, tab, tab + depth + 1, plan.n_blocks,
                                                         (uint32_t)depth, m, verdict, f->compact.p, plan.rows, d_walk.p, st));
@@ -226,7 +257,9 @@ extern "C" int cp2_fill_add(void* fill, const uint64_t* slot_block, const uint8_
   };
   std::vector<uint32_t> verdict(n), st(n);
   CP2_TRY(repair_check_with(ctx, c.cell_size, c.block_size, data, n, verdict.data(), judge));
-  if (keeps) plan.mark_proved(slot_block, verdict.data(), n);   // written or not: the nodes of a proved path are authentic and stored
+  // written or not: the nodes of a proved path are authentic and stored
+  if (levels) plan.mark_proved_anchored(slot_block, levels, verdict.data(), n);
+  else if (keeps) plan.mark_proved(slot_block, verdict.data(), n);
   plan.resolve(slot_block, verdict.data(), n, st.data());
   int r = CP2_OK;
   if (f->from_file) {                                // the NEW blocks into "<file_base><slot>.dat": repair's writer and its rules
@@ -240,8 +273,30 @@ extern "C" int cp2_fill_add(void* fill, const uint64_t* slot_block, const uint8_
   std::copy(st.begin(), st.end(), status);
   if (n_new) *n_new = set;
   if (r != CP2_OK) ctx->err = err;
-  fill_trace(n, status, set, c.block_size, plan.n_missing(), std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+  fill_trace(n, status, set, c.block_size, plan.n_missing(), std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(),
+             levels ? path_off[n] : WHOLE_PATHS, depth);
   return r;
+}
+
+extern "C" int cp2_fill_add(void* fill, const uint64_t* slot_block, const uint8_t* data, const uint8_t* paths, size_t n, uint32_t* status,
+                            size_t* n_new) try {
+  cp2_fill_session* f = session(fill);
+  if (!f) return CP2_ERR_INVALID;
+  cp2_ctx* ctx = f->ctx;
+  if (n && (!slot_block || !data || !paths || !status)) {
+    ctx->err = "fill: slot_block, data, paths and status must not be NULL when n > 0";
+    return CP2_ERR_INVALID;
+  }
+  std::string err;
+  if (!f->plan.validate(slot_block, n, &err)) {
+    ctx->err = err;
+    return CP2_ERR_INVALID;
+  }
+  if (n == 0) {
+    if (n_new) *n_new = 0;
+    return CP2_OK;
+  }
+  return fill_add_checked(f, slot_block, data, paths, nullptr, n, status, n_new);
 } catch (const std::bad_alloc&) {
   return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
 } catch (...) {
@@ -748,6 +803,62 @@ extern "C" int cp2_fill_block_proofs(void* fill, const uint64_t* slot_block, siz
     std::fprintf(stderr, "[cp2 trace] fill proofs: %zu request(s), %zu served, %zu absent, %zu partial, %.6f s\n", n, count[FILL_PROOF_OK],
                  count[FILL_PROOF_ABSENT], count[FILL_PROOF_PARTIAL], std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
   return CP2_OK;
+} catch (const std::bad_alloc&) {
+  return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
+} catch (...) {
+  return CP2_ERR_INVALID;
+}
+
+// ---- paths that stop at a node the session holds ---------------------------------------------------------------------------------------------
+extern "C" int cp2_fill_anchors(const void* fill, const uint64_t* slot_block, size_t n, uint32_t* levels) try {
+  const cp2_fill_session* f = session(fill);
+  if (!f) return CP2_ERR_INVALID;
+  cp2_ctx* ctx = f->ctx;
+  const FillPlan& plan = f->plan;
+  if (n && (!slot_block || !levels)) {
+    ctx->err = "fill anchors: slot_block and levels must not be NULL when n > 0";
+    return CP2_ERR_INVALID;
+  }
+  if (plan.finished) {
+    ctx->err = "fill anchors: the session is finished: it accepts only cp2_fill_free";
+    return CP2_ERR_INVALID;
+  }
+  std::string err;
+  if (!block_proofs_validate(slot_block, n, plan.first_slot, plan.n_local, plan.n_blocks, &err)) {
+    ctx->err = "fill anchors:" + err.substr(err.find(':') + 1);
+    return CP2_ERR_INVALID;
+  }
+  for (size_t i = 0; i < n; ++i) levels[i] = (uint32_t)plan.anchor_level(slot_block[2 * i] - plan.first_slot, slot_block[2 * i + 1]);
+  return CP2_OK;
+} catch (...) {
+  return CP2_ERR_INVALID;
+}
+
+extern "C" int cp2_fill_add_anchored(void* fill, const uint64_t* slot_block, const uint8_t* data, const uint32_t* levels, const uint8_t* paths,
+                                     size_t n, uint32_t* status, size_t* n_new) try {
+  cp2_fill_session* f = session(fill);
+  if (!f) return CP2_ERR_INVALID;
+  cp2_ctx* ctx = f->ctx;
+  if (n && (!slot_block || !data || !levels || !status)) {
+    ctx->err = "fill: slot_block, data, levels and status must not be NULL when n > 0";
+    return CP2_ERR_INVALID;
+  }
+  std::string err;
+  if (!f->plan.validate_anchored(slot_block, levels, n, &err)) {
+    ctx->err = err;
+    return CP2_ERR_INVALID;
+  }
+  if (!paths)
+    for (size_t i = 0; i < n; ++i)
+      if (levels[i]) {
+        ctx->err = "fill: request " + std::to_string(i) + ": paths must not be NULL when a level is not 0";
+        return CP2_ERR_INVALID;
+      }
+  if (n == 0) {
+    if (n_new) *n_new = 0;
+    return CP2_OK;
+  }
+  return fill_add_checked(f, slot_block, data, paths, levels, n, status, n_new);
 } catch (const std::bad_alloc&) {
   return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
 } catch (...) {

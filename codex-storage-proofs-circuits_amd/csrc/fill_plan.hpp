@@ -1,9 +1,11 @@
 // The host side of a fill session (csrc/fill.cpp: cp2_fill_begin / _add / _missing / _finish): which sessions and requests are accepted,
 // where a proved block root goes in the compact layout, which blocks are present, how the device's verdicts become NEW / DUPLICATE, how a
 // failed write takes its blocks back, the ordered list of what is missing, and when a session may finish; for a session that serves
-// (cp2_fill_keep_nodes, cp2_fill_block_proofs): which rows of the compact layout hold authentic nodes, and which proofs can be served.  No
-// HIP in here: tests/host_check/fill_plan_check.cpp and fill_nodes_check.cpp walk it over random geometries and request sets on the CPU,
-// under AddressSanitizer + UBSan.
+// (cp2_fill_keep_nodes, cp2_fill_block_proofs): which rows of the compact layout hold authentic nodes, and which proofs can be served; for
+// an add whose paths stop at a node the session holds (cp2_fill_anchors, cp2_fill_add_anchored): the lowest such node of a block, which
+// stated levels are accepted, the packed tables the device reads and the rows a proved request makes known.  No HIP in here:
+// tests/host_check/fill_plan_check.cpp, fill_nodes_check.cpp and fill_anchor_check.cpp walk it over random geometries and request sets on
+// the CPU, under AddressSanitizer + UBSan.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -101,18 +103,20 @@ struct FillPlan {
       *err = "fill: the session is finished: it accepts only cp2_fill_free";
       return false;
     }
-    for (size_t i = 0; i < n; ++i) {
-      const uint64_t s = slot_block[2 * i], b = slot_block[2 * i + 1];
-      if (s < first_slot || s - first_slot >= n_local) {
-        *err = "fill: request " + std::to_string(i) + ": slot " + std::to_string(s) + " is not inside the local range " +
-               std::to_string(first_slot) + " + " + std::to_string(n_local);
-        return false;
-      }
-      if (b >= n_blocks) {
-        *err = "fill: request " + std::to_string(i) + ": block " + std::to_string(b) + " of slot " + std::to_string(s) + " is not below nBlocks = " +
-               std::to_string(n_blocks);
-        return false;
-      }
+    for (size_t i = 0; i < n; ++i)
+      if (!validate_pair(i, slot_block[2 * i], slot_block[2 * i + 1], err)) return false;
+    return true;
+  }
+  bool validate_pair(size_t i, uint64_t s, uint64_t b, std::string* err) const {
+    if (s < first_slot || s - first_slot >= n_local) {
+      *err = "fill: request " + std::to_string(i) + ": slot " + std::to_string(s) + " is not inside the local range " +
+             std::to_string(first_slot) + " + " + std::to_string(n_local);
+      return false;
+    }
+    if (b >= n_blocks) {
+      *err = "fill: request " + std::to_string(i) + ": block " + std::to_string(b) + " of slot " + std::to_string(s) + " is not below nBlocks = " +
+             std::to_string(n_blocks);
+      return false;
     }
     return true;
   }
@@ -264,6 +268,78 @@ struct FillPlan {
   }
   uint32_t proof_status(uint64_t local, uint64_t block) const {
     return !present(local, block) ? FILL_PROOF_ABSENT : servable(local, block) ? FILL_PROOF_OK : FILL_PROOF_PARTIAL;
+  }
+
+  // ---- paths that stop at a node the session holds (cp2_fill_anchors, cp2_fill_add_anchored) -------------------------------------------
+  // A computed node that equals an authentic node proves everything below it, by the collision argument the whole walk rests on: so a
+  // block whose ancestor at level a is known needs its a lowest siblings only.  Level depth() is the stated slot root, which a session
+  // holds from the start whether or not the top row's bit is set.
+  // the lowest level whose node on the block's way up is known; depth() throughout for a session that keeps no nodes
+  size_t anchor_level(uint64_t local, uint64_t block) const {
+    if (!keeps_nodes) return depth();
+    for (size_t l = 0; l < depth(); ++l)
+      if (is_known(node_row(l, local, block >> l))) return l;
+    return depth();
+  }
+  // validate's rules, a session that keeps nodes, and per request a level of at most depth() whose node is known NOW (a node another
+  // request of the same call would prove does not count: the device reads every anchor before any request of the call is judged) or
+  // that is depth() itself.  Any known level may be stated, not only the lowest.  false with *err naming the lowest offending index.
+  bool validate_anchored(const uint64_t* slot_block, const uint32_t* levels, size_t n, std::string* err) const {
+    if (finished) {
+      *err = "fill: the session is finished: it accepts only cp2_fill_free";
+      return false;
+    }
+    if (!keeps_nodes) {
+      *err = "fill: this session does not keep the nodes of the paths it proves: call cp2_fill_keep_nodes first";
+      return false;
+    }
+    for (size_t i = 0; i < n; ++i) {
+      const uint64_t s = slot_block[2 * i], b = slot_block[2 * i + 1];
+      if (!validate_pair(i, s, b, err)) return false;
+      const size_t a = levels[i];
+      if (a > depth()) {
+        *err = "fill: request " + std::to_string(i) + ": level " + std::to_string(a) + " is above the depth " + std::to_string(depth());
+        return false;
+      }
+      if (a < depth() && !is_known(node_row(a, s - first_slot, b >> a))) {
+        *err = "fill: request " + std::to_string(i) + ": the node at level " + std::to_string(a) + " above block " + std::to_string(b) +
+               " of slot " + std::to_string(s) + " is not known to the session";
+        return false;
+      }
+    }
+    return true;
+  }
+  static constexpr uint64_t ANCHOR_SLOT_ROOT = UINT64_MAX;   // anchor_row: compare with the stated slot root instead of a row
+  // device_requests, and per request where its siblings start in the packed path buffer (path_off: n + 1 entries, rows; the last is the
+  // sum of all levels) and the row its walk must arrive at
+  void device_requests_anchored(const uint64_t* slot_block, const uint32_t* levels, size_t n, std::vector<uint64_t>* local_block,
+                                std::vector<uint64_t>* dest, std::vector<uint64_t>* path_off, std::vector<uint64_t>* anchor_row) const {
+    device_requests(slot_block, n, local_block, dest);
+    path_off->resize(n + 1);
+    anchor_row->resize(n);
+    uint64_t at = 0;
+    for (size_t i = 0; i < n; ++i) {
+      const size_t a = levels[i];
+      (*path_off)[i] = at;
+      at += a;
+      (*anchor_row)[i] = a >= depth() ? ANCHOR_SLOT_ROOT : node_row(a, slot_block[2 * i] - first_slot, slot_block[2 * i + 1] >> a);
+    }
+    (*path_off)[n] = at;
+  }
+  // The rows the kernel stored for the anchored requests it proved: the block root, the in-range siblings below the level and the
+  // ancestors strictly between; the anchor and everything above it were known already (or are not this request's to vouch for).
+  void mark_proved_anchored(const uint64_t* slot_block, const uint32_t* levels, const uint32_t* verdict, size_t n) {
+    for (size_t i = 0; i < n; ++i) {
+      if (verdict[i] != 0) continue;
+      const uint64_t local = slot_block[2 * i] - first_slot, b = slot_block[2 * i + 1];
+      const size_t a = std::min<size_t>(levels[i], depth());
+      if (a > 0) set_known(node_row(0, local, b));     // (at level 0 the block root is the anchor)
+      for (size_t l = 0; l < a; ++l) {
+        const uint64_t sib = (b >> l) ^ 1;
+        if (sib < csizes[l]) set_known(node_row(l, local, sib));
+        if (l + 1 < a) set_known(node_row(l + 1, local, b >> (l + 1)));
+      }
+    }
   }
 
   // ---- what is missing ----------------------------------------------------------------------------------------------------------------

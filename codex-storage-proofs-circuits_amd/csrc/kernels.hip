@@ -13,6 +13,7 @@
 //   k_block_path_roots    a13 candidate block roots walked up their Merkle paths to the slot root, merkle.nim:51-74 (block_proofs.cpp)
 //   k_block_path_commit   the same walk; a proved block root is also stored into layer 0 of a fill session's compact buffer (fill.cpp)
 //   k_block_path_commit_nodes   the same walk; a proved path's 2 x depth + 1 nodes are stored where the session's tree has them (fill.cpp)
+//   k_block_path_commit_anchored   the same walk, stopped per lane at a node the session's tree already holds (fill.cpp)
 //   k_block_root_recheck  re-read block roots against layer 0 of a resumed fill session; a row the disk no longer backs is zeroed (fill.cpp)
 //
 // All global-memory field elements are 32-byte little-endian canonical integers (the ABI format).
@@ -954,6 +955,98 @@ __global__ void __launch_bounds__(TPB) k_block_path_commit_nodes(const uint4* __
 }
 
 // ------------------------------------------------------------------------------------------------
+// Slot filling with paths that stop at a kept node (fill.cpp, cp2_fill_add_anchored): k_block_path_commit_nodes' walk with a per-lane length
+// and a per-lane target.  A computed node that equals an authentic node proves everything below it -- the collision argument the whole
+// walk rests on -- so a block whose ancestor at level a the session already knows needs its a lowest siblings only.  Lane i takes fresh
+// block root i, levels[i] (at most depth; anything above is a mismatch), its (local slot, block) pair and its levels[i] siblings at row
+// path_off[i] - path_base of the PACKED path buffer `paths` (path_off is the prefix sum of levels over the whole call, path_base the
+// entry of the first request whose siblings `paths` holds).
+//   The walk runs levels[i] levels of the same schedule (left / right by limb masks, key (lvl == 0) + 2 (even last node), j and m carried
+//   from level 0) and writes the canonical sibling and ancestor of each level into rows 2 l and 2 l + 1 of the lane's own 2 x levels[i]
+//   rows of `scratch`, which start at row 2 (path_off[i] - path_base): staging memory, never the tree.
+//   The result is compared with row anchor_row[i] of `tree`, loaded as a canonical element; anchor_row[i] == UINT64_MAX stands for
+//   slot_roots[slot]; any other row at or past n_rows is a mismatch.  levels[i] == 0 runs no permutation: the fresh root against the kept row.
+//   On a match only, a second loop with no permutation in it copies rows: the block root to row dest[i] (unless levels[i] == 0, where
+//   that row is the anchor), sibling l where its index is in range to layer l, ancestor l + 1 to layer l + 1 for l + 1 < levels[i].  The
+//   anchor row and every row above it are never written.  On a mismatch nothing outside the lane's scratch rows and its verdict word is.
+// The host states only anchors that were known before the launch (FillPlan::validate_anchored), so an anchor row that another lane of the
+// launch rewrites is rewritten with the value it holds: a known row can only be proved equal to itself.  No atomics, as in
+// k_block_path_commit_nodes; LDS is the QTab only.  Lanes of a wave walk different lengths; a wave lasts as long as its longest lane.
+__global__ void __launch_bounds__(TPB) k_block_path_commit_anchored(const uint4* __restrict__ fresh, const uint4* __restrict__ paths,
+                                                                      const uint32_t* __restrict__ levels, const uint64_t* __restrict__ path_off,
+                                                                      uint64_t path_base, const uint64_t* __restrict__ slot_block,
+                                                                      const uint4* __restrict__ slot_roots, const uint64_t* __restrict__ dest,
+                                                                      const uint64_t* __restrict__ anchor_row,
+                                                                      const uint64_t* __restrict__ layer_off,
+                                                                      const uint64_t* __restrict__ layer_size, uint64_t n_blocks, uint32_t depth,
+                                                                      size_t n, uint32_t* __restrict__ verdict, uint4* tree, uint64_t n_rows,
+                                                                      uint4* scratch) {
+  __shared__ fr::QTab qtab;
+  fr::qtab_fill(qtab, threadIdx.x, TPB);
+  __syncthreads();
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t len = levels[i];
+  if (len > depth) {                                   // (never: the host validated every level)
+    verdict[i] = 1u;
+    return;
+  }
+  Fe cur;
+  {
+    const uint4 f0 = fresh[2 * i], f1 = fresh[2 * i + 1];
+    const uint32_t fw[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
+    cur = fr::to_mont(fr::from_words(fw));
+  }
+  const uint64_t at = path_off[i] - path_base;
+  const uint4* path = paths + 2 * at;
+  uint4* mine = scratch + 4 * at;                      // rows 2 l (sibling l) and 2 l + 1 (ancestor l), two uint4 a row
+  uint64_t j = slot_block[2 * i + 1], m = n_blocks;
+  State s;
+#pragma unroll 1
+  for (uint32_t lvl = 0; lvl < len; ++lvl) {
+    const Fe sib = load_fe_canonical(path + 2 * lvl);
+    store_fe_canonical(mine + 4 * lvl, sib);
+    const uint32_t b = (uint32_t)j & 1u;
+    const uint32_t key = (lvl == 0 ? 1u : 0u) + 2u * ((j == m - 1 ? 1u : 0u) & (b ^ 1u));
+    const uint32_t sw = 0u - b;
+#pragma unroll
+    for (int l = 0; l < fr::NL; ++l) {
+      s.x.l[l] = (cur.l[l] & ~sw) | (sib.l[l] & sw);
+      s.y.l[l] = (sib.l[l] & ~sw) | (cur.l[l] & sw);
+    }
+    s.z = key_fe(key);
+    p2::permute(s, qtab);
+    cur = fr::norm(s.x);
+    store_fe_canonical(mine + 4 * lvl + 2, cur);
+    j >>= 1;
+    m = (m + 1) >> 1;
+  }
+  const uint64_t slot = slot_block[2 * i], target = anchor_row[i];
+  const bool stated = target == ~(uint64_t)0;
+  if (!stated && target >= n_rows) {
+    verdict[i] = 1u;
+    return;
+  }
+  const Fe want = load_fe_canonical(stated ? slot_roots + 2 * slot : tree + 2 * target);
+  const uint64_t r = dest[i];
+  const bool keep = fe_equal(cur, want) && r < n_rows;
+  verdict[i] = keep ? 0u : 1u;
+  if (!keep || len == 0) return;
+  copy_row(tree + 2 * r, fresh + 2 * i);
+  const uint64_t blk = slot_block[2 * i + 1];
+#pragma unroll 1
+  for (uint32_t lvl = 0; lvl < len; ++lvl) {
+    const uint64_t size = layer_size[lvl], sib = (blk >> lvl) ^ 1;
+    const uint64_t rs = layer_off[lvl] + slot * size + sib;
+    if (sib < size && rs < n_rows) copy_row(tree + 2 * rs, mine + 4 * lvl);
+    if (lvl + 1 == len) break;                         // the ancestor of the last level is the anchor: already there
+    const uint64_t up = layer_size[lvl + 1], anc = blk >> (lvl + 1);
+    const uint64_t ra = layer_off[lvl + 1] + slot * up + anc;
+    if (anc < up && ra < n_rows) copy_row(tree + 2 * ra, mine + 4 * lvl + 2);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Resuming a fill session (fill.cpp): k_repair_compare's comparison, with what a resumed session does about a block whose bytes on disk no
 // longer hash to the root the checkpoint kept -- as k_block_path_commit is k_block_path_roots' walk with what a session keeps of a proved
 // block.  Lane i takes the freshly built block root of re-read block i (fresh row i) and row dest[i] of `layer0`, the session's compact
@@ -1212,6 +1305,26 @@ hipError_t launch_block_path_commit_nodes(const void* fresh, const void* paths, 
     CP2K_LAUNCH(k_block_path_commit_nodes, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)fresh + 2 * i0, (const uint4*)paths + 2 * i0 * depth,
                 slot_block + 2 * i0, (const uint4*)slot_roots, dest + i0, layer_off, layer_size, n_blocks, depth, m, verdict + i0, (uint4*)tree,
                 n_rows, (uint4*)scratch + 4 * i0 * depth);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+hipError_t launch_block_path_commit_anchored(const void* fresh, const void* paths, const uint32_t* levels, const uint64_t* path_off,
+                                             uint64_t path_base, const uint64_t* slot_block, const void* slot_roots, const uint64_t* dest,
+                                             const uint64_t* anchor_row, const uint64_t* layer_off, const uint64_t* layer_size,
+                                             uint64_t n_blocks, uint32_t depth, size_t n, uint32_t* verdict, void* tree, uint64_t n_rows,
+                                             void* scratch, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  if (!fresh || !paths || !levels || !path_off || !slot_block || !slot_roots || !dest || !anchor_row || !layer_off || !layer_size || !verdict ||
+      !tree || !scratch || depth == 0 || n_blocks == 0)
+    return hipErrorInvalidValue;
+  for (size_t i0 = 0; i0 < n; i0 += MAX_ITEMS) {     // path_off is absolute: `paths` and `scratch` stay where they are
+    const size_t m = n - i0 < MAX_ITEMS ? n - i0 : MAX_ITEMS;
+    CP2K_LAUNCH(k_block_path_commit_anchored, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)fresh + 2 * i0, (const uint4*)paths, levels + i0,
+                path_off + i0, path_base, slot_block + 2 * i0, (const uint4*)slot_roots, dest + i0, anchor_row + i0, layer_off, layer_size, n_blocks,
+                depth, m, verdict + i0, (uint4*)tree, n_rows, (uint4*)scratch);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }

@@ -91,6 +91,20 @@ hipError_t launch_block_path_commit_nodes(const void* fresh, const void* paths, 
                                           const uint64_t* dest, const uint64_t* layer_off, const uint64_t* layer_size, uint64_t n_blocks,
                                           uint32_t depth, size_t n, uint32_t* verdict, void* tree, uint64_t n_rows, void* scratch, hipStream_t st);
 
+// Slot filling with paths that stop at a kept node (fill.cpp, k_block_path_commit_anchored): launch_block_path_commit_nodes' walk, request i
+// over its lowest levels[i] <= depth levels only.  `paths` is PACKED: request i's levels[i] canonical siblings, bottom first, start at row
+// path_off[i] - path_base (path_off: the prefix sum of levels, one entry per request; path_base: the entry of the first request whose
+// siblings `paths` holds, 0 for a whole call).  verdict[i] = 0 when the node reached equals row anchor_row[i] of `tree` as a field element
+// (anchor_row[i] == UINT64_MAX: slot_roots[local slot]; any other row >= n_rows: a mismatch).  A match stores the block root to row dest[i],
+// the in-range siblings of levels 0 ... levels[i] - 1 and the ancestors of levels 1 ... levels[i] - 1 where the compact layout has them;
+// the anchor row and every row above it are never written, levels[i] == 0 stores nothing.  `scratch` (device, sum(levels) x 64 bytes,
+// 16-byte aligned) receives request i's siblings and ancestors at row 2 (path_off[i] - path_base); a mismatch writes nothing else.
+hipError_t launch_block_path_commit_anchored(const void* fresh, const void* paths, const uint32_t* levels, const uint64_t* path_off,
+                                             uint64_t path_base, const uint64_t* slot_block, const void* slot_roots, const uint64_t* dest,
+                                             const uint64_t* anchor_row, const uint64_t* layer_off, const uint64_t* layer_size,
+                                             uint64_t n_blocks, uint32_t depth, size_t n, uint32_t* verdict, void* tree, uint64_t n_rows,
+                                             void* scratch, hipStream_t st);
+
 // Resuming a fill session (fill.cpp, k_block_root_recheck): verdict[i] = 0 when the 32-byte row i of `fresh` (the root a re-read block
 // hashed to) equals row dest[i] of `layer0` (n_rows rows), else 1 -- and then that row of layer0 is overwritten with zeros.  dest[i] >=
 // n_rows: verdict 1, nothing read or written.  The rows of one call are distinct.

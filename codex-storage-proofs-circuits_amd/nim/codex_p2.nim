@@ -106,6 +106,11 @@ proc cp2_fill_resume(ctx: Cp2Ctx, cfg: ptr Cp2Config, firstSlot, nLocal: uint64,
 # the proofs of present blocks from its buffer; status = n x CP2_FILL_PROOF_* (0 served, 1 absent, 2 partial), blockRoots and paths may be nil
 proc cp2_fill_keep_nodes(fill: pointer): cint {.importc.}
 proc cp2_fill_block_proofs(fill: pointer, slotBlock: ptr uint64, n: csize_t, status: ptr uint32, blockRoots, paths: ptr byte): cint {.importc.}
+# anchored fill adds: cp2_fill_anchors names the lowest level at which a keeping session knows the node above a block, and
+# cp2_fill_add_anchored takes blocks with their `levels[i]` lowest siblings only, packed in request order
+proc cp2_fill_anchors(fill: pointer, slotBlock: ptr uint64, n: csize_t, levels: ptr uint32): cint {.importc.}
+proc cp2_fill_add_anchored(fill: pointer, slotBlock: ptr uint64, data: ptr byte, levels: ptr uint32, paths: ptr byte, n: csize_t,
+                           status: ptr uint32, nNew: ptr csize_t): cint {.importc.}
 proc cp2_proof_input_write_json(p: Cp2ProofInput, path: cstring): cint {.importc.}
 proc cp2_proof_input_roots(p: Cp2ProofInput, datasetRoot, slotRoot, entropy: ptr byte): cint {.importc.}
 proc cp2_proof_input_nsamples(p: Cp2ProofInput): csize_t {.importc.}

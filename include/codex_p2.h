@@ -45,8 +45,8 @@ extern "C" {
  *                cp2_multi_dataset_repair_blocks (repair), cp2_block_proof_depth, cp2_dataset_block_proofs, cp2_blocks_verify and
  *                cp2_dataset_repair_blocks_proved (block proofs), cp2_fill_begin, cp2_fill_add, cp2_fill_missing, cp2_fill_finish and
  *                cp2_fill_free (fill sessions), cp2_fill_save and cp2_fill_resume (fill checkpoints), cp2_fill_keep_nodes and
- *                cp2_fill_block_proofs (fill sessions that serve).  MINOR stays 2 until the release that carries them: the bump to 1.3
- *                goes in its own commit with that release.                                                                            */
+ *                cp2_fill_block_proofs (fill sessions that serve), cp2_fill_anchors and cp2_fill_add_anchored (anchored fill adds).
+ *                MINOR stays 2 until the release that carries them: the bump to 1.3 goes in its own commit with that release.         */
 #define CP2_ABI_VERSION_MAJOR 1
 #define CP2_ABI_VERSION_MINOR 2
 #define CP2_ABI_VERSION ((CP2_ABI_VERSION_MAJOR << 16) | CP2_ABI_VERSION_MINOR)
@@ -734,7 +734,8 @@ int cp2_fill_resume(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, ui
  *
  * Checkpoints stay as they are (layer 0 and the presence bitmap): a resumed session keeps no nodes until cp2_fill_keep_nodes is called.
  * cp2_fill_finish is unchanged: it rebuilds every layer, which overwrites the kept nodes with equal values.
- * Out of scope: cp2_multi_*; accepting a block without its whole path on the strength of kept nodes; deriving nodes a second time.
+ * Out of scope: cp2_multi_*; deriving nodes a second time.  Accepting a block without its whole path on the strength of kept nodes: the
+ * section on anchored fill adds below.
  * The three values are written in parentheses: the per-request results of cp2_fill_add above stay the only bare CP2_FILL_* numbers. */
 #define CP2_FILL_PROOF_OK      (0)  /* status: the proof is served                                                      */
 #define CP2_FILL_PROOF_ABSENT  (1)  /* status: the block is not present                                                 */
@@ -743,6 +744,50 @@ int cp2_fill_keep_nodes(void* f /* cp2_fill* */);
 int cp2_fill_block_proofs(void* f /* cp2_fill* */, const uint64_t* slot_block /* n x 2: dataset slot, block */, size_t n,
                           uint32_t* status /* n */, uint8_t* block_roots /* n x 32, may be NULL */,
                           uint8_t* paths /* n x depth x 32, may be NULL */);
+
+/* ---- anchored fill adds: blocks whose path stops at a node the session already holds ---------------------------------------------------
+ * After cp2_fill_keep_nodes every proved path leaves its siblings and ancestors in the session's buffer.  They also shorten what the next
+ * peer has to send: a computed node that equals an authentic node proves everything below it, by the collision argument the whole walk
+ * rests on, so a block whose ancestor at level a is known needs its a lowest siblings only.  When every add uses its lowest known
+ * ancestor, a slot of nBlocks = 2^k blocks receives nBlocks - 1 siblings in all, in any arrival order, instead of depth x nBlocks, and
+ * half of its blocks need none: their block root arrived as the level-0 sibling of their neighbour's path, so their bytes can come from
+ * any source, a peer without a tree or an untrusted cache included.  What this saves is bytes on the wire and on the upload; a block
+ * still costs its own hashing, next to which a path is nothing.  Serving needs nothing new: paths are stored bottom first, so a server
+ * truncates a proof of cp2_fill_block_proofs or cp2_dataset_block_proofs by sending its first a rows.
+ *
+ * cp2_fill_anchors: host only, read-only.  levels[i] = the lowest level l in [0, depth] at which the session knows the node above block
+ * slot_block[i] (level 0: its block root; level depth: the stated slot root, which always counts).  A session that does not keep nodes is
+ * not refused: it answers depth throughout.
+ *   Refused    CP2_ERR_INVALID, the request index (where there is one) in cp2_last_error, outputs untouched: a NULL session; NULL
+ *              slot_block or levels when n > 0; a slot outside the local range; a block >= nBlocks; a finished session.  n == 0: CP2_OK.
+ *
+ * cp2_fill_add_anchored is cp2_fill_add with paths of stated lengths.
+ *   Requests   levels[i] <= depth siblings for request i, bottom first; `paths` holds them packed in request order, sum(levels) x 32 bytes
+ *              (may be NULL when every level is 0).  Any level whose node is known may be stated, not only the lowest; level depth is
+ *              cp2_fill_add's whole path.
+ *   Data path  cp2_fill_add's, unchanged; a chunk's packed paths are one contiguous range and are uploaded with it.  The last device step
+ *              (k_block_path_commit_anchored) walks request i up levels[i] levels and compares the result with the kept row of that node
+ *              (level depth: with the stated slot root); level 0 runs no permutation, it compares the fresh block root with the kept
+ *              row.  A request that proves stores its block root, its in-range siblings and the ancestors below the level where the
+ *              tree has them, and their bits are set; the anchor and everything above it are never written.  A request that does not
+ *              prove leaves nothing in the buffer.
+ *   Refused    before any device or file work, CP2_ERR_INVALID, the request index (where there is one) in cp2_last_error, outputs
+ *              untouched: everything cp2_fill_add refuses; a session that does not keep nodes; a level above depth; a level whose node
+ *              was not known WHEN THE CALL STARTED (a node that another request of the same call would prove does not count); NULL
+ *              levels when n > 0; NULL paths when any level is not 0.  n == 0: CP2_OK.
+ *   Result     status[i] = CP2_FILL_NEW, _MISMATCH, _DUPLICATE or _UNWRITTEN with cp2_fill_add's meaning, rules of writing, roll-back and
+ *              presence; a proved CP2_FILL_UNWRITTEN block stays missing and its nodes stay known.  CP2_TRACE prints cp2_fill_add's line
+ *              and the siblings received against n x depth.
+ *
+ * cp2_fill_add, cp2_fill_keep_nodes, cp2_fill_block_proofs, checkpoints and cp2_fill_finish are unchanged.
+ * Out of scope: cp2_multi_*; checkpointing the known siblings of absent blocks (a resumed session derives what presence gives it, as
+ * before); adopting blocks from disk; any change to what is served. */
+int cp2_fill_anchors(const void* f /* const cp2_fill* */, const uint64_t* slot_block /* n x 2: dataset slot, block */, size_t n,
+                     uint32_t* levels /* n */);
+int cp2_fill_add_anchored(void* f /* cp2_fill* */, const uint64_t* slot_block /* n x 2: dataset slot, block */,
+                          const uint8_t* data /* n x blockSize */, const uint32_t* levels /* n */,
+                          const uint8_t* paths /* sum(levels) x 32, packed in request order */, size_t n, uint32_t* status /* n */,
+                          size_t* n_new);
 
 /* replaces `writeCircomMainComponent`, reference/nim/proof_input/src/cli.nim:186-204 */
 int cp2_write_circom_main(const cp2_config* cfg, const char* path);
