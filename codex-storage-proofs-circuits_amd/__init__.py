@@ -233,6 +233,7 @@ def load_library():
         "cp2_fill_block_proofs": (i32, [vp, vp, sz, vp, vp, vp]),
         "cp2_fill_anchors": (i32, [vp, vp, sz, vp]),
         "cp2_fill_add_anchored": (i32, [vp, vp, vp, vp, vp, sz, vp, ctypes.POINTER(sz)]),
+        "cp2_fill_adopt": (i32, [vp, u64, u64, i32, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
     }
     for name, (res, args) in sigs.items():
         if v is None and name == "cp2_abi_version":
@@ -848,6 +849,7 @@ class Dataset:
 FILL_NEW, FILL_MISMATCH, FILL_DUPLICATE, FILL_UNWRITTEN = 0, 1, 2, 3   # CP2_FILL_* (include/codex_p2.h): the per-request results of cp2_fill_add
 RESUME_TRUST_FILES = 1                                                 # CP2_RESUME_TRUST_FILES: cp2_fill_resume reads no slot byte
 FILL_PROOF_OK, FILL_PROOF_ABSENT, FILL_PROOF_PARTIAL = 0, 1, 2         # CP2_FILL_PROOF_*: the per-request results of cp2_fill_block_proofs
+ADOPT_NO_READ = 1                                                      # CP2_ADOPT_NO_READ: cp2_fill_adopt judges what earlier calls read
 
 
 class FillSession:
@@ -974,6 +976,20 @@ class FillSession:
             e.fill_status, e.n_new = status, new.value
             raise
         return status, new.value
+
+    def adopt(self, first_slot=None, n_slots=0, no_read=False):
+        """cp2_fill_adopt: the absent blocks the slot files of slots first_slot .. + n_slots (0: every local slot) cover are read, hashed and
+        kept where the tree above them reaches a node the session knows, the stated slot root included; no_read judges what earlier calls
+        read.  Returns (n_read, n_adopted); a file that cannot be synced raises with both in the error's `n_read` / `n_adopted`."""
+        first = self.first_slot if first_slot is None else first_slot
+        read, adopted = ctypes.c_uint64(), ctypes.c_uint64()
+        st = self.ctx.L.cp2_fill_adopt(self.h, first, n_slots, ADOPT_NO_READ if no_read else 0, ctypes.byref(read), ctypes.byref(adopted))
+        try:
+            self.ctx._ck(st, "cp2_fill_adopt")
+        except CodexP2Error as e:
+            e.n_read, e.n_adopted = read.value, adopted.value
+            raise
+        return read.value, adopted.value
 
     def missing(self, cap=1 << 20):
         """cp2_fill_missing: (missing: uint64[k, 2] of (slot, block), ascending, the lowest k = min(cap, n_missing), n_missing); cap = 0 counts"""

@@ -1,6 +1,7 @@
 // Fill sessions behind the C ABI (include/codex_p2.h): cp2_fill_begin, cp2_fill_add, cp2_fill_missing, cp2_fill_finish, cp2_fill_free,
-// their checkpoints: cp2_fill_save, cp2_fill_resume, the sessions that serve while they fill: cp2_fill_keep_nodes, cp2_fill_block_proofs, and
-// the adds whose paths stop at a node the session holds: cp2_fill_anchors, cp2_fill_add_anchored.
+// their checkpoints: cp2_fill_save, cp2_fill_resume, the sessions that serve while they fill: cp2_fill_keep_nodes, cp2_fill_block_proofs,
+// the adds whose paths stop at a node the session holds: cp2_fill_anchors, cp2_fill_add_anchored, and the blocks taken over from the slot
+// files on the strength of those nodes: cp2_fill_adopt.
 //
 // A node that takes on a slot holds the manifest's slot root and receives the slot's network blocks from peers, in any order, each with
 // its Merkle path.  cp2_blocks_verify checks such blocks and forgets the block roots it computed; a session KEEPS them.  It owns the compact
@@ -26,6 +27,11 @@
 // block whose ancestor at level a is known needs its a lowest siblings only: cp2_fill_anchors names that level per block, and
 // cp2_fill_add_anchored is cp2_fill_add with packed paths of those lengths, ending in k_block_path_commit_anchored, which compares each
 // walk's result with the kept row instead of the slot root.  With the lowest anchors throughout a slot takes nBlocks - 1 siblings in all.
+//
+// The same argument lets a session take blocks from its own disk.  cp2_fill_adopt reads the absent blocks the slot files cover (the
+// re-check's reads and data path), keeps their fresh block roots in a buffer of the session's own, builds the tree above them with the
+// kept nodes wherever there are any (k_adopt_layer, one launch per layer) and keeps every subtree whose computed root equals a node the
+// session knows, the stated slot root included (k_adopt_resolve); adopt_plan.hpp holds the host side.
 #include <hip/hip_runtime.h>
 
 #include <fcntl.h>
@@ -43,6 +49,7 @@
 #include <string>
 #include <vector>
 
+#include "adopt_plan.hpp"
 #include "block_proof_plan.hpp"
 #include "dataset_obj.hpp"
 #include "fill_checkpoint.hpp"
@@ -55,6 +62,8 @@ static_assert(FILL_NEW == CP2_FILL_NEW && FILL_MISMATCH == CP2_FILL_MISMATCH && 
               FILL_UNWRITTEN == CP2_FILL_UNWRITTEN, "fill_plan.hpp restates the header's statuses");
 static_assert(FILL_PROOF_OK == CP2_FILL_PROOF_OK && FILL_PROOF_ABSENT == CP2_FILL_PROOF_ABSENT && FILL_PROOF_PARTIAL == CP2_FILL_PROOF_PARTIAL,
               "fill_plan.hpp restates the header's proof statuses");
+static_assert(ADOPT_F_KNOWN == cp2k::ADOPT_KNOWN && ADOPT_F_CAND == cp2k::ADOPT_CAND && ADOPT_F_MATCH == cp2k::ADOPT_MATCH &&
+              ADOPT_F_PROVED == cp2k::ADOPT_PROVED && ADOPT_F_ADOPTED == cp2k::ADOPT_ADOPTED, "adopt_plan.hpp restates the kernels' flag bits");
 static_assert(BLOCK_PROOF_NO_ROW == NO_ROW, "k_gather_rows zero-fills the rows the plan marks as absent");
 static_assert(FILL_WRITE == CP2_REPAIR_MATCH && FILL_SKIP == CP2_REPAIR_MISMATCH && FILL_WRITE_FAILED == CP2_REPAIR_UNWRITTEN,
               "repair_write takes and leaves repair's statuses");
@@ -70,6 +79,8 @@ struct cp2_fill_session {
   DevBuf slot_roots;                    // the stated roots, canonical: n_local x 32 bytes
   std::vector<uint8_t> roots;           // ... and on the host, for a checkpoint
   DevBuf layer_tab;                     // a session that keeps nodes: coff then csizes as uint64, depth + 1 entries each, uploaded once
+  DevBuf adopt_roots;                   // cp2_fill_adopt: the fresh block roots of the candidates, n_local x n_blocks rows, from the first adopt on
+  std::vector<uint64_t> adopt_have;     // ... and which of its rows hold one
 };
 
 namespace {
@@ -859,6 +870,178 @@ extern "C" int cp2_fill_add_anchored(void* fill, const uint64_t* slot_block, con
     return CP2_OK;
   }
   return fill_add_checked(f, slot_block, data, paths, levels, n, status, n_new);
+} catch (const std::bad_alloc&) {
+  return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
+} catch (...) {
+  return CP2_ERR_INVALID;
+}
+
+// ---- adopting blocks from disk ------------------------------------------------------------------------------------------------------------
+namespace {
+
+// The absent blocks of local slots [s0, s0 + ns) that their files cover, read and reduced to their block roots as recheck_present reads
+// and reduces the present ones; the roots land in `fresh` (one row per block of the read plan, in its order).  Nothing of the session is
+// touched: the caller takes the roots over once every read has succeeded.
+int adopt_read(cp2_fill_session* f, uint64_t s0, uint64_t ns, std::vector<uint64_t>* read_bits, FillReadPlan* rp, DevBuf* fresh) {
+  cp2_ctx* ctx = f->ctx;
+  const cp2_config& c = f->cfg;
+  const FillPlan& plan = f->plan;
+  const size_t bs = c.block_size;
+  std::vector<uint64_t> whole((size_t)ns, 0);
+  for (uint64_t i = 0; i < ns; ++i) {
+    const std::string fname = slot_file_name(f->file_base, plan.first_slot + s0 + i);
+    struct stat sb;
+    if (stat(fname.c_str(), &sb) == 0) whole[(size_t)i] = (uint64_t)sb.st_size / bs;
+    else if (errno != ENOENT && errno != ENOTDIR) {       // absence is a state, as in cp2_fill_resume; anything else is an error
+      ctx->err = slot_file_error(fname, 0);
+      return CP2_ERR_IO;
+    }
+  }
+  *read_bits = adopt_read_bits(plan, s0, ns, whole);
+  const size_t chunk = std::max<size_t>(1, (ctx->stage_bytes / 2) / bs);          // repair_check_with's chunks
+  *rp = fill_read_plan(*read_bits, plan.total(), plan.n_blocks, chunk);
+  const size_t n = rp->g.size();
+  if (n == 0) return CP2_OK;
+  CP2_TRY(fresh->scratch(ctx, n * 32));
+  std::unique_ptr<uint8_t[]> host(new uint8_t[std::min(n, chunk) * bs]);
+  std::vector<uint32_t> verdict(std::min(n, chunk));
+  for (size_t k = 0; k < rp->n_chunks(); ++k) {
+    const size_t i0 = rp->chunk_begin(k), m = rp->chunk_end(k) - i0;
+    for (const FillReadPlan::Run& run : rp->runs(k)) {
+      const std::string fname = slot_file_name(f->file_base, plan.first_slot + run.local);
+      const int fd = open(fname.c_str(), O_RDONLY | O_CLOEXEC);
+      if (fd < 0) { ctx->err = slot_file_error(fname, 0); return CP2_ERR_IO; }
+      int err = 0;
+      for (size_t i = run.i0; i < run.i1 && !err; ++i)
+        err = slot_file_read_rest(fd, host.get() + (i - i0) * bs, bs, (rp->g[i] % plan.n_blocks) * bs);
+      close(fd);
+      if (err) { ctx->err = slot_file_error(fname, err); return CP2_ERR_IO; }
+    }
+    RepairJudge judge;                                   // no verdict here: the chunk's roots are kept for the judgement of the whole tree
+    judge.verdicts = [&](const uint8_t* roots, size_t c0, size_t mm, uint32_t* v, hipStream_t st) -> int {
+      CP2_HIP(ctx, hipMemsetAsync(v, 0, mm * 4, st));
+      CP2_HIP(ctx, hipMemcpyAsync(fresh->u8() + (i0 + c0) * 32, roots, mm * 32, hipMemcpyDeviceToDevice, st));
+      return CP2_OK;
+    };
+    CP2_TRY(repair_check_with(ctx, c.cell_size, bs, host.get(), m, verdict.data(), judge));
+  }
+  return CP2_OK;
+}
+
+}  // namespace
+
+extern "C" int cp2_fill_adopt(void* fill, uint64_t first_slot, uint64_t n_slots, int flags, uint64_t* n_read, uint64_t* n_adopted) try {
+  cp2_fill_session* f = session(fill);
+  if (!f) return CP2_ERR_INVALID;
+  cp2_ctx* ctx = f->ctx;
+  FillPlan& plan = f->plan;
+  if (plan.finished) {
+    ctx->err = "fill adopt: the session is finished: it accepts only cp2_fill_free";
+    return CP2_ERR_INVALID;
+  }
+  if (!plan.keeps_nodes) {
+    ctx->err = "fill: this session does not keep the nodes of the paths it proves: call cp2_fill_keep_nodes first";
+    return CP2_ERR_INVALID;
+  }
+  if (flags & ~CP2_ADOPT_NO_READ) {
+    ctx->err = "fill adopt: unknown flag bits";
+    return CP2_ERR_INVALID;
+  }
+  if (n_slots == 0) {
+    first_slot = plan.first_slot;
+    n_slots = plan.n_local;
+  }
+  if (first_slot < plan.first_slot || first_slot - plan.first_slot >= plan.n_local || n_slots > plan.n_local - (first_slot - plan.first_slot)) {
+    ctx->err = "fill adopt: slots " + std::to_string(first_slot) + " + " + std::to_string(n_slots) + " are not inside the local range " +
+               std::to_string(plan.first_slot) + " + " + std::to_string(plan.n_local);
+    return CP2_ERR_INVALID;
+  }
+  if (!f->from_file) {
+    ctx->err = "fill adopt: a session of the fake source has no slot files to adopt from";
+    return CP2_ERR_INVALID;
+  }
+  CP2_REFUSE_STUCK(ctx);
+  CP2_HIP(ctx, hipSetDevice(ctx->device));
+  const auto t0 = std::chrono::steady_clock::now();
+  const uint64_t s0 = first_slot - plan.first_slot, ns = n_slots;
+  const size_t depth = plan.depth(), total = (size_t)plan.total();
+  // the reads: nothing of the session changes until every one of them has succeeded
+  uint64_t read = 0;
+  if (!(flags & CP2_ADOPT_NO_READ)) {
+    std::vector<uint64_t> read_bits;
+    FillReadPlan rp;
+    DevBuf fresh;
+    CP2_TRY(adopt_read(f, s0, ns, &read_bits, &rp, &fresh));
+    read = rp.g.size();
+    if (!f->adopt_roots.p) CP2_TRY(f->adopt_roots.alloc(ctx, total * 32));
+    for (size_t i = 0; i < rp.g.size();) {               // runs of consecutive blocks: one copy each (an intact file is one run)
+      size_t j = i + 1;
+      while (j < rp.g.size() && rp.g[j] == rp.g[j - 1] + 1) ++j;
+      CP2_HIP(ctx, hipMemcpyAsync(f->adopt_roots.u8() + (size_t)rp.g[i] * 32, fresh.u8() + i * 32, (j - i) * 32, hipMemcpyDeviceToDevice, ctx->stream));
+      i = j;
+    }
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) {
+      (void)hipGetLastError();
+      ctx->err = "fill adopt: keeping the block roots failed on the device";
+      return CP2_ERR_HIP;
+    }
+    adopt_remember(plan, s0, ns, read_bits, &f->adopt_have);
+  }
+  // the judgement: flag bytes up, one launch per layer, the resolve, flag bytes down
+  uint64_t n_cand = 0;
+  std::vector<uint8_t> up = adopt_flags(plan, s0, ns, &f->adopt_have, &n_cand);
+  AdoptVerdict verdict;
+  verdict.adopted.resize((size_t)ns);
+  if (n_cand) {
+    const size_t rows = plan.rows;
+    std::vector<uint64_t> off(plan.coff.begin(), plan.coff.end()), sizes(plan.csizes.begin(), plan.csizes.end());
+    const uint64_t* tab = static_cast<const uint64_t*>(f->layer_tab.p);
+    DevBuf d_cand, d_flags, d_out;
+    CP2_TRY(d_cand.scratch(ctx, rows * 32));
+    CP2_TRY(d_flags.scratch(ctx, rows));
+    CP2_TRY(d_out.scratch(ctx, rows));
+    std::vector<uint8_t> down(rows);
+    CP2_HIP(ctx, hipMemcpyAsync(d_cand.p, f->adopt_roots.p, total * 32, hipMemcpyDeviceToDevice, ctx->stream));   // (coff[0] == 0: layer 0 comes first)
+    CP2_HIP(ctx, hipMemcpyAsync(d_flags.p, up.data(), rows, hipMemcpyHostToDevice, ctx->stream));
+    CP2_HIP(ctx, hipMemsetAsync(d_out.p, 0, rows, ctx->stream));
+    CP2_HIP(ctx, cp2k::launch_adopt_layers(f->compact.p, d_cand.p, d_flags.u8(), f->slot_roots.p, off.data(), sizes.data(), (uint32_t)depth,
+                                           plan.n_local, s0, ns, rows, ctx->stream));
+    CP2_HIP(ctx, cp2k::launch_adopt_resolve(f->compact.p, d_cand.p, d_flags.u8(), d_out.u8(), tab, tab + depth + 1, (uint32_t)depth, plan.n_local,
+                                            s0, ns, plan.coff[depth], rows, ctx->stream));
+    CP2_HIP(ctx, hipMemcpyAsync(down.data(), d_out.p, rows, hipMemcpyDeviceToHost, ctx->stream));
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) {
+      (void)hipGetLastError();
+      ctx->err = "fill adopt: the judgement failed on the device";
+      return CP2_ERR_HIP;
+    }
+    verdict = adopt_apply(&plan, s0, ns, down);           // the proved rows are known from here on: they are authentic and stored
+  }
+  // presence: each file with adopted blocks made durable once, then its bits
+  int r = CP2_OK;
+  uint64_t adopted = 0;
+  for (uint64_t i = 0; i < ns; ++i) {
+    const std::vector<uint64_t>& blocks = verdict.adopted[(size_t)i];
+    if (blocks.empty()) continue;
+    const std::string fname = slot_file_name(f->file_base, plan.first_slot + s0 + i);
+    const int fd = open(fname.c_str(), O_RDONLY | O_CLOEXEC);
+    const int e = fd < 0 ? errno : fdatasync(fd) != 0 ? errno : 0;
+    if (fd >= 0) close(fd);
+    if (e) {                                             // this file's blocks stay absent; their nodes stay known, as with CP2_FILL_UNWRITTEN
+      if (r == CP2_OK) ctx->err = "fill adopt: cannot sync " + fname + ": " + std::strerror(e);
+      r = CP2_ERR_IO;
+      continue;
+    }
+    adopted += adopt_commit(&plan, blocks);
+  }
+  if (n_read) *n_read = read;
+  if (n_adopted) *n_adopted = adopted;
+  if (std::getenv("CP2_TRACE")) {
+    const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), bytes = (double)read * (double)f->cfg.block_size;
+    std::fprintf(stderr, "[cp2 trace] fill adopt: %llu block(s) read, %llu candidate(s), %llu adopted, %llu row(s) proved, %.0f bytes, %.3f s (%.2f GB/s)\n",
+                 (unsigned long long)read, (unsigned long long)n_cand, (unsigned long long)adopted, (unsigned long long)verdict.rows_proved, bytes,
+                 seconds, seconds > 0 ? bytes / seconds / 1e9 : 0.0);
+  }
+  return r;
 } catch (const std::bad_alloc&) {
   return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
 } catch (...) {

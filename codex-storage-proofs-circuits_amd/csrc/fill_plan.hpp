@@ -210,6 +210,21 @@ struct FillPlan {
     n_present -= cleared;
     return cleared;
   }
+  // ... and commit by global index (cp2_fill_adopt, adopt_plan.hpp): the presence bits of blocks whose bytes the disk already holds and the
+  // device has proved; returns how many were clear
+  size_t set_present(const uint64_t* global, size_t n) {
+    size_t set = 0;
+    for (size_t i = 0; i < n; ++i) {
+      if (global[i] >= total()) continue;
+      uint64_t& w = bits[(size_t)(global[i] >> 6)];
+      if (!((w >> (global[i] & 63)) & 1)) {
+        w |= 1ULL << (global[i] & 63);
+        ++set;
+      }
+    }
+    n_present += set;
+    return set;
+  }
   // a saved bitmap taken over (cp2_fill_resume): false when it is not a bitmap of this session (its size, or a bit past the last block)
   bool restore(const std::vector<uint64_t>& saved) {
     if (saved.size() != bits.size()) return false;

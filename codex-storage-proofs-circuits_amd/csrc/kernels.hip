@@ -15,6 +15,7 @@
 //   k_block_path_commit_nodes   the same walk; a proved path's 2 x depth + 1 nodes are stored where the session's tree has them (fill.cpp)
 //   k_block_path_commit_anchored   the same walk, stopped per lane at a node the session's tree already holds (fill.cpp)
 //   k_block_root_recheck  re-read block roots against layer 0 of a resumed fill session; a row the disk no longer backs is zeroed (fill.cpp)
+//   k_adopt_layer, k_adopt_resolve   the tree over block roots read back from disk, judged against the nodes a fill session keeps (fill.cpp)
 //
 // All global-memory field elements are 32-byte little-endian canonical integers (the ABI format).
 #include "kernels.hpp"
@@ -1073,6 +1074,116 @@ __global__ void __launch_bounds__(TPB) k_block_root_recheck(const uint4* __restr
 }
 
 // ------------------------------------------------------------------------------------------------
+// Adopting blocks from disk (fill.cpp, cp2_fill_adopt): the tree over the block roots of blocks read back from the slot files, built with
+// the session's authentic nodes wherever it has them, and judged against those nodes.  One flag byte per row of the compact layout travels
+// with the values: bit 0 the session knows the row (the host sets it, and sets it for every top row: that is the stated slot root), bit 1
+// the row has a computed value in `cand`, bit 2 that value equals the kept one.  A node is DEFINED when bit 0 or bit 1 is set; its value is
+// the kept row where it is known, the computed one otherwise -- a known node never passes a computed value upward.
+//
+// k_adopt_layer: one lane per node of layer l + 1 of the n_sel selected slots, one launch per layer (the flags and candidates of layer l
+// come from the launch before, earlier on the same stream).  Lane (slot, j) reads the flag bytes of children 2 j and 2 j + 1 of its slot;
+// the last node of an odd layer and the one-block slot have one child, a zero sibling and key + 2 (k_compress_layer's rule, key = 1 at
+// layer 0 and 0 above).  With both children defined it loads each from `tree` or `cand` -- the base address is picked with an integer mask,
+// the missing sibling is cleared by a limb mask -- runs one keyed compression, stores the canonical result to its row of `cand` and writes
+// its flag byte: bit 0 as it was, bit 1, and bit 2 where the node is known and the result equals its kept row (the top layer: the stated
+// root of its slot).  With an undefined child it writes the flag byte with bits 1 and 2 clear and nothing else.  A lane whose rows do not
+// all lie below n_rows (never: the host made the tables) reads and writes nothing.  `tree` is only read.  LDS is the QTab only; no atomics.
+//
+// k_adopt_resolve: one lane per row below the top layer, no permutation, no LDS.  It reads `flags`, `cand` and, for a known row of layer
+// 0, that row of `tree`; it writes its own byte of `out` (bits 0-2 as judged, bit 3 proved, bit 4 adopted) and, for a proved row, that
+// row of `tree`.  THE LAYER-0 MATCH IS SET HERE: a layer-0 row that is known and has a candidate gets bit 2, and with it bit 4, when its
+// 32 candidate bytes equal the kept row; nobody else reads that bit.  A row that is not known and has a candidate walks up its ancestors'
+// flag bytes, at most `depth` of them: an ancestor without a computed value ends the walk unproved; the first known one decides it by its
+// bit 2.  A proved row is copied from `cand` into `tree` (two 16-byte loads, two 16-byte stores) and gets bit 3, at layer 0 also bit 4.
+// Only rows that are not known are written and only known rows of `tree` are read, so no lane reads what another writes.  Rows of slots
+// outside the selection, and rows at or past n_rows, are left alone.
+__global__ void __launch_bounds__(TPB) k_adopt_layer(const uint4* __restrict__ tree, uint4* cand, uint8_t* flags,
+                                                       const uint4* __restrict__ slot_roots, uint64_t off_in, uint64_t m_in, uint64_t off_out,
+                                                       uint64_t m_out, uint64_t first_sel, uint64_t n_sel, uint32_t bottom, uint32_t top,
+                                                       uint64_t n_rows) {
+  __shared__ fr::QTab qtab;
+  fr::qtab_fill(qtab, threadIdx.x, TPB);
+  __syncthreads();
+  const size_t t = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (t >= m_out * n_sel) return;
+  const uint64_t seg = t / m_out, j = t - seg * m_out, slot = first_sel + seg;
+  const uint64_t rl = off_in + slot * m_in + 2 * j, rp = off_out + slot * m_out + j;
+  const bool pair = 2 * j + 1 < m_in;
+  if (rl + (pair ? 1u : 0u) >= n_rows || rp >= n_rows) return;
+  const uint32_t fl = flags[rl], fr_ = pair ? (uint32_t)flags[rl + 1] : ADOPT_KNOWN;
+  const uint32_t fp = flags[rp] & ADOPT_KNOWN;
+  if (!(fl & (ADOPT_KNOWN | ADOPT_CAND)) || !(fr_ & (ADOPT_KNOWN | ADOPT_CAND))) {
+    flags[rp] = (uint8_t)fp;
+    return;
+  }
+  // tree where the child is known, cand otherwise: the two bases differ in the bits the mask lets through
+  const uintptr_t bt = (uintptr_t)tree, bc = (uintptr_t)cand;
+  const uintptr_t kl = (uintptr_t)0 - (uintptr_t)(fl & ADOPT_KNOWN), kr = (uintptr_t)0 - (uintptr_t)(fr_ & ADOPT_KNOWN);
+  State s;
+  s.x = load_fe_canonical((const uint4*)((bt & kl) | (bc & ~kl)) + 2 * rl);
+  s.y = load_fe_canonical((const uint4*)((bt & kr) | (bc & ~kr)) + 2 * (rl + (pair ? 1u : 0u)));   // no pair: the left row once more, cleared below
+  const uint32_t have = 0u - (pair ? 1u : 0u);
+#pragma unroll
+  for (int l = 0; l < fr::NL; ++l) s.y.l[l] &= have;
+  s.z = key_fe((bottom ? 1u : 0u) + (pair ? 0u : 2u));
+  p2::permute(s, qtab);
+  const Fe cur = fr::norm(s.x);
+  store_fe_canonical(cand + 2 * rp, cur);
+  uint32_t f = fp | ADOPT_CAND;
+  if (fp) {
+    const Fe want = load_fe_canonical(top ? slot_roots + 2 * slot : tree + 2 * rp);
+    f |= fe_equal(cur, want) ? ADOPT_MATCH : 0u;
+  }
+  flags[rp] = (uint8_t)f;
+}
+
+__global__ void __launch_bounds__(TPB) k_adopt_resolve(uint4* tree, const uint4* __restrict__ cand, const uint8_t* __restrict__ flags,
+                                                         uint8_t* __restrict__ out, const uint64_t* __restrict__ layer_off,
+                                                         const uint64_t* __restrict__ layer_size, uint32_t depth, uint64_t n_local,
+                                                         uint64_t first_sel, uint64_t n_sel, uint64_t n_below, uint64_t n_rows) {
+  const size_t r = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (r >= n_below || r >= n_rows) return;
+  uint32_t lvl = 0;
+#pragma unroll 1
+  while (lvl + 1 < depth && r >= layer_off[lvl + 1]) ++lvl;   // layer_off ascends; n_below == layer_off[depth]
+  uint64_t size = layer_size[lvl];
+  const uint64_t in_layer = r - layer_off[lvl], slot = in_layer / size;
+  if (slot < first_sel || slot - first_sel >= n_sel || slot >= n_local) return;
+  uint64_t k = in_layer - slot * size;
+  const uint32_t f = flags[r] & (ADOPT_KNOWN | ADOPT_CAND | ADOPT_MATCH);
+  if (!(f & ADOPT_CAND)) {
+    out[r] = (uint8_t)f;
+    return;
+  }
+  if (f & ADOPT_KNOWN) {
+    uint32_t g = f;
+    if (lvl == 0) {
+      const uint4 a0 = cand[2 * r], a1 = cand[2 * r + 1], b0 = tree[2 * r], b1 = tree[2 * r + 1];
+      const bool same = ((a0.x ^ b0.x) | (a0.y ^ b0.y) | (a0.z ^ b0.z) | (a0.w ^ b0.w) | (a1.x ^ b1.x) | (a1.y ^ b1.y) | (a1.z ^ b1.z) | (a1.w ^ b1.w)) == 0;
+      g = (f & ~ADOPT_MATCH) | (same ? ADOPT_MATCH | ADOPT_ADOPTED : 0u);
+    }
+    out[r] = (uint8_t)g;
+    return;
+  }
+  bool proved = false;
+#pragma unroll 1
+  for (uint32_t up = lvl + 1; up <= depth; ++up) {
+    k >>= 1;
+    size = layer_size[up];
+    const uint64_t ra = layer_off[up] + slot * size + k;
+    if (k >= size || ra >= n_rows) break;              // (never: the host made the tables)
+    const uint32_t fa = flags[ra];
+    if (!(fa & ADOPT_CAND)) break;
+    if (fa & ADOPT_KNOWN) {
+      proved = (fa & ADOPT_MATCH) != 0;
+      break;
+    }
+  }
+  if (proved) copy_row(tree + 2 * r, cand + 2 * r);
+  out[r] = (uint8_t)(f | (proved ? ADOPT_PROVED | (lvl == 0 ? ADOPT_ADOPTED : 0u) : 0u));
+}
+
+// ------------------------------------------------------------------------------------------------
 // Workgroups for n work items.  A grid holds at most 2^31 - 1 workgroups in x; the per-item kernels are launched in slices of
 // at most MAX_ITEMS items (every item is independent and addressed from a base pointer), the layer / sampling kernels, whose
 // item index is decomposed inside the kernel, refuse what does not fit one grid (2^38 nodes: far beyond any HBM).
@@ -1343,6 +1454,43 @@ hipError_t launch_block_root_recheck(const void* fresh, const uint64_t* dest, si
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+hipError_t launch_adopt_layers(const void* tree, void* cand, uint8_t* flags, const void* slot_roots, const uint64_t* layer_off_host,
+                               const uint64_t* layer_size_host, uint32_t depth, uint64_t n_local, uint64_t first_sel, uint64_t n_sel, uint64_t n_rows,
+                               hipStream_t st) {
+  if (n_sel == 0) return hipSuccess;
+  if (!tree || !cand || !flags || !slot_roots || !layer_off_host || !layer_size_host || depth == 0 || first_sel > n_local ||
+      n_sel > n_local - first_sel)
+    return hipErrorInvalidValue;
+  for (uint32_t l = 0; l < depth; ++l) {               // the tables must describe a compact layout: the kernel derives every row from them
+    const uint64_t m_in = layer_size_host[l], m_out = layer_size_host[l + 1];
+    if (m_in == 0 || m_out != (m_in + 1) / 2 || layer_off_host[l + 1] != layer_off_host[l] + n_local * m_in)
+      return hipErrorInvalidValue;
+    if (!fits_one_grid(m_out * n_sel)) return hipErrorInvalidValue;
+  }
+  if (layer_size_host[depth] != 1) return hipErrorInvalidValue;
+  for (uint32_t l = 0; l < depth; ++l) {
+    const uint64_t m_out = layer_size_host[l + 1];
+    CP2K_LAUNCH(k_adopt_layer, dim3(grid_for(m_out * n_sel)), dim3(TPB), 0, st, (const uint4*)tree, (uint4*)cand, flags, (const uint4*)slot_roots,
+                layer_off_host[l], layer_size_host[l], layer_off_host[l + 1], m_out, first_sel, n_sel, l == 0 ? 1u : 0u, l + 1 == depth ? 1u : 0u,
+                n_rows);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+hipError_t launch_adopt_resolve(void* tree, const void* cand, const uint8_t* flags, uint8_t* out, const uint64_t* layer_off,
+                                const uint64_t* layer_size, uint32_t depth, uint64_t n_local, uint64_t first_sel, uint64_t n_sel, uint64_t n_below,
+                                uint64_t n_rows, hipStream_t st) {
+  if (n_sel == 0 || n_below == 0) return hipSuccess;
+  if (!tree || !cand || !flags || !out || !layer_off || !layer_size || depth == 0 || first_sel > n_local || n_sel > n_local - first_sel ||
+      !fits_one_grid(n_below))
+    return hipErrorInvalidValue;
+  CP2K_LAUNCH(k_adopt_resolve, dim3(grid_for(n_below)), dim3(TPB), 0, st, (uint4*)tree, (const uint4*)cand, flags, out, layer_off, layer_size, depth,
+              n_local, first_sel, n_sel, n_below, n_rows);
+  return hipGetLastError();
 }
 
 hipError_t launch_verify_samples(const VerifyGeom& g, const uint64_t* prm, const void* heads, const void* cells, const void* paths,

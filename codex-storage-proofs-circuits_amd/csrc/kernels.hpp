@@ -111,6 +111,27 @@ hipError_t launch_block_path_commit_anchored(const void* fresh, const void* path
 hipError_t launch_block_root_recheck(const void* fresh, const uint64_t* dest, size_t n, uint32_t* verdict, void* layer0, uint64_t n_rows,
                                      hipStream_t st);
 
+// Adopting blocks from disk (fill.cpp, cp2_fill_adopt).  `tree` is the session's compact buffer (n_rows rows of 32 bytes), `cand` a buffer of
+// the same shape whose layer 0 holds the block roots of the candidates, `flags` one byte per row: bit 0 (ADOPT_KNOWN) the session knows
+// the row -- set by the host, and for every top row -- bit 1 (ADOPT_CAND) the row of `cand` holds a computed value, bit 2 (ADOPT_MATCH)
+// that value equals the kept one.  Both calls work on local slots [first_sel, first_sel + n_sel) of n_local and leave the rows, bytes and
+// flags of every other slot alone; rows at or past n_rows are neither read nor written.
+constexpr uint8_t ADOPT_KNOWN = 1, ADOPT_CAND = 2, ADOPT_MATCH = 4, ADOPT_PROVED = 8, ADOPT_ADOPTED = 16;
+// k_adopt_layer once per layer, bottom first: layer l + 1 of `cand` and `flags` from layer l, a node's value taken from `tree` where it is
+// known and from `cand` otherwise, bit 2 against the kept row or, in the top layer, against slot_roots[local slot].  The layer tables are
+// HOST arrays of depth + 1 entries (FillPlan::coff / csizes); tables that are not a compact layout of n_local slots are refused.
+hipError_t launch_adopt_layers(const void* tree, void* cand, uint8_t* flags, const void* slot_roots, const uint64_t* layer_off_host,
+                               const uint64_t* layer_size_host, uint32_t depth, uint64_t n_local, uint64_t first_sel, uint64_t n_sel, uint64_t n_rows,
+                               hipStream_t st);
+// k_adopt_resolve over the n_below rows under the top layer (n_below = layer_off[depth]); layer_off / layer_size are DEVICE tables of
+// depth + 1 entries.  out[r] (one byte per row, written for the selected slots only) = bits 0-2 of flags[r], bit 2 of a known layer-0 row
+// set here from a bytewise comparison, bit 3 (ADOPT_PROVED) where an unknown row with a computed value reaches a matching known ancestor
+// through computed rows only -- that row of `cand` is then copied into `tree` -- and bit 4 (ADOPT_ADOPTED) on a layer-0 row that is
+// proved, or known and equal.  No known row of `tree` is written.
+hipError_t launch_adopt_resolve(void* tree, const void* cand, const uint8_t* flags, uint8_t* out, const uint64_t* layer_off,
+                                const uint64_t* layer_size, uint32_t depth, uint64_t n_local, uint64_t first_sel, uint64_t n_sel, uint64_t n_below,
+                                uint64_t n_rows, hipStream_t st);
+
 // Proof-input verification (k_verify_samples, circuit/codex/sample_cells.circom:58-148) over n inputs that share the circuit
 // parameters.  Device arrays: prm n x 4 (nCellsPerSlot, nSlotsPerDataSet, slotIndex, shape ok), heads n x (3 + m) felts
 // (dataSetRoot, entropy, slotRoot, slotProof), cells n x ns x nf felts, paths n x ns x md felts; ok receives n x ns sample

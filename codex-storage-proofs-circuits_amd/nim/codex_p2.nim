@@ -111,6 +111,10 @@ proc cp2_fill_block_proofs(fill: pointer, slotBlock: ptr uint64, n: csize_t, sta
 proc cp2_fill_anchors(fill: pointer, slotBlock: ptr uint64, n: csize_t, levels: ptr uint32): cint {.importc.}
 proc cp2_fill_add_anchored(fill: pointer, slotBlock: ptr uint64, data: ptr byte, levels: ptr uint32, paths: ptr byte, n: csize_t,
                            status: ptr uint32, nNew: ptr csize_t): cint {.importc.}
+# adopting blocks from disk: the absent blocks the slot files cover are read, hashed and kept where the tree above them reaches a node the
+# session knows (the stated slot root included); flags = 0 or CP2_ADOPT_NO_READ (judge what earlier calls read); nRead, nAdopted may be nil
+const CP2_ADOPT_NO_READ* = 1.cint
+proc cp2_fill_adopt(fill: pointer, firstSlot, nSlots: uint64, flags: cint, nRead, nAdopted: ptr uint64): cint {.importc.}
 proc cp2_proof_input_write_json(p: Cp2ProofInput, path: cstring): cint {.importc.}
 proc cp2_proof_input_roots(p: Cp2ProofInput, datasetRoot, slotRoot, entropy: ptr byte): cint {.importc.}
 proc cp2_proof_input_nsamples(p: Cp2ProofInput): csize_t {.importc.}

@@ -45,7 +45,8 @@ extern "C" {
  *                cp2_multi_dataset_repair_blocks (repair), cp2_block_proof_depth, cp2_dataset_block_proofs, cp2_blocks_verify and
  *                cp2_dataset_repair_blocks_proved (block proofs), cp2_fill_begin, cp2_fill_add, cp2_fill_missing, cp2_fill_finish and
  *                cp2_fill_free (fill sessions), cp2_fill_save and cp2_fill_resume (fill checkpoints), cp2_fill_keep_nodes and
- *                cp2_fill_block_proofs (fill sessions that serve), cp2_fill_anchors and cp2_fill_add_anchored (anchored fill adds).
+ *                cp2_fill_block_proofs (fill sessions that serve), cp2_fill_anchors and cp2_fill_add_anchored (anchored fill adds),
+ *                cp2_fill_adopt (adopting blocks from disk).
  *                MINOR stays 2 until the release that carries them: the bump to 1.3 goes in its own commit with that release.         */
 #define CP2_ABI_VERSION_MAJOR 1
 #define CP2_ABI_VERSION_MINOR 2
@@ -781,7 +782,7 @@ int cp2_fill_block_proofs(void* f /* cp2_fill* */, const uint64_t* slot_block /*
  *
  * cp2_fill_add, cp2_fill_keep_nodes, cp2_fill_block_proofs, checkpoints and cp2_fill_finish are unchanged.
  * Out of scope: cp2_multi_*; checkpointing the known siblings of absent blocks (a resumed session derives what presence gives it, as
- * before); adopting blocks from disk; any change to what is served. */
+ * before); adopting blocks from disk (its own section, further down); any change to what is served. */
 int cp2_fill_anchors(const void* f /* const cp2_fill* */, const uint64_t* slot_block /* n x 2: dataset slot, block */, size_t n,
                      uint32_t* levels /* n */);
 int cp2_fill_add_anchored(void* f /* cp2_fill* */, const uint64_t* slot_block /* n x 2: dataset slot, block */,
@@ -791,6 +792,51 @@ int cp2_fill_add_anchored(void* f /* cp2_fill* */, const uint64_t* slot_block /*
 
 /* replaces `writeCircomMainComponent`, reference/nim/proof_input/src/cli.nim:186-204 */
 int cp2_write_circom_main(const cp2_config* cfg, const char* path);
+
+/* ---- adopting blocks from disk: bytes the slot files hold but the session does not count ---------------------------------------------------
+ * A session learns of a block's bytes through cp2_fill_add*, from the caller's memory.  Bytes that are in "<file_base><slot>.dat" already
+ * but not in the presence bitmap -- blocks added after the last cp2_fill_save and before a crash, a slot file restored from a backup or
+ * copied from another node, a file whose checkpoint was lost -- are dead weight to it.  The kept nodes make them cheap to take over: a
+ * computed node that equals an authentic node proves everything below it, so after cp2_fill_keep_nodes one proved path leaves depth
+ * authentic siblings, the top one vouches for half the slot, and the stated slot root vouches for all of it.  An intact file is adopted
+ * whole with no network traffic; a file with a few damaged blocks costs about depth siblings and one block per damaged block.
+ *
+ * cp2_fill_adopt(f, first_slot, n_slots, flags, n_read, n_adopted) works on slots first_slot .. + n_slots (n_slots == 0: every local slot).
+ *   Candidates the ABSENT blocks of those slots that their file covers completely.  A file that does not exist, or ends before the block
+ *              does, yields no candidate for that block: absence is a state, as in cp2_fill_resume.  The candidates are read file by file
+ *              in ascending offset order, in chunks of half the context's staging, and reduced to fresh block roots on cp2_fill_add's data
+ *              path, exactly as the re-check of cp2_fill_resume reads the present ones.  Present blocks are never read.  A read that
+ *              fails is CP2_ERR_IO with the builders' message, and nothing of the session has changed.  *n_read = the blocks read.
+ *   Remembered the session keeps the fresh block roots of its candidates in a device buffer of its own (n_local x nBlocks rows, allocated
+ *              by the first adopt) and a host bitmap of the rows that hold one.  A read refreshes them for the slots it covers.
+ *              CP2_ADOPT_NO_READ reads no slot byte and judges what is remembered: use it after later adds have made more nodes known.
+ *              It TRUSTS THE FILES UNCHANGED SINCE THEY WERE READ, as everything after a resume's re-check does.  A block that has become
+ *              present in the meantime is no longer a candidate.
+ *   Judgement  on the device.  Per row of the compact layout of those slots: `known` is the session's bit, the top row always known (it is
+ *              the stated slot root).  A layer-0 row has a computed value where a candidate exists; a node above has one when both
+ *              children are known or computed (one child for the last node of an odd layer and for the one-block slot), namely
+ *              compress(vL, vR, key) with v = the kept value where known, the computed one otherwise, and the keys of the tree builders
+ *              (k_adopt_layer, one launch per layer).  A known node whose computed value equals its kept value matches.  A row that is
+ *              not known and has a computed value is PROVED when the first known node on its way up matches and every row between has a
+ *              computed value (k_adopt_resolve): it is copied into the session's buffer and its bit is set.  A block is ADOPTED when its
+ *              layer-0 row is proved, or is known and equals its candidate.  Nothing else of the buffer is written; a known row is never
+ *              written, a computed value can only be proved equal to it.
+ *   Presence   every file with adopted blocks is fdatasync'ed once, then its presence bits are set; *n_adopted = the bits set.  A sync
+ *              that fails is CP2_ERR_IO naming the file: that file's blocks stay absent and their nodes stay known -- they are authentic,
+ *              as with CP2_FILL_UNWRITTEN.  Adopting nothing is CP2_OK.  An adopted block is served by cp2_fill_block_proofs at once, and
+ *              a checkpoint saved afterwards covers it.
+ *   Refused    CP2_ERR_INVALID, the reason in cp2_last_error, nothing changed, outputs untouched: a NULL session; a finished session; a
+ *              session that does not keep nodes; slots outside the local range; an unknown flag; a session of the fake source (it has no
+ *              files).  A context whose stream will not drain: CP2_ERR_HIP.
+ *   CP2_TRACE  one line per call: blocks read, candidates, adopted, rows proved, bytes, seconds, GB/s.
+ *
+ * cp2_fill_add*, cp2_fill_missing, cp2_fill_anchors, cp2_fill_block_proofs, checkpoints and cp2_fill_finish are unchanged.
+ * Out of scope: cp2_multi_*; deriving a parent from two known children without a match; checkpointing known siblings or candidates (a
+ * resumed session adopts again); pipelining the reads -- they are the re-check's reads, which are host-bound. */
+#define CP2_ADOPT_NO_READ 1   /* flag: read no slot byte; judge the candidates remembered from earlier calls */
+int cp2_fill_adopt(void* f /* cp2_fill* */, uint64_t first_slot, uint64_t n_slots /* 0: every local slot */, int flags,
+                   uint64_t* n_read /* may be NULL */, uint64_t* n_adopted /* may be NULL */);
+
 
 /* ---- e: every GPU of the node behind one handle ------------------------------------------------------ */
 /* `generateProofInput` hashes every slot of the dataset before it proves one (reference/nim/proof_input/src/gen_input/
