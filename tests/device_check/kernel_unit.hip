@@ -12,6 +12,7 @@ extern "C" {
 
 size_t ku_sizeof_tree_geom() { return sizeof(cp2k::TreeGeom); }
 size_t ku_sizeof_many_req() { return sizeof(cp2k::ManyReq); }
+size_t ku_sizeof_verify_geom() { return sizeof(cp2k::VerifyGeom); }
 size_t ku_scrub_tile() { return cp2k::SCRUB_TILE; }
 
 int ku_scrub_compare(const void* fresh, size_t fstride, const void* kept, size_t kstride, size_t rows, size_t n_items, uint64_t* bits,
@@ -57,6 +58,10 @@ int ku_block_path_roots(const void* fresh, const void* paths, const uint64_t* ro
 int ku_block_path_commit(const void* fresh, const void* paths, const uint64_t* slot_block, const void* slot_roots, const uint64_t* dest,
                          uint64_t n_blocks, uint32_t depth, size_t n, uint32_t* verdict, void* layer0, uint64_t n_rows) {
   return (int)cp2k::launch_block_path_commit(fresh, paths, slot_block, slot_roots, dest, n_blocks, depth, n, verdict, layer0, n_rows, nullptr);
+}
+
+int ku_verify_samples(const cp2k::VerifyGeom* g, const uint64_t* prm, const void* heads, const void* cells, const void* paths, uint8_t* ok) {
+  return (int)cp2k::launch_verify_samples(*g, prm, heads, cells, paths, ok, nullptr);
 }
 
 }  // extern "C"

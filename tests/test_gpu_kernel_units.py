@@ -1,4 +1,4 @@
-"""GPU suite: the compare, sampling, gather, layer and path-walk kernels one launcher at a time.
+"""GPU suite: the compare, sampling, gather, layer, path-walk and proof-input verify kernels one launcher at a time.
 
 The feature tests (scrub, repair, proof_many, block proofs, fill) reach these kernels only behind hosts that validate every request, so
 the kernels there see nothing but well-formed hashes.  Here each cp2k::launch_* is called directly, through the forwarders of
@@ -16,11 +16,19 @@ bit of the mask instead, the cases from 2^33 up a bit above 31 (kernel_models.re
 Sampling also runs on four trees with layers of odd size (kernel_models.SAMPLE_ODD_GEOMS): with n_cells a power of two and
 nblocks = n_cells / cpb no big-tree layer is odd, and the (m + 1) >> 1 of the path loops could be m >> 1 unnoticed.
 
+k_verify_samples runs the launches of kernel_models.verify_plan: every nCellsPerSlot side by side in one launch, each felt of each
+accepted input mutated in turn, the top walk over every (nSlots, slotIndex), field edges, lane layouts, refused inputs whose unread
+regions are 0xFF bytes.  What it owes, byte for byte, is tests/circuit_verdict.py; the plan's own expectations are held against that
+model by the CPU suite.  Each ok buffer lies between guards, and the four input arrays are read back after every launch.
+
 Counts and times, printed by each test ("[kernel units] ...") and by test_summary.  On an MI355X the module ran in 4.5 s, 1.5 s of
 it loading the libraries: scrub compare 320 cases 0.4 s, repair compare 36 cases 0.01 s, sample paths / sample many 176 cases (37 776
 lanes through each kernel) 0.4 s, compact sampling 20 cases 0.01 s, gather rows 28 cases 0.2 s, gather addr 149 cases 0.3 s, compress
 layer 240 cases 0.3 s, fake cells with many seeds 270 cases 0.1 s, block path roots 2547 requests 0.02 s (0.16 s before it for the
-oracle's trees and the model's verdicts), block path commit 2816 requests 0.01 s.  Its summary line: "6602 cases, 0 skipped"."""
+oracle's trees and the model's verdicts), block path commit 2816 requests 0.01 s.  Those are 6602 cases.  The k_verify_samples plan adds
+3241 inputs (7990 lanes in 19 launches: five geometries 144 / 105 / 248 / 261 / 374 inputs, top walks 1 / 5 / 92 / 1520 / 92, edges,
+layouts and refused shapes 399); building it and taking the model's verdicts costs about 8 s of pure Python on the host, most of it in
+the 2048-byte geometry (2.6 s) and in the model's first pass.  The summary line: "9843 cases, 0 skipped"."""
 import ctypes
 import os
 import subprocess
@@ -46,6 +54,11 @@ class TreeGeom(ctypes.Structure):
     _fields_ = [("nb", ctypes.c_uint32), ("nt", ctypes.c_uint32), ("cpb", ctypes.c_uint64), ("nblocks", ctypes.c_uint64),
                 ("n_cells", ctypes.c_uint64), ("boff", ctypes.c_uint64 * K.MAX_LAYERS), ("bsz", ctypes.c_uint64 * K.MAX_LAYERS),
                 ("toff", ctypes.c_uint64 * K.MAX_LAYERS), ("tsz", ctypes.c_uint64 * K.MAX_LAYERS)]
+
+
+class VerifyGeom(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_size_t), ("ns", ctypes.c_uint32), ("nf", ctypes.c_uint32), ("md", ctypes.c_uint32), ("m", ctypes.c_uint32),
+                ("bd", ctypes.c_uint32)]
 
 
 class ManyReq(ctypes.Structure):
@@ -82,14 +95,16 @@ def ku(pkg):
             "ku_gen_fake_cells_many": [vp, vp, u64, sz, sz, vp],
             "ku_compress_layer": [vp, vp, sz, sz, i32, sz, sz],
             "ku_block_path_roots": [vp, vp, vp, vp, u64, u32, sz, vp, vp],
-            "ku_block_path_commit": [vp, vp, vp, vp, vp, u64, u32, sz, vp, vp, u64]}
+            "ku_block_path_commit": [vp, vp, vp, vp, vp, u64, u32, sz, vp, vp, u64],
+            "ku_verify_samples": [ctypes.POINTER(VerifyGeom), vp, vp, vp, vp, vp]}
     for name, args in sigs.items():
         f = getattr(lib, name)
         f.restype, f.argtypes = i32, args
-    for name in ("ku_sizeof_tree_geom", "ku_sizeof_many_req", "ku_scrub_tile"):
+    for name in ("ku_sizeof_tree_geom", "ku_sizeof_many_req", "ku_sizeof_verify_geom", "ku_scrub_tile"):
         getattr(lib, name).restype = sz
     assert lib.ku_sizeof_tree_geom() == ctypes.sizeof(TreeGeom) == 1312
     assert lib.ku_sizeof_many_req() == ctypes.sizeof(ManyReq) == 112
+    assert lib.ku_sizeof_verify_geom() == ctypes.sizeof(VerifyGeom) == 32
     assert lib.ku_scrub_tile() == K.SCRUB_TILE
     return lib
 
@@ -617,12 +632,101 @@ def test_block_path_commit_stores_what_it_proved_and_nothing_else(ku, torch_, wa
     report(capsys, "block path commit", cases, bad, t0)
 
 
+# ---- k_verify_samples ------------------------------------------------------------------------------------------------------------------
+def run_verify_launch(ku, torch, launch, bad):
+    """One launch of the plan: the inputs packed as VerifyGeom documents, every byte of ok against tests/circuit_verdict.py (and against
+    what the plan itself states for that input), the guards around ok, and the four input arrays read back unchanged."""
+    md, bd, m, nf = launch.geom
+    n, ns = len(launch.items), launch.ns
+    what = "verify_samples %s (n=%d)" % (launch.name, n)
+    arrays = K.verify_pack([it.d for it in launch.items], launch.geom)
+    want = np.empty(n * ns + n, dtype=np.uint8)
+    for i, it in enumerate(launch.items):
+        e = K.verify_expected(it.d, launch.geom)
+        assert it.expect is None or it.expect == e, (launch.name, it.tag)
+        want[i * ns:(i + 1) * ns], want[n * ns + i] = e[:ns], e[ns]
+    dev = [up(torch, a) for a in arrays]
+    ptrs = [t.data_ptr() if t.numel() else None for t in dev]
+    assert ptrs[0] and ptrs[1] and (ns == 0) == (ptrs[2] is None) == (ptrs[3] is None)
+    ok = Out(torch, n * ns + n)
+    g = VerifyGeom(n, ns, nf, md, m, bd)
+    status = ku.ku_verify_samples(ctypes.byref(g), ptrs[0], ptrs[1], ptrs[2], ptrs[3], ok.ptr)
+    if status != 0:
+        bad.append("%s: status %d" % (what, status))
+        return 0
+    body = ok.fetch()
+    if not ok.guards_ok():
+        bad.append("%s: bytes around ok changed" % what)
+    wrong = np.nonzero(body != want)[0]
+    for t in wrong[:8].tolist():
+        i, lane = (t - n * ns, "dataset root") if t >= n * ns else (t // ns, "sample %d" % (t % ns))
+        bad.append("%s: lane %d = input %d [%s], %s: device %#04x, the circuit %#04x (%d lanes differ)" % (
+            what, t, i, launch.items[i].tag, lane, int(body[t]), int(want[t]), wrong.size))
+    for name, a, t in zip(("prm", "heads", "cells", "paths"), arrays, dev):
+        if not np.array_equal(t.cpu().numpy(), a.view(np.uint8).reshape(-1)):
+            bad.append("%s: the kernel changed %s" % (what, name))
+    return n * ns + n
+
+
+def run_verify_launches(ku, torch_, capsys, name, launches):
+    t0, bad = time.time(), []
+    lanes = sum(run_verify_launch(ku, torch_, x, bad) for x in launches)
+    with capsys.disabled():
+        print("\n[kernel units] %s: %d launches, %d lanes" % (name, len(launches), lanes))
+    report(capsys, name, K.verify_plan_cases(launches), bad, t0)
+
+
+def verify_name(gi):
+    return "verify samples, geometry %d" % gi
+
+
+@pytest.mark.parametrize("gi", range(len(K.VERIFY_GEOMS)), ids=["-".join(map(str, g)) for g in K.VERIFY_GEOMS])
+def test_verify_samples_every_depth_in_one_launch_and_every_felt(ku, torch_, capsys, gi):
+    """Accepted inputs of every nCellsPerSlot = 2^1..2^maxDepth side by side in one launch, over several (nSlots, slotIndex), with the
+    sampled index at 0, at nCells - 1 and at a block's last cell; and of each one copy per cell felt, path level, slot-proof level and
+    head felt, that felt + 1: a felt the circuit reads clears its own byte, one it does not read clears none."""
+    run_verify_launches(ku, torch_, capsys, verify_name(gi), [K.verify_geometry_launch(gi)])
+
+
+VERIFY_TOP_RUNS = tuple((m, 0) for m in K.VERIFY_TOP_M) + ((3, 2),)
+
+
+@pytest.mark.parametrize("m,ns", VERIFY_TOP_RUNS, ids=["m%d-ns%d" % r for r in VERIFY_TOP_RUNS])
+def test_verify_samples_top_walk_over_every_slot_count_and_index(ku, torch_, capsys, m, ns):
+    """Every nSlots <= 2^m with every slotIndex < 2^m, past nSlots too (rejected with the true root, accepted with the one the circuit
+    reaches); ns == 0: a launch of top lanes only, cells and paths NULL."""
+    run_verify_launches(ku, torch_, capsys, "verify samples, top walk m=%d ns=%d" % (m, ns), [K.verify_top_launch(m, ns)])
+
+
+def test_verify_samples_field_edges_lane_layouts_and_refused_shapes(ku, torch_, capsys):
+    """Cells and siblings at the field's edges with the compared root off by one and in bit 253; launches of 1, 255, 256, 257 and 513
+    lanes whose first top lane falls on, after and before a wave's first lane and on a workgroup's; refused inputs full of 0xFF bytes."""
+    run_verify_launches(ku, torch_, capsys, "verify samples, edges, layouts, refused", [K.verify_edge_launch()] + K.verify_layout_launches() + [K.verify_refused_launch()])
+
+
+def test_verify_samples_no_inputs_no_work(ku, torch_):
+    launch = K.verify_geometry_launch(2)
+    arrays = K.verify_pack([it.d for it in launch.items[:2]], launch.geom)
+    dev = [up(torch_, a) for a in arrays]
+    ok = Out(torch_, 2 * launch.ns + 2)
+    md, bd, m, nf = launch.geom
+    g = VerifyGeom(0, launch.ns, nf, md, m, bd)
+    assert ku.ku_verify_samples(ctypes.byref(g), dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr(), dev[3].data_ptr(), ok.ptr) == 0
+    bad = []
+    ok.check(ok.prefill(), "ok", bad)
+    assert not bad, bad
+
+
 def test_summary():
     """Runs last in this module: every plan ran whole."""
     walk = sum(len(K.walk_plan(n)) for n in K.WALK_N_BLOCKS)
     want = {"scrub compare": len(K.scrub_plan()), "repair compare": len(K.repair_plan()), "sample paths / sample many": len(K.sample_plan()),
             "sample many, compact": len(K.compact_plan()), "gather rows": len(K.gather_rows_plan()), "gather addr": len(K.gather_addr_plan()),
             "compress layer": len(K.layer_plan()), "fake cells, many seeds": len(K.fake_many_plan()), "block path roots": walk}
+    want.update({verify_name(gi): len(K.verify_geometry_launch(gi).items) for gi in range(len(K.VERIFY_GEOMS))})
+    want.update({"verify samples, top walk m=%d ns=%d" % (m, ns): len(K.verify_top_launch(m, ns).items) for m, ns in VERIFY_TOP_RUNS})
+    want["verify samples, edges, layouts, refused"] = K.verify_plan_cases([K.verify_edge_launch()] + K.verify_layout_launches() + [K.verify_refused_launch()])
+    assert sum(n for name, n in want.items() if name.startswith("verify samples")) == K.verify_plan_cases()
     for name, n in want.items():
         assert TALLY.get(name) == n, name
     assert TALLY.get("block path commit", 0) > walk

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import circuit_verdict as V
+import kernel_models as K
 
 pytestmark = pytest.mark.gpu
 
@@ -175,6 +176,30 @@ def test_random_mutations_match_the_helper(pkg, ctx):
             d["nSlotsPerDataSet"] = rng.randrange((1 << m) + 2)
         out.append(d)
     _check(pkg, ctx, c, out)
+
+
+def test_mixed_shapes_in_one_call(pkg, ctx):
+    """Three inputs of one circuit, (maxDepth 5, blockTreeDepth 2, maxLog2NSlots 3, 3 felts a cell), that state different nCellsPerSlot
+    (below, at and above a block's cells) and nSlotsPerDataSet, each followed by a mutant of itself, parsed and verified in ONE call: the
+    host's per-input parameter words and array layout are the ones tests/test_gpu_kernel_units.py hands the launcher directly."""
+    geom = (5, 2, 3, 3)
+    md, bd, m, nf = geom
+    c, ns = K.verify_cfg(geom), 4
+    ds = []
+    for j, (k, n_slots, si) in enumerate(((1, 1, 0), (2, 5, 4), (5, 8, 2))):
+        d = K.verify_build(md, bd, m, nf, ns, 1 << k, n_slots, si, 1000 + j, K.verify_values("mixed shapes", j))
+        e = V.copy(d)
+        if j == 0:
+            e["merklePaths"][3][bd] = (e["merklePaths"][3][bd] + 1) % V.R_MOD          # k < bd: the middle walk's sibling
+        elif j == 1:
+            e["slotProof"][2] = (e["slotProof"][2] + 1) % V.R_MOD                      # nSlots = 5: all three levels are read
+        else:
+            e["cellData"][1][nf - 1] = (e["cellData"][1][nf - 1] + 1) % V.R_MOD
+        ds += [d, e]
+    assert len({d["nCellsPerSlot"] for d in ds}) == 3 and len({d["nSlotsPerDataSet"] for d in ds}) == 3
+    status, ok = _check(pkg, ctx, c, ds)
+    assert status.tolist() == [0, V.SAMPLE, 0, V.DATASET_ROOT, 0, V.SAMPLE]
+    assert ok.tolist() == [[1, 1, 1, 1], [1, 1, 1, 0], [1, 1, 1, 1], [1, 1, 1, 1], [1, 1, 1, 1], [1, 0, 1, 1]]
 
 
 def test_rows_that_encode_no_bytes_are_checked_as_felts(pkg, ctx, oracle):

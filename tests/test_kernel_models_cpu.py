@@ -1,11 +1,14 @@
 """CPU suite: the models of tests/kernel_models.py against oracle/poseidon2_ref.py, the case plans of tests/test_gpu_kernel_units.py
-against what that module says it covers, and the build of tests/device_check/libkernel_unit.so."""
+against what that module says it covers (the k_verify_samples plan against tests/circuit_verdict.py), and the build of
+tests/device_check/libkernel_unit.so."""
 import os
 import subprocess
+import time
 
 import numpy as np
 import pytest
 
+import circuit_verdict as V
 import kernel_models as K
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -227,6 +230,238 @@ def test_walk_plan():
             assert all(r.index == b for r in mine if r.kind != "neighbour")
 
 
+# ---- k_verify_samples: the builder, the packer, the plan ----------------------------------------------------------------------------------
+def _log2(n):
+    return n.bit_length() - 1
+
+
+def _bases(launch):
+    return [it for it in launch.items if it.kind == "base"]
+
+
+def _indices(it):
+    return [V.sample_index(it.d, None, c) for c in range(len(it.d["cellData"]))]
+
+
+def test_verify_plan_agrees_with_the_circuit(capsys):
+    """Every input the plan calls accepted gets (0, [1] * ns) from circuit_verdict.verdict, every expectation a mutant's tag states is
+    the model's, and the model's own time over the whole plan stays bounded (its hashing memoised)."""
+    t0 = time.time()
+    plan = K.verify_plan()
+    t_build = time.time() - t0
+    kinds, open_ = {}, 0
+    with K.memoised_hashing():
+        for launch in plan:
+            cfg = K.verify_cfg(launch.geom)
+            for it in launch.items:
+                kinds[it.kind] = kinds.get(it.kind, 0) + 1
+                got = K.verify_expected(it.d, launch.geom)
+                assert len(got) == launch.ns + 1 == len(it.d["cellData"]) + 1
+                if it.kind in ("base", "top", "top past accepted", "edge base"):
+                    assert V.verdict(it.d, cfg) == (0, [1] * launch.ns), (launch.name, it.tag)
+                    assert it.expect == (1,) * (launch.ns + 1)
+                if it.expect is None:
+                    open_ += 1
+                else:
+                    assert it.expect == got, (launch.name, it.tag, it.expect, got)
+                if it.kind in ("cell", "path read", "proof read", "dataSetRoot"):            # exactly its own byte, or the top byte
+                    assert it.expect.count(0) == 1, it.tag
+                if it.kind in ("path above", "proof above", "cell, not compared"):
+                    assert it.expect == (1,) * (launch.ns + 1), it.tag
+                if it.kind in ("slotRoot", "entropy", "top past"):
+                    assert it.expect is None
+                if it.kind == "refused":
+                    assert got == (0,) * (launch.ns + 1) == it.expect
+    t_all = time.time() - t0
+    with capsys.disabled():
+        print("\n[kernel units] verify plan: %d launches, %d inputs, %d lanes; %d expectations stated by the plan, %d the model's alone; "
+              "built in %.1f s, model %.1f s" % (len(plan), K.verify_plan_cases(), sum(len(x.items) * (x.ns + 1) for x in plan),
+                                                K.verify_plan_cases() - open_, open_, t_build, t_all - t_build))
+        print("[kernel units] verify plan by kind: %s" % ", ".join("%s %d" % kv for kv in sorted(kinds.items())))
+    assert t_all < 60
+
+
+def test_verify_plan_geometries_and_branches():
+    launches = [K.verify_geometry_launch(gi) for gi in range(len(K.VERIFY_GEOMS))]
+    assert [x.geom for x in launches] == [(3, 1, 0, 1), (2, 2, 1, 2), (5, 2, 3, 3), (6, 3, 5, 4), (8, 2, 4, 67)]
+    for launch in launches:
+        md, bd, m, nf = launch.geom
+        bases = _bases(launch)
+        assert 2 <= launch.ns <= 5 and launch.items[:len(bases)] == bases
+        ks = [_log2(it.d["nCellsPerSlot"]) for it in bases]
+        assert set(ks) == set(range(1, md + 1))                                          # every k, in one launch
+        first = ks[:md]
+        assert all(a != b for a, b in zip(first, first[1:]))                              # neighbouring inputs differ in k
+        pairs = {(it.d["nSlotsPerDataSet"], it.d["slotIndex"]) for it in bases}
+        assert len(pairs) >= min(3, sum(n for n in range(1, (1 << m) + 1)))              # m = 0 has the one pair only
+        assert {n for n, _ in pairs} >= {1, 1 << m}
+        assert all(len(r) == nf for it in launch.items for r in it.d["cellData"])
+        # index extremes, by the model
+        at_md = [i for it in bases if _log2(it.d["nCellsPerSlot"]) == md for i in _indices(it)]
+        assert 0 in at_md and (1 << md) - 1 in at_md, launch.name
+        if md > bd:
+            cpb = 1 << bd
+            assert any(i & (cpb - 1) == cpb - 1 and i >> bd != (1 << (md - bd)) - 1 for i in at_md), launch.name
+    by_geom = {x.geom: _bases(x) for x in launches}
+    # k < bd: the middle walk's one compression takes path index bd, everything between is padding
+    for geom in ((2, 2, 1, 2), (5, 2, 3, 3), (6, 3, 5, 4), (8, 2, 4, 67)):
+        md, bd, m, nf = geom
+        low = [it for it in by_geom[geom] if _log2(it.d["nCellsPerSlot"]) < bd]
+        assert low
+        for it in low:
+            k = _log2(it.d["nCellsPerSlot"])
+            for path in it.d["merklePaths"]:
+                assert all(path[:k]) and not any(path[k:bd]) and not any(path[bd + 1:]) and (md == bd or path[bd] != 0)
+    # md == bd: the sample compares 0 with slotRoot
+    assert all(it.d["slotRoot"] == 0 for it in by_geom[(2, 2, 1, 2)]) and all(it.d["slotRoot"] != 0 for it in by_geom[(5, 2, 3, 3)])
+    # m == 0: the top lane compares 0 with dataSetRoot
+    assert all(it.d["dataSetRoot"] == 0 and it.d["slotProof"] == [] for it in by_geom[(3, 1, 0, 1)])
+    assert {g[3] for g in by_geom} == {1, 2, 3, 4, 67}                                   # the sponge's 1 at j == nf and at j + 1 == nf
+    assert (8, 2, 4, 67) in by_geom and K.verify_cfg((8, 2, 4, 67))["cellSize"] == 2048   # the product's cell
+
+
+def test_verify_plan_top_walk_is_exhaustive():
+    assert K.VERIFY_TOP_M == (0, 1, 3, 5)
+    launches = {(m, 0): K.verify_top_launch(m, 0) for m in K.VERIFY_TOP_M}
+    launches[(3, 2)] = K.verify_top_launch(3, 2)
+    for (m, ns), launch in launches.items():
+        assert launch.ns == ns and launch.geom[2] == m
+        seen = {}
+        for it in launch.items:
+            seen.setdefault((it.d["nSlotsPerDataSet"], it.d["slotIndex"]), []).append(it.kind)
+            assert len(it.d["cellData"]) == ns
+        assert set(seen) == {(n, si) for n in range(1, (1 << m) + 1) for si in range(1 << m)}
+        for (n, si), kinds in seen.items():
+            assert kinds == (["top"] if si < n else ["top past", "top past accepted"]), (m, n, si)
+        # the odd-node key (+2) below the highest level that is read: slotIndex the last of an odd nSlots, and the layers above it
+        if m >= 3:
+            assert any(n % 2 == 1 and si == n - 1 and n > 2 for (n, si) in seen)
+    plan = K.verify_plan()
+    assert [x for x in plan if x.ns == 0 and x.name.startswith("top walk")] == [launches[(m, 0)] for m in K.VERIFY_TOP_M]
+    assert launches[(3, 2)] in plan
+
+
+def test_verify_plan_mutates_every_felt():
+    for gi, geom in enumerate(K.VERIFY_GEOMS):
+        md, bd, m, nf = geom
+        launch = K.verify_geometry_launch(gi)
+        felts = set(range(nf)) if nf != 67 else {0, 1, 32, 65, 66}
+        levels_read = set()
+        for base in _bases(launch):
+            mine = [it for it in launch.items if it.kind != "base" and it.tag.startswith(base.tag + "; ")]
+            changed = set()
+            for it in mine:
+                diff = [(key, base.d[key], it.d[key]) for key in V.KEYS if base.d[key] != it.d[key]]
+                assert len(diff) == 1
+                key, a, b = diff[0]
+                if key in ("cellData", "merklePaths"):
+                    at = [(s, j) for s in range(launch.ns) for j in range(len(a[s])) if a[s][j] != b[s][j]]
+                    assert len(at) == 1 and b[at[0][0]][at[0][1]] == (a[at[0][0]][at[0][1]] + 1) % K.R_MOD
+                    changed.add((key,) + at[0])
+                    if it.kind == "path read":
+                        levels_read.add(at[0][1])
+                elif key == "slotProof":
+                    at = [j for j in range(m) if a[j] != b[j]]
+                    assert len(at) == 1 and b[at[0]] == (a[at[0]] + 1) % K.R_MOD
+                    changed.add((key, at[0]))
+                else:
+                    assert b == (a + 1) % K.R_MOD
+                    changed.add((key,))
+            want = {("cellData", s, j) for s in range(launch.ns) for j in felts} | {("merklePaths", s, j) for s in range(launch.ns) for j in range(md)}
+            want |= {("slotProof", j) for j in range(m)} | {("dataSetRoot",), ("slotRoot",), ("entropy",)}
+            assert changed == want and len(mine) == len(want), (launch.name, base.tag)
+        kinds = {it.kind for it in launch.items}
+        if md > bd:
+            assert levels_read == set(range(md)) and {"cell", "path read", "path above"} <= kinds
+        else:
+            assert not levels_read and "cell, not compared" in kinds and "cell" not in kinds
+        assert kinds >= ({"proof read", "proof above"} if m > 1 else {"proof read"} if m else set())
+        # mutants travel in their base's launch, after the bases, base after base in turn
+        n_bases = len(_bases(launch))
+        tail = launch.items[n_bases:2 * n_bases]
+        assert len({it.tag.split("; ")[0] for it in tail}) == n_bases
+
+
+def test_verify_plan_field_edges_layouts_and_refused_shapes():
+    edge = K.verify_edge_launch()
+    bases = [it for it in edge.items if it.kind == "edge base"]
+    md, bd, m, nf = edge.geom
+    assert {_log2(it.d["nCellsPerSlot"]) - bd for it in bases} == {-1, 0, 2}
+    assert {v for it in bases for r in it.d["cellData"] for v in r} == set(K.VERIFY_EDGES) == {0, 1, K.R_MOD - 1, 1 << 253, (1 << 29) - 1, 1 << 29, 1 << 58, 1 << 232}
+    assert {v for it in bases for v in K.verify_free_siblings(it.d, edge.geom)} == set(K.VERIFY_EDGES)
+    mutated = bases[:3]
+    assert {_log2(it.d["nCellsPerSlot"]) - bd for it in mutated} == {-1, 0, 2}
+    for base in mutated:
+        for key in ("dataSetRoot", "slotRoot"):
+            mine = [it for it in edge.items if it.kind == "edge " + key and it.tag.startswith(base.tag + "; ")]
+            assert {it.d[key] for it in mine} == {base.d[key] + 1, base.d[key] - 1, base.d[key] ^ (1 << 253)}
+            assert all(it.expect[-1] == 0 for it in mine) and all(it.expect == (0,) * (edge.ns + 1) for it in mine if key == "slotRoot")
+    # nothing at or above r is fed where the kernel reads it
+    for launch in K.verify_plan():
+        cfg = K.verify_cfg(launch.geom)
+        for it in launch.items:
+            if V.shape_ok(it.d, cfg):
+                felts = [it.d["dataSetRoot"], it.d["entropy"], it.d["slotRoot"]] + it.d["slotProof"] + [v for r in it.d["cellData"] + it.d["merklePaths"] for v in r]
+                assert all(0 <= v < K.R_MOD for v in felts), (launch.name, it.tag)
+    layouts = K.verify_layout_launches()
+    sizes = [(len(x.items), x.ns) for x in layouts]
+    assert {n * ns % 64 for n, ns in sizes} >= {0, 1, 63}
+    assert any(n * ns and n * ns % 256 == 0 for n, ns in sizes)
+    assert {n * (ns + 1) for n, ns in sizes} >= {1, 255, 256, 257, 513}
+    for launch in layouts:
+        n, ns = len(launch.items), launch.ns
+        if n > 1:
+            assert launch.items[0].expect[-1] == 0 and (ns == 0 or launch.items[-1].expect[ns - 1] == 0)      # both sides of lane n * ns
+            assert len({it.d["nCellsPerSlot"] for it in launch.items}) == 3 and len({it.d["nSlotsPerDataSet"] for it in launch.items}) == 3
+    refused = K.verify_refused_launch()
+    cfg = K.verify_cfg(refused.geom)
+    ff = K.VERIFY_UNWRITTEN
+    assert ff.to_bytes(32, "little") == b"\xff" * 32
+    assert [it.kind == "refused" for it in refused.items] == [False, True] * (len(refused.items) // 2)
+    assert {it.d["nCellsPerSlot"] for it in refused.items if it.kind == "refused"} == {0, 3}
+    for it in refused.items:
+        if it.kind == "refused":
+            assert not V.shape_ok(it.d, cfg) and set(it.d["slotProof"]) == {ff} and {v for r in it.d["cellData"] + it.d["merklePaths"] for v in r} == {ff}
+            assert it.expect == (0,) * (refused.ns + 1)
+        else:
+            assert V.shape_ok(it.d, cfg)
+    assert {it.kind for it in refused.items} >= {"base", "cell", "dataSetRoot", "refused"}
+
+
+def test_verify_pack_round_trips():
+    """The arrays hold the dicts, laid out as the comment above VerifyGeom says; prm[3] is circuit_verdict.shape_ok."""
+    for launch in K.verify_plan():
+        md, bd, m, nf = launch.geom
+        dicts = [it.d for it in launch.items]
+        prm, heads, cells, paths = K.verify_pack(dicts, launch.geom)
+        n, ns = len(dicts), launch.ns
+        assert prm.dtype == np.uint64 and prm.shape == (n, 4)
+        assert all(a.dtype == np.uint8 and a.flags["C_CONTIGUOUS"] for a in (heads, cells, paths))
+        assert heads.shape == (n, 3 + m, 32) and cells.shape == (n, ns, nf, 32) and paths.shape == (n, ns, md, 32)
+        back, shape = K.verify_unpack(prm, heads, cells, paths)
+        assert back == dicts
+        assert shape == [1 if V.shape_ok(d, K.verify_cfg(launch.geom)) else 0 for d in dicts]
+    launch = K.verify_geometry_launch(2)
+    d = launch.items[1].d
+    prm, heads, cells, paths = K.verify_pack([launch.items[0].d, d], launch.geom)
+    assert prm[1].tolist() == [d["nCellsPerSlot"], d["nSlotsPerDataSet"], d["slotIndex"], 1]
+    flat = heads.reshape(-1)
+    at = (3 + 3) * 32                                                                       # input 1: after input 0's 3 + m felts
+    assert [int.from_bytes(flat[at + 32 * i:at + 32 * i + 32].tobytes(), "little") for i in range(6)] == [d["dataSetRoot"], d["entropy"], d["slotRoot"]] + d["slotProof"]
+    assert int.from_bytes(cells.reshape(-1)[((1 * 3 + 2) * 3 + 1) * 32:][:32].tobytes(), "little") == d["cellData"][2][1]
+    assert int.from_bytes(paths.reshape(-1)[((1 * 3 + 2) * 5 + 4) * 32:][:32].tobytes(), "little") == d["merklePaths"][2][4]
+    e = K.verify_pack([], launch.geom)
+    assert e[0].shape == (0, 4) and e[1].shape == (0, 6, 32)
+
+
+def test_verify_build_is_accepted_where_the_producer_has_no_counterpart():
+    """The builder alone, at the placements it makes by hand: k < bd, md == bd, m == 0; and with the oracle's hashing as it is."""
+    for (md, bd, m, nf, n_cells, n_slots, si) in ((5, 3, 2, 3, 2, 3, 2), (5, 3, 2, 2, 4, 1, 0), (3, 3, 1, 1, 8, 2, 1), (3, 3, 0, 4, 2, 1, 0), (4, 1, 0, 2, 16, 1, 0)):
+        d = K.verify_build(md, bd, m, nf, 3, n_cells, n_slots, si, 99, K.verify_values("alone", md, bd, m, nf))
+        assert V.verdict(d, K.verify_cfg((md, bd, m, nf)) if nf in K.VERIFY_CELL_SIZE else None) == (0, [1, 1, 1])
+        assert (d["slotRoot"] == 0) == (md == bd) and (d["dataSetRoot"] == 0) == (m == 0)
+
+
 # ---- the check library -------------------------------------------------------------------------------------------------------------
 def dynamic_symbols(path, defined):
     out = subprocess.check_output(["nm", "-D", "--defined-only" if defined else "--undefined-only", path], text=True)
@@ -239,9 +474,9 @@ def test_check_library_builds_and_forwards_to_the_product(pkg):
     subprocess.check_call(["make", "-C", PKG_DIR, "../tests/device_check/libkernel_unit.so"], stdout=subprocess.DEVNULL)
     lib = os.path.join(ROOT, "tests", "device_check", "libkernel_unit.so")
     launchers = ("scrub_compare", "repair_compare", "sample_paths", "sample_many", "gather_rows", "gather_addr", "gen_fake_cells_many",
-                 "compress_layer", "block_path_roots", "block_path_commit")
+                 "compress_layer", "block_path_roots", "block_path_commit", "verify_samples")
     mine, wanted, product = dynamic_symbols(lib, True), dynamic_symbols(lib, False), dynamic_symbols(pkg.LIB_PATH, True)
-    assert {"ku_" + n for n in launchers} | {"ku_sizeof_tree_geom", "ku_sizeof_many_req", "ku_scrub_tile"} <= mine
+    assert {"ku_" + n for n in launchers} | {"ku_sizeof_tree_geom", "ku_sizeof_many_req", "ku_sizeof_verify_geom", "ku_scrub_tile"} <= mine
     for n in launchers:
         sym = [s for s in wanted if s.startswith("_ZN4cp2k%d%s" % (len("launch_" + n), "launch_" + n))]
         assert len(sym) == 1 and sym[0] in product, n
