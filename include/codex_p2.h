@@ -623,6 +623,7 @@ int cp2_dataset_repair_blocks_proved(cp2_dataset* ds, const uint64_t* slot_block
  *
  * cp2_fill_missing: host only.  The lowest min(cap, *n_missing) absent (dataset slot, block) pairs in ascending order into `missing`;
  * *n_missing = the number of all absent blocks.  cap == 0 with a NULL `missing` only counts.
+ * A finished session is not refused: it answers 0.
  *
  * cp2_fill_finish turns a complete session into a dataset.
  *   Refused    CP2_ERR_INVALID while any block is absent, cp2_last_error naming the count and the first missing pair; the session stays
@@ -759,6 +760,9 @@ int cp2_fill_block_proofs(void* f /* cp2_fill* */, const uint64_t* slot_block /*
  * cp2_fill_anchors: host only, read-only.  levels[i] = the lowest level l in [0, depth] at which the session knows the node above block
  * slot_block[i] (level 0: its block root; level depth: the stated slot root, which always counts).  A session that does not keep nodes is
  * not refused: it answers depth throughout.
+ * A PRESENT block of a session that keeps nodes answers 0 (its block root is known: kept by the add or the adopt that brought it, or derived
+ * from presence by cp2_fill_keep_nodes); of a session that keeps none it answers depth like any other.  An absent block answers 0 when
+ * its block root arrived as a neighbour's sibling, or with a CP2_FILL_UNWRITTEN add of its own.
  *   Refused    CP2_ERR_INVALID, the request index (where there is one) in cp2_last_error, outputs untouched: a NULL session; NULL
  *              slot_block or levels when n > 0; a slot outside the local range; a block >= nBlocks; a finished session.  n == 0: CP2_OK.
  *
@@ -807,6 +811,9 @@ int cp2_write_circom_main(const cp2_config* cfg, const char* path);
  *              in ascending offset order, in chunks of half the context's staging, and reduced to fresh block roots on cp2_fill_add's data
  *              path, exactly as the re-check of cp2_fill_resume reads the present ones.  Present blocks are never read.  A read that
  *              fails is CP2_ERR_IO with the builders' message, and nothing of the session has changed.  *n_read = the blocks read.
+ *              *n_read counts what THIS call read: every absent block of the selected slots that its file covers, whether or not an earlier
+ *              call read and remembers it (a second reading adopt of an unchanged slot reads the same blocks again); 0 with
+ *              CP2_ADOPT_NO_READ.
  *   Remembered the session keeps the fresh block roots of its candidates in a device buffer of its own (n_local x nBlocks rows, allocated
  *              by the first adopt) and a host bitmap of the rows that hold one.  A read refreshes them for the slots it covers.
  *              CP2_ADOPT_NO_READ reads no slot byte and judges what is remembered: use it after later adds have made more nodes known.
