@@ -234,6 +234,9 @@ def load_library():
         "cp2_fill_anchors": (i32, [vp, vp, sz, vp]),
         "cp2_fill_add_anchored": (i32, [vp, vp, vp, vp, vp, sz, vp, ctypes.POINTER(sz)]),
         "cp2_fill_adopt": (i32, [vp, u64, u64, i32, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "cp2_fill_save_nodes": (i32, [vp, cp]),
+        "cp2_fill_resume_nodes": (i32, [vp, ctypes.POINTER(Config), u64, u64, vp, cp, i32, pvp, ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                        ctypes.POINTER(u64), ctypes.POINTER(u64)]),
     }
     for name, (res, args) in sigs.items():
         if v is None and name == "cp2_abi_version":
@@ -515,6 +518,12 @@ class Context:
         """cp2_fill_resume: the session saved at `path` (FillSession.save), every block it calls present re-checked on the device against what
         the source holds now unless trust_files; the session's `n_dropped` says how many blocks the disk no longer backs"""
         return FillSession.resume(self, cfg, slot_roots, path, first_slot, cfg.n_slots - first_slot if n_local is None else n_local, trust_files)
+
+    def fill_resume_nodes(self, cfg, slot_roots, path, first_slot=0, n_local=None, trust_files=False):
+        """cp2_fill_resume_nodes: the keeping session saved at `path` (FillSession.save_nodes, or FillSession.save), resumed as fill_resume
+        resumes it, keeping nodes, with every saved node restored that the device re-derives from the stated roots; the session's
+        `n_dropped`, `n_restored`, `n_unproved` and `n_rejected` say what became of the blocks and the saved rows"""
+        return FillSession.resume_nodes(self, cfg, slot_roots, path, first_slot, cfg.n_slots - first_slot if n_local is None else n_local, trust_files)
 
     def dataset(self, cfg, first_slot=0, n_local=None, cache=None):
         return Dataset(self, cfg, first_slot, cfg.n_slots if n_local is None else n_local, cache)
@@ -882,9 +891,30 @@ class FillSession:
         ctx._children.add(f)
         return f
 
+    @classmethod
+    def resume_nodes(cls, ctx, cfg, slot_roots, path, first_slot, n_local, trust_files=False):
+        """cp2_fill_resume_nodes: a keeping session around the checkpoint at `path` (CP2FILL2 or CP2FILL1); n_dropped = the blocks the
+        re-check took back, n_restored / n_unproved / n_rejected = what became of the saved rows presence does not give"""
+        r = _u8(slot_roots).reshape(-1, 32)
+        if r.shape[0] != n_local:
+            raise ValueError("fill: %d local slot(s) need %d roots, got %d" % (n_local, n_local, r.shape[0]))
+        f = cls.__new__(cls)
+        f.ctx, f.cfg, f.first_slot, f.n_local, f.h = ctx, cfg, first_slot, n_local, None
+        h, dropped, restored, unproved, rejected = ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        ctx._ck(ctx.L.cp2_fill_resume_nodes(ctx.h, ctypes.byref(cfg), first_slot, n_local, _p(r) if r.size else None, os.fsencode(path),
+                                            RESUME_TRUST_FILES if trust_files else 0, ctypes.byref(h), ctypes.byref(dropped), ctypes.byref(restored),
+                                            ctypes.byref(unproved), ctypes.byref(rejected)), "cp2_fill_resume_nodes")
+        f.h, f.n_dropped, f.n_restored, f.n_unproved, f.n_rejected = h, dropped.value, restored.value, unproved.value, rejected.value
+        ctx._children.add(f)
+        return f
+
     def save(self, path):
         """cp2_fill_save: a checkpoint of this unfinished session at `path` (written beside it and renamed)"""
         self.ctx._ck(self.ctx.L.cp2_fill_save(self.h, os.fsencode(path)), "cp2_fill_save")
+
+    def save_nodes(self, path):
+        """cp2_fill_save_nodes: a checkpoint of this unfinished keeping session at `path` with its known nodes (format CP2FILL2)"""
+        self.ctx._ck(self.ctx.L.cp2_fill_save_nodes(self.h, os.fsencode(path)), "cp2_fill_save_nodes")
 
     def free(self):
         if self.h:

@@ -32,6 +32,11 @@
 // re-check's reads and data path), keeps their fresh block roots in a buffer of the session's own, builds the tree above them with the
 // kept nodes wherever there are any (k_adopt_layer, one launch per layer) and keeps every subtree whose computed root equals a node the
 // session knows, the stated slot root included (k_adopt_resolve); adopt_plan.hpp holds the host side.
+//
+// A checkpoint can carry the kept nodes too (cp2_fill_save_nodes, format CP2FILL2, node_ckpt_plan.hpp).  cp2_fill_resume_nodes is
+// cp2_fill_resume and cp2_fill_keep_nodes, after which the rows the file calls known are candidates in a buffer of their own: top-down, one
+// launch per layer, k_nodes_restore_layer recomputes every known parent that has a candidate child and takes the children over where the
+// parent comes out, so a resumed session knows exactly what the device has re-derived from the stated slot roots.
 #include <hip/hip_runtime.h>
 
 #include <fcntl.h>
@@ -54,6 +59,7 @@
 #include "dataset_obj.hpp"
 #include "fill_checkpoint.hpp"
 #include "fill_plan.hpp"
+#include "node_ckpt_plan.hpp"
 #include "repair.hpp"
 
 using namespace cp2i;
@@ -64,6 +70,8 @@ static_assert(FILL_PROOF_OK == CP2_FILL_PROOF_OK && FILL_PROOF_ABSENT == CP2_FIL
               "fill_plan.hpp restates the header's proof statuses");
 static_assert(ADOPT_F_KNOWN == cp2k::ADOPT_KNOWN && ADOPT_F_CAND == cp2k::ADOPT_CAND && ADOPT_F_MATCH == cp2k::ADOPT_MATCH &&
               ADOPT_F_PROVED == cp2k::ADOPT_PROVED && ADOPT_F_ADOPTED == cp2k::ADOPT_ADOPTED, "adopt_plan.hpp restates the kernels' flag bits");
+static_assert(NODE_F_KNOWN == cp2k::NODE_KNOWN && NODE_F_CAND == cp2k::NODE_CAND && NODE_F_RESTORED == cp2k::NODE_RESTORED &&
+              NODE_F_REJECTED == cp2k::NODE_REJECTED, "node_ckpt_plan.hpp restates the kernel's flag states");
 static_assert(BLOCK_PROOF_NO_ROW == NO_ROW, "k_gather_rows zero-fills the rows the plan marks as absent");
 static_assert(FILL_WRITE == CP2_REPAIR_MATCH && FILL_SKIP == CP2_REPAIR_MISMATCH && FILL_WRITE_FAILED == CP2_REPAIR_UNWRITTEN,
               "repair_write takes and leaves repair's statuses");
@@ -421,6 +429,26 @@ bool write_all(int fd, const uint8_t* p, size_t n) {
   return true;
 }
 
+// a checkpoint's bytes at `path`: written beside it, synced and renamed, so that an older checkpoint there stays whole until the new one is
+int write_checkpoint_file(cp2_ctx* ctx, const char* path, const std::vector<uint8_t>& buf) {
+  const std::string tmp = std::string(path) + ".tmp." + std::to_string((long)getpid());
+  const int fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_NOFOLLOW | O_CLOEXEC, 0644);
+  if (fd < 0) {
+    ctx->err = "fill: cannot create checkpoint " + tmp + ": " + std::strerror(errno);
+    return CP2_ERR_IO;
+  }
+  const char* what = nullptr;
+  if (!write_all(fd, buf.data(), buf.size()) || fsync(fd) != 0) what = std::strerror(errno);
+  if (close(fd) != 0 && !what) what = std::strerror(errno);
+  if (!what && std::rename(tmp.c_str(), path) != 0) what = std::strerror(errno);
+  if (what) {                                         // an older checkpoint at `path` stays as it is
+    ctx->err = "fill: cannot write checkpoint " + std::string(path) + " (through " + tmp + "): " + what;
+    std::remove(tmp.c_str());
+    return CP2_ERR_IO;
+  }
+  return CP2_OK;
+}
+
 // the whole checkpoint file in memory, its size checked against what its header states before the buffer is sized
 int read_checkpoint(cp2_ctx* ctx, const char* path, FillCheckpoint* ck) {
   const std::string name(path);
@@ -586,21 +614,7 @@ extern "C" int cp2_fill_save(const void* fill, const char* path) try {
   CP2_HIP(ctx, hipMemcpyAsync(buf.data() + l.layer0_at, f->compact.p, (size_t)l.total * 32, hipMemcpyDeviceToHost, ctx->stream));
   CP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
   fill_ckpt_seal(&buf, l);
-  const std::string tmp = std::string(path) + ".tmp." + std::to_string((long)getpid());
-  const int fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_NOFOLLOW | O_CLOEXEC, 0644);
-  if (fd < 0) {
-    ctx->err = "fill: cannot create checkpoint " + tmp + ": " + std::strerror(errno);
-    return CP2_ERR_IO;
-  }
-  const char* what = nullptr;
-  if (!write_all(fd, buf.data(), buf.size()) || fsync(fd) != 0) what = std::strerror(errno);
-  if (close(fd) != 0 && !what) what = std::strerror(errno);
-  if (!what && std::rename(tmp.c_str(), path) != 0) what = std::strerror(errno);
-  if (what) {                                         // an older checkpoint at `path` stays as it is
-    ctx->err = "fill: cannot write checkpoint " + std::string(path) + " (through " + tmp + "): " + what;
-    std::remove(tmp.c_str());
-    return CP2_ERR_IO;
-  }
+  CP2_TRY(write_checkpoint_file(ctx, path, buf));
   if (std::getenv("CP2_TRACE"))
     std::fprintf(stderr, "[cp2 trace] fill save: %llu of %llu block(s) present, %zu bytes\n", (unsigned long long)f->plan.n_present,
                  (unsigned long long)f->plan.total(), buf.size());
@@ -611,19 +625,12 @@ extern "C" int cp2_fill_save(const void* fill, const char* path) try {
   return CP2_ERR_INVALID;
 }
 
-extern "C" int cp2_fill_resume(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local, const uint8_t* slot_roots, const char* path,
-                               int flags, void** out, uint64_t* n_dropped) try {
-  if (!ctx || !cfg || !out || !path) return CP2_ERR_INVALID;
-  *out = nullptr;
-  if (flags & ~CP2_RESUME_TRUST_FILES) {
-    ctx->err = "fill: unknown resume flag bits";
-    return CP2_ERR_INVALID;
-  }
-  CP2_TRY(session_check(ctx, cfg, first_slot, n_local, slot_roots));
+// What cp2_fill_resume and cp2_fill_resume_nodes do with a checkpoint they have read (`ck`: meta, presence bitmap, layer 0): is it a
+// description of exactly this session, what the slot files can no longer back, the session, the re-check.  `dropped`: the global indices
+// of the blocks taken back.
+static int resume_checked(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local, const uint8_t* slot_roots, const char* path,
+                          int flags, FillCheckpoint& ck, std::unique_ptr<cp2_fill_session>* out, std::vector<uint64_t>* dropped_out) {
   const auto t0 = std::chrono::steady_clock::now();
-  // the checkpoint: intact, then a description of exactly this session
-  FillCheckpoint ck;
-  CP2_TRY(read_checkpoint(ctx, path, &ck));
   FillCkptMeta want;
   want.cell_size = cfg->cell_size; want.block_size = cfg->block_size; want.n_cells = cfg->n_cells; want.n_slots = cfg->n_slots;
   want.first_slot = first_slot; want.n_local = n_local;
@@ -642,7 +649,8 @@ extern "C" int cp2_fill_resume(cp2_ctx* ctx, const cp2_config* cfg, uint64_t fir
   uint64_t present = 0;
   for (uint64_t w : ck.bits) present += (uint64_t)__builtin_popcountll(w);
   // slot files first: what a file is too short to back (or no file at all) is dropped without a read; absence is a state, not an error
-  std::vector<uint64_t> dropped;
+  std::vector<uint64_t>& dropped = *dropped_out;
+  dropped.clear();
   if (recheck && cfg->file_base) {
     std::vector<uint64_t> whole(n_local, 0);
     for (uint64_t s = 0; s < n_local; ++s) {
@@ -677,6 +685,25 @@ extern "C" int cp2_fill_resume(cp2_ctx* ctx, const cp2_config* cfg, uint64_t fir
     std::fprintf(stderr, "[cp2 trace] fill resume: %llu block(s) present in the checkpoint, %llu re-read, %zu dropped, %.0f bytes, %.3f s (%.2f GB/s)\n",
                  (unsigned long long)present, (unsigned long long)n_read, dropped.size(), bytes, seconds, seconds > 0 ? bytes / seconds / 1e9 : 0.0);
   }
+  *out = std::move(f);
+  return CP2_OK;
+}
+
+extern "C" int cp2_fill_resume(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local, const uint8_t* slot_roots, const char* path,
+                               int flags, void** out, uint64_t* n_dropped) try {
+  if (!ctx || !cfg || !out || !path) return CP2_ERR_INVALID;
+  *out = nullptr;
+  if (flags & ~CP2_RESUME_TRUST_FILES) {
+    ctx->err = "fill: unknown resume flag bits";
+    return CP2_ERR_INVALID;
+  }
+  CP2_TRY(session_check(ctx, cfg, first_slot, n_local, slot_roots));
+  // the checkpoint: intact, then a description of exactly this session
+  FillCheckpoint ck;
+  CP2_TRY(read_checkpoint(ctx, path, &ck));
+  std::unique_ptr<cp2_fill_session> f;
+  std::vector<uint64_t> dropped;
+  CP2_TRY(resume_checked(ctx, cfg, first_slot, n_local, slot_roots, path, flags, ck, &f, &dropped));
   if (n_dropped) *n_dropped = dropped.size();
   *out = f.release();
   return CP2_OK;
@@ -1042,6 +1069,180 @@ extern "C" int cp2_fill_adopt(void* fill, uint64_t first_slot, uint64_t n_slots,
                  seconds, seconds > 0 ? bytes / seconds / 1e9 : 0.0);
   }
   return r;
+} catch (const std::bad_alloc&) {
+  return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
+} catch (...) {
+  return CP2_ERR_INVALID;
+}
+
+// ---- checkpoints that carry the kept nodes ----------------------------------------------------------------------------------------------------
+namespace {
+
+// the whole CP2FILL2 file in memory, its size checked against what its header allows before the buffer is sized
+int read_node_checkpoint(cp2_ctx* ctx, const char* path, NodeCheckpoint* ck) {
+  const std::string name(path);
+  const int fd = open(path, O_RDONLY | O_CLOEXEC);
+  if (fd < 0) {
+    ctx->err = "fill: cannot open checkpoint " + name + ": " + std::strerror(errno);
+    return CP2_ERR_IO;
+  }
+  struct Closer { int fd; ~Closer() { close(fd); } } closer{fd};
+  struct stat sb;
+  if (fstat(fd, &sb) != 0) {
+    ctx->err = "fill: cannot stat checkpoint " + name + ": " + std::strerror(errno);
+    return CP2_ERR_IO;
+  }
+  const size_t size = (size_t)sb.st_size;
+  uint8_t fixed[FILL_CKPT_FIXED] = {};
+  std::string why;
+  FillCkptMeta m;
+  NodeCkptLayout l;
+  const size_t head = std::min(size, sizeof fixed);
+  const int eh = head ? slot_file_read_rest(fd, fixed, head, 0) : 0;
+  if (eh) {
+    ctx->err = "fill: cannot read checkpoint " + name + ": " + std::strerror(eh);
+    return CP2_ERR_IO;
+  }
+  if (!node_ckpt_fixed(fixed, size, &m, &l, &why) || !node_ckpt_size_ok(l, size, &why)) {
+    ctx->err = "fill: checkpoint " + name + " " + why;
+    return CP2_ERR_IO;
+  }
+  std::vector<uint8_t> buf(size);
+  const int e = slot_file_read_rest(fd, buf.data(), size, 0);
+  if (e) {
+    ctx->err = "fill: cannot read checkpoint " + name + ": " + std::strerror(e);
+    return CP2_ERR_IO;
+  }
+  if (!node_ckpt_parse(buf.data(), size, ck, &why)) {
+    ctx->err = "fill: checkpoint " + name + " " + why;
+    return CP2_ERR_IO;
+  }
+  return CP2_OK;
+}
+
+}  // namespace
+
+extern "C" int cp2_fill_save_nodes(const void* fill, const char* path) try {
+  const cp2_fill_session* f = session(fill);
+  if (!f || !path) return CP2_ERR_INVALID;
+  cp2_ctx* ctx = f->ctx;
+  const FillPlan& plan = f->plan;
+  if (plan.finished) {
+    ctx->err = "fill: the session is finished: its durable form is the kept cache of cp2_fill_finish, not a checkpoint";
+    return CP2_ERR_INVALID;
+  }
+  if (!plan.keeps_nodes) {
+    ctx->err = "fill: this session does not keep the nodes of the paths it proves: call cp2_fill_keep_nodes first, or save it with cp2_fill_save";
+    return CP2_ERR_INVALID;
+  }
+  CP2_REFUSE_STUCK(ctx);
+  CP2_HIP(ctx, hipSetDevice(ctx->device));
+  const FillCkptMeta meta = session_meta(f);
+  NodeCkptLayout l;
+  if (meta.cell_size == 0 || meta.block_size < meta.cell_size || !node_ckpt_layout(meta.file_base.size(), meta.n_local, meta.n_blocks(), &l)) {
+    ctx->err = "fill: the session is larger than a checkpoint describes";
+    return CP2_ERR_INVALID;
+  }
+  // the buffer below the top rows in one download; what is neither present nor known never reaches the file
+  std::vector<uint8_t> image(plan.rows * 32), buf;
+  const size_t below_top = plan.coff[plan.depth()] * 32;
+  CP2_HIP(ctx, hipMemcpyAsync(image.data(), f->compact.p, below_top, hipMemcpyDeviceToHost, ctx->stream));
+  CP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (!node_ckpt_serialise(meta, plan, image.data(), &buf)) {
+    ctx->err = "fill: the session is larger than a checkpoint describes";
+    return CP2_ERR_INVALID;
+  }
+  CP2_TRY(write_checkpoint_file(ctx, path, buf));
+  if (std::getenv("CP2_TRACE")) {
+    uint64_t known = 0;
+    for (uint64_t w : plan.known) known += (uint64_t)__builtin_popcountll(w);
+    std::fprintf(stderr, "[cp2 trace] fill save nodes: %llu of %llu block(s) present, %llu of %zu row(s) known, %zu bytes\n",
+                 (unsigned long long)plan.n_present, (unsigned long long)plan.total(), (unsigned long long)known, plan.rows, buf.size());
+  }
+  return CP2_OK;
+} catch (const std::bad_alloc&) {
+  return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
+} catch (...) {
+  return CP2_ERR_INVALID;
+}
+
+extern "C" int cp2_fill_resume_nodes(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local, const uint8_t* slot_roots,
+                                     const char* path, int flags, void** out, uint64_t* n_dropped, uint64_t* n_restored, uint64_t* n_unproved,
+                                     uint64_t* n_rejected) try {
+  if (!ctx || !cfg || !out || !path) return CP2_ERR_INVALID;
+  *out = nullptr;
+  if (flags & ~CP2_RESUME_TRUST_FILES) {
+    ctx->err = "fill: unknown resume flag bits";
+    return CP2_ERR_INVALID;
+  }
+  CP2_TRY(session_check(ctx, cfg, first_slot, n_local, slot_roots));
+  const auto t0 = std::chrono::steady_clock::now();
+  // either format: a CP2FILL1 file states no nodes, and the result is cp2_fill_resume followed by cp2_fill_keep_nodes
+  NodeCheckpoint ck;
+  const bool with_nodes = !file_has_magic(path, "CP2FILL1");
+  if (with_nodes) CP2_TRY(read_node_checkpoint(ctx, path, &ck));
+  else CP2_TRY(read_checkpoint(ctx, path, &ck.base));
+  // layer 0 as the file states it: the shared resume zeroes the rows of the blocks it drops, and those rows are candidates
+  const std::vector<uint8_t> stated0 = with_nodes ? ck.base.layer0 : std::vector<uint8_t>();
+  std::unique_ptr<cp2_fill_session> f;
+  std::vector<uint64_t> dropped;
+  CP2_TRY(resume_checked(ctx, cfg, first_slot, n_local, slot_roots, path, flags, ck.base, &f, &dropped));
+  // step 1: D, what presence gives -- absent rows zeroed, every upper layer built once, derive_from_presence
+  CP2_TRY(cp2_fill_keep_nodes(f.get()));
+  FillPlan& plan = f->plan;
+  NodeRestoreCounts counts;
+  uint64_t n_cand = 0;
+  if (with_nodes) {
+    // step 2: the candidates, in a buffer of their own
+    NodeRestorePlan rp;
+    if (!node_restore_plan(plan, ck.known, stated0, ck.mid, &rp)) {
+      ctx->err = "fill: checkpoint " + std::string(path) + " is corrupt: its known bitmap is not one of this session";
+      return CP2_ERR_IO;
+    }
+    n_cand = rp.n_cand;
+    std::vector<uint8_t> down = rp.flags;
+    if (n_cand) {
+      // step 3: top-down, one launch per layer; the flag bytes come back once
+      const size_t rows = plan.rows;
+      std::vector<uint64_t> off(plan.coff.begin(), plan.coff.end()), sizes(plan.csizes.begin(), plan.csizes.end());
+      DevBuf d_cand, d_flags;
+      CP2_TRY(d_cand.scratch(ctx, rows * 32));
+      CP2_TRY(d_flags.scratch(ctx, rows));
+      CP2_HIP(ctx, hipMemcpyAsync(d_cand.p, rp.cand.data(), rows * 32, hipMemcpyHostToDevice, ctx->stream));
+      CP2_HIP(ctx, hipMemcpyAsync(d_flags.p, rp.flags.data(), rows, hipMemcpyHostToDevice, ctx->stream));
+      CP2_HIP(ctx, cp2k::launch_nodes_restore_layers(f->compact.p, d_cand.p, d_flags.u8(), f->slot_roots.p, off.data(), sizes.data(),
+                                                     (uint32_t)plan.depth(), plan.n_local, rows, ctx->stream));
+      CP2_HIP(ctx, hipMemcpyAsync(down.data(), d_flags.p, rows, hipMemcpyDeviceToHost, ctx->stream));
+      if (hipStreamSynchronize(ctx->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        ctx->err = "fill: restoring the kept nodes failed on the device";
+        return CP2_ERR_HIP;
+      }
+    }
+    // a top row whose bit is taken over holds what a proved path left there: the stated root
+    const uint64_t top = plan.coff[plan.depth()];
+    for (uint64_t s = 0; s < plan.n_local;) {
+      if (!node_ckpt_bit(ck.known, top + s) || plan.is_known(top + s)) { ++s; continue; }
+      uint64_t e = s + 1;
+      while (e < plan.n_local && node_ckpt_bit(ck.known, top + e) && !plan.is_known(top + e)) ++e;
+      CP2_HIP(ctx, hipMemcpyAsync(f->compact.u8() + (size_t)(top + s) * 32, f->slot_roots.u8() + (size_t)s * 32, (size_t)(e - s) * 32,
+                                  hipMemcpyDeviceToDevice, ctx->stream));
+      s = e;
+    }
+    CP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    counts = node_restore_apply(&plan, ck.known, rp.flags, down);
+  }
+  if (std::getenv("CP2_TRACE"))
+    std::fprintf(stderr, "[cp2 trace] fill resume nodes: %s, %llu candidate row(s), %llu restored, %llu rejected, %llu unproved, %zu dropped, %.3f s\n",
+                 with_nodes ? "CP2FILL2" : "CP2FILL1 (no nodes stated)", (unsigned long long)n_cand, (unsigned long long)counts.restored,
+                 (unsigned long long)counts.rejected, (unsigned long long)counts.unproved, dropped.size(),
+                 std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+  if (n_dropped) *n_dropped = dropped.size();
+  if (n_restored) *n_restored = counts.restored;
+  if (n_unproved) *n_unproved = counts.unproved;
+  if (n_rejected) *n_rejected = counts.rejected;
+  *out = f.release();
+  return CP2_OK;
 } catch (const std::bad_alloc&) {
   return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
 } catch (...) {

@@ -16,6 +16,7 @@
 //   k_block_path_commit_anchored   the same walk, stopped per lane at a node the session's tree already holds (fill.cpp)
 //   k_block_root_recheck  re-read block roots against layer 0 of a resumed fill session; a row the disk no longer backs is zeroed (fill.cpp)
 //   k_adopt_layer, k_adopt_resolve   the tree over block roots read back from disk, judged against the nodes a fill session keeps (fill.cpp)
+//   k_nodes_restore_layer   the kept nodes a checkpoint states, authenticated top-down from the stated slot roots (fill.cpp)
 //
 // All global-memory field elements are 32-byte little-endian canonical integers (the ABI format).
 #include "kernels.hpp"
@@ -1184,6 +1185,63 @@ __global__ void __launch_bounds__(TPB) k_adopt_resolve(uint4* tree, const uint4*
 }
 
 // ------------------------------------------------------------------------------------------------
+// Restoring kept nodes from a checkpoint (fill.cpp, cp2_fill_resume_nodes): the rows a checkpoint calls known are candidates until a node
+// the resumed session knows vouches for them.  One flag byte per row of the compact layout travels with the values, a row being in one
+// state: NODE_KNOWN (the session knows it -- the host sets it, and sets it for every top row: that is the stated slot root), NODE_CAND
+// (the row of `cand` holds what the file states), NODE_RESTORED, NODE_REJECTED, or 0 (undefined).
+//
+// k_nodes_restore_layer: one lane per node p of layer l + 1 of every local slot, one launch per layer, TOP FIRST (the flags and rows of
+// layer l + 1 come from the launch before, earlier on the same stream).  p must be known or restored; each child known or a candidate (the
+// last node of an odd layer and the one-block slot have one child, a zero sibling and key + 2: k_compress_layer's rule, key = 1 at layer 0
+// and 0 above), at least one of them a candidate: a lane with nothing to restore returns before the permutation.  It loads each child from
+// `tree` where it is known and from `cand` otherwise -- the base address picked with an integer mask, as k_adopt_layer does -- runs one
+// keyed compression and compares the canonical result with p's row of `tree` (the top layer: the stated root of its slot).  Equal: every
+// candidate child is stored into `tree` in canonical form (two 16-byte stores) and flagged NODE_RESTORED; unequal: flagged NODE_REJECTED,
+// nothing stored.  Only the parent's lane writes its children's rows and flag bytes, and a lane reads rows of `tree` only where they are
+// known or restored, so no lane reads what another writes in the same launch.  A lane whose rows do not all lie below n_rows (never: the
+// host made the tables) reads and writes nothing.  LDS is the QTab only; no atomics.
+__global__ void __launch_bounds__(TPB) k_nodes_restore_layer(uint4* tree, const uint4* __restrict__ cand, uint8_t* flags,
+                                                               const uint4* __restrict__ slot_roots, uint64_t off_in, uint64_t m_in,
+                                                               uint64_t off_out, uint64_t m_out, uint64_t n_local, uint32_t bottom, uint32_t top,
+                                                               uint64_t n_rows) {
+  __shared__ fr::QTab qtab;
+  fr::qtab_fill(qtab, threadIdx.x, TPB);
+  __syncthreads();
+  const size_t t = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (t >= m_out * n_local) return;
+  const uint64_t slot = t / m_out, j = t - slot * m_out;
+  const uint64_t rl = off_in + slot * m_in + 2 * j, rp = off_out + slot * m_out + j;
+  const bool pair = 2 * j + 1 < m_in;
+  const uint64_t rr = rl + (pair ? 1u : 0u);
+  if (rr >= n_rows || rp >= n_rows) return;
+  if (!(flags[rp] & (NODE_KNOWN | NODE_RESTORED))) return;
+  const uint32_t fl = flags[rl], fr_ = pair ? (uint32_t)flags[rr] : NODE_KNOWN;
+  if (!(fl & (NODE_KNOWN | NODE_CAND)) || !(fr_ & (NODE_KNOWN | NODE_CAND)) || !((fl | fr_) & NODE_CAND)) return;
+  // tree where the child is known, cand otherwise: the two bases differ in the bits the mask lets through
+  const uintptr_t bt = (uintptr_t)tree, bc = (uintptr_t)cand;
+  const uintptr_t kl = (uintptr_t)0 - (uintptr_t)(fl & NODE_KNOWN), kr = (uintptr_t)0 - (uintptr_t)(fr_ & NODE_KNOWN);
+  State s;
+  s.x = load_fe_canonical((const uint4*)((bt & kl) | (bc & ~kl)) + 2 * rl);
+  s.y = load_fe_canonical((const uint4*)((bt & kr) | (bc & ~kr)) + 2 * rr);   // no pair: the left row once more, cleared below
+  const uint32_t have = 0u - (pair ? 1u : 0u);
+#pragma unroll
+  for (int l = 0; l < fr::NL; ++l) s.y.l[l] &= have;
+  s.z = key_fe((bottom ? 1u : 0u) + (pair ? 0u : 2u));
+  p2::permute(s, qtab);
+  const Fe cur = fr::norm(s.x);
+  const Fe want = load_fe_canonical(top ? slot_roots + 2 * slot : (const uint4*)tree + 2 * rp);
+  const bool ok = fe_equal(cur, want);
+  if (fl & NODE_CAND) {
+    if (ok) store_fe_canonical(tree + 2 * rl, load_fe_canonical(cand + 2 * rl));
+    flags[rl] = ok ? NODE_RESTORED : NODE_REJECTED;
+  }
+  if (pair && (fr_ & NODE_CAND)) {
+    if (ok) store_fe_canonical(tree + 2 * rr, load_fe_canonical(cand + 2 * rr));
+    flags[rr] = ok ? NODE_RESTORED : NODE_REJECTED;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Workgroups for n work items.  A grid holds at most 2^31 - 1 workgroups in x; the per-item kernels are launched in slices of
 // at most MAX_ITEMS items (every item is independent and addressed from a base pointer), the layer / sampling kernels, whose
 // item index is decomposed inside the kernel, refuse what does not fit one grid (2^38 nodes: far beyond any HBM).
@@ -1491,6 +1549,36 @@ hipError_t launch_adopt_resolve(void* tree, const void* cand, const uint8_t* fla
   CP2K_LAUNCH(k_adopt_resolve, dim3(grid_for(n_below)), dim3(TPB), 0, st, (uint4*)tree, (const uint4*)cand, flags, out, layer_off, layer_size, depth,
               n_local, first_sel, n_sel, n_below, n_rows);
   return hipGetLastError();
+}
+
+hipError_t launch_nodes_restore_layer(void* tree, const void* cand, uint8_t* flags, const void* slot_roots, uint64_t off_in, uint64_t m_in,
+                                      uint64_t off_out, uint64_t n_local, bool bottom, bool top, uint64_t n_rows, hipStream_t st) {
+  if (n_local == 0) return hipSuccess;
+  if (!tree || !cand || !flags || !slot_roots || m_in == 0) return hipErrorInvalidValue;
+  const uint64_t m_out = (m_in + 1) / 2;
+  if (!fits_one_grid(m_out * n_local)) return hipErrorInvalidValue;
+  CP2K_LAUNCH(k_nodes_restore_layer, dim3(grid_for(m_out * n_local)), dim3(TPB), 0, st, (uint4*)tree, (const uint4*)cand, flags,
+              (const uint4*)slot_roots, off_in, m_in, off_out, m_out, n_local, bottom ? 1u : 0u, top ? 1u : 0u, n_rows);
+  return hipGetLastError();
+}
+
+hipError_t launch_nodes_restore_layers(void* tree, const void* cand, uint8_t* flags, const void* slot_roots, const uint64_t* layer_off_host,
+                                       const uint64_t* layer_size_host, uint32_t depth, uint64_t n_local, uint64_t n_rows, hipStream_t st) {
+  if (n_local == 0) return hipSuccess;
+  if (!tree || !cand || !flags || !slot_roots || !layer_off_host || !layer_size_host || depth == 0) return hipErrorInvalidValue;
+  for (uint32_t l = 0; l < depth; ++l) {               // the tables must describe a compact layout: the kernel derives every row from them
+    const uint64_t m_in = layer_size_host[l], m_out = layer_size_host[l + 1];
+    if (m_in == 0 || m_out != (m_in + 1) / 2 || layer_off_host[l + 1] != layer_off_host[l] + n_local * m_in)
+      return hipErrorInvalidValue;
+    if (!fits_one_grid(m_out * n_local)) return hipErrorInvalidValue;
+  }
+  if (layer_size_host[depth] != 1) return hipErrorInvalidValue;
+  for (uint32_t l = depth; l-- > 0;) {                 // top first: a restored node vouches for its children in the next launch
+    hipError_t e = launch_nodes_restore_layer(tree, cand, flags, slot_roots, layer_off_host[l], layer_size_host[l], layer_off_host[l + 1], n_local,
+                                              l == 0, l + 1 == depth, n_rows, st);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 hipError_t launch_verify_samples(const VerifyGeom& g, const uint64_t* prm, const void* heads, const void* cells, const void* paths,

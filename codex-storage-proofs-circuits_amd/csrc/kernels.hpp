@@ -132,6 +132,24 @@ hipError_t launch_adopt_resolve(void* tree, const void* cand, const uint8_t* fla
                                 const uint64_t* layer_size, uint32_t depth, uint64_t n_local, uint64_t first_sel, uint64_t n_sel, uint64_t n_below,
                                 uint64_t n_rows, hipStream_t st);
 
+// Restoring kept nodes from a checkpoint (fill.cpp, cp2_fill_resume_nodes).  `tree` is the session's compact buffer (n_rows rows of 32
+// bytes), `cand` a buffer of the same shape that holds what the checkpoint states in its candidate rows, `flags` one byte per row, a row
+// being in one state: NODE_KNOWN the session knows the row -- set by the host, and for every top row -- NODE_CAND the row of `cand` is a
+// candidate, NODE_RESTORED / NODE_REJECTED what the kernel made of a candidate, 0 undefined.
+constexpr uint8_t NODE_KNOWN = 1, NODE_CAND = 2, NODE_RESTORED = 4, NODE_REJECTED = 8;
+// k_nodes_restore_layer once per layer, TOP FIRST, over every local slot: a parent that is known or restored, with every child known or a
+// candidate and at least one a candidate, is recomputed from its children (a known child from `tree`, a candidate from `cand`) and compared
+// with its row of `tree` or, in the top layer, with slot_roots[local slot].  Equal: the candidate children are stored into `tree` and
+// flagged NODE_RESTORED; unequal: flagged NODE_REJECTED.  Nothing else is written; rows at or past n_rows are neither read nor written.
+// One layer: the children are rows off_in + slot x m_in + k (k < m_in) of the n_local slots, the parents rows off_out + slot x ceil(m_in / 2)
+// + j; bottom: the children are layer 0 (key 1); top: a parent's value is slot_roots[slot] and its row of `tree` is not read.
+hipError_t launch_nodes_restore_layer(void* tree, const void* cand, uint8_t* flags, const void* slot_roots, uint64_t off_in, uint64_t m_in,
+                                      uint64_t off_out, uint64_t n_local, bool bottom, bool top, uint64_t n_rows, hipStream_t st);
+// Every layer of a compact layout, top first.  The layer tables are HOST arrays of depth + 1 entries (FillPlan::coff / csizes); tables
+// that are not a compact layout of n_local slots are refused.
+hipError_t launch_nodes_restore_layers(void* tree, const void* cand, uint8_t* flags, const void* slot_roots, const uint64_t* layer_off_host,
+                                       const uint64_t* layer_size_host, uint32_t depth, uint64_t n_local, uint64_t n_rows, hipStream_t st);
+
 // Proof-input verification (k_verify_samples, circuit/codex/sample_cells.circom:58-148) over n inputs that share the circuit
 // parameters.  Device arrays: prm n x 4 (nCellsPerSlot, nSlotsPerDataSet, slotIndex, shape ok), heads n x (3 + m) felts
 // (dataSetRoot, entropy, slotRoot, slotProof), cells n x ns x nf felts, paths n x ns x md felts; ok receives n x ns sample

@@ -115,6 +115,12 @@ proc cp2_fill_add_anchored(fill: pointer, slotBlock: ptr uint64, data: ptr byte,
 # session knows (the stated slot root included); flags = 0 or CP2_ADOPT_NO_READ (judge what earlier calls read); nRead, nAdopted may be nil
 const CP2_ADOPT_NO_READ* = 1.cint
 proc cp2_fill_adopt(fill: pointer, firstSlot, nSlots: uint64, flags: cint, nRead, nAdopted: ptr uint64): cint {.importc.}
+# fill checkpoints with nodes: cp2_fill_save_nodes writes a keeping session's known rows beside presence and layer 0 (format CP2FILL2), and
+# cp2_fill_resume_nodes is cp2_fill_resume + cp2_fill_keep_nodes with every saved row restored that the device re-derives from the stated
+# slot roots; nDropped, nRestored, nUnproved, nRejected may be nil
+proc cp2_fill_save_nodes(fill: pointer, path: cstring): cint {.importc.}
+proc cp2_fill_resume_nodes(ctx: Cp2Ctx, cfg: ptr Cp2Config, firstSlot, nLocal: uint64, slotRoots: ptr byte, path: cstring, flags: cint,
+                           fill: ptr pointer, nDropped, nRestored, nUnproved, nRejected: ptr uint64): cint {.importc.}
 proc cp2_proof_input_write_json(p: Cp2ProofInput, path: cstring): cint {.importc.}
 proc cp2_proof_input_roots(p: Cp2ProofInput, datasetRoot, slotRoot, entropy: ptr byte): cint {.importc.}
 proc cp2_proof_input_nsamples(p: Cp2ProofInput): csize_t {.importc.}

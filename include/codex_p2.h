@@ -46,7 +46,7 @@ extern "C" {
  *                cp2_dataset_repair_blocks_proved (block proofs), cp2_fill_begin, cp2_fill_add, cp2_fill_missing, cp2_fill_finish and
  *                cp2_fill_free (fill sessions), cp2_fill_save and cp2_fill_resume (fill checkpoints), cp2_fill_keep_nodes and
  *                cp2_fill_block_proofs (fill sessions that serve), cp2_fill_anchors and cp2_fill_add_anchored (anchored fill adds),
- *                cp2_fill_adopt (adopting blocks from disk).
+ *                cp2_fill_adopt (adopting blocks from disk), cp2_fill_save_nodes and cp2_fill_resume_nodes (checkpoints with nodes).
  *                MINOR stays 2 until the release that carries them: the bump to 1.3 goes in its own commit with that release.         */
 #define CP2_ABI_VERSION_MAJOR 1
 #define CP2_ABI_VERSION_MINOR 2
@@ -843,6 +843,51 @@ int cp2_write_circom_main(const cp2_config* cfg, const char* path);
 #define CP2_ADOPT_NO_READ 1   /* flag: read no slot byte; judge the candidates remembered from earlier calls */
 int cp2_fill_adopt(void* f /* cp2_fill* */, uint64_t first_slot, uint64_t n_slots /* 0: every local slot */, int flags,
                    uint64_t* n_read /* may be NULL */, uint64_t* n_adopted /* may be NULL */);
+
+/* ---- fill checkpoints with nodes: the kept nodes saved, and restored only as far as the device re-derives them -----------------------------
+ * cp2_fill_save writes presence and layer 0.  Everything a keeping session has beside them -- the proved siblings and ancestors its proofs,
+ * anchors and adopts rest on -- lives in the upper rows of its buffer and in its known bitmap, and a cp2_fill_resume followed by
+ * cp2_fill_keep_nodes knows a node only where both children are present: in a slot half filled in network order nearly every present block
+ * answers CP2_FILL_PROOF_PARTIAL after a restart.  These two calls save the kept nodes and bring them back by the rule of every checkpoint
+ * here: nothing a file states is believed until the device has re-derived it from the stated slot roots.
+ *
+ * cp2_fill_save_nodes(f, path)  everything cp2_fill_save does and refuses, for a session that keeps nodes; one that does not is
+ *   CP2_ERR_INVALID.  The file is format CP2FILL2: CP2FILL1's ten words, base name, stated roots and presence bitmap where and what they
+ *   are there (the magic differs); the known bitmap, ceil(rows / 64) words, bit r = row r of the compact layout, bits past the last row 0;
+ *   layer 0, n_local x nBlocks rows, a row zero unless its block is present or its row known; the known rows of the layers strictly
+ *   between layer 0 and the top, packed in ascending row order; the checksum.  The top rows are not stored: their bits are, their value is
+ *   the stated root.  Rows that are not known are zeros or left out, so two saves of one state are byte-identical.  Written beside `path`,
+ *   synced and renamed, as cp2_fill_save writes.  Nothing of the session changes; the candidates cp2_fill_adopt remembers are not saved.
+ *
+ * cp2_fill_resume_nodes(ctx, cfg, first_slot, n_local, slot_roots, path, flags, &f, &n_dropped, &n_restored, &n_unproved, &n_rejected)
+ *   accepts CP2FILL2, and CP2FILL1, for which the result is exactly cp2_fill_resume followed by cp2_fill_keep_nodes (the three new counts
+ *   0).  Checks, refusals, the drop of blocks a short file cannot back, the re-check and CP2_RESUME_TRUST_FILES are cp2_fill_resume's.
+ *   A CP2FILL2 file with known bits past the last row, a packed-row count that disagrees with its known bitmap, or a size its header does
+ *   not allow is CP2_ERR_IO naming the path.  cp2_fill_resume keeps refusing a CP2FILL2 file by its magic.
+ *   The resumed session keeps nodes.  Its known set:
+ *     D          what presence gives: cp2_fill_keep_nodes on the bitmap and layer 0 that survived the re-check.
+ *     Candidates the file's known rows below the top that are not in D, with the values the file states, in a device buffer of their own:
+ *                never in the session's buffer unproved.  The layer-0 rows of dropped blocks are among them.
+ *     Restore    on the device, top-down, one launch per layer (k_nodes_restore_layer).  A node that is known -- in D, restored by the
+ *                launch before, or a top row: the stated slot root -- whose children are all known or candidates (one child for the last
+ *                node of an odd layer and for the one-block slot), at least one a candidate, is recomputed from them with the tree
+ *                builders' keys.  Where the result equals its value, the candidate children are copied into the session's buffer and are
+ *                RESTORED: known from here on.  Where it differs they are REJECTED.  A candidate whose parent is not known in the resumed
+ *                session, or whose sibling is neither known nor a candidate, is reached by no launch: UNPROVED.
+ *     Top rows   a top row's bit is taken over as saved: its value is the stated root.
+ *   *n_restored, *n_rejected, *n_unproved count those rows (each may be NULL).  Neither rejected nor unproved rows are an error: they are
+ *   simply not known, and the call returns CP2_OK.  With unchanged files every saved row is in D or restored.
+ *   The session is indistinguishable from one that has proved exactly D and the restored rows: cp2_fill_block_proofs, cp2_fill_anchors,
+ *   cp2_fill_add_anchored, cp2_fill_adopt, both saves and cp2_fill_finish.  A dropped block whose root was restored is absent with anchor
+ *   level 0: cp2_fill_add_anchored takes it back as bare bytes.
+ *   CP2_TRACE  cp2_fill_resume's line, cp2_fill_keep_nodes' line, then one line: format, candidates, restored, rejected, unproved, dropped.
+ *
+ * Out of scope: cp2_multi_*; saving the candidates cp2_fill_adopt remembers; deriving a parent from two known children. */
+int cp2_fill_save_nodes(const void* f /* cp2_fill* */, const char* path);
+int cp2_fill_resume_nodes(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local, const uint8_t* slot_roots,
+                          const char* path, int flags /* 0 or CP2_RESUME_TRUST_FILES */, void** out /* cp2_fill** */,
+                          uint64_t* n_dropped /* may be NULL */, uint64_t* n_restored /* may be NULL */,
+                          uint64_t* n_unproved /* may be NULL */, uint64_t* n_rejected /* may be NULL */);
 
 
 /* ---- e: every GPU of the node behind one handle ------------------------------------------------------ */
