@@ -53,6 +53,18 @@ __device__ __forceinline__ void store_fe_canonical(uint4* p, const Fe& v) {
   p[1] = make_uint4(w[4], w[5], w[6], w[7]);
 }
 
+// a 32-byte row as it stands: two 16-byte loads, two 16-byte stores
+__device__ __forceinline__ void copy_row(uint4* __restrict__ to, const uint4* from) {
+  const uint4 a = from[0], b = from[1];
+  to[0] = a;
+  to[1] = b;
+}
+
+// two 32-byte rows, each held as two loaded uint4, compared byte for byte
+__device__ __forceinline__ bool rows_equal(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1) {
+  return ((a0.x ^ b0.x) | (a0.y ^ b0.y) | (a0.z ^ b0.z) | (a0.w ^ b0.w) | (a1.x ^ b1.x) | (a1.y ^ b1.y) | (a1.z ^ b1.z) | (a1.w ^ b1.w)) == 0;
+}
+
 // nodeKey (Merkle.hs:162-165) in Montgomery form, lane-varying key in {0,1,2,3}: mont(1)*bit0 + mont(2)*bit1
 // with and-masks (v_cndmask_b32 costs ~23 cycles on gfx950).  The sum for key 3 is a
 // lazy value < 2N with limbs < 2U, inside permute()'s input bounds.
@@ -603,7 +615,7 @@ __global__ void __launch_bounds__(TPB) k_scrub_compare(const uint4* __restrict__
         ko = item * kstride + r;
       }
       const uint4 a0 = fresh[2 * fo], a1 = fresh[2 * fo + 1], b0 = kept[2 * ko], b1 = kept[2 * ko + 1];
-      diff = ((a0.x ^ b0.x) | (a0.y ^ b0.y) | (a0.z ^ b0.z) | (a0.w ^ b0.w) | (a1.x ^ b1.x) | (a1.y ^ b1.y) | (a1.z ^ b1.z) | (a1.w ^ b1.w)) != 0;
+      diff = !rows_equal(a0, a1, b0, b1);
     }
     const unsigned long long m = __ballot(diff);
     if (lane == 0) bits[(tile0 + (size_t)j * TPB) / 64 + wave] = m;
@@ -630,8 +642,7 @@ __global__ void __launch_bounds__(TPB) k_repair_compare(const uint4* __restrict_
   const uint64_t r = rows[i];
   uint32_t v = 1;
   if (r < kept_rows) {
-    const uint4 a0 = fresh[2 * i], a1 = fresh[2 * i + 1], b0 = kept[2 * r], b1 = kept[2 * r + 1];
-    v = ((a0.x ^ b0.x) | (a0.y ^ b0.y) | (a0.z ^ b0.z) | (a0.w ^ b0.w) | (a1.x ^ b1.x) | (a1.y ^ b1.y) | (a1.z ^ b1.z) | (a1.w ^ b1.w)) != 0;
+    v = rows_equal(fresh[2 * i], fresh[2 * i + 1], kept[2 * r], kept[2 * r + 1]) ? 0u : 1u;
   }
   verdict[i] = v;
 }
@@ -773,13 +784,67 @@ __global__ void __launch_bounds__(TPB) k_verify_samples(VerifyGeom g, const uint
 }
 
 // ------------------------------------------------------------------------------------------------
+// The block-path walk, shared by the four k_block_path_* kernels: reconstructRoot (merkle.nim:51-74) from a block root up `len` levels,
+// the schedule of block_proof_schedule (block_proof_plan.hpp).  j is the running index and m the layer size, both carried from level 0;
+// the node goes right where j is odd (left / right by limb masks), the key is (level 0 ? 1 : 0) + 2 where j is the even last node of its
+// layer (by arithmetic), one permutation per level.  Level l reads row l of `path`.  Returns the node reached; len == 0 returns `cur`.
+//   STAGE: lane-private staging.  For every level l the canonical sibling (a value of at least r lands as its residue) and the canonical
+//   ancestor (`cur` after level l) go to rows 2 l and 2 l + 1 of `mine`, two uint4 a row: staging memory, never the tree, so unproved
+//   data goes nowhere else, and the walk holds none of the 2 x len rows in registers.  Without STAGE `mine` is not used and nothing is
+//   stored.
+template <bool STAGE>
+__device__ __forceinline__ Fe walk_block_path(Fe cur, const uint4* __restrict__ path, uint4* mine, uint64_t j, uint64_t m, uint32_t len,
+                                              const fr::QTab& qtab) {
+  State s;
+#pragma unroll 1
+  for (uint32_t lvl = 0; lvl < len; ++lvl) {
+    const Fe sib = load_fe_canonical(path + 2 * lvl);
+    if constexpr (STAGE) store_fe_canonical(mine + 4 * lvl, sib);
+    const uint32_t b = (uint32_t)j & 1u;
+    const uint32_t key = (lvl == 0 ? 1u : 0u) + 2u * ((j == m - 1 ? 1u : 0u) & (b ^ 1u));
+    const uint32_t sw = 0u - b;
+#pragma unroll
+    for (int l = 0; l < fr::NL; ++l) {
+      s.x.l[l] = (cur.l[l] & ~sw) | (sib.l[l] & sw);
+      s.y.l[l] = (sib.l[l] & ~sw) | (cur.l[l] & sw);
+    }
+    s.z = key_fe(key);
+    p2::permute(s, qtab);
+    cur = fr::norm(s.x);
+    if constexpr (STAGE) store_fe_canonical(mine + 4 * lvl + 2, cur);
+    j >>= 1;
+    m = (m + 1) >> 1;
+  }
+  return cur;
+}
+
+// What a staged walk keeps after a match: a loop with no permutation in it that copies rows of `mine` into the session's compact buffer,
+// two 16-byte loads and two 16-byte stores each.  Sibling l goes to layer l, index (blk >> l) ^ 1, for l < len; ancestor l to layer l + 1,
+// index blk >> (l + 1), for l < n_anc only.  The row of (layer l, index) is layer_off[l] + slot * layer_size[l] + index (FillPlan::node_row,
+// fill_plan.hpp), from two device tables of depth + 1 entries.  An index at or past layer_size[l] -- the ZERO sibling of an odd layer's
+// last node, or of the one-block slot -- is skipped, and so is a row at or past n_rows (never: the host validated every request and made
+// the tables).  Nothing at layer n_anc + 1 or above is written, and above layer len - 1 no sibling either.
+__device__ __forceinline__ void keep_path_rows(uint4* tree, const uint4* mine, const uint64_t* __restrict__ layer_off,
+                                               const uint64_t* __restrict__ layer_size, uint64_t slot, uint64_t blk, uint32_t len,
+                                               uint32_t n_anc, uint64_t n_rows) {
+#pragma unroll 1
+  for (uint32_t lvl = 0; lvl < len; ++lvl) {
+    const uint64_t size = layer_size[lvl], sib = (blk >> lvl) ^ 1;
+    const uint64_t rs = layer_off[lvl] + slot * size + sib;
+    if (sib < size && rs < n_rows) copy_row(tree + 2 * rs, mine + 4 * lvl);
+    if (lvl >= n_anc) break;
+    const uint64_t up = layer_size[lvl + 1], anc = blk >> (lvl + 1);
+    const uint64_t ra = layer_off[lvl + 1] + slot * up + anc;
+    if (anc < up && ra < n_rows) copy_row(tree + 2 * ra, mine + 4 * lvl + 2);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Block proofs (block_proofs.cpp): lane i takes request i's freshly built block root (fresh row i, where k_repair_compare reads it), its
-// (slot root index, block) pair and its path of `depth` siblings, and runs reconstructRoot (merkle.nim:51-74) up to the slot root: the
-// schedule of block_proof_schedule (block_proof_plan.hpp) -- running index j, layer size m; the node goes right where j is odd, the key
-// is (level 0 ? 1 : 0) + 2 where j is the even last node of its layer -- with left / right by limb masks and the key by arithmetic, one
-// permutation per level.  The result is compared with slot_roots[root] as canonical words; one verdict word: 0 equal, 1 not.  depth is
-// uniform over the launch, j and m are per lane.  The host validated every request (root < n_roots, block < n_blocks).  roots_out (may be
-// NULL) receives the block root each candidate hashed to.
+// (slot root index, block) pair and its path of `depth` siblings, and walks up to the slot root.  The result is compared with
+// slot_roots[root] as canonical words; one verdict word: 0 equal, 1 not.  depth is uniform over the launch, j and m are per lane.  The
+// host validated every request (root < n_roots, block < n_blocks).  roots_out (may be NULL) receives the block root each candidate
+// hashed to.
 __global__ void __launch_bounds__(TPB) k_block_path_roots(const uint4* __restrict__ fresh, const uint4* __restrict__ paths,
                                                             const uint64_t* __restrict__ root_block, const uint4* __restrict__ slot_roots,
                                                             uint64_t n_blocks, uint32_t depth, size_t n, uint32_t* __restrict__ verdict,
@@ -789,47 +854,22 @@ __global__ void __launch_bounds__(TPB) k_block_path_roots(const uint4* __restric
   __syncthreads();
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
-  const uint4 f0 = fresh[2 * i], f1 = fresh[2 * i + 1];
-  if (roots_out) {
-    roots_out[2 * i] = f0;
-    roots_out[2 * i + 1] = f1;
-  }
-  const uint32_t fw[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
-  Fe cur = fr::to_mont(fr::from_words(fw));
-  const uint4* path = paths + 2 * i * depth;
-  uint64_t j = root_block[2 * i + 1], m = n_blocks;
-  State s;
-#pragma unroll 1
-  for (uint32_t lvl = 0; lvl < depth; ++lvl) {
-    const Fe sib = load_fe_canonical(path + 2 * lvl);
-    const uint32_t b = (uint32_t)j & 1u;
-    const uint32_t key = (lvl == 0 ? 1u : 0u) + 2u * ((j == m - 1 ? 1u : 0u) & (b ^ 1u));
-    const uint32_t sw = 0u - b;
-#pragma unroll
-    for (int l = 0; l < fr::NL; ++l) {
-      s.x.l[l] = (cur.l[l] & ~sw) | (sib.l[l] & sw);
-      s.y.l[l] = (sib.l[l] & ~sw) | (cur.l[l] & sw);
-    }
-    s.z = key_fe(key);
-    p2::permute(s, qtab);
-    cur = fr::norm(s.x);
-    j >>= 1;
-    m = (m + 1) >> 1;
-  }
+  if (roots_out) copy_row(roots_out + 2 * i, fresh + 2 * i);
+  const Fe cur = walk_block_path<false>(load_fe_canonical(fresh + 2 * i), paths + 2 * i * depth, nullptr, root_block[2 * i + 1], n_blocks,
+                                        depth, qtab);
   const Fe want = load_fe_canonical(slot_roots + 2 * root_block[2 * i]);
   verdict[i] = fe_equal(cur, want) ? 0u : 1u;
 }
 
 // ------------------------------------------------------------------------------------------------
-// Slot filling (fill.cpp): k_block_path_roots' walk, with what a fill session keeps of a proved block.  Lane i takes request i's freshly
-// built block root, its (local slot, block) pair and its path, runs reconstructRoot (merkle.nim:51-74, the schedule of block_proof_schedule:
-// key, odd and last rules) and compares the result with slot_roots[slot] as canonical words.  Where they are equal it also copies the
-// canonical block root (row i of `fresh`, as the layer kernel wrote it) to row dest[i] of `layer0`, the session's compact buffer: the host
-// computed dest[i] = coff[0] + local_slot * csizes[0] + block, a row of layer 0.  Two 16-byte vector stores; the row is read again from
-// `fresh` after the walk instead of being held in registers across it.  No atomics and no device bitmap: the host's bitmap is the authority
-// on presence.  Two matching requests for the same (slot, block) in one launch store identical bytes to one row, which is benign: a block
-// root that reconstructs the slot root at that position is the one block root the tree has there.  A row at or past n_rows (never: the
-// host validated every request) is a mismatch and nothing is stored.
+// Slot filling (fill.cpp): the same walk, with what a fill session keeps of a proved block.  Lane i takes request i's freshly built block
+// root, its (local slot, block) pair and its path, and compares the result with slot_roots[slot] as canonical words.  Where they are equal
+// it also copies the canonical block root (row i of `fresh`, as the layer kernel wrote it) to row dest[i] of `layer0`, the session's
+// compact buffer: the host computed dest[i] = coff[0] + local_slot * csizes[0] + block, a row of layer 0.  Two 16-byte vector stores; the
+// row is read again from `fresh` after the walk instead of being held in registers across it.  No atomics and no device bitmap: the host's
+// bitmap is the authority on presence.  Two matching requests for the same (slot, block) in one launch store identical bytes to one row,
+// which is benign: a block root that reconstructs the slot root at that position is the one block root the tree has there.  A row at or
+// past n_rows (never: the host validated every request) is a mismatch and nothing is stored.
 __global__ void __launch_bounds__(TPB) k_block_path_commit(const uint4* __restrict__ fresh, const uint4* __restrict__ paths,
                                                              const uint64_t* __restrict__ slot_block, const uint4* __restrict__ slot_roots,
                                                              const uint64_t* __restrict__ dest, uint64_t n_blocks, uint32_t depth, size_t n,
@@ -839,64 +879,27 @@ __global__ void __launch_bounds__(TPB) k_block_path_commit(const uint4* __restri
   __syncthreads();
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
-  Fe cur;
-  {
-    const uint4 f0 = fresh[2 * i], f1 = fresh[2 * i + 1];
-    const uint32_t fw[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
-    cur = fr::to_mont(fr::from_words(fw));
-  }
-  const uint4* path = paths + 2 * i * depth;
-  uint64_t j = slot_block[2 * i + 1], m = n_blocks;
-  State s;
-#pragma unroll 1
-  for (uint32_t lvl = 0; lvl < depth; ++lvl) {
-    const Fe sib = load_fe_canonical(path + 2 * lvl);
-    const uint32_t b = (uint32_t)j & 1u;
-    const uint32_t key = (lvl == 0 ? 1u : 0u) + 2u * ((j == m - 1 ? 1u : 0u) & (b ^ 1u));
-    const uint32_t sw = 0u - b;
-#pragma unroll
-    for (int l = 0; l < fr::NL; ++l) {
-      s.x.l[l] = (cur.l[l] & ~sw) | (sib.l[l] & sw);
-      s.y.l[l] = (sib.l[l] & ~sw) | (cur.l[l] & sw);
-    }
-    s.z = key_fe(key);
-    p2::permute(s, qtab);
-    cur = fr::norm(s.x);
-    j >>= 1;
-    m = (m + 1) >> 1;
-  }
+  const Fe cur = walk_block_path<false>(load_fe_canonical(fresh + 2 * i), paths + 2 * i * depth, nullptr, slot_block[2 * i + 1], n_blocks,
+                                        depth, qtab);
   const Fe want = load_fe_canonical(slot_roots + 2 * slot_block[2 * i]);
   const uint64_t r = dest[i];
   const bool keep = fe_equal(cur, want) && r < n_rows;
   verdict[i] = keep ? 0u : 1u;
-  if (keep) {
-    layer0[2 * r] = fresh[2 * i];
+  if (keep) {                                          // load, store, load, store.  Not copy_row: with its two loads first this kernel
+    layer0[2 * r] = fresh[2 * i];                      // compiles to 133 VGPRs and three waves per SIMD instead of 82 and five
     layer0[2 * r + 1] = fresh[2 * i + 1];
   }
 }
 
 // ------------------------------------------------------------------------------------------------
-// Slot filling with the nodes kept (fill.cpp, a session after cp2_fill_keep_nodes): k_block_path_commit's walk -- same schedule, keys, odd /
-// last rules and comparison with slot_roots[slot] -- with what a serving session keeps of a proved path: all of it.  A path that ends in
-// the stated slot root proves every node on it, the `depth` siblings the peer sent and the `depth` ancestors the walk computed (were one
-// of them wrong, another root would have come out), and the session's compact buffer has a row for each.
-//   During the walk lane i writes, for every level l, the canonical sibling (a value of at least r lands as its residue) and the canonical
-//   ancestor (`cur` after level l) into rows 2 l and 2 l + 1 of its own `depth` x 2 rows of `scratch`: staging memory, never the tree, so
-//   unproved data goes nowhere else, and the walk holds none of the 2 x depth rows in registers.
-//   After the verdict, on a match only, a second loop over the levels with no permutation in it copies rows, two 16-byte loads and two
-//   16-byte stores each: the block root to layer 0, row dest[i] (as k_block_path_commit); sibling l to layer l, index (b >> l) ^ 1;
-//   ancestor l to layer l + 1, index b >> (l + 1).  The row of (layer l, index) is layer_off[l] + local_slot * layer_size[l] + index
-//   (FillPlan::node_row, fill_plan.hpp), from two device tables of depth + 1 entries.  An index at or past layer_size[l] -- the ZERO sibling
-//   of an odd layer's last node, or of the one-block slot -- is skipped, and so is a row at or past n_rows (never: the host validated every
-//   request and made the tables).  On a mismatch nothing outside the lane's scratch rows and its verdict word is written.
+// Slot filling with the nodes kept (fill.cpp, a session after cp2_fill_keep_nodes): k_block_path_commit's walk and comparison with
+// slot_roots[slot], staged, with what a serving session keeps of a proved path: all of it.  A path that ends in the stated slot root
+// proves every node on it, the `depth` siblings the peer sent and the `depth` ancestors the walk computed (were one of them wrong,
+// another root would have come out), and the session's compact buffer has a row for each.  Lane i stages into its own `depth` x 2 rows
+// of `scratch`.  After the verdict, on a match only, it copies the block root to layer 0, row dest[i] (as k_block_path_commit), and every
+// sibling and ancestor where the tables put them.  On a mismatch nothing outside the lane's scratch rows and its verdict word is written.
 // No atomics: two proved requests that name the same node store identical bytes, the argument k_block_path_commit makes for layer 0, which
 // holds for every authentic node.  LDS is the QTab only.
-__device__ __forceinline__ void copy_row(uint4* __restrict__ to, const uint4* from) {
-  const uint4 a = from[0], b = from[1];
-  to[0] = a;
-  to[1] = b;
-}
-
 __global__ void __launch_bounds__(TPB) k_block_path_commit_nodes(const uint4* __restrict__ fresh, const uint4* __restrict__ paths,
                                                                    const uint64_t* __restrict__ slot_block, const uint4* __restrict__ slot_roots,
                                                                    const uint64_t* __restrict__ dest, const uint64_t* __restrict__ layer_off,
@@ -908,69 +911,31 @@ __global__ void __launch_bounds__(TPB) k_block_path_commit_nodes(const uint4* __
   __syncthreads();
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
-  Fe cur;
-  {
-    const uint4 f0 = fresh[2 * i], f1 = fresh[2 * i + 1];
-    const uint32_t fw[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
-    cur = fr::to_mont(fr::from_words(fw));
-  }
-  const uint4* path = paths + 2 * i * depth;
-  uint4* mine = scratch + 4 * i * depth;               // rows 2 l (sibling l) and 2 l + 1 (ancestor l), two uint4 a row
-  uint64_t j = slot_block[2 * i + 1], m = n_blocks;
-  State s;
-#pragma unroll 1
-  for (uint32_t lvl = 0; lvl < depth; ++lvl) {
-    const Fe sib = load_fe_canonical(path + 2 * lvl);
-    store_fe_canonical(mine + 4 * lvl, sib);
-    const uint32_t b = (uint32_t)j & 1u;
-    const uint32_t key = (lvl == 0 ? 1u : 0u) + 2u * ((j == m - 1 ? 1u : 0u) & (b ^ 1u));
-    const uint32_t sw = 0u - b;
-#pragma unroll
-    for (int l = 0; l < fr::NL; ++l) {
-      s.x.l[l] = (cur.l[l] & ~sw) | (sib.l[l] & sw);
-      s.y.l[l] = (sib.l[l] & ~sw) | (cur.l[l] & sw);
-    }
-    s.z = key_fe(key);
-    p2::permute(s, qtab);
-    cur = fr::norm(s.x);
-    store_fe_canonical(mine + 4 * lvl + 2, cur);
-    j >>= 1;
-    m = (m + 1) >> 1;
-  }
-  const uint64_t slot = slot_block[2 * i];
+  uint4* mine = scratch + 4 * i * depth;
+  const uint64_t slot = slot_block[2 * i], blk = slot_block[2 * i + 1];
+  const Fe cur = walk_block_path<true>(load_fe_canonical(fresh + 2 * i), paths + 2 * i * depth, mine, blk, n_blocks, depth, qtab);
   const Fe want = load_fe_canonical(slot_roots + 2 * slot);
   const uint64_t r = dest[i];
   const bool keep = fe_equal(cur, want) && r < n_rows;
   verdict[i] = keep ? 0u : 1u;
   if (!keep) return;
   copy_row(tree + 2 * r, fresh + 2 * i);
-  const uint64_t blk = slot_block[2 * i + 1];
-#pragma unroll 1
-  for (uint32_t lvl = 0; lvl < depth; ++lvl) {
-    const uint64_t size = layer_size[lvl], sib = (blk >> lvl) ^ 1;
-    const uint64_t rs = layer_off[lvl] + slot * size + sib;
-    if (sib < size && rs < n_rows) copy_row(tree + 2 * rs, mine + 4 * lvl);
-    const uint64_t up = layer_size[lvl + 1], anc = blk >> (lvl + 1);
-    const uint64_t ra = layer_off[lvl + 1] + slot * up + anc;
-    if (anc < up && ra < n_rows) copy_row(tree + 2 * ra, mine + 4 * lvl + 2);
-  }
+  keep_path_rows(tree, mine, layer_off, layer_size, slot, blk, depth, depth, n_rows);
 }
 
 // ------------------------------------------------------------------------------------------------
-// Slot filling with paths that stop at a kept node (fill.cpp, cp2_fill_add_anchored): k_block_path_commit_nodes' walk with a per-lane length
-// and a per-lane target.  A computed node that equals an authentic node proves everything below it -- the collision argument the whole
-// walk rests on -- so a block whose ancestor at level a the session already knows needs its a lowest siblings only.  Lane i takes fresh
-// block root i, levels[i] (at most depth; anything above is a mismatch), its (local slot, block) pair and its levels[i] siblings at row
+// Slot filling with paths that stop at a kept node (fill.cpp, cp2_fill_add_anchored): the staged walk with a per-lane length and a
+// per-lane target.  A computed node that equals an authentic node proves everything below it -- the collision argument the whole walk
+// rests on -- so a block whose ancestor at level a the session already knows needs its a lowest siblings only.  Lane i takes fresh block
+// root i, levels[i] (at most depth; anything above is a mismatch), its (local slot, block) pair and its levels[i] siblings at row
 // path_off[i] - path_base of the PACKED path buffer `paths` (path_off is the prefix sum of levels over the whole call, path_base the
-// entry of the first request whose siblings `paths` holds).
-//   The walk runs levels[i] levels of the same schedule (left / right by limb masks, key (lvl == 0) + 2 (even last node), j and m carried
-//   from level 0) and writes the canonical sibling and ancestor of each level into rows 2 l and 2 l + 1 of the lane's own 2 x levels[i]
-//   rows of `scratch`, which start at row 2 (path_off[i] - path_base): staging memory, never the tree.
+// entry of the first request whose siblings `paths` holds).  It stages into its own 2 x levels[i] rows of `scratch`, which start at row
+// 2 (path_off[i] - path_base).
 //   The result is compared with row anchor_row[i] of `tree`, loaded as a canonical element; anchor_row[i] == UINT64_MAX stands for
 //   slot_roots[slot]; any other row at or past n_rows is a mismatch.  levels[i] == 0 runs no permutation: the fresh root against the kept row.
-//   On a match only, a second loop with no permutation in it copies rows: the block root to row dest[i] (unless levels[i] == 0, where
-//   that row is the anchor), sibling l where its index is in range to layer l, ancestor l + 1 to layer l + 1 for l + 1 < levels[i].  The
-//   anchor row and every row above it are never written.  On a mismatch nothing outside the lane's scratch rows and its verdict word is.
+//   On a match only, rows are copied: the block root to row dest[i] (unless levels[i] == 0, where that row is the anchor), every sibling,
+//   and the ancestors below the last level's, which is the anchor and already there.  The anchor row and every row above it are never
+//   written.  On a mismatch nothing outside the lane's scratch rows and its verdict word is.
 // The host states only anchors that were known before the launch (FillPlan::validate_anchored), so an anchor row that another lane of the
 // launch rewrites is rewritten with the value it holds: a known row can only be proved equal to itself.  No atomics, as in
 // k_block_path_commit_nodes; LDS is the QTab only.  Lanes of a wave walk different lengths; a wave lasts as long as its longest lane.
@@ -993,37 +958,11 @@ __global__ void __launch_bounds__(TPB) k_block_path_commit_anchored(const uint4*
     verdict[i] = 1u;
     return;
   }
-  Fe cur;
-  {
-    const uint4 f0 = fresh[2 * i], f1 = fresh[2 * i + 1];
-    const uint32_t fw[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
-    cur = fr::to_mont(fr::from_words(fw));
-  }
   const uint64_t at = path_off[i] - path_base;
-  const uint4* path = paths + 2 * at;
-  uint4* mine = scratch + 4 * at;                      // rows 2 l (sibling l) and 2 l + 1 (ancestor l), two uint4 a row
-  uint64_t j = slot_block[2 * i + 1], m = n_blocks;
-  State s;
-#pragma unroll 1
-  for (uint32_t lvl = 0; lvl < len; ++lvl) {
-    const Fe sib = load_fe_canonical(path + 2 * lvl);
-    store_fe_canonical(mine + 4 * lvl, sib);
-    const uint32_t b = (uint32_t)j & 1u;
-    const uint32_t key = (lvl == 0 ? 1u : 0u) + 2u * ((j == m - 1 ? 1u : 0u) & (b ^ 1u));
-    const uint32_t sw = 0u - b;
-#pragma unroll
-    for (int l = 0; l < fr::NL; ++l) {
-      s.x.l[l] = (cur.l[l] & ~sw) | (sib.l[l] & sw);
-      s.y.l[l] = (sib.l[l] & ~sw) | (cur.l[l] & sw);
-    }
-    s.z = key_fe(key);
-    p2::permute(s, qtab);
-    cur = fr::norm(s.x);
-    store_fe_canonical(mine + 4 * lvl + 2, cur);
-    j >>= 1;
-    m = (m + 1) >> 1;
-  }
-  const uint64_t slot = slot_block[2 * i], target = anchor_row[i];
+  uint4* mine = scratch + 4 * at;
+  const uint64_t slot = slot_block[2 * i], blk = slot_block[2 * i + 1];
+  const Fe cur = walk_block_path<true>(load_fe_canonical(fresh + 2 * i), paths + 2 * at, mine, blk, n_blocks, len, qtab);
+  const uint64_t target = anchor_row[i];
   const bool stated = target == ~(uint64_t)0;
   if (!stated && target >= n_rows) {
     verdict[i] = 1u;
@@ -1035,17 +974,7 @@ __global__ void __launch_bounds__(TPB) k_block_path_commit_anchored(const uint4*
   verdict[i] = keep ? 0u : 1u;
   if (!keep || len == 0) return;
   copy_row(tree + 2 * r, fresh + 2 * i);
-  const uint64_t blk = slot_block[2 * i + 1];
-#pragma unroll 1
-  for (uint32_t lvl = 0; lvl < len; ++lvl) {
-    const uint64_t size = layer_size[lvl], sib = (blk >> lvl) ^ 1;
-    const uint64_t rs = layer_off[lvl] + slot * size + sib;
-    if (sib < size && rs < n_rows) copy_row(tree + 2 * rs, mine + 4 * lvl);
-    if (lvl + 1 == len) break;                         // the ancestor of the last level is the anchor: already there
-    const uint64_t up = layer_size[lvl + 1], anc = blk >> (lvl + 1);
-    const uint64_t ra = layer_off[lvl + 1] + slot * up + anc;
-    if (anc < up && ra < n_rows) copy_row(tree + 2 * ra, mine + 4 * lvl + 2);
-  }
+  keep_path_rows(tree, mine, layer_off, layer_size, slot, blk, len, len - 1, n_rows);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1064,14 +993,33 @@ __global__ void __launch_bounds__(TPB) k_block_root_recheck(const uint4* __restr
   const uint64_t r = dest[i];
   uint32_t v = 1;
   if (r < n_rows) {
-    const uint4 a0 = fresh[2 * i], a1 = fresh[2 * i + 1], b0 = layer0[2 * r], b1 = layer0[2 * r + 1];
-    v = ((a0.x ^ b0.x) | (a0.y ^ b0.y) | (a0.z ^ b0.z) | (a0.w ^ b0.w) | (a1.x ^ b1.x) | (a1.y ^ b1.y) | (a1.z ^ b1.z) | (a1.w ^ b1.w)) != 0;
+    v = rows_equal(fresh[2 * i], fresh[2 * i + 1], layer0[2 * r], layer0[2 * r + 1]) ? 0u : 1u;
     if (v) {
       layer0[2 * r] = make_uint4(0, 0, 0, 0);
       layer0[2 * r + 1] = make_uint4(0, 0, 0, 0);
     }
   }
   verdict[i] = v;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The children of one node of a fill session's tree, ready for the keyed compression: rows rl and rl + 1 of the compact layout, each from
+// `tree` where the session knows it (known_l / known_r: the child's KNOWN bit, 0 or 1) and from `cand` otherwise.  The base address is
+// picked with an integer mask: the two bases differ in the bits the mask lets through.  Without a pair (the last node of an odd layer,
+// the one-block slot) the right child is the left row once more, cleared by a limb mask, and the key gets + 2: k_compress_layer's rule.
+static_assert(ADOPT_KNOWN == 1 && NODE_KNOWN == 1, "load_children takes the KNOWN bit as 0 or 1");
+__device__ __forceinline__ State load_children(const uint4* tree, const uint4* cand, uint32_t known_l, uint32_t known_r, uint64_t rl, bool pair,
+                                               uint32_t bottom) {
+  const uintptr_t bt = (uintptr_t)tree, bc = (uintptr_t)cand;
+  const uintptr_t kl = (uintptr_t)0 - (uintptr_t)known_l, kr = (uintptr_t)0 - (uintptr_t)known_r;
+  State s;
+  s.x = load_fe_canonical((const uint4*)((bt & kl) | (bc & ~kl)) + 2 * rl);
+  s.y = load_fe_canonical((const uint4*)((bt & kr) | (bc & ~kr)) + 2 * (rl + (pair ? 1u : 0u)));
+  const uint32_t have = 0u - (pair ? 1u : 0u);
+#pragma unroll
+  for (int l = 0; l < fr::NL; ++l) s.y.l[l] &= have;
+  s.z = key_fe((bottom ? 1u : 0u) + (pair ? 0u : 2u));
+  return s;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1084,11 +1032,11 @@ __global__ void __launch_bounds__(TPB) k_block_root_recheck(const uint4* __restr
 // k_adopt_layer: one lane per node of layer l + 1 of the n_sel selected slots, one launch per layer (the flags and candidates of layer l
 // come from the launch before, earlier on the same stream).  Lane (slot, j) reads the flag bytes of children 2 j and 2 j + 1 of its slot;
 // the last node of an odd layer and the one-block slot have one child, a zero sibling and key + 2 (k_compress_layer's rule, key = 1 at
-// layer 0 and 0 above).  With both children defined it loads each from `tree` or `cand` -- the base address is picked with an integer mask,
-// the missing sibling is cleared by a limb mask -- runs one keyed compression, stores the canonical result to its row of `cand` and writes
-// its flag byte: bit 0 as it was, bit 1, and bit 2 where the node is known and the result equals its kept row (the top layer: the stated
-// root of its slot).  With an undefined child it writes the flag byte with bits 1 and 2 clear and nothing else.  A lane whose rows do not
-// all lie below n_rows (never: the host made the tables) reads and writes nothing.  `tree` is only read.  LDS is the QTab only; no atomics.
+// layer 0 and 0 above).  With both children defined it loads each from `tree` or `cand` (load_children), runs one keyed compression, stores
+// the canonical result to its row of `cand` and writes its flag byte: bit 0 as it was, bit 1, and bit 2 where the node is known and the
+// result equals its kept row (the top layer: the stated root of its slot).  With an undefined child it writes the flag byte with bits 1 and
+// 2 clear and nothing else.  A lane whose rows do not all lie below n_rows (never: the host made the tables) reads and writes
+// nothing.  `tree` is only read.  LDS is the QTab only; no atomics.
 //
 // k_adopt_resolve: one lane per row below the top layer, no permutation, no LDS.  It reads `flags`, `cand` and, for a known row of layer
 // 0, that row of `tree`; it writes its own byte of `out` (bits 0-2 as judged, bit 3 proved, bit 4 adopted) and, for a proved row, that
@@ -1117,16 +1065,7 @@ __global__ void __launch_bounds__(TPB) k_adopt_layer(const uint4* __restrict__ t
     flags[rp] = (uint8_t)fp;
     return;
   }
-  // tree where the child is known, cand otherwise: the two bases differ in the bits the mask lets through
-  const uintptr_t bt = (uintptr_t)tree, bc = (uintptr_t)cand;
-  const uintptr_t kl = (uintptr_t)0 - (uintptr_t)(fl & ADOPT_KNOWN), kr = (uintptr_t)0 - (uintptr_t)(fr_ & ADOPT_KNOWN);
-  State s;
-  s.x = load_fe_canonical((const uint4*)((bt & kl) | (bc & ~kl)) + 2 * rl);
-  s.y = load_fe_canonical((const uint4*)((bt & kr) | (bc & ~kr)) + 2 * (rl + (pair ? 1u : 0u)));   // no pair: the left row once more, cleared below
-  const uint32_t have = 0u - (pair ? 1u : 0u);
-#pragma unroll
-  for (int l = 0; l < fr::NL; ++l) s.y.l[l] &= have;
-  s.z = key_fe((bottom ? 1u : 0u) + (pair ? 0u : 2u));
+  State s = load_children(tree, cand, fl & ADOPT_KNOWN, fr_ & ADOPT_KNOWN, rl, pair, bottom);
   p2::permute(s, qtab);
   const Fe cur = fr::norm(s.x);
   store_fe_canonical(cand + 2 * rp, cur);
@@ -1159,8 +1098,7 @@ __global__ void __launch_bounds__(TPB) k_adopt_resolve(uint4* tree, const uint4*
   if (f & ADOPT_KNOWN) {
     uint32_t g = f;
     if (lvl == 0) {
-      const uint4 a0 = cand[2 * r], a1 = cand[2 * r + 1], b0 = tree[2 * r], b1 = tree[2 * r + 1];
-      const bool same = ((a0.x ^ b0.x) | (a0.y ^ b0.y) | (a0.z ^ b0.z) | (a0.w ^ b0.w) | (a1.x ^ b1.x) | (a1.y ^ b1.y) | (a1.z ^ b1.z) | (a1.w ^ b1.w)) == 0;
+      const bool same = rows_equal(cand[2 * r], cand[2 * r + 1], tree[2 * r], tree[2 * r + 1]);
       g = (f & ~ADOPT_MATCH) | (same ? ADOPT_MATCH | ADOPT_ADOPTED : 0u);
     }
     out[r] = (uint8_t)g;
@@ -1194,12 +1132,12 @@ __global__ void __launch_bounds__(TPB) k_adopt_resolve(uint4* tree, const uint4*
 // layer l + 1 come from the launch before, earlier on the same stream).  p must be known or restored; each child known or a candidate (the
 // last node of an odd layer and the one-block slot have one child, a zero sibling and key + 2: k_compress_layer's rule, key = 1 at layer 0
 // and 0 above), at least one of them a candidate: a lane with nothing to restore returns before the permutation.  It loads each child from
-// `tree` where it is known and from `cand` otherwise -- the base address picked with an integer mask, as k_adopt_layer does -- runs one
-// keyed compression and compares the canonical result with p's row of `tree` (the top layer: the stated root of its slot).  Equal: every
-// candidate child is stored into `tree` in canonical form (two 16-byte stores) and flagged NODE_RESTORED; unequal: flagged NODE_REJECTED,
-// nothing stored.  Only the parent's lane writes its children's rows and flag bytes, and a lane reads rows of `tree` only where they are
-// known or restored, so no lane reads what another writes in the same launch.  A lane whose rows do not all lie below n_rows (never: the
-// host made the tables) reads and writes nothing.  LDS is the QTab only; no atomics.
+// `tree` where it is known and from `cand` otherwise (load_children, as k_adopt_layer does), runs one keyed compression and compares the
+// canonical result with p's row of `tree` (the top layer: the stated root of its slot).  Equal: every candidate child is stored into `tree`
+// in canonical form (two 16-byte stores) and flagged NODE_RESTORED; unequal: flagged NODE_REJECTED, nothing stored.  Only the parent's lane
+// writes its children's rows and flag bytes, and a lane reads rows of `tree` only where they are known or restored, so no lane reads what
+// another writes in the same launch.  A lane whose rows do not all lie below n_rows (never: the host made the tables) reads and writes
+// nothing.  LDS is the QTab only; no atomics.
 __global__ void __launch_bounds__(TPB) k_nodes_restore_layer(uint4* tree, const uint4* __restrict__ cand, uint8_t* flags,
                                                                const uint4* __restrict__ slot_roots, uint64_t off_in, uint64_t m_in,
                                                                uint64_t off_out, uint64_t m_out, uint64_t n_local, uint32_t bottom, uint32_t top,
@@ -1217,16 +1155,7 @@ __global__ void __launch_bounds__(TPB) k_nodes_restore_layer(uint4* tree, const 
   if (!(flags[rp] & (NODE_KNOWN | NODE_RESTORED))) return;
   const uint32_t fl = flags[rl], fr_ = pair ? (uint32_t)flags[rr] : NODE_KNOWN;
   if (!(fl & (NODE_KNOWN | NODE_CAND)) || !(fr_ & (NODE_KNOWN | NODE_CAND)) || !((fl | fr_) & NODE_CAND)) return;
-  // tree where the child is known, cand otherwise: the two bases differ in the bits the mask lets through
-  const uintptr_t bt = (uintptr_t)tree, bc = (uintptr_t)cand;
-  const uintptr_t kl = (uintptr_t)0 - (uintptr_t)(fl & NODE_KNOWN), kr = (uintptr_t)0 - (uintptr_t)(fr_ & NODE_KNOWN);
-  State s;
-  s.x = load_fe_canonical((const uint4*)((bt & kl) | (bc & ~kl)) + 2 * rl);
-  s.y = load_fe_canonical((const uint4*)((bt & kr) | (bc & ~kr)) + 2 * rr);   // no pair: the left row once more, cleared below
-  const uint32_t have = 0u - (pair ? 1u : 0u);
-#pragma unroll
-  for (int l = 0; l < fr::NL; ++l) s.y.l[l] &= have;
-  s.z = key_fe((bottom ? 1u : 0u) + (pair ? 0u : 2u));
+  State s = load_children(tree, cand, fl & NODE_KNOWN, fr_ & NODE_KNOWN, rl, pair, bottom);
   p2::permute(s, qtab);
   const Fe cur = fr::norm(s.x);
   const Fe want = load_fe_canonical(top ? slot_roots + 2 * slot : (const uint4*)tree + 2 * rp);
@@ -1253,14 +1182,33 @@ constexpr size_t MAX_ITEMS = MAX_BLOCKS * TPB;
 static inline bool fits_one_grid(size_t n) { return (n + TPB - 1) / TPB <= MAX_BLOCKS; }
 static inline unsigned grid_for(size_t n) { return (unsigned)((n + TPB - 1) / TPB); }   // n <= MAX_ITEMS
 
-hipError_t launch_permute_batch(const void* in, void* out, size_t n, hipStream_t st) {
-  for (size_t i0 = 0; i0 < n; i0 += MAX_ITEMS) {
-    const size_t m = n - i0 < MAX_ITEMS ? n - i0 : MAX_ITEMS;
-    CP2K_LAUNCH(k_permute_batch, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)in + 6 * i0, (uint4*)out + 6 * i0, m);
+// launch(i0, m) for every slice [i0, i0 + m) of n items, m <= max_items; each launch between a cleared error and a read of its own, as in
+// CP2K_LAUNCH.  Stops at the first launch that fails.
+template <typename F>
+static inline hipError_t for_slices(size_t n, F launch, size_t max_items = MAX_ITEMS) {
+  for (size_t i0 = 0; i0 < n; i0 += max_items) {
+    (void)hipGetLastError();
+    launch(i0, n - i0 < max_items ? n - i0 : max_items);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+// Whether host tables of depth + 1 entries describe a compact layout of n_local slots, which the layer kernels derive every row from:
+// each layer half the one below (rounded up) down to a single root, the layers of all slots one after the other.
+static inline bool is_compact_layout(const uint64_t* layer_off_host, const uint64_t* layer_size_host, uint32_t depth, uint64_t n_local) {
+  for (uint32_t l = 0; l < depth; ++l) {
+    const uint64_t m_in = layer_size_host[l];
+    if (m_in == 0 || layer_size_host[l + 1] != (m_in + 1) / 2 || layer_off_host[l + 1] != layer_off_host[l] + n_local * m_in) return false;
+  }
+  return layer_size_host[depth] == 1;
+}
+
+hipError_t launch_permute_batch(const void* in, void* out, size_t n, hipStream_t st) {
+  return for_slices(n, [&](size_t i0, size_t m) {
+    hipLaunchKernelGGL(k_permute_batch, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)in + 6 * i0, (uint4*)out + 6 * i0, m);
+  });
 }
 
 hipError_t launch_compress_layer(const void* in, void* out, size_t m_in, size_t nseg, bool bottom,
@@ -1274,23 +1222,15 @@ hipError_t launch_compress_layer(const void* in, void* out, size_t m_in, size_t 
 }
 
 hipError_t launch_compress_pairs(const void* xy, uint32_t key, void* out, size_t n, hipStream_t st) {
-  for (size_t i0 = 0; i0 < n; i0 += MAX_ITEMS) {
-    const size_t m = n - i0 < MAX_ITEMS ? n - i0 : MAX_ITEMS;
-    CP2K_LAUNCH(k_compress_pairs, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)xy + 4 * i0, key, (uint4*)out + 2 * i0, m);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return for_slices(n, [&](size_t i0, size_t m) {
+    hipLaunchKernelGGL(k_compress_pairs, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)xy + 4 * i0, key, (uint4*)out + 2 * i0, m);
+  });
 }
 
 hipError_t launch_sponge2_felts(const void* felts, size_t nf, size_t nitems, void* out, hipStream_t st) {
-  for (size_t i0 = 0; i0 < nitems; i0 += MAX_ITEMS) {
-    const size_t m = nitems - i0 < MAX_ITEMS ? nitems - i0 : MAX_ITEMS;
-    CP2K_LAUNCH(k_sponge2_felts, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)felts + 2 * nf * i0, nf, m, (uint4*)out + 2 * i0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return for_slices(nitems, [&](size_t i0, size_t m) {
+    hipLaunchKernelGGL(k_sponge2_felts, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)felts + 2 * nf * i0, nf, m, (uint4*)out + 2 * i0);
+  });
 }
 
 // Workgroup size of k_hash_cells: 256 unless CP2_HASH_BLOCK=64 is in the environment (A/B tooling only).
@@ -1341,17 +1281,12 @@ hipError_t launch_hash_cells_block(int block, const void* cells, size_t cell_siz
   if (block != 64 && block != 256) return hipErrorInvalidValue;
   if (block == 256) block = CP2_HASH_BT;
   const unsigned dyn = (leave_room && block != 64) ? HASH_ROOM_BYTES : 0u;
-  const size_t max_items = MAX_BLOCKS * (size_t)block;
-  for (size_t i0 = 0; i0 < n_cells; i0 += max_items) {
-    const size_t m = n_cells - i0 < max_items ? n_cells - i0 : max_items;
+  return for_slices(n_cells, [&](size_t i0, size_t m) {
     const unsigned grid = (unsigned)((m + block - 1) / block);
     const uint8_t* src = (const uint8_t*)cells + i0 * cell_size;
-    if (block == 64) CP2K_LAUNCH(k_hash_cells<64>, dim3(grid), dim3(64), 0, st, src, cell_size, m, (uint4*)out + 2 * i0);
-    else CP2K_LAUNCH(k_hash_cells<CP2_HASH_BT>, dim3(grid), dim3(CP2_HASH_BT), dyn, st, src, cell_size, m, (uint4*)out + 2 * i0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+    if (block == 64) hipLaunchKernelGGL(k_hash_cells<64>, dim3(grid), dim3(64), 0, st, src, cell_size, m, (uint4*)out + 2 * i0);
+    else hipLaunchKernelGGL(k_hash_cells<CP2_HASH_BT>, dim3(grid), dim3(CP2_HASH_BT), dyn, st, src, cell_size, m, (uint4*)out + 2 * i0);
+  }, MAX_BLOCKS * (size_t)block);
 }
 
 hipError_t launch_hash_cells(const void* cells, size_t cell_size, size_t n_cells, void* out, hipStream_t st, bool leave_room) {
@@ -1438,28 +1373,20 @@ hipError_t launch_block_path_roots(const void* fresh, const void* paths, const u
                                    uint32_t depth, size_t n, uint32_t* verdict, void* roots_out, hipStream_t st) {
   if (n == 0) return hipSuccess;
   if (!fresh || !paths || !root_block || !slot_roots || !verdict || depth == 0 || n_blocks == 0) return hipErrorInvalidValue;
-  for (size_t i0 = 0; i0 < n; i0 += MAX_ITEMS) {
-    const size_t m = n - i0 < MAX_ITEMS ? n - i0 : MAX_ITEMS;
-    CP2K_LAUNCH(k_block_path_roots, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)fresh + 2 * i0, (const uint4*)paths + 2 * i0 * depth,
+  return for_slices(n, [&](size_t i0, size_t m) {
+    hipLaunchKernelGGL(k_block_path_roots, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)fresh + 2 * i0, (const uint4*)paths + 2 * i0 * depth,
                 root_block + 2 * i0, (const uint4*)slot_roots, n_blocks, depth, m, verdict + i0, roots_out ? (uint4*)roots_out + 2 * i0 : nullptr);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  });
 }
 
 hipError_t launch_block_path_commit(const void* fresh, const void* paths, const uint64_t* slot_block, const void* slot_roots, const uint64_t* dest,
                                     uint64_t n_blocks, uint32_t depth, size_t n, uint32_t* verdict, void* layer0, uint64_t n_rows, hipStream_t st) {
   if (n == 0) return hipSuccess;
   if (!fresh || !paths || !slot_block || !slot_roots || !dest || !verdict || !layer0 || depth == 0 || n_blocks == 0) return hipErrorInvalidValue;
-  for (size_t i0 = 0; i0 < n; i0 += MAX_ITEMS) {
-    const size_t m = n - i0 < MAX_ITEMS ? n - i0 : MAX_ITEMS;
-    CP2K_LAUNCH(k_block_path_commit, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)fresh + 2 * i0, (const uint4*)paths + 2 * i0 * depth,
+  return for_slices(n, [&](size_t i0, size_t m) {
+    hipLaunchKernelGGL(k_block_path_commit, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)fresh + 2 * i0, (const uint4*)paths + 2 * i0 * depth,
                 slot_block + 2 * i0, (const uint4*)slot_roots, dest + i0, n_blocks, depth, m, verdict + i0, (uint4*)layer0, n_rows);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  });
 }
 
 hipError_t launch_block_path_commit_nodes(const void* fresh, const void* paths, const uint64_t* slot_block, const void* slot_roots,
@@ -1469,15 +1396,11 @@ hipError_t launch_block_path_commit_nodes(const void* fresh, const void* paths, 
   if (!fresh || !paths || !slot_block || !slot_roots || !dest || !layer_off || !layer_size || !verdict || !tree || !scratch || depth == 0 ||
       n_blocks == 0)
     return hipErrorInvalidValue;
-  for (size_t i0 = 0; i0 < n; i0 += MAX_ITEMS) {
-    const size_t m = n - i0 < MAX_ITEMS ? n - i0 : MAX_ITEMS;
-    CP2K_LAUNCH(k_block_path_commit_nodes, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)fresh + 2 * i0, (const uint4*)paths + 2 * i0 * depth,
+  return for_slices(n, [&](size_t i0, size_t m) {
+    hipLaunchKernelGGL(k_block_path_commit_nodes, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)fresh + 2 * i0, (const uint4*)paths + 2 * i0 * depth,
                 slot_block + 2 * i0, (const uint4*)slot_roots, dest + i0, layer_off, layer_size, n_blocks, depth, m, verdict + i0, (uint4*)tree,
                 n_rows, (uint4*)scratch + 4 * i0 * depth);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  });
 }
 
 hipError_t launch_block_path_commit_anchored(const void* fresh, const void* paths, const uint32_t* levels, const uint64_t* path_off,
@@ -1489,29 +1412,21 @@ hipError_t launch_block_path_commit_anchored(const void* fresh, const void* path
   if (!fresh || !paths || !levels || !path_off || !slot_block || !slot_roots || !dest || !anchor_row || !layer_off || !layer_size || !verdict ||
       !tree || !scratch || depth == 0 || n_blocks == 0)
     return hipErrorInvalidValue;
-  for (size_t i0 = 0; i0 < n; i0 += MAX_ITEMS) {     // path_off is absolute: `paths` and `scratch` stay where they are
-    const size_t m = n - i0 < MAX_ITEMS ? n - i0 : MAX_ITEMS;
-    CP2K_LAUNCH(k_block_path_commit_anchored, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)fresh + 2 * i0, (const uint4*)paths, levels + i0,
+  return for_slices(n, [&](size_t i0, size_t m) {     // path_off is absolute: `paths` and `scratch` stay where they are
+    hipLaunchKernelGGL(k_block_path_commit_anchored, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)fresh + 2 * i0, (const uint4*)paths, levels + i0,
                 path_off + i0, path_base, slot_block + 2 * i0, (const uint4*)slot_roots, dest + i0, anchor_row + i0, layer_off, layer_size, n_blocks,
                 depth, m, verdict + i0, (uint4*)tree, n_rows, (uint4*)scratch);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  });
 }
 
 hipError_t launch_block_root_recheck(const void* fresh, const uint64_t* dest, size_t n, uint32_t* verdict, void* layer0, uint64_t n_rows,
                                      hipStream_t st) {
   if (n == 0) return hipSuccess;
   if (!fresh || !dest || !verdict || !layer0) return hipErrorInvalidValue;
-  for (size_t i0 = 0; i0 < n; i0 += MAX_ITEMS) {
-    const size_t m = n - i0 < MAX_ITEMS ? n - i0 : MAX_ITEMS;
-    CP2K_LAUNCH(k_block_root_recheck, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)fresh + 2 * i0, dest + i0, m, verdict + i0, (uint4*)layer0,
+  return for_slices(n, [&](size_t i0, size_t m) {
+    hipLaunchKernelGGL(k_block_root_recheck, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)fresh + 2 * i0, dest + i0, m, verdict + i0, (uint4*)layer0,
                 n_rows);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  });
 }
 
 hipError_t launch_adopt_layers(const void* tree, void* cand, uint8_t* flags, const void* slot_roots, const uint64_t* layer_off_host,
@@ -1521,13 +1436,9 @@ hipError_t launch_adopt_layers(const void* tree, void* cand, uint8_t* flags, con
   if (!tree || !cand || !flags || !slot_roots || !layer_off_host || !layer_size_host || depth == 0 || first_sel > n_local ||
       n_sel > n_local - first_sel)
     return hipErrorInvalidValue;
-  for (uint32_t l = 0; l < depth; ++l) {               // the tables must describe a compact layout: the kernel derives every row from them
-    const uint64_t m_in = layer_size_host[l], m_out = layer_size_host[l + 1];
-    if (m_in == 0 || m_out != (m_in + 1) / 2 || layer_off_host[l + 1] != layer_off_host[l] + n_local * m_in)
-      return hipErrorInvalidValue;
-    if (!fits_one_grid(m_out * n_sel)) return hipErrorInvalidValue;
-  }
-  if (layer_size_host[depth] != 1) return hipErrorInvalidValue;
+  if (!is_compact_layout(layer_off_host, layer_size_host, depth, n_local)) return hipErrorInvalidValue;
+  for (uint32_t l = 1; l <= depth; ++l)
+    if (!fits_one_grid(layer_size_host[l] * n_sel)) return hipErrorInvalidValue;
   for (uint32_t l = 0; l < depth; ++l) {
     const uint64_t m_out = layer_size_host[l + 1];
     CP2K_LAUNCH(k_adopt_layer, dim3(grid_for(m_out * n_sel)), dim3(TPB), 0, st, (const uint4*)tree, (uint4*)cand, flags, (const uint4*)slot_roots,
@@ -1566,13 +1477,9 @@ hipError_t launch_nodes_restore_layers(void* tree, const void* cand, uint8_t* fl
                                        const uint64_t* layer_size_host, uint32_t depth, uint64_t n_local, uint64_t n_rows, hipStream_t st) {
   if (n_local == 0) return hipSuccess;
   if (!tree || !cand || !flags || !slot_roots || !layer_off_host || !layer_size_host || depth == 0) return hipErrorInvalidValue;
-  for (uint32_t l = 0; l < depth; ++l) {               // the tables must describe a compact layout: the kernel derives every row from them
-    const uint64_t m_in = layer_size_host[l], m_out = layer_size_host[l + 1];
-    if (m_in == 0 || m_out != (m_in + 1) / 2 || layer_off_host[l + 1] != layer_off_host[l] + n_local * m_in)
-      return hipErrorInvalidValue;
-    if (!fits_one_grid(m_out * n_local)) return hipErrorInvalidValue;
-  }
-  if (layer_size_host[depth] != 1) return hipErrorInvalidValue;
+  if (!is_compact_layout(layer_off_host, layer_size_host, depth, n_local)) return hipErrorInvalidValue;
+  for (uint32_t l = 1; l <= depth; ++l)
+    if (!fits_one_grid(layer_size_host[l] * n_local)) return hipErrorInvalidValue;
   for (uint32_t l = depth; l-- > 0;) {                 // top first: a restored node vouches for its children in the next launch
     hipError_t e = launch_nodes_restore_layer(tree, cand, flags, slot_roots, layer_off_host[l], layer_size_host[l], layer_off_host[l + 1], n_local,
                                               l == 0, l + 1 == depth, n_rows, st);
