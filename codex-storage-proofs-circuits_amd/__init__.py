@@ -216,6 +216,7 @@ def load_library():
         "cp2_proof_inputs_export_many": (i32, [vp, vp, vp, vp, sz, ctypes.POINTER(cp), i32, sz, ctypes.POINTER(u64)]),
         "cp2_dataset_scrub": (i32, [vp, u64, u64, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_int)]),
         "cp2_multi_dataset_scrub": (i32, [vp, u64, u64, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_int)]),
+        "cp2_datasets_scrub_many": (i32, [vp, vp, sz, vp, sz, ctypes.POINTER(sz), vp, vp]),
         "cp2_dataset_repair_blocks": (i32, [vp, vp, vp, sz, i32, cp, vp, ctypes.POINTER(sz)]),
         "cp2_multi_dataset_repair_blocks": (i32, [vp, vp, vp, sz, i32, cp, vp, ctypes.POINTER(sz)]),
         "cp2_block_proof_depth": (sz, [sz, sz, sz]),
@@ -564,6 +565,20 @@ class Context:
             pi.slot_idx = int(r[1])
             pis.append(pi)
         return pis
+
+    def scrub_many(self, datasets, cap=1 << 20):
+        """cp2_datasets_scrub_many: every local slot of each Dataset of this context in one pass.  Returns (granularity: int32[n] of
+        SCRUB_*, bad: uint64[k, 3] of (request, slot, index), the lowest k = min(cap, n_bad), counts: uint64[n] mismatches per request,
+        complete whatever cap is, n_bad)."""
+        n, cap = len(datasets), int(cap)
+        hs = (ctypes.c_void_p * max(n, 1))(*[d.h for d in datasets])
+        bad = np.empty((cap, 3), dtype=np.uint64)
+        counts = np.zeros(max(n, 1), dtype=np.uint64)
+        gran = np.zeros(max(n, 1), dtype=np.int32)
+        nb = ctypes.c_size_t()
+        self._ck(self.L.cp2_datasets_scrub_many(self.h, hs, n, _p(bad) if cap else None, cap, ctypes.byref(nb), _p(counts), _p(gran)),
+                 "cp2_datasets_scrub_many")
+        return gran[:n].copy(), bad[:min(cap, nb.value)].copy(), counts[:n].copy(), nb.value
 
     def export_proof_inputs_many(self, requests, paths=None, threads=1, batch=0):
         """cp2_proof_inputs_export_many: generate + serialise (+ write paths[i] where it is not None) as a pipeline; returns the

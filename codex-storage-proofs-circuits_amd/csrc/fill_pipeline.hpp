@@ -2,7 +2,8 @@
 // (memcpy) on several threads.  No HIP in here: tests/host_check/fill_pipeline_check.cpp runs it against real files on the CPU, under
 // AddressSanitizer + UBSan and again under ThreadSanitizer.
 //
-// Bytes [0, m * cell_size) of the turn [c0, c0 + m) of batch `g` go into `buf`, from the slot files "<base><slot>.dat" (dataset.nim:34),
+// Bytes [0, m * cell_size) of the turn [c0, c0 + m) of batch `g` go into `buf`, from the slot files "<base><slot>.dat" (dataset.nim:34)
+// -- or, with a name table, from the files it lists, one per unit of the batch (scrubbing many datasets at once: scrub.cpp) --
 // zero-filled past the end of a file (slot.nim:61-66).  The turn is cut into GRAINS of 4 MiB which the fill threads take from a shared
 // counter (round 6; equal byte ranges, one per thread, joined per turn, before): the formatting threads of a streamed build compete for
 // the same cores, and a fill thread that loses its core for a scheduler slice no longer holds up a whole turn.  Every thread walks the
@@ -85,10 +86,14 @@ class FillPipeline {
 
   // post the fill of the turn [c0, c0 + m) into `buf`: the workers start on it as soon as they run out of grains of the job before.
   // mem != nullptr: the turn's bytes are copied from host memory at `mem` (host arrays) instead of read from slot files.
-  void begin(const IngestGeom& g, const std::string& base, size_t c0, size_t m, uint8_t* buf, bool want_direct, const uint8_t* mem = nullptr) {
+  // names != nullptr: a NAME TABLE indexed by IngestPiece::unit -- unit i of the batch is the file names[i] (g.n_units entries, which the
+  // caller keeps alive until the fill is joined) instead of "<base><slot>.dat"; the lowest UNIT's file is the one a failed join names.
+  void begin(const IngestGeom& g, const std::string& base, size_t c0, size_t m, uint8_t* buf, bool want_direct, const uint8_t* mem = nullptr,
+             const std::string* names = nullptr) {
     auto job = std::make_shared<Job>();
     job->g = g;
     job->base = base;
+    job->names = names;
     job->c0 = c0;
     job->mem = mem;
     job->nbytes = m * g.cell_size;
@@ -126,6 +131,7 @@ class FillPipeline {
   struct Job {
     IngestGeom g;
     std::string base;
+    const std::string* names = nullptr;     // the name table (not owned), or null: fill_slot_file_name(base, slot)
     size_t c0 = 0, nbytes = 0, n_grains = 0;
     uint8_t* buf = nullptr;
     const uint8_t* mem = nullptr;
@@ -150,10 +156,11 @@ class FillPipeline {
     uint8_t* buf = job.buf;
     for (size_t p = a; p < b;) {
       const IngestPiece q = ingest_piece(g, job.c0, p, b);
-      const std::string fname = fill_slot_file_name(job.base, q.slot);
+      const std::string fname = job.names ? job.names[q.unit] : fill_slot_file_name(job.base, q.slot);
+      const uint64_t key = job.names ? (uint64_t)q.unit : q.slot;   // what "lowest" means among the files that failed
       const int fd = open(fname.c_str(), O_RDONLY);
       if (fd < 0) {
-        report(job, q.slot, fname, 0);
+        report(job, key, fname, 0);
         std::memset(buf + p, 0, q.len);
         p += q.len;
         continue;
@@ -173,7 +180,7 @@ class FillPipeline {
         }
       }
       const int err = slot_file_read_rest(fd, buf + p, q.len, q.file_off, pos);
-      if (err) report(job, q.slot, fname, err);
+      if (err) report(job, key, fname, err);
       close(fd);
       p += q.len;
     }

@@ -9,6 +9,7 @@
 //   k_sample_many, k_gather_addr, k_gen_fake_cells_many   the same across datasets (proof_many.cpp)
 //   k_verify_samples      what SampleAndProve accepts: sample_cells.circom:58-148, single_cell.circom:30-73, merkle.circom:44-114
 //   k_scrub_compare       a rebuilt layer against the kept one, mismatch bitmap + per-workgroup counts (scrub.cpp)
+//   k_scrub_compare_many  the same with the kept rows of every item behind an address table (many datasets in one batch)
 //   k_repair_compare      candidate block roots against the kept rows they would replace, one verdict per request (repair.cpp)
 //   k_block_path_roots    a13 candidate block roots walked up their Merkle paths to the slot root, merkle.nim:51-74 (block_proofs.cpp)
 //   k_block_path_commit   the same walk; a proved block root is also stored into layer 0 of a fill session's compact buffer (fill.cpp)
@@ -615,6 +616,41 @@ __global__ void __launch_bounds__(TPB) k_scrub_compare(const uint4* __restrict__
         ko = item * kstride + r;
       }
       const uint4 a0 = fresh[2 * fo], a1 = fresh[2 * fo + 1], b0 = kept[2 * ko], b1 = kept[2 * ko + 1];
+      diff = !rows_equal(a0, a1, b0, b1);
+    }
+    const unsigned long long m = __ballot(diff);
+    if (lane == 0) bits[(tile0 + (size_t)j * TPB) / 64 + wave] = m;
+    n += (uint32_t)__popcll(m);
+  }
+  if (lane == 0) wave_count[wave] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t s = 0;
+    for (int w = 0; w < TPB / 64; ++w) s += wave_count[w];
+    counts[blockIdx.x] = s;
+  }
+}
+
+// The same over items whose kept layers lie anywhere (scrub.cpp, cp2_datasets_scrub_many: the slots of many datasets in one batch): the
+// kept row of global row g is at kept_addr[g / rows] + (g % rows) * 32, kept_addr holding one device address per item -- row 0 of that
+// item's kept layer, 16-byte aligned like every 32-byte row.  The fresh side, the 64-row ballot words, the one count per tile and the zero
+// words past the last row are k_scrub_compare's; so is what the host reads of them.  The 64 lanes of a wave read one table entry (rows
+// >= 64) or a few neighbouring ones: 8 bytes per item beside 64 bytes per row.
+__global__ void __launch_bounds__(TPB) k_scrub_compare_many(const uint4* __restrict__ fresh, size_t fstride, const uint64_t* __restrict__ kept_addr,
+                                                              size_t rows, size_t total, unsigned long long* __restrict__ bits,
+                                                              uint32_t* __restrict__ counts) {
+  __shared__ uint32_t wave_count[TPB / 64];
+  const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const size_t tile0 = (size_t)blockIdx.x * SCRUB_TILE;
+  uint32_t n = 0;
+  for (int j = 0; j < SCRUB_STEPS; ++j) {
+    const size_t g = tile0 + (size_t)j * TPB + threadIdx.x;
+    bool diff = false;
+    if (g < total) {
+      const size_t item = g / rows, r = g - item * rows;
+      const size_t fo = item * fstride + r;
+      const uint4* k = reinterpret_cast<const uint4*>(kept_addr[item]) + 2 * r;
+      const uint4 a0 = fresh[2 * fo], a1 = fresh[2 * fo + 1], b0 = k[0], b1 = k[1];
       diff = !rows_equal(a0, a1, b0, b1);
     }
     const unsigned long long m = __ballot(diff);
@@ -1356,6 +1392,17 @@ hipError_t launch_scrub_compare(const void* fresh, size_t fstride, const void* k
   const size_t total = n_items * rows, groups = scrub_groups(total);
   if (groups > MAX_BLOCKS) return hipErrorInvalidValue;
   CP2K_LAUNCH(k_scrub_compare, dim3((unsigned)groups), dim3(TPB), 0, st, (const uint4*)fresh, fstride, (const uint4*)kept, kstride, rows, total,
+              (unsigned long long*)bits, counts);
+  return hipGetLastError();
+}
+
+hipError_t launch_scrub_compare_many(const void* fresh, size_t fstride, const uint64_t* kept_addr, size_t rows, size_t n_items, uint64_t* bits,
+                                     uint32_t* counts, hipStream_t st) {
+  if (n_items == 0 || rows == 0) return hipSuccess;
+  if (!fresh || !kept_addr || !bits || !counts || fstride < rows) return hipErrorInvalidValue;
+  const size_t total = n_items * rows, groups = scrub_groups(total);
+  if (groups > MAX_BLOCKS) return hipErrorInvalidValue;
+  CP2K_LAUNCH(k_scrub_compare_many, dim3((unsigned)groups), dim3(TPB), 0, st, (const uint4*)fresh, fstride, kept_addr, rows, total,
               (unsigned long long*)bits, counts);
   return hipGetLastError();
 }

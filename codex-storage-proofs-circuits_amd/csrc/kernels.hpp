@@ -63,6 +63,10 @@ constexpr size_t SCRUB_TILE = 4096;
 inline size_t scrub_groups(size_t n_rows) { return (n_rows + SCRUB_TILE - 1) / SCRUB_TILE; }
 hipError_t launch_scrub_compare(const void* fresh, size_t fstride, const void* kept, size_t kstride, size_t rows, size_t n_items,
                                 uint64_t* bits, uint32_t* counts, hipStream_t st);
+// The same with the kept layer of item i anywhere: kept_addr (device, n_items entries) holds the device address of row 0 of item i's
+// kept layer, so the kept row of global row g is at kept_addr[g / rows] + (g % rows) * 32.  Same bits, same counts, same zero words.
+hipError_t launch_scrub_compare_many(const void* fresh, size_t fstride, const uint64_t* kept_addr, size_t rows, size_t n_items, uint64_t* bits,
+                                     uint32_t* counts, hipStream_t st);
 
 // Block repair (repair.cpp): verdict[i] = 0 when the 32-byte row i of `fresh` equals row rows[i] of `kept` (kept_rows rows), else 1.
 hipError_t launch_repair_compare(const void* fresh, const void* kept, size_t kept_rows, const uint64_t* rows, size_t n, uint32_t* verdict,

@@ -557,8 +557,9 @@ struct IngestPipe {
   // The fills of the turns (csrc/fill_pipeline.hpp: host threads, grains from a shared counter, two turns deep; no HIP in it -- the CPU
   // suite runs it against real files under ASan/UBSan and under TSan)
   std::unique_ptr<FillPipeline> fill;
-  void fill_begin(const IngestGeom& g, const std::string& base, size_t c0, size_t m, uint8_t* buf, bool want_direct, const uint8_t* mem = nullptr) {
-    fill->begin(g, base, c0, m, buf, want_direct, mem);
+  void fill_begin(const IngestGeom& g, const std::string& base, size_t c0, size_t m, uint8_t* buf, bool want_direct, const uint8_t* mem = nullptr,
+                  const std::string* names = nullptr) {
+    fill->begin(g, base, c0, m, buf, want_direct, mem, names);
   }
   int fill_join() {
     std::string bad;
@@ -822,9 +823,14 @@ extern "C" int cp2_slot_trees_build_host(cp2_ctx* ctx, const uint8_t* cells, siz
 // THIRD stream while the two hashing streams carry on with the next turns; the hash launches leave a third of every CU free for
 // them (launch_hash_cells' leave_room); nothing joins the two hashing streams per slot.  Rounds 2-5 launched at full occupancy and
 // made the first stream wait for the second after every slot.
-int cp2i::trees_build_files(cp2_ctx* ctx, const std::string& base, uint64_t first_slot, size_t n_slots, size_t cell_size,
-                            size_t block_size, size_t n_cells, size_t group, const SlotsDone& done, cp2_slot_trees** out,
-                            uint64_t units_per_slot, bool pooled_nodes, BuildScratch* scratch, int node_slot) {
+//
+// The files of a batch are named by base + first item ("<base><slot>.dat", units_per_slot units to a file: trees_build_files) or by a
+// NAME TABLE, names[i] being the whole file of unit i (trees_build_file_list: first_slot 0, units_per_slot 1).  Everything else -- the
+// pipe, the turns, the fills, O_DIRECT, the layer passes -- is this one body.  The mapped mode keys its mappings by DATASET unit, which
+// a name table does not have: a listed batch always goes through the ring.
+static int build_files(cp2_ctx* ctx, const std::string& base, const std::string* names, uint64_t first_slot, size_t n_slots, size_t cell_size,
+                       size_t block_size, size_t n_cells, size_t group, const SlotsDone& done, cp2_slot_trees** out,
+                       uint64_t units_per_slot, bool pooled_nodes, BuildScratch* scratch, int node_slot) {
   *out = nullptr;
   if (units_per_slot == 0 || cell_size > SLOT_FILE_MAX_CELL) return CP2_ERR_INVALID;   // slot.nim:60-61
   CP2_REFUSE_STUCK(ctx);
@@ -879,7 +885,7 @@ int cp2i::trees_build_files(cp2_ctx* ctx, const std::string& base, uint64_t firs
     }
     // mapped mode (cp2_set_ingest_mapped / CP2_INGEST_MAPPED, default off): chunks that sit in the page cache are uploaded straight
     // from a mapping of the file, no CPU copy; not with O_DIRECT, whose point is to leave the page cache alone
-    pipe->mapped_allowed = !want_direct && (ctx->ingest_mapped > 0 || (ctx->ingest_mapped < 0 && env_size("CP2_INGEST_MAPPED", 0) != 0));
+    pipe->mapped_allowed = !names && !want_direct && (ctx->ingest_mapped > 0 || (ctx->ingest_mapped < 0 && env_size("CP2_INGEST_MAPPED", 0) != 0));
     const size_t mapped0 = pipe->mapped_chunks, ring0 = pipe->ring_chunks;
     StageTimer ingest_trace;
     // One turn = cells [c0, c0 + m) of the batch.  Ring turns are double-buffered on the HOST side too: turn k + 1's fill is posted
@@ -899,7 +905,7 @@ int cp2i::trees_build_files(cp2_ctx* ctx, const std::string& base, uint64_t firs
     auto begin_turn = [&](size_t c0, size_t ahead, Turn* tn) -> int {      // size the turn, take a pinned buffer, post its fill
       CP2_TRY(turn_cells(c0, ahead, &tn->m));
       CP2_TRY(pipe->acquire(&tn->buf, ahead));
-      pipe->fill_begin(g, base, c0, tn->m, tn->buf, want_direct);
+      pipe->fill_begin(g, base, c0, tn->m, tn->buf, want_direct, nullptr, names);
       tn->filling = true;
       return CP2_OK;
     };
@@ -953,6 +959,21 @@ int cp2i::trees_build_files(cp2_ctx* ctx, const std::string& base, uint64_t firs
   if (st != CP2_OK) return st;
   *out = t.release();
   return CP2_OK;
+}
+
+int cp2i::trees_build_files(cp2_ctx* ctx, const std::string& base, uint64_t first_slot, size_t n_slots, size_t cell_size,
+                            size_t block_size, size_t n_cells, size_t group, const SlotsDone& done, cp2_slot_trees** out,
+                            uint64_t units_per_slot, bool pooled_nodes, BuildScratch* scratch, int node_slot) {
+  return build_files(ctx, base, nullptr, first_slot, n_slots, cell_size, block_size, n_cells, group, done, out, units_per_slot, pooled_nodes,
+                     scratch, node_slot);
+}
+
+int cp2i::trees_build_file_list(cp2_ctx* ctx, const std::string* names, size_t n_names, size_t cell_size, size_t block_size, size_t n_cells,
+                                size_t group, const SlotsDone& done, cp2_slot_trees** out, bool pooled_nodes, BuildScratch* scratch,
+                                int node_slot) {
+  if (!names && n_names) return CP2_ERR_INVALID;
+  return build_files(ctx, std::string(), names, 0, n_names, cell_size, block_size, n_cells, group, done, out, 1, pooled_nodes,
+                     scratch, node_slot);
 }
 
 extern "C" int cp2_set_ingest_mapped(cp2_ctx* ctx, int on) try {

@@ -64,6 +64,20 @@ int trees_build_fake(cp2_ctx* ctx, uint64_t dataset_seed, uint64_t first_slot, s
 int trees_build_files(cp2_ctx* ctx, const std::string& base, uint64_t first_slot, size_t n_slots, size_t cell_size,
                       size_t block_size, size_t n_cells, size_t group, const SlotsDone& done, cp2_slot_trees** out,
                       uint64_t units_per_slot = 1, bool pooled_nodes = false, BuildScratch* scratch = nullptr, int node_slot = 0);
+// The same over a NAME TABLE: unit i of the batch is the whole file names[i] (units_per_slot 1), whatever it is called -- the slots of
+// many datasets in one batch (scrub.cpp).  One body with trees_build_files, which is the base + first-item case of it.  O_DIRECT is
+// honoured as there and the slot.nim:60-61 cell-size cap applies; the MAPPED mode keys its mappings by dataset unit, which a listed
+// batch does not have: it is not used, every turn goes through the ring.  The batch's file_base is empty and its first_slot 0.
+// The table is names[0 .. n_names): the caller keeps it alive for the call (every fill is joined before the builder returns), so a batch
+// of a longer table is a pointer into it, nothing is copied.
+int trees_build_file_list(cp2_ctx* ctx, const std::string* names, size_t n_names, size_t cell_size, size_t block_size, size_t n_cells,
+                          size_t group, const SlotsDone& done, cp2_slot_trees** out, bool pooled_nodes = false,
+                          BuildScratch* scratch = nullptr, int node_slot = 0);
+inline int trees_build_file_list(cp2_ctx* ctx, const std::vector<std::string>& names, size_t cell_size, size_t block_size, size_t n_cells,
+                                 size_t group, const SlotsDone& done, cp2_slot_trees** out, bool pooled_nodes = false,
+                                 BuildScratch* scratch = nullptr, int node_slot = 0) {
+  return trees_build_file_list(ctx, names.data(), names.size(), cell_size, block_size, n_cells, group, done, out, pooled_nodes, scratch, node_slot);
+}
 // bytes of the node buffer of a batch of n_slots slots of this geometry (all layers, 32 bytes per node)
 size_t trees_node_bytes(size_t n_slots, size_t cell_size, size_t block_size, size_t n_cells);
 void trees_geom(const cp2_slot_trees* t, cp2k::TreeGeom* g);

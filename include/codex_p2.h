@@ -41,7 +41,7 @@ extern "C" {
  * History: 1.0 = the 105 entry points of round 5 + this function + cp2_set_ingest's two rings (round 6).
  *          1.1 = + cp2_proof_input_parse_json, _shape, _cell_felts and cp2_proof_inputs_verify (verification).
  *          1.2 = + cp2_proof_inputs_generate_many and cp2_proof_inputs_export_many (proof inputs across datasets).
- *          next: + cp2_dataset_scrub and cp2_multi_dataset_scrub (scrub), cp2_dataset_repair_blocks and
+ *          next: + cp2_dataset_scrub, cp2_multi_dataset_scrub and cp2_datasets_scrub_many (scrub), cp2_dataset_repair_blocks and
  *                cp2_multi_dataset_repair_blocks (repair), cp2_block_proof_depth, cp2_dataset_block_proofs, cp2_blocks_verify and
  *                cp2_dataset_repair_blocks_proved (block proofs), cp2_fill_begin, cp2_fill_add, cp2_fill_missing, cp2_fill_finish and
  *                cp2_fill_free (fill sessions), cp2_fill_save and cp2_fill_resume (fill checkpoints), cp2_fill_keep_nodes and
@@ -482,6 +482,35 @@ int cp2_proof_inputs_verify(cp2_ctx* ctx, const cp2_proof_input* const* ps, size
 #define CP2_SCRUB_CELL  2
 int cp2_dataset_scrub(cp2_dataset* ds, uint64_t first_slot, uint64_t n_slots, uint64_t* bad /* cap x 2: (slot, index) */, size_t cap,
                       size_t* n_bad, int* granularity);
+/* Every local slot of n datasets of one context in ONE pass -- the storage node of cp2_proof_inputs_generate_many above, which holds
+ * one slot each of many datasets (first_slot = k, n_local = 1): scrubbed one by one, every dataset pays a whole pipe (rings and events
+ * set up and torn down, one small hash launch, a drain), whatever its size.  Request i scrubs every local slot of ds[i]: what
+ * cp2_dataset_scrub(ds[i], 0, 0, ...) does, at the finest level that dataset keeps.
+ *   Same result  the triples of request i are exactly the (slot, index) pairs the single call reports for ds[i], with i in front.  bad
+ *            (cap x 3 uint64: request, slot, index) receives the lowest min(cap, *n_bad) triples in (request, slot, index) order;
+ *            *n_bad counts all mismatches; counts (n entries, may be NULL) receives the mismatches of each request, complete even when
+ *            the report is capped (which datasets are damaged is never lost); granularity (n entries, may be NULL) the CP2_SCRUB_* level
+ *            of each request.  cap == 0 with bad == NULL only counts.
+ *   Datasets may differ in n_cells, n_slots, first_slot, n_local, source, base name, seed and in what they keep.  A dataset may appear
+ *            twice: each request gets its own report.
+ *   Refused  before any device or file work, outputs untouched, the request index in cp2_last_error (CP2_ERR_INVALID): ctx or n_bad
+ *            NULL; ds NULL with n > 0; cap > 0 with bad NULL; ds[i] NULL; ds[i] not a dataset of ctx (the shards of a cp2_multi_dataset
+ *            belong to that object's contexts).  n == 0: CP2_OK, *n_bad = 0.  A context whose stream will not drain: CP2_ERR_HIP.
+ *   Errors   a slot file that cannot be opened or read is CP2_ERR_IO with the builders' message naming the file, and nothing is written
+ *            to any output; neither on any other error.  Changed data is not an error.  Read-only, as a scrub is.
+ *   How      the requests are grouped into classes of equal (cell_size, block_size, n_cells, level, source kind).  The slots of a
+ *            file-sourced class are one run of items through the scrub's batch loop -- the same turns, batches and ingestion settings
+ *            (cp2_set_ingest, O_DIRECT) as one dataset holding those slots -- read through a table of file names and compared through
+ *            a table of the addresses of their kept layers.  The mapped ingestion mode keys its mappings by dataset unit: a listed
+ *            batch does not use it and always goes through the pinned ring.  Fake-source requests are regenerated (always clean) one
+ *            by one inside the call, as cp2_dataset_scrub does.  Datasets that each have a geometry of their own make every class one
+ *            dataset, which is the loop over cp2_dataset_scrub: accepted.  Each class keeps at most cap triples; the classes are merged
+ *            by (request, slot, index) and truncated at the end.  CP2_TRACE prints one line for the whole call (requests, classes,
+ *            items, batches, bytes, seconds, GB/s, mismatches; items and bytes count the slot files read, not the fake-source requests).
+ *            A batch holds half a staging chunk (CODEX_P2_STAGE_MB) of nodes, 129 slots of 64 cells at its minimum of 1 MiB: with fewer
+ *            small slots than that, several batches can only be had by listing datasets more than once. */
+int cp2_datasets_scrub_many(cp2_ctx* ctx, cp2_dataset* const* ds, size_t n, uint64_t* bad /* cap x 3: (request, slot, index) */, size_t cap,
+                            size_t* n_bad, uint64_t* counts /* n, may be NULL */, int* granularity /* n, may be NULL */);
 
 /* ---- repair: replacement blocks checked against the kept block roots, then written back ----------------------------------------
  * A scrub names the network blocks whose data no longer hashes to what the dataset keeps; the node fetches or re-decodes them (erasure
