@@ -65,3 +65,12 @@ inline void canonical_felt(const uint8_t in[32], uint8_t out[32]) {
 const void* dataset_roots_dev(const cp2_dataset* ds);
 // slotProof = padMerkleProof(merkleProof(dsetTree, slotIdx), maxLog2NSlots), gen_input/bn254.nim:51,72
 void fill_slot_proof(const cp2_dataset* ds, uint64_t slot_idx, std::vector<uint8_t>& out);
+
+namespace cp2i {
+// The one pass that makes proof inputs for n (dataset, slot, entropy) requests of one circuit (proof_many.cpp): every request's
+// out[i], or none.  `named`: error texts start with "request <at0 + i>: " (the *_many entry points) or with nothing (the compact
+// branch of cp2_proof_inputs_generate_batch).  proof_many.cpp and proof_input.cpp call each other here: a compact one-dataset batch
+// comes in through this, and a roots-only request goes back out through cp2_proof_inputs_generate_batch, one slot at a time.
+int prove_requests(cp2_ctx* ctx, cp2_dataset* const* ds, const uint64_t* slot_idx, const uint8_t* entropies, size_t n, size_t at0,
+                   bool named, cp2_proof_input** out);
+}  // namespace cp2i

@@ -176,6 +176,9 @@ namespace cp2i {
     if (s__ != CP2_OK) return s__;    \
   } while (0)
 
+// host threads for slot-file reads outside the ingestion pipe (on_threads, workers.hpp): cp2_set_ingest's fill threads, 8 by default
+inline int fill_threads(const cp2_ctx* ctx) { return ctx->ingest_threads > 0 ? ctx->ingest_threads : 8; }
+
 // RAII device buffer.  alloc() = plain hipMalloc (long-lived: tree nodes); scratch() = from the context's
 // pool (staging / temporaries).  A pooled block goes back only after the context's stream has drained.
 struct DevBuf {

@@ -595,36 +595,27 @@ static int host_cells_global(cp2_slot_trees* t, const uint64_t* g, size_t n, uin
   if (t->src == CellSrc::File) {
     // a batch of proof inputs samples hundreds of thousands of cells (4096 slots x 100): the reads are spread over the
     // context's fill threads, each taking a contiguous range of the (slot-ordered) list and opening a slot file once per run
-    const int threads = (int)std::min<size_t>(ctx->ingest_threads > 0 ? (size_t)ctx->ingest_threads : 8, std::max<size_t>(1, n / 256));
-    std::vector<std::string> failed(threads);   // per worker: slot_file_error of the file it could not open or read
-    auto work = [&](int w) {
-      int fd = -1;
-      size_t open_slot = ~(size_t)0;
-      std::string fname;
-      for (size_t i = n * w / threads; i < n * (w + 1) / threads; ++i) {
-        size_t slot = g[i] / t->n_cells, cell = g[i] % t->n_cells;
-        if (slot != open_slot) {
-          if (fd >= 0) close(fd);
-          fname = slot_file_name(t->file_base, (t->first_slot + slot) / t->units_per_slot);
-          fd = open(fname.c_str(), O_RDONLY);
-          if (fd < 0) { failed[w] = slot_file_error(fname, 0); return; }
-          open_slot = slot;
-        }
-        const int err = read_file_cell(fd, cs, ((t->first_slot + slot) % t->units_per_slot) * t->n_cells + cell, out + i * cs);
-        if (err) { failed[w] = slot_file_error(fname, err); break; }
+    const int threads = (int)std::min<size_t>((size_t)fill_threads(ctx), std::max<size_t>(1, n / 256));
+    struct Run { int fd = -1; size_t slot = ~(size_t)0; std::string fname, failed; };   // per worker: the file it has open, and slot_file_error of the one it could not open or read
+    std::vector<Run> runs(threads);
+    on_threads(threads, n, [&](int w, size_t i) {
+      Run& r = runs[w];
+      const size_t slot = g[i] / t->n_cells, cell = g[i] % t->n_cells;
+      if (slot != r.slot) {
+        if (r.fd >= 0) close(r.fd);
+        r.fname = slot_file_name(t->file_base, (t->first_slot + slot) / t->units_per_slot);
+        r.fd = open(r.fname.c_str(), O_RDONLY);
+        if (r.fd < 0) { r.failed = slot_file_error(r.fname, 0); return false; }
+        r.slot = slot;
       }
-      if (fd >= 0) close(fd);
-    };
-    if (threads <= 1) {
-      work(0);
-    } else {
-      Workers pool(threads - 1);
-      for (int w = 1; w < threads; ++w) pool.submit([&work, w] { work(w); });
-      work(0);
-      pool.wait_idle();
-    }
-    for (const auto& f : failed)
-      if (!f.empty()) { ctx->err = f; return CP2_ERR_IO; }
+      const int err = read_file_cell(r.fd, cs, ((t->first_slot + slot) % t->units_per_slot) * t->n_cells + cell, out + i * cs);
+      if (err) r.failed = slot_file_error(r.fname, err);
+      return !err;
+    });
+    for (const Run& r : runs)
+      if (r.fd >= 0) close(r.fd);
+    for (const Run& r : runs)
+      if (!r.failed.empty()) { ctx->err = r.failed; return CP2_ERR_IO; }
     return CP2_OK;
   }
   if (t->src == CellSrc::Dev) {   // cell sizes the row gather cannot take: plain copies
@@ -637,159 +628,10 @@ static int host_cells_global(cp2_slot_trees* t, const uint64_t* g, size_t n, uin
   return CP2_ERR_INVALID;
 }
 
-
-// generateProofInput (gen_input/bn254.nim:53-74) on a COMPACT dataset, for `n` slots in one pass: the top of every path -- block
-// root to slot root -- is gathered from the stored layers; the bottom -- cell to block root (merkleProof on the block's tree,
-// blocks/bn254.nim:60-67) -- comes from the trees of the touched blocks (at most nSamples per slot), rebuilt here from the blocks'
-// own cells (regenerated, or read from the slot files) as ONE batch of one-block "slots" and checked against the stored block
-// roots.  One sampling launch, one generator launch, one hash + layer pass and two gathers for all n slots (a node that proves
-// every slot it holds each period: 4096 slots cost one pass over 26 GB of touched blocks, not 4096 latency-bound little ones).
-// The caller chunks n so that the blocks fit the scratch; entropy canonical.
-static int compact_proof_inputs(cp2_dataset* ds, const uint64_t* slots, size_t n, const uint8_t entropy[32], cp2_proof_input** out) {
-  cp2_ctx* ctx = ds->ctx;
-  const cp2_config& c = ds->cfg;
-  const size_t ns = c.n_samples, md = (size_t)c.max_depth, cs = c.cell_size, cpb = c.block_size / c.cell_size, nblocks = c.n_cells / cpb;
-  const size_t depth_b = layer_sizes_of(cpb).size() - 1, depth_t = ds->csizes.size() - 1;
-  if (depth_b + depth_t > md) return CP2_ERR_INVALID;                                   // padMerkleProof assert, types.nim:29
-  CP2_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t total = n * ns;                                                          // (slot, counter) pairs = touched blocks
-  std::vector<uint64_t> idx(total);
-  if (total) {                                                                          // cellIndices, sample/bn254.nim:16-27, for all pairs at once
-    std::vector<uint8_t> felts(total * 96, 0), dig(total * 32);
-    for (size_t i = 0; i < n; ++i)
-      for (size_t k = 0; k < ns; ++k) {
-        uint8_t* f = &felts[(i * ns + k) * 96];
-        std::memcpy(f, entropy, 32);
-        std::memcpy(f + 32, &ds->dlayers[slots[i] * 32], 32);                           // the slot root: layer 0 of the dataset tree
-        const uint64_t counter = k + 1;
-        std::memcpy(f + 64, &counter, 8);
-      }
-    CP2_TRY(cp2_sponge2_felts_batch(ctx, felts.data(), 3, total, dig.data()));
-    for (size_t p = 0; p < total; ++p) {
-      uint64_t lo;
-      std::memcpy(&lo, &dig[32 * p], 8);                                                // extractLowBits, types/bn254.nim:47-59
-      idx[p] = lo & (c.n_cells - 1);
-    }
-  }
-  std::vector<uint8_t> paths(total * md * 32, 0), leaves(total * 32), cells(total * cs);
-  if (total) {
-    // the cells of the touched blocks, block after block, in device scratch
-    const size_t n_bc = total * cpb;
-    DevBuf d_cells, d_list, d_rows, d_got;
-    CP2_TRY(d_cells.scratch(ctx, n_bc * cs));
-    std::vector<uint8_t> h_blocks;                                                       // SlotFile: read on the host first
-    if (ds->from_file) {
-      h_blocks.resize(n_bc * cs);
-      for (size_t i = 0; i < n; ++i) {
-        const std::string fname = slot_file_name(ds->file_base, slots[i]);
-        const int fd = open(fname.c_str(), O_RDONLY);
-        if (fd < 0) { ctx->err = slot_file_error(fname, 0); return CP2_ERR_IO; }
-        int err = 0;
-        for (size_t k = 0; k < ns && !err; ++k)
-          for (size_t j = 0; j < cpb && !err; ++j) err = read_file_cell(fd, cs, (idx[i * ns + k] / cpb) * cpb + j, &h_blocks[((i * ns + k) * cpb + j) * cs]);
-        close(fd);
-        if (err) { ctx->err = slot_file_error(fname, err); return CP2_ERR_IO; }   // (before the block roots are checked: the read failed, not the data)
-      }
-      CP2_HIP(ctx, hipMemcpyAsync(d_cells.p, h_blocks.data(), h_blocks.size(), hipMemcpyHostToDevice, ctx->stream));
-    } else {
-      // the generator's list form over "global cells" of the local slots: g = local slot * nCells + cell, seed of local slot 0
-      std::vector<uint64_t> list(n_bc);
-      for (size_t i = 0; i < n; ++i)
-        for (size_t k = 0; k < ns; ++k)
-          for (size_t j = 0; j < cpb; ++j)
-            list[(i * ns + k) * cpb + j] = (slots[i] - ds->first_slot) * c.n_cells + (idx[i * ns + k] / cpb) * cpb + j;
-      CP2_TRY(d_list.scratch(ctx, n_bc * 8));
-      CP2_HIP(ctx, hipMemcpyAsync(d_list.p, list.data(), n_bc * 8, hipMemcpyHostToDevice, ctx->stream));
-      CP2_HIP(ctx, cp2k::launch_gen_fake_cells(cp2_slot_seed(c.seed, ds->first_slot), c.n_cells, 0, static_cast<const uint64_t*>(d_list.p), n_bc, cs,
-                                               d_cells.p, ctx->stream));
-      CP2_HIP(ctx, hipStreamSynchronize(ctx->stream));                                   // `list` leaves scope below
-    }
-    // one-block "slots": hash the cells, build the block trees (the singleton layer on top of each is not used)
-    cp2_slot_trees* mini = nullptr;
-    CP2_TRY(cp2_slot_trees_build_dev(ctx, d_cells.p, total, cs, c.block_size, cpb, &mini));
-    struct Mini { cp2_slot_trees* t; ~Mini() { cp2_slot_trees_free(t); } } mini_guard{mini};
-    // rows to gather: per pair the depth_b siblings inside its block, its leaf, the rebuilt block root (from `mini`), then the
-    // depth_t siblings above the block and the stored block root (from the compact layers)
-    const size_t per_m = depth_b + 2, per_c = depth_t + 1;
-    std::vector<uint64_t> rows_m(total * per_m), rows_c(total * per_c), r(depth_b + 1);
-    for (size_t i = 0; i < n; ++i) {
-      const size_t ls = (size_t)(slots[i] - ds->first_slot);
-      for (size_t k = 0; k < ns; ++k) {
-        const size_t p = i * ns + k;
-        const uint64_t in_block = idx[p] % cpb, b = idx[p] / cpb;
-        path_rows(mini, p, in_block, depth_b + 1, r.data());                             // block layers, then the singleton's (unused) entry
-        for (size_t d = 0; d < depth_b; ++d) rows_m[p * per_m + d] = r[d];
-        rows_m[p * per_m + depth_b] = p * cpb + in_block;                                // the leaf: layer 0 of `mini`
-        rows_m[p * per_m + depth_b + 1] = mini->toff[0] + p;                             // the block root: layer 0 of its singleton tree
-        uint64_t q = b, m = nblocks;
-        for (size_t d = 0; d < depth_t; ++d) {                                           // merkleProof(bigTree, blockIdx), merkle.nim:21-42
-          const uint64_t sib = q ^ 1;
-          rows_c[p * per_c + d] = sib < m ? ds->coff[d] + ls * ds->csizes[d] + sib : NO_ROW;
-          q >>= 1;
-          m = (m + 1) >> 1;
-        }
-        rows_c[p * per_c + depth_t] = ds->coff[0] + ls * ds->csizes[0] + b;              // the stored root of the block
-      }
-    }
-    const size_t n_m = rows_m.size(), n_c = rows_c.size();
-    CP2_TRY(d_rows.scratch(ctx, (n_m + n_c) * 8));
-    CP2_TRY(d_got.scratch(ctx, (n_m + n_c) * 32));
-    uint64_t* dr = static_cast<uint64_t*>(d_rows.p);
-    CP2_HIP(ctx, hipMemcpyAsync(dr, rows_m.data(), n_m * 8, hipMemcpyHostToDevice, ctx->stream));
-    CP2_HIP(ctx, hipMemcpyAsync(dr + n_m, rows_c.data(), n_c * 8, hipMemcpyHostToDevice, ctx->stream));
-    CP2_HIP(ctx, cp2k::launch_gather_rows(mini->nodes.p, dr, n_m, 32, d_got.p, ctx->stream));
-    CP2_HIP(ctx, cp2k::launch_gather_rows(ds->compact.p, dr + n_m, n_c, 32, d_got.u8() + n_m * 32, ctx->stream));
-    std::vector<uint8_t> got((n_m + n_c) * 32);
-    CP2_HIP(ctx, hipMemcpyAsync(got.data(), d_got.p, got.size(), hipMemcpyDeviceToHost, ctx->stream));
-    // the sampled cells themselves: one row of cellSize bytes per pair out of the block scratch (device sources), or the host copy
-    DevBuf d_sel, d_sel_rows;
-    if (!ds->from_file) {
-      if ((cs & 3) == 0) {
-        std::vector<uint64_t> sel(total);
-        for (size_t p = 0; p < total; ++p) sel[p] = p * cpb + idx[p] % cpb;
-        CP2_TRY(d_sel_rows.scratch(ctx, total * 8));
-        CP2_TRY(d_sel.scratch(ctx, total * cs));
-        CP2_HIP(ctx, hipMemcpyAsync(d_sel_rows.p, sel.data(), total * 8, hipMemcpyHostToDevice, ctx->stream));
-        CP2_HIP(ctx, cp2k::launch_gather_rows(d_cells.p, static_cast<const uint64_t*>(d_sel_rows.p), total, cs, d_sel.p, ctx->stream));
-        CP2_HIP(ctx, hipMemcpyAsync(cells.data(), d_sel.p, total * cs, hipMemcpyDeviceToHost, ctx->stream));
-        CP2_HIP(ctx, hipStreamSynchronize(ctx->stream));                                 // `sel` leaves scope
-      } else {                                                                           // cell sizes the row gather cannot take: plain copies
-        for (size_t p = 0; p < total; ++p)
-          CP2_HIP(ctx, hipMemcpyAsync(&cells[p * cs], d_cells.u8() + (p * cpb + idx[p] % cpb) * cs, cs, hipMemcpyDeviceToHost, ctx->stream));
-      }
-    }
-    CP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (size_t i = 0; i < n; ++i)
-      for (size_t k = 0; k < ns; ++k) {
-        const size_t p = i * ns + k;
-        const uint8_t* gm = &got[p * per_m * 32];
-        const uint8_t* gc = &got[(n_m + p * per_c) * 32];
-        if (std::memcmp(gm + (depth_b + 1) * 32, gc + depth_t * 32, 32) != 0) {          // the data no longer hashes to the stored block root
-          ctx->err = "block " + std::to_string(idx[p] / cpb) + " of slot " + std::to_string(slots[i]) +
-                     " does not hash to its stored root (slot data changed since the build?)";
-          return CP2_ERR_IO;
-        }
-        std::memcpy(&paths[p * md * 32], gm, depth_b * 32);
-        std::memcpy(&paths[(p * md + depth_b) * 32], gc, depth_t * 32);
-        std::memcpy(&leaves[p * 32], gm + depth_b * 32, 32);
-        if (ds->from_file) std::memcpy(&cells[p * cs], &h_blocks[(p * cpb + idx[p] % cpb) * cs], cs);
-      }
-  }
-  std::vector<uint8_t> proof;
-  for (size_t i = 0; i < n; ++i) {
-    fill_slot_proof(ds, slots[i], proof);
-    int st = cp2_proof_input_create(&c, slots[i], &ds->dlayers[ds->dlayers.size() - 32], entropy, &ds->dlayers[slots[i] * 32], proof.data(), ns,
-                                    &idx[i * ns], &cells[i * ns * cs], &paths[i * ns * md * 32], &leaves[i * ns * 32], out + i);
-    if (st != CP2_OK) {
-      for (size_t j = 0; j < i; ++j) { cp2_proof_input_free(out[j]); out[j] = nullptr; }
-      return st;
-    }
-  }
-  return CP2_OK;
-}
-
-// generateProofInput (gen_input/bn254.nim:35-79) for `n` slots of the dataset at once: one sampling launch,
-// one path gather, one cell fetch for all of them.
+// generateProofInput (gen_input/bn254.nim:35-79) for `n` slots of the dataset at once.  Every node kept: one sampling launch, one
+// path gather, one cell fetch for all of them, here.  Compact: the n slots are n requests to the pass of proof_many.cpp
+// (cp2i::prove_requests: the top of every path from the stored layers, the bottom from the touched blocks, rebuilt and checked
+// against their stored roots), in chunks whose touched blocks fit the staging chunk (CODEX_P2_STAGE_MB).  Roots only: slot by slot.
 extern "C" int cp2_proof_inputs_generate_batch(cp2_dataset* ds, const uint64_t* slot_idx, size_t n, const uint8_t entropy_in[32],
                                                cp2_proof_input** out) try {
   if (!ds || !entropy_in || (n && (!slot_idx || !out))) return CP2_ERR_INVALID;
@@ -803,21 +645,15 @@ extern "C" int cp2_proof_inputs_generate_batch(cp2_dataset* ds, const uint64_t* 
     if (slot_idx[i] < ds->first_slot || slot_idx[i] >= ds->first_slot + ds->n_local) return CP2_ERR_INVALID;
   if (!is_pow2(cfg.n_cells)) return CP2_ERR_INVALID;                    // sample/bn254.nim:19-20
   if (cfg.n_samples && cfg.n_cells < 2) return CP2_ERR_INVALID;         // extractLowBits asserts k > 0, types/bn254.nim:48
-  if (!ds->trees && ds->tree_mode == 2) {                               // compact dataset: stored upper layers + the touched blocks, slot by slot
+  if (!ds->trees && ds->tree_mode == 2) {                               // compact dataset: stored upper layers + the touched blocks
     if (!ds->have_roots) CP2_TRY(cp2_dataset_set_roots(ds, nullptr));
     if (ds->dsizes.size() - 1 > (size_t)cfg.max_log2_nslots) return CP2_ERR_INVALID;   // padMerkleProof assert
-    // as many slots per pass as keep the touched blocks within about 2 GiB of scratch (327 slots at 100 samples of 64 KiB blocks)
-    const size_t per_slot = std::max<size_t>(1, (size_t)cfg.n_samples * cfg.block_size);
-    const size_t chunk = std::max<size_t>(1, ((size_t)2 << 30) / per_slot);
-    for (size_t i0 = 0; i0 < n; i0 += chunk) {
-      const size_t m = std::min(chunk, n - i0);
-      int st = compact_proof_inputs(ds, slot_idx + i0, m, entropy, out + i0);
-      if (st != CP2_OK) {
-        for (size_t j = 0; j < i0; ++j) { cp2_proof_input_free(out[j]); out[j] = nullptr; }
-        return st;
-      }
-    }
-    return CP2_OK;
+    const size_t cpb = cfg.block_size / cfg.cell_size;
+    if (layer_sizes_of(cpb).size() - 1 + ds->csizes.size() - 1 > (size_t)cfg.max_depth) return CP2_ERR_INVALID;   // padMerkleProof assert, types.nim:29
+    std::vector<cp2_dataset*> same(n, ds);
+    std::vector<uint8_t> entropies(n * 32);
+    for (size_t i = 0; i < n; ++i) std::memcpy(&entropies[i * 32], entropy, 32);
+    return prove_requests(ctx, same.data(), slot_idx, entropies.data(), n, 0, false, out);
   }
   if (!ds->trees && n > 1) {                                            // roots-only dataset: one slot, one rebuilt tree, at a time
     for (size_t i = 0; i < n; ++i) {
@@ -889,28 +725,9 @@ extern "C" int cp2_proof_inputs_generate_batch(cp2_dataset* ds, const uint64_t* 
   }
   const uint8_t* cells = dev_cells ? store->cells.u8() : store->cells_heap.data();
   // ---- split
-  for (size_t i = 0; i < n; ++i) {
-    cp2_proof_input* p = new (std::nothrow) cp2_proof_input();
-    if (!p) {
-      for (size_t j = 0; j < i; ++j) { delete out[j]; out[j] = nullptr; }
-      return CP2_ERR_ALLOC;
-    }
-    p->cfg = cfg;
-    p->slot_idx = slot_idx[i];
-    std::memcpy(p->entropy, entropy, 32);
-    std::memcpy(p->dataset_root, &ds->dlayers[ds->dlayers.size() - 32], 32);
-    std::memcpy(p->slot_root, &ds->dlayers[slot_idx[i] * 32], 32);      // layer 0 of the dataset tree = slot roots
-    fill_slot_proof(ds, slot_idx[i], p->slot_proof);
-    p->n_samples = ns;
-    p->store = store;
-    if (total) {
-      p->indices = static_cast<const uint64_t*>(store->idx.p) + i * ns;
-      p->cell_data = cells + i * ns * cs;
-      p->paths = store->paths.u8() + i * ns * md * 32;
-      p->leaves = store->leaves.u8() + i * ns * 32;
-    }
-    out[i] = p;
-  }
+  std::vector<ProofItem> items(n);
+  for (size_t i = 0; i < n; ++i) items[i] = {ds, slot_idx[i], entropy, out + i};
+  CP2_TRY(proof_inputs_from_store(items.data(), n, store, cells));
   trace.lap("split into proof inputs");
   return CP2_OK;
 } catch (const std::bad_alloc&) {

@@ -11,12 +11,15 @@
 //      requests the touched network block.  One synchronise: the host needs the touched blocks.
 //   2. Compact requests: the touched blocks are regenerated (k_gen_fake_cells_many, one launch for every fake-source dataset) or read
 //      whole from the slot files on the context's fill threads, hashed as one batch of one-block "slots" (k_hash_cells and the layer
-//      kernels, as compact_proof_inputs does for one dataset), and each rebuilt block root is checked against its own dataset's
+//      kernels: the singleton layer on top of each is not used), and each rebuilt block root is checked against its own dataset's
 //      stored one.  The sampled cells of resident fake-source requests are regenerated in the same way (one more launch).
 //   3. k_gather_addr: one launch fetches the paths and leaves of every request, one more the sampled cells out of the rebuilt blocks.
 //   4. One download, then the cells of resident file-source requests are read on the host, and the objects are made.
 // The compact work is cut into passes whose touched blocks fit the context's staging chunk (CODEX_P2_STAGE_MB).  Requests whose
 // dataset keeps only its slot roots are proved one at a time (one slot rebuild each), as cp2_proof_inputs_generate_batch does.
+//
+// The engine behind both entry points (cp2i::prove_requests, dataset_obj.hpp) is also the compact branch of
+// cp2_proof_inputs_generate_batch (proof_input.cpp): n requests on one dataset under one entropy, error texts without the request.
 #include <hip/hip_runtime.h>
 
 #include <fcntl.h>
@@ -26,7 +29,6 @@
 #include <cstring>
 #include <map>
 #include <memory>
-#include <new>
 #include <string>
 #include <vector>
 
@@ -117,22 +119,11 @@ int prepare(cp2_ctx* ctx, cp2_dataset* const* ds, const uint64_t* slot_idx, size
   return check_roots(ctx, ds, slot_idx, n);
 }
 
-// f(w, k) for k in [0, count) on `threads` threads, worker w taking a contiguous share
-template <typename F>
-void on_threads(int threads, size_t count, F f) {
-  threads = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(threads, 1), count));
-  auto run = [&](int w) { for (size_t k = count * w / threads; k < count * (w + 1) / threads; ++k) if (!f(w, k)) break; };
-  if (threads == 1) { run(0); return; }
-  Workers pool(threads - 1);
-  for (int w = 1; w < threads; ++w) pool.submit([&run, w] { run(w); });
-  run(0);
-  pool.wait_idle();
-}
-
-int fill_threads(const cp2_ctx* ctx) { return ctx->ingest_threads > 0 ? ctx->ingest_threads : 8; }
+// what an error text of this call starts with: the *_many entry points name the request, the one-dataset calls have none to name
+std::string who(bool named, const Req* r) { return named ? "request " + std::to_string(r->id) + ": " : std::string(); }
 
 // One pass.  rq in this order: resident fake-source, resident file-source, compact fake-source, compact file-source requests.
-int run_pass(cp2_ctx* ctx, const std::vector<const Req*>& rq, size_t n_rf, size_t n_rfile, size_t n_cf, cp2_proof_input** out) {
+int run_pass(cp2_ctx* ctx, const std::vector<const Req*>& rq, size_t n_rf, size_t n_rfile, size_t n_cf, bool named, cp2_proof_input** out) {
   const size_t n = rq.size(), nr = n_rf + n_rfile;
   const cp2_config& c0 = rq[0]->ds->cfg;
   const size_t ns = c0.n_samples, md = (size_t)c0.max_depth, cs = c0.cell_size, bs = c0.block_size, cpb = bs / cs;
@@ -224,13 +215,13 @@ int run_pass(cp2_ctx* ctx, const std::vector<const Req*>& rq, size_t n_rf, size_
         const Req* r = rq[nr + q0 / ns];
         const std::string fname = slot_file_name(r->ds->file_base, r->slot);
         const int fd = open(fname.c_str(), O_RDONLY);
-        if (fd < 0) { failed[w] = "request " + std::to_string(r->id) + ": slot " + std::to_string(r->slot) + ": " + slot_file_error(fname, 0); return false; }
+        if (fd < 0) { failed[w] = who(named, r) + "slot " + std::to_string(r->slot) + ": " + slot_file_error(fname, 0); return false; }
         int err = 0;
         size_t c = 0;
         for (; c < ns && !err; ++c) err = slot_file_read_rest(fd, h_blocks.u8() + (q0 - CF + c) * bs, bs, blk[q0 + c] * bs);
         close(fd);
         if (err) {
-          failed[w] = "request " + std::to_string(r->id) + ": block " + std::to_string(blk[q0 + c - 1]) + " of slot " + std::to_string(r->slot) +
+          failed[w] = who(named, r) + "block " + std::to_string(blk[q0 + c - 1]) + " of slot " + std::to_string(r->slot) +
                       ": " + slot_file_error(fname, err);
           return false;
         }
@@ -287,7 +278,7 @@ int run_pass(cp2_ctx* ctx, const std::vector<const Req*>& rq, size_t n_rf, size_
     for (size_t q = 0; q < C; ++q)
       if (std::memcmp(&checks[2 * q * 32], &checks[(2 * q + 1) * 32], 32) != 0) {   // the data no longer hashes to the stored block root
         const Req* r = rq[nr + q / ns];
-        ctx->err = "request " + std::to_string(r->id) + ": block " + std::to_string(blk[q]) + " of slot " + std::to_string(r->slot) +
+        ctx->err = who(named, r) + "block " + std::to_string(blk[q]) + " of slot " + std::to_string(r->slot) +
                    " does not hash to its stored root (slot data changed since the build?)";
         return CP2_ERR_IO;
       }
@@ -298,12 +289,12 @@ int run_pass(cp2_ctx* ctx, const std::vector<const Req*>& rq, size_t n_rf, size_
         const Req* r = rq[n_rf + k];
         const std::string fname = slot_file_name(r->ds->file_base, r->slot);
         const int fd = open(fname.c_str(), O_RDONLY);
-        if (fd < 0) { failed[w] = "request " + std::to_string(r->id) + ": " + slot_file_error(fname, 0); return false; }
+        if (fd < 0) { failed[w] = who(named, r) + slot_file_error(fname, 0); return false; }
         int err = 0;
         const size_t p0 = (n_rf + k) * ns;
         for (size_t c = 0; c < ns && !err; ++c) err = read_file_cell(fd, cs, idx[p0 + c], store->cells.u8() + (p0 + c) * cs);
         close(fd);
-        if (err) { failed[w] = "request " + std::to_string(r->id) + ": " + slot_file_error(fname, err); return false; }
+        if (err) { failed[w] = who(named, r) + slot_file_error(fname, err); return false; }
         return true;
       });
       for (const auto& f : failed)
@@ -311,37 +302,16 @@ int run_pass(cp2_ctx* ctx, const std::vector<const Req*>& rq, size_t n_rf, size_
     }
   }
   // ---- the objects (nothing can fail on the device any more)
-  std::vector<cp2_proof_input*> made(n, nullptr);
-  for (size_t j = 0; j < n; ++j) {
-    const cp2_dataset* ds = rq[j]->ds;
-    cp2_proof_input* p = new (std::nothrow) cp2_proof_input();
-    if (!p) {
-      for (auto* q : made) delete q;
-      return CP2_ERR_ALLOC;
-    }
-    made[j] = p;
-    p->cfg = ds->cfg;
-    p->slot_idx = rq[j]->slot;
-    std::memcpy(p->entropy, rq[j]->entropy, 32);
-    std::memcpy(p->dataset_root, &ds->dlayers[ds->dlayers.size() - 32], 32);
-    std::memcpy(p->slot_root, &ds->dlayers[rq[j]->slot * 32], 32);       // layer 0 of the dataset tree = slot roots
-    fill_slot_proof(ds, rq[j]->slot, p->slot_proof);
-    p->n_samples = ns;
-    p->store = store;
-    if (T) {
-      p->indices = static_cast<const uint64_t*>(store->idx.p) + j * ns;
-      p->cell_data = store->cells.u8() + j * ns * cs;
-      p->paths = store->paths.u8() + j * ns * md * 32;
-      p->leaves = store->leaves.u8() + j * ns * 32;
-    }
-  }
-  for (size_t j = 0; j < n; ++j) out[rq[j]->at] = made[j];
-  return CP2_OK;
+  std::vector<ProofItem> items(n);
+  for (size_t j = 0; j < n; ++j) items[j] = {rq[j]->ds, rq[j]->slot, rq[j]->entropy, &out[rq[j]->at]};
+  return proof_inputs_from_store(items.data(), n, store, store->cells.u8());
 }
 
-// After prepare(): the proof inputs of requests [0, n) (arrays already offset by the caller).  All or nothing.
-int produce(cp2_ctx* ctx, cp2_dataset* const* ds, const uint64_t* slot_idx, const uint8_t* entropies, size_t n, size_t at0,
-            cp2_proof_input** out) {
+}  // namespace
+
+// The proof inputs of requests [0, n) (arrays already offset by the caller; the *_many entry points have run prepare()).  All or nothing.
+int cp2i::prove_requests(cp2_ctx* ctx, cp2_dataset* const* ds, const uint64_t* slot_idx, const uint8_t* entropies, size_t n, size_t at0,
+                         bool named, cp2_proof_input** out) {
   for (size_t i = 0; i < n; ++i) out[i] = nullptr;
   if (n == 0) return CP2_OK;
   CP2_HIP(ctx, hipSetDevice(ctx->device));
@@ -364,7 +334,7 @@ int produce(cp2_ctx* ctx, cp2_dataset* const* ds, const uint64_t* slot_idx, cons
   for (const Req* r : roots_only) {
     const int st = cp2_proof_inputs_generate_batch(r->ds, &r->slot, 1, r->entropy, &out[r->at]);
     if (st != CP2_OK) {
-      ctx->err = "request " + std::to_string(r->id) + ": " + ctx->err;
+      ctx->err = who(named, r) + ctx->err;
       return fail(st);
     }
   }
@@ -385,14 +355,12 @@ int produce(cp2_ctx* ctx, cp2_dataset* const* ds, const uint64_t* slot_idx, cons
     const size_t c1 = std::min(compact.size(), c + chunk);
     rq.insert(rq.end(), compact.begin() + (long)c, compact.begin() + (long)c1);
     const size_t n_cf = c < cmp_fake.size() ? std::min(c1, cmp_fake.size()) - c : 0;
-    const int st = run_pass(ctx, rq, first ? res_fake.size() : 0, first ? res_file.size() : 0, n_cf, out);
+    const int st = run_pass(ctx, rq, first ? res_fake.size() : 0, first ? res_file.size() : 0, n_cf, named, out);
     if (st != CP2_OK) return fail(st);
     c = c1;
   }
   return CP2_OK;
 }
-
-}  // namespace
 
 extern "C" int cp2_proof_inputs_generate_many(cp2_ctx* ctx, cp2_dataset* const* ds, const uint64_t* slot_idx, const uint8_t* entropies, size_t n,
                                               cp2_proof_input** out) try {
@@ -405,7 +373,7 @@ extern "C" int cp2_proof_inputs_generate_many(cp2_ctx* ctx, cp2_dataset* const* 
   if (n == 0) return CP2_OK;
   CP2_REFUSE_STUCK(ctx);
   CP2_TRY(prepare(ctx, ds, slot_idx, n));
-  return produce(ctx, ds, slot_idx, entropies, n, 0, out);
+  return prove_requests(ctx, ds, slot_idx, entropies, n, 0, true, out);
 } catch (const std::bad_alloc&) {
   return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
 } catch (...) {
@@ -433,7 +401,7 @@ extern "C" int cp2_proof_inputs_export_many(cp2_ctx* ctx, cp2_dataset* const* ds
   auto generate = [&](size_t b0, std::vector<cp2_proof_input*>& o) -> int {
     const size_t m = std::min(batch, n - b0);
     o.assign(m, nullptr);
-    return produce(ctx, ds + b0, slot_idx + b0, entropies + 32 * b0, m, b0, o.data());
+    return prove_requests(ctx, ds + b0, slot_idx + b0, entropies + 32 * b0, m, b0, true, o.data());
   };
   struct Release {   // whatever leaves this scope, the objects are freed
     std::vector<cp2_proof_input*>& v;

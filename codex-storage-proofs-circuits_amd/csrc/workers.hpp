@@ -4,6 +4,7 @@
 #include <sys/syscall.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <condition_variable>
 #include <deque>
 #include <functional>
@@ -74,5 +75,17 @@ class Workers {
   bool stop_ = false;
   int nice_inc_ = 0;
 };
+
+// f(w, k) for k in [0, count) on `threads` threads, worker w taking a contiguous share (and leaving it when f returns false)
+template <typename F>
+void on_threads(int threads, size_t count, F f) {
+  threads = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(threads, 1), count));
+  auto run = [&](int w) { for (size_t k = count * w / threads; k < count * (w + 1) / threads; ++k) if (!f(w, k)) break; };
+  if (threads == 1) { run(0); return; }
+  Workers pool(threads - 1);
+  for (int w = 1; w < threads; ++w) pool.submit([&run, w] { run(w); });
+  run(0);
+  pool.wait_idle();
+}
 
 }  // namespace cp2i

@@ -244,12 +244,18 @@ reqs = [(dss[i %% 4], (i * 7) %% (4, 3, 2, 2)[i %% 4], 1000 + i) for i in range(
 got = [p.json() for p in ctx.proof_inputs_many(reqs)]
 want = [ds.proof_input(s, e).json() for ds, s, e in reqs]
 total = ctx.export_proof_inputs_many(reqs, None, threads=2, batch=4)
-print(json.dumps({"same": got == want, "total_ok": total == sum(len(w) for w in want), "n": len(got)}))
+# the one-dataset batch over every slot of a compact dataset, fake source and slot files: one slot per pass as well
+# ... and equal to what the same configurations give slot by slot with every node kept
+full = [ctx.dataset(cfg(5, 4)), ctx.dataset(cfg(6, 3, base))]
+batch_same = all([p.json() for p in ds.proof_inputs(list(range(k)), 2000 + k)] == [ds.proof_input(s, 2000 + k).json() for s in range(k)] ==
+                 [f.proof_input(s, 2000 + k).json() for s in range(k)] for ds, f, k in ((dss[0], full[0], 4), (dss[1], full[1], 3)))
+print(json.dumps({"same": got == want, "total_ok": total == sum(len(w) for w in want), "n": len(got), "batch_same": batch_same}))
 """
 
 
 def test_compact_work_in_several_chunks(pkg, tmp_path):
-    """CODEX_P2_STAGE_MB=1 with 64 KiB blocks and 10 samples: one compact request per chunk."""
+    """CODEX_P2_STAGE_MB=1 with 64 KiB blocks and 10 samples: one compact request per chunk, from cp2_proof_inputs_generate_many and
+    from cp2_proof_inputs_generate_batch on one compact dataset."""
     base = str(tmp_path / "slot")
     write_slot_files(base, 3, 64, 2048, 5)
     env = {k: v for k, v in os.environ.items() if not k.startswith("CODEX_P2_") and not k.startswith("CP2_")}
@@ -258,7 +264,7 @@ def test_compact_work_in_several_chunks(pkg, tmp_path):
                        timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     res = json.loads(r.stdout.strip().splitlines()[-1])
-    assert res == {"same": True, "total_ok": True, "n": 14}
+    assert res == {"same": True, "total_ok": True, "n": 14, "batch_same": True}
 
 
 def test_scale_1024_requests_over_256_datasets(pkg, mctx):
