@@ -76,6 +76,29 @@ void verify_trace(size_t n, const uint32_t* status, size_t block_size, size_t de
 
 }  // namespace
 
+int cp2i::gather_block_proofs(cp2_ctx* ctx, const void* nodes, size_t n_rows, const std::vector<uint64_t>& rows, size_t depth, const char* outside,
+                              uint8_t* block_roots, uint8_t* paths) {
+  for (uint64_t r : rows)
+    if (r != BLOCK_PROOF_NO_ROW && r >= n_rows) {
+      ctx->err = outside;
+      return CP2_ERR_INVALID;
+    }
+  const size_t per = depth + 1, n = rows.size() / per;
+  DevBuf d_rows, d_out;
+  CP2_TRY(d_rows.scratch(ctx, rows.size() * 8));
+  CP2_TRY(d_out.scratch(ctx, rows.size() * 32));
+  std::vector<uint8_t> out(rows.size() * 32);
+  CP2_HIP(ctx, hipMemcpyAsync(d_rows.p, rows.data(), rows.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+  CP2_HIP(ctx, cp2k::launch_gather_rows(nodes, static_cast<const uint64_t*>(d_rows.p), rows.size(), 32, d_out.p, ctx->stream));
+  CP2_HIP(ctx, hipMemcpyAsync(out.data(), d_out.p, out.size(), hipMemcpyDeviceToHost, ctx->stream));
+  CP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (size_t i = 0; i < n; ++i) {
+    if (block_roots) std::memcpy(block_roots + i * 32, &out[i * per * 32], 32);
+    if (paths) std::memcpy(paths + i * depth * 32, &out[(i * per + 1) * 32], depth * 32);
+  }
+  return CP2_OK;
+}
+
 extern "C" size_t cp2_block_proof_depth(size_t cell_size, size_t block_size, size_t n_cells) {
   if (trees_check_geometry(cell_size, block_size, n_cells, 1) != CP2_OK) return 0;
   return block_proof_depth(n_cells / (block_size / cell_size));
@@ -118,24 +141,7 @@ extern "C" int cp2_dataset_block_proofs(cp2_dataset* ds, const uint64_t* slot_bl
     rows[i * per] = repair_dataset_row(ds, s, b);
     block_proof_rows(offs, sizes, s - ds->first_slot, b, depth, &rows[i * per + 1]);
   }
-  for (uint64_t r : rows)
-    if (r != BLOCK_PROOF_NO_ROW && r >= k.rows) {
-      ctx->err = "block proofs: a row lies outside the kept nodes";
-      return CP2_ERR_INVALID;
-    }
-  DevBuf d_rows, d_out;
-  CP2_TRY(d_rows.scratch(ctx, rows.size() * 8));
-  CP2_TRY(d_out.scratch(ctx, rows.size() * 32));
-  std::vector<uint8_t> out(rows.size() * 32);
-  CP2_HIP(ctx, hipMemcpyAsync(d_rows.p, rows.data(), rows.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-  CP2_HIP(ctx, cp2k::launch_gather_rows(k.nodes, static_cast<const uint64_t*>(d_rows.p), rows.size(), 32, d_out.p, ctx->stream));
-  CP2_HIP(ctx, hipMemcpyAsync(out.data(), d_out.p, out.size(), hipMemcpyDeviceToHost, ctx->stream));
-  CP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  for (size_t i = 0; i < n; ++i) {
-    if (block_roots) std::memcpy(block_roots + i * 32, &out[i * per * 32], 32);
-    std::memcpy(paths + i * depth * 32, &out[(i * per + 1) * 32], depth * 32);
-  }
-  return CP2_OK;
+  return gather_block_proofs(ctx, k.nodes, k.rows, rows, depth, "block proofs: a row lies outside the kept nodes", block_roots, paths);
 } catch (const std::bad_alloc&) {
   return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
 } catch (...) {

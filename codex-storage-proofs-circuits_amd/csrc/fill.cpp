@@ -16,7 +16,10 @@
 // bitmap and layer 0 under a checksum, fill_checkpoint.hpp) and resumed by a later process (cp2_fill_resume).  Resume trusts the disk only as
 // far as the device has re-checked it: every block the checkpoint calls present is read back (or, fake source, regenerated), hashed and
 // reduced to its block root by the builders' kernels on repair's data path, and k_block_root_recheck compares that root with the row of
-// layer 0 the checkpoint kept, zeroing the row where they differ; the host clears those blocks' bits, and they are missing again.
+// layer 0 the checkpoint kept, zeroing the row where they differ; the host clears those blocks' bits, and they are missing again.  That is
+// one judge for repair_check_with and two sources: slot files go through the host-side readers of fill_checkpoint.hpp
+// (fill_slot_files_cover: what each file holds; fill_read_chunk: a chunk of the read plan into a host buffer), the fake source through
+// the judge's `cells` hook (repair.hpp), which generates a chunk's cells on the device where a candidate chunk would be uploaded.
 //
 // A session that is still filling can vouch for the blocks it holds.  A path that ends in the stated slot root proves every node on it, and
 // the compact buffer has a row for each, unused until finish.  After cp2_fill_keep_nodes every add ends in k_block_path_commit_nodes, which
@@ -28,10 +31,10 @@
 // cp2_fill_add_anchored is cp2_fill_add with packed paths of those lengths, ending in k_block_path_commit_anchored, which compares each
 // walk's result with the kept row instead of the slot root.  With the lowest anchors throughout a slot takes nBlocks - 1 siblings in all.
 //
-// The same argument lets a session take blocks from its own disk.  cp2_fill_adopt reads the absent blocks the slot files cover (the
-// re-check's reads and data path), keeps their fresh block roots in a buffer of the session's own, builds the tree above them with the
-// kept nodes wherever there are any (k_adopt_layer, one launch per layer) and keeps every subtree whose computed root equals a node the
-// session knows, the stated slot root included (k_adopt_resolve); adopt_plan.hpp holds the host side.
+// The same argument lets a session take blocks from its own disk.  cp2_fill_adopt reads the absent blocks the slot files cover (with
+// fill_slot_files_cover and fill_read_chunk, then repair_check_with), keeps their fresh block roots in a buffer of the session's own,
+// builds the tree above them with the kept nodes wherever there are any (k_adopt_layer, one launch per layer) and keeps every subtree
+// whose computed root equals a node the session knows, the stated slot root included (k_adopt_resolve); adopt_plan.hpp holds the host side.
 //
 // A checkpoint can carry the kept nodes too (cp2_fill_save_nodes, format CP2FILL2, node_ckpt_plan.hpp).  cp2_fill_resume_nodes is
 // cp2_fill_resume and cp2_fill_keep_nodes, after which the rows the file calls known are candidates in a buffer of their own: top-down, one
@@ -95,15 +98,6 @@ namespace {
 
 cp2_fill_session* session(void* f) { return static_cast<cp2_fill_session*>(f); }
 const cp2_fill_session* session(const void* f) { return static_cast<const cp2_fill_session*>(f); }
-
-bool file_has_magic(const char* path, const char* magic8) {
-  char m[8] = {};
-  const int fd = open(path, O_RDONLY | O_CLOEXEC);
-  if (fd < 0) return false;
-  const bool ok = pread(fd, m, 8, 0) == 8 && std::memcmp(m, magic8, 8) == 0;
-  close(fd);
-  return ok;
-}
 
 // the kept form of the session's layers, under the name and with the contents cp2_dataset_build_cached writes for a compact dataset: a
 // tree cache at the path stays, the kept form goes beside it
@@ -449,8 +443,10 @@ int write_checkpoint_file(cp2_ctx* ctx, const char* path, const std::vector<uint
   return CP2_OK;
 }
 
-// the whole checkpoint file in memory, its size checked against what its header states before the buffer is sized
-int read_checkpoint(cp2_ctx* ctx, const char* path, FillCheckpoint* ck) {
+// A checkpoint file of either format in memory.  Its fixed head is read first and head_ok(fixed, size, &why) compares what it announces with
+// the file's size before the buffer is sized; the whole file then goes to parse(buf, size, &why).
+template <class HeadOk, class Parse>
+int read_checkpoint_file(cp2_ctx* ctx, const char* path, HeadOk head_ok, Parse parse) {
   const std::string name(path);
   const int fd = open(path, O_RDONLY | O_CLOEXEC);
   if (fd < 0) {
@@ -466,125 +462,109 @@ int read_checkpoint(cp2_ctx* ctx, const char* path, FillCheckpoint* ck) {
   const size_t size = (size_t)sb.st_size;
   uint8_t fixed[FILL_CKPT_FIXED] = {};
   std::string why;
-  FillCkptMeta m;
-  FillCkptLayout l;
-  const size_t head = std::min(size, sizeof fixed);
-  const int eh = head ? slot_file_read_rest(fd, fixed, head, 0) : 0;
-  if (eh) {
-    ctx->err = "fill: cannot read checkpoint " + name + ": " + std::strerror(eh);
-    return CP2_ERR_IO;
-  }
-  bool ok = fill_ckpt_fixed(fixed, size, &m, &l, &why);
-  if (ok && size != l.size) {
-    why = size < l.size ? "is truncated: " + std::to_string(size) + " bytes of " + std::to_string(l.size) : "is corrupt: longer than its header states";
-    ok = false;
-  }
-  if (!ok) {
-    ctx->err = "fill: checkpoint " + name + " " + why;
-    return CP2_ERR_IO;
-  }
-  std::vector<uint8_t> buf(size);
-  const int e = slot_file_read_rest(fd, buf.data(), size, 0);
+  int e = size ? slot_file_read_rest(fd, fixed, std::min(size, sizeof fixed), 0) : 0;
+  const bool ok = !e && head_ok(fixed, size, &why);
+  std::vector<uint8_t> buf(ok ? size : 0);
+  if (ok) e = slot_file_read_rest(fd, buf.data(), size, 0);
   if (e) {
     ctx->err = "fill: cannot read checkpoint " + name + ": " + std::strerror(e);
     return CP2_ERR_IO;
   }
-  if (!fill_ckpt_parse(buf.data(), size, ck, &why)) {
+  if (!ok || !parse(buf.data(), size, &why)) {
     ctx->err = "fill: checkpoint " + name + " " + why;
     return CP2_ERR_IO;
   }
   return CP2_OK;
 }
 
-// The blocks of plan entries [i0, i0 + m) of a fake-source session regenerated on the device and reduced to their block roots as
-// repair_check_with reduces candidate blocks (cells hashed, one tree segment per block), verdicts by k_block_root_recheck.  Everything is
-// queued on the context's stream; d_seeds / d_firsts / d_dest hold the whole plan.
-int recheck_fake_chunk(cp2_fill_session* f, size_t i0, size_t m, const uint64_t* d_seeds, const uint64_t* d_firsts, const uint64_t* d_dest,
-                       DevBuf& d_cells, DevBuf& d_nodes, uint32_t* d_verdict, size_t below_root) {
-  cp2_ctx* ctx = f->ctx;
-  const cp2_config& c = f->cfg;
-  const size_t cpb = c.block_size / c.cell_size;
-  CP2_HIP(ctx, cp2k::launch_gen_fake_cells_many(d_seeds + i0, d_firsts + i0, cpb, m * cpb, c.cell_size, d_cells.p, ctx->stream));
-  CP2_HIP(ctx, cp2k::launch_hash_cells(d_cells.p, c.cell_size, m * cpb, d_nodes.p, ctx->stream));
-  CP2_TRY(merkle_trees_dev(ctx, d_nodes.p, cpb, m, d_nodes.p, true));
-  CP2_HIP(ctx, cp2k::launch_block_root_recheck(d_nodes.u8() + below_root * m * 32, d_dest + i0, m, d_verdict + i0, f->compact.p, f->plan.total(), ctx->stream));
-  return CP2_OK;
+// a CP2FILL1 file: of exactly the size its header states
+int read_checkpoint(cp2_ctx* ctx, const char* path, FillCheckpoint* ck) {
+  return read_checkpoint_file(
+      ctx, path,
+      [](const uint8_t* fixed, size_t size, std::string* why) {
+        FillCkptMeta m;
+        FillCkptLayout l;
+        if (!fill_ckpt_fixed(fixed, size, &m, &l, why)) return false;
+        if (size != l.size)
+          *why = size < l.size ? "is truncated: " + std::to_string(size) + " bytes of " + std::to_string(l.size) : "is corrupt: longer than its header states";
+        return size == l.size;
+      },
+      [&](const uint8_t* buf, size_t size, std::string* why) { return fill_ckpt_parse(buf, size, ck, why); });
+}
+
+// the same for a CP2FILL2 file, whose header bounds its size
+int read_node_checkpoint(cp2_ctx* ctx, const char* path, NodeCheckpoint* ck) {
+  return read_checkpoint_file(
+      ctx, path,
+      [](const uint8_t* fixed, size_t size, std::string* why) {
+        FillCkptMeta m;
+        NodeCkptLayout l;
+        return node_ckpt_fixed(fixed, size, &m, &l, why) && node_ckpt_size_ok(l, size, why);
+      },
+      [&](const uint8_t* buf, size_t size, std::string* why) { return node_ckpt_parse(buf, size, ck, why); });
 }
 
 // Every block the session calls present against what its source holds now; the global indices of those that no longer hash to their kept
-// root are appended to `dropped` (their rows of layer 0 are zeros by then).  *bytes = what was read or regenerated.
+// root are appended to `dropped` (their rows of layer 0 are zeros by then).  *bytes = what was read or regenerated.  One judge on repair's
+// data path (repair_check_with) and two sources of the blocks: the fake source regenerates them on the device (the `cells` hook), slot
+// files are read chunk by chunk (fill_read_chunk) and uploaded.
 int recheck_present(cp2_fill_session* f, std::vector<uint64_t>* dropped, uint64_t* n_read, double* bytes) {
   cp2_ctx* ctx = f->ctx;
   const cp2_config& c = f->cfg;
   const FillPlan& plan = f->plan;
   const size_t bs = c.block_size, cpb = bs / c.cell_size;
-  const size_t chunk = std::max<size_t>(1, (ctx->stage_bytes / 2) / bs);          // repair_check_with's chunks
+  // the same expression as repair_check_with's chunks: a chunk of the read plan is a chunk of the data path, in one call over all entries
+  // (fake source) as in one call per chunk (slot files)
+  const size_t chunk = std::max<size_t>(1, (ctx->stage_bytes / 2) / bs);
   const FillReadPlan rp = fill_read_plan(plan.bits, plan.total(), plan.n_blocks, chunk);
   const size_t n = rp.g.size();
   *n_read = n;
   *bytes = (double)n * (double)bs;
   if (n == 0) return CP2_OK;
   std::vector<uint32_t> verdict(n);
+  std::vector<uint64_t> seeds, firsts;
+  DevBuf d_dest, d_seeds, d_firsts;                  // (go after the streams have drained: DevBuf::release)
+  size_t at = 0;                                     // the plan entry that is request 0 of the current call
+  RepairJudge judge;
+  judge.begin = [&](size_t) -> int {                 // the destination rows of the whole plan, once, whatever the number of calls
+    if (d_dest.p) return CP2_OK;
+    CP2_TRY(d_dest.scratch(ctx, n * 8));
+    CP2_HIP(ctx, hipMemcpyAsync(d_dest.p, rp.g.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));   // (coff[0] == 0: a global index is its row)
+    if (f->from_file) return CP2_OK;
+    CP2_TRY(d_seeds.scratch(ctx, n * 8));
+    CP2_TRY(d_firsts.scratch(ctx, n * 8));
+    CP2_HIP(ctx, hipMemcpyAsync(d_seeds.p, seeds.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
+    CP2_HIP(ctx, hipMemcpyAsync(d_firsts.p, firsts.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
+    return CP2_OK;
+  };
+  judge.verdicts = [&](const uint8_t* fresh, size_t c0, size_t m, uint32_t* v, hipStream_t st) -> int {
+    CP2_HIP(ctx, cp2k::launch_block_root_recheck(fresh, static_cast<const uint64_t*>(d_dest.p) + at + c0, m, v, f->compact.p, plan.total(), st));
+    return CP2_OK;
+  };
   if (!f->from_file) {
-    std::vector<uint64_t> seeds(n), firsts(n);
+    seeds.resize(n);
+    firsts.resize(n);
     for (size_t i = 0; i < n; ++i) {
       seeds[i] = cp2_slot_seed(c.seed, plan.first_slot + rp.g[i] / plan.n_blocks);
       firsts[i] = (rp.g[i] % plan.n_blocks) * cpb;
     }
-    const std::vector<size_t> sizes = layer_sizes_of(cpb);
-    size_t below_root = 0, per_block = 0;
-    for (size_t j = 0; j < sizes.size(); ++j) {
-      per_block += sizes[j];
-      if (j + 1 < sizes.size()) below_root += sizes[j];
-    }
-    const size_t most = std::min(n, chunk);
-    DevBuf d_seeds, d_firsts, d_dest, d_verdict, d_cells, d_nodes;     // (go after the streams have drained: DevBuf::release)
-    CP2_TRY(d_seeds.scratch(ctx, n * 8));
-    CP2_TRY(d_firsts.scratch(ctx, n * 8));
-    CP2_TRY(d_dest.scratch(ctx, n * 8));
-    CP2_TRY(d_verdict.scratch(ctx, n * 4));
-    CP2_TRY(d_cells.scratch(ctx, most * bs));
-    CP2_TRY(d_nodes.scratch(ctx, most * per_block * 32));
-    CP2_HIP(ctx, hipMemcpyAsync(d_seeds.p, seeds.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
-    CP2_HIP(ctx, hipMemcpyAsync(d_firsts.p, firsts.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
-    CP2_HIP(ctx, hipMemcpyAsync(d_dest.p, rp.g.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));   // (coff[0] == 0: a global index is its row)
-    for (size_t k = 0; k < rp.n_chunks(); ++k)
-      CP2_TRY(recheck_fake_chunk(f, rp.chunk_begin(k), rp.chunk_end(k) - rp.chunk_begin(k), static_cast<const uint64_t*>(d_seeds.p),
-                                 static_cast<const uint64_t*>(d_firsts.p), static_cast<const uint64_t*>(d_dest.p), d_cells, d_nodes,
-                                 static_cast<uint32_t*>(d_verdict.p), below_root));
-    CP2_HIP(ctx, hipMemcpyAsync(verdict.data(), d_verdict.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) {
-      (void)hipGetLastError();
-      ctx->err = "fill: the re-check failed on the device";
-      return CP2_ERR_HIP;
-    }
+    judge.cells = [&](size_t c0, size_t m, uint8_t* d_cells, hipStream_t st) -> int {
+      CP2_HIP(ctx, cp2k::launch_gen_fake_cells_many(static_cast<const uint64_t*>(d_seeds.p) + c0, static_cast<const uint64_t*>(d_firsts.p) + c0, cpb,
+                                                    m * cpb, c.cell_size, d_cells, st));
+      return CP2_OK;
+    };
+    CP2_TRY(repair_check_with(ctx, c.cell_size, bs, nullptr, n, verdict.data(), judge));
   } else {
-    // slot files: a chunk's blocks read file by file in ascending offset order into one host buffer, then repair's data path, unchanged
     std::unique_ptr<uint8_t[]> host(new uint8_t[std::min(n, chunk) * bs]);
-    DevBuf d_dest;
     for (size_t k = 0; k < rp.n_chunks(); ++k) {
-      const size_t i0 = rp.chunk_begin(k), m = rp.chunk_end(k) - i0;
-      for (const FillReadPlan::Run& run : rp.runs(k)) {
-        const std::string fname = slot_file_name(f->file_base, plan.first_slot + run.local);
-        const int fd = open(fname.c_str(), O_RDONLY | O_CLOEXEC);
-        if (fd < 0) { ctx->err = slot_file_error(fname, 0); return CP2_ERR_IO; }
-        int err = 0;
-        for (size_t i = run.i0; i < run.i1 && !err; ++i)
-          err = slot_file_read_rest(fd, host.get() + (i - i0) * bs, bs, (rp.g[i] % plan.n_blocks) * bs);
-        close(fd);
-        if (err) { ctx->err = slot_file_error(fname, err); return CP2_ERR_IO; }   // a read that fails is an error, never a dropped block
+      std::string bad;
+      int err = 0;
+      if (!fill_read_chunk(rp, k, f->file_base, plan.first_slot, bs, host.get(), &bad, &err)) {
+        ctx->err = slot_file_error(bad, err);
+        return CP2_ERR_IO;
       }
-      RepairJudge judge;
-      judge.begin = [&](size_t) -> int {
-        CP2_TRY(d_dest.scratch(ctx, m * 8));
-        CP2_HIP(ctx, hipMemcpyAsync(d_dest.p, rp.g.data() + i0, m * 8, hipMemcpyHostToDevice, ctx->stream));
-        return CP2_OK;
-      };
-      judge.verdicts = [&](const uint8_t* fresh, size_t c0, size_t mm, uint32_t* v, hipStream_t st) -> int {
-        CP2_HIP(ctx, cp2k::launch_block_root_recheck(fresh, static_cast<const uint64_t*>(d_dest.p) + c0, mm, v, f->compact.p, plan.total(), st));
-        return CP2_OK;
-      };
-      CP2_TRY(repair_check_with(ctx, c.cell_size, bs, host.get(), m, verdict.data() + i0, judge));
+      at = rp.chunk_begin(k);
+      CP2_TRY(repair_check_with(ctx, c.cell_size, bs, host.get(), rp.chunk_end(k) - at, verdict.data() + at, judge));
     }
   }
   for (size_t i = 0; i < n; ++i)
@@ -652,15 +632,11 @@ static int resume_checked(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_sl
   std::vector<uint64_t>& dropped = *dropped_out;
   dropped.clear();
   if (recheck && cfg->file_base) {
-    std::vector<uint64_t> whole(n_local, 0);
-    for (uint64_t s = 0; s < n_local; ++s) {
-      const std::string fname = slot_file_name(want.file_base, first_slot + s);
-      struct stat sb;
-      if (stat(fname.c_str(), &sb) == 0) whole[s] = (uint64_t)sb.st_size / cfg->block_size;
-      else if (errno != ENOENT && errno != ENOTDIR) {
-        ctx->err = slot_file_error(fname, 0);
-        return CP2_ERR_IO;
-      }
+    std::vector<uint64_t> whole;
+    std::string bad;
+    if (!fill_slot_files_cover(want.file_base, first_slot, n_local, cfg->block_size, &whole, &bad)) {
+      ctx->err = slot_file_error(bad, 0);
+      return CP2_ERR_IO;
     }
     fill_ckpt_drop_short(whole, n_blocks, &ck.bits, &ck.layer0, &dropped);
   }
@@ -818,23 +794,7 @@ extern "C" int cp2_fill_block_proofs(void* fill, const uint64_t* slot_block, siz
       rows[i * per] = plan.dest_row(s, b);
       block_proof_rows(plan.coff, plan.csizes, s - plan.first_slot, b, depth, &rows[i * per + 1]);
     }
-    for (uint64_t r : rows)
-      if (r != BLOCK_PROOF_NO_ROW && r >= plan.rows) {
-        ctx->err = "fill proofs: a row lies outside the session's buffer";
-        return CP2_ERR_INVALID;
-      }
-    DevBuf d_rows, d_out;
-    CP2_TRY(d_rows.scratch(ctx, rows.size() * 8));
-    CP2_TRY(d_out.scratch(ctx, rows.size() * 32));
-    std::vector<uint8_t> out(rows.size() * 32);
-    CP2_HIP(ctx, hipMemcpyAsync(d_rows.p, rows.data(), rows.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    CP2_HIP(ctx, cp2k::launch_gather_rows(f->compact.p, static_cast<const uint64_t*>(d_rows.p), rows.size(), 32, d_out.p, ctx->stream));
-    CP2_HIP(ctx, hipMemcpyAsync(out.data(), d_out.p, out.size(), hipMemcpyDeviceToHost, ctx->stream));
-    CP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (size_t i = 0; i < n; ++i) {
-      if (block_roots) std::memcpy(block_roots + i * 32, &out[i * per * 32], 32);
-      if (paths) std::memcpy(paths + i * depth * 32, &out[(i * per + 1) * 32], depth * 32);
-    }
+    CP2_TRY(gather_block_proofs(ctx, f->compact.p, plan.rows, rows, depth, "fill proofs: a row lies outside the session's buffer", block_roots, paths));
   }
   std::copy(st.begin(), st.end(), status);
   if (std::getenv("CP2_TRACE"))
@@ -906,23 +866,19 @@ extern "C" int cp2_fill_add_anchored(void* fill, const uint64_t* slot_block, con
 // ---- adopting blocks from disk ------------------------------------------------------------------------------------------------------------
 namespace {
 
-// The absent blocks of local slots [s0, s0 + ns) that their files cover, read and reduced to their block roots as recheck_present reads
-// and reduces the present ones; the roots land in `fresh` (one row per block of the read plan, in its order).  Nothing of the session is
-// touched: the caller takes the roots over once every read has succeeded.
+// The absent blocks of local slots [s0, s0 + ns) that their files cover (fill_slot_files_cover), read with the re-check's reader
+// (fill_read_chunk) and reduced to their block roots on repair's data path; the roots land in `fresh` (one row per block of the read plan,
+// in its order).  Nothing of the session is touched: the caller takes the roots over once every read has succeeded.
 int adopt_read(cp2_fill_session* f, uint64_t s0, uint64_t ns, std::vector<uint64_t>* read_bits, FillReadPlan* rp, DevBuf* fresh) {
   cp2_ctx* ctx = f->ctx;
   const cp2_config& c = f->cfg;
   const FillPlan& plan = f->plan;
   const size_t bs = c.block_size;
-  std::vector<uint64_t> whole((size_t)ns, 0);
-  for (uint64_t i = 0; i < ns; ++i) {
-    const std::string fname = slot_file_name(f->file_base, plan.first_slot + s0 + i);
-    struct stat sb;
-    if (stat(fname.c_str(), &sb) == 0) whole[(size_t)i] = (uint64_t)sb.st_size / bs;
-    else if (errno != ENOENT && errno != ENOTDIR) {       // absence is a state, as in cp2_fill_resume; anything else is an error
-      ctx->err = slot_file_error(fname, 0);
-      return CP2_ERR_IO;
-    }
+  std::vector<uint64_t> whole;
+  std::string bad;
+  if (!fill_slot_files_cover(f->file_base, plan.first_slot + s0, ns, bs, &whole, &bad)) {   // absence is a state, as in cp2_fill_resume
+    ctx->err = slot_file_error(bad, 0);
+    return CP2_ERR_IO;
   }
   *read_bits = adopt_read_bits(plan, s0, ns, whole);
   const size_t chunk = std::max<size_t>(1, (ctx->stage_bytes / 2) / bs);          // repair_check_with's chunks
@@ -934,15 +890,10 @@ int adopt_read(cp2_fill_session* f, uint64_t s0, uint64_t ns, std::vector<uint64
   std::vector<uint32_t> verdict(std::min(n, chunk));
   for (size_t k = 0; k < rp->n_chunks(); ++k) {
     const size_t i0 = rp->chunk_begin(k), m = rp->chunk_end(k) - i0;
-    for (const FillReadPlan::Run& run : rp->runs(k)) {
-      const std::string fname = slot_file_name(f->file_base, plan.first_slot + run.local);
-      const int fd = open(fname.c_str(), O_RDONLY | O_CLOEXEC);
-      if (fd < 0) { ctx->err = slot_file_error(fname, 0); return CP2_ERR_IO; }
-      int err = 0;
-      for (size_t i = run.i0; i < run.i1 && !err; ++i)
-        err = slot_file_read_rest(fd, host.get() + (i - i0) * bs, bs, (rp->g[i] % plan.n_blocks) * bs);
-      close(fd);
-      if (err) { ctx->err = slot_file_error(fname, err); return CP2_ERR_IO; }
+    int err = 0;
+    if (!fill_read_chunk(*rp, k, f->file_base, plan.first_slot, bs, host.get(), &bad, &err)) {
+      ctx->err = slot_file_error(bad, err);
+      return CP2_ERR_IO;
     }
     RepairJudge judge;                                   // no verdict here: the chunk's roots are kept for the judgement of the whole tree
     judge.verdicts = [&](const uint8_t* roots, size_t c0, size_t mm, uint32_t* v, hipStream_t st) -> int {
@@ -1076,52 +1027,6 @@ extern "C" int cp2_fill_adopt(void* fill, uint64_t first_slot, uint64_t n_slots,
 }
 
 // ---- checkpoints that carry the kept nodes ----------------------------------------------------------------------------------------------------
-namespace {
-
-// the whole CP2FILL2 file in memory, its size checked against what its header allows before the buffer is sized
-int read_node_checkpoint(cp2_ctx* ctx, const char* path, NodeCheckpoint* ck) {
-  const std::string name(path);
-  const int fd = open(path, O_RDONLY | O_CLOEXEC);
-  if (fd < 0) {
-    ctx->err = "fill: cannot open checkpoint " + name + ": " + std::strerror(errno);
-    return CP2_ERR_IO;
-  }
-  struct Closer { int fd; ~Closer() { close(fd); } } closer{fd};
-  struct stat sb;
-  if (fstat(fd, &sb) != 0) {
-    ctx->err = "fill: cannot stat checkpoint " + name + ": " + std::strerror(errno);
-    return CP2_ERR_IO;
-  }
-  const size_t size = (size_t)sb.st_size;
-  uint8_t fixed[FILL_CKPT_FIXED] = {};
-  std::string why;
-  FillCkptMeta m;
-  NodeCkptLayout l;
-  const size_t head = std::min(size, sizeof fixed);
-  const int eh = head ? slot_file_read_rest(fd, fixed, head, 0) : 0;
-  if (eh) {
-    ctx->err = "fill: cannot read checkpoint " + name + ": " + std::strerror(eh);
-    return CP2_ERR_IO;
-  }
-  if (!node_ckpt_fixed(fixed, size, &m, &l, &why) || !node_ckpt_size_ok(l, size, &why)) {
-    ctx->err = "fill: checkpoint " + name + " " + why;
-    return CP2_ERR_IO;
-  }
-  std::vector<uint8_t> buf(size);
-  const int e = slot_file_read_rest(fd, buf.data(), size, 0);
-  if (e) {
-    ctx->err = "fill: cannot read checkpoint " + name + ": " + std::strerror(e);
-    return CP2_ERR_IO;
-  }
-  if (!node_ckpt_parse(buf.data(), size, ck, &why)) {
-    ctx->err = "fill: checkpoint " + name + " " + why;
-    return CP2_ERR_IO;
-  }
-  return CP2_OK;
-}
-
-}  // namespace
-
 extern "C" int cp2_fill_save_nodes(const void* fill, const char* path) try {
   const cp2_fill_session* f = session(fill);
   if (!f || !path) return CP2_ERR_INVALID;

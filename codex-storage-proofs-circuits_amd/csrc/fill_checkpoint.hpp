@@ -1,7 +1,8 @@
 // The host side of a fill session's checkpoint (csrc/fill.cpp: cp2_fill_save / cp2_fill_resume): the file layout, writing and parsing it
 // with every size checked before anything is allocated, whether a checkpoint describes the session that is being resumed (and the first
-// field that does not), which blocks a slot file is too short to back, and the plan of the re-check's reads.  No HIP in here:
-// tests/host_check/fill_checkpoint_check.cpp walks it on the CPU, under AddressSanitizer + UBSan.
+// field that does not), which blocks a slot file is too short to back, the plan of the re-check's reads, and the two readers the re-check
+// and cp2_fill_adopt share: how many whole blocks each slot file holds, and a chunk of the plan read into a host buffer.  No HIP in here:
+// tests/host_check/fill_checkpoint_check.cpp walks it on the CPU and against real files, under AddressSanitizer + UBSan.
 //
 // The file, every integer a little-endian 64-bit word:
 //   offset 0    "CP2FILL1"
@@ -13,6 +14,11 @@
 //   then        layer 0 of the compact buffer: n_local x n_blocks rows of 32 bytes, row (local x n_blocks + block); rows of absent blocks are 0
 //   then        one word: Checksum64 (checksum64.hpp, the checksum of the kept form) over every byte before it
 #pragma once
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <cerrno>
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
@@ -20,6 +26,7 @@
 #include <vector>
 
 #include "checksum64.hpp"
+#include "fill_pipeline.hpp"   // fill_slot_file_name and the slot-file read rule: slot_file_read_rest, slot_file_error
 
 namespace cp2i {
 
@@ -168,6 +175,20 @@ inline std::string fill_ckpt_differs(const FillCkptMeta& got, const FillCkptMeta
 }
 
 // ---- what the slot files can still back ----------------------------------------------------------------------------------------------------
+// (*whole)[i]: how many whole blocks "<base><first_slot + i>.dat" holds, i < n; 0 for a file that does not exist (ENOENT, ENOTDIR): absence is
+// a state.  false: a stat failed otherwise and *bad names the file -- slot_file_error(*bad, 0) says so.
+inline bool fill_slot_files_cover(const std::string& base, uint64_t first_slot, uint64_t n, size_t block_size, std::vector<uint64_t>* whole,
+                                  std::string* bad) {
+  whole->assign((size_t)n, 0);
+  for (uint64_t i = 0; i < n; ++i) {
+    const std::string fname = fill_slot_file_name(base, first_slot + i);
+    struct stat sb;
+    if (stat(fname.c_str(), &sb) == 0) (*whole)[(size_t)i] = (uint64_t)sb.st_size / block_size;
+    else if (errno != ENOENT && errno != ENOTDIR) { *bad = fname; return false; }
+  }
+  return true;
+}
+
 // whole_blocks[local]: how many whole blocks the file of that local slot holds (size / block_size; 0 for a file that does not exist).  Every
 // present block at or past it is dropped without a read: its bit cleared, its row of layer 0 zeroed, its global index (local x n_blocks +
 // block) appended to `dropped` in ascending order.
@@ -218,6 +239,25 @@ inline FillReadPlan fill_read_plan(const std::vector<uint64_t>& bits, uint64_t t
     }
   }
   return p;
+}
+
+// Chunk k of the plan into `host` (chunk x block_size bytes; entry i of the chunk at i - chunk_begin(k)), run by run: each file
+// "<base><first_slot + local>.dat" opened once, read in ascending offset order by the slot-file read rule, and closed.  false: *bad names the
+// first file that could not be opened (*err 0) or whose read failed (*err its errno), as slot_file_error takes them; a read that fails is an
+// error, never a dropped block.
+inline bool fill_read_chunk(const FillReadPlan& rp, size_t k, const std::string& base, uint64_t first_slot, size_t block_size, uint8_t* host,
+                            std::string* bad, int* err) {
+  const size_t i0 = rp.chunk_begin(k);
+  for (const FillReadPlan::Run& run : rp.runs(k)) {
+    const std::string fname = fill_slot_file_name(base, first_slot + run.local);
+    const int fd = open(fname.c_str(), O_RDONLY | O_CLOEXEC);
+    int e = 0;
+    for (size_t i = run.i0; fd >= 0 && i < run.i1 && !e; ++i)
+      e = slot_file_read_rest(fd, host + (i - i0) * block_size, block_size, (rp.g[i] % rp.n_blocks) * block_size);
+    if (fd >= 0) close(fd);
+    if (fd < 0 || e) { *bad = fname; *err = e; return false; }
+  }
+  return true;
 }
 
 }  // namespace cp2i

@@ -271,16 +271,16 @@ extern "C" int cp2_dataset_build(cp2_ctx* ctx, const cp2_config* cfg, uint64_t f
 //   * saving never overwrites a tree cache ("CP2TREE3") with the smaller kept form: that goes to "<cache_path>.kept" beside it,
 //     and loading looks there too.
 // To pin the representation, pin the mode: cp2_set_keep_trees / CODEX_P2_KEEP_TREES.
-namespace {
-
-bool file_has_magic(const char* path, const char* magic8) {
+bool cp2i::file_has_magic(const char* path, const char* magic8) {
   char m[8] = {};
-  const int fd = open(path, O_RDONLY);
+  const int fd = open(path, O_RDONLY | O_CLOEXEC);
   if (fd < 0) return false;
   const bool ok = pread(fd, m, 8, 0) == 8 && std::memcmp(m, magic8, 8) == 0;
   close(fd);
   return ok;
 }
+
+namespace {
 
 // the kept form of `mode` (2 compact, 0 roots) from `path`: CP2_OK with *out set, CP2_ERR_IO when the file is not that, other errors as they come
 int load_kept_dataset(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local, int mode, const char* path, cp2_dataset** out) {

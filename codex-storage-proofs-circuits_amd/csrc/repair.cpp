@@ -73,13 +73,13 @@ int cp2i::repair_check_with(cp2_ctx* ctx, size_t cell_size, size_t block_size, c
   }
   // requests per chunk: half the context's staging in candidate bytes (the node buffer of a chunk holds about as much again)
   const size_t chunk = std::max<size_t>(1, std::min<size_t>(n, (ctx->stage_bytes / 2) / block_size));
-  const bool pinned = host_array_pinned(data, n * block_size, PIECE_BYTES);
+  const bool pinned = !judge.cells && host_array_pinned(data, n * block_size, PIECE_BYTES);
   DevBuf d_verdict, d_nodes, d_cells;                // (device buffers go after every stream has drained: DevBuf::release)
   if (judge.begin) CP2_TRY(judge.begin(chunk));
   CP2_TRY(d_verdict.scratch(ctx, n * 4));
   CP2_TRY(d_nodes.scratch(ctx, chunk * per_block * 32));
   const size_t last = n - (n - 1) / chunk * chunk;   // requests of the last chunk
-  if (pinned || chunk * block_size <= SMALL_BYTES || last * block_size <= SMALL_BYTES) CP2_TRY(d_cells.scratch(ctx, chunk * block_size));
+  if (judge.cells || pinned || chunk * block_size <= SMALL_BYTES || last * block_size <= SMALL_BYTES) CP2_TRY(d_cells.scratch(ctx, chunk * block_size));
   hipStream_t aux = nullptr, copy = nullptr;
   hipEvent_t ready = nullptr, up = nullptr, aux_done = nullptr;
   struct Guard {
@@ -99,7 +99,7 @@ int cp2i::repair_check_with(cp2_ctx* ctx, size_t cell_size, size_t block_size, c
   const size_t piece = std::max<size_t>(1, PIECE_BYTES / block_size) * block_size;
   for (size_t c0 = 0; c0 < n; c0 += chunk) {
     const size_t m = std::min(chunk, n - c0), bytes = m * block_size;
-    const uint8_t* src = data + c0 * block_size;
+    const uint8_t* src = data ? data + c0 * block_size : nullptr;
     if (pinned) {
       // the copy engine reads the caller's memory in place, piece by piece; each piece is hashed as soon as it has landed, the pieces
       // alternating between the context's two hashing streams.  Nothing of this chunk starts before the previous one is compared.
@@ -117,13 +117,14 @@ int cp2i::repair_check_with(cp2_ctx* ctx, size_t cell_size, size_t block_size, c
       }
       CP2_HIP(ctx, hipEventRecord(aux_done, aux));
       CP2_HIP(ctx, hipStreamWaitEvent(ctx->stream, aux_done, 0));
-    } else if (bytes > SMALL_BYTES) {
+    } else if (!judge.cells && bytes > SMALL_BYTES) {
       // large pageable chunks: the pinned ingestion ring, uploads and hashing overlapped (cp2_hash_cells' path); the ring writes the
       // leaves from both hashing streams, so the previous chunk's reads of the node buffer are waited for first
       if (c0) CP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
       CP2_TRY(hash_host_cells_pipelined(ctx, src, cell_size, m * cpb, d_nodes.u8()));
-    } else {
-      CP2_HIP(ctx, hipMemcpyAsync(d_cells.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    } else {                                         // one upload, or the caller's device-side source in its place
+      if (judge.cells) CP2_TRY(judge.cells(c0, m, d_cells.u8(), ctx->stream));
+      else CP2_HIP(ctx, hipMemcpyAsync(d_cells.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
       CP2_HIP(ctx, cp2k::launch_hash_cells(d_cells.p, cell_size, m * cpb, d_nodes.p, ctx->stream));
     }
     // what the verdicts of this chunk read beside its roots, queued behind the hashing; the block trees of the chunk (segment = block,

@@ -32,13 +32,23 @@ int repair_check(cp2_ctx* ctx, const RepairKept& k, size_t cell_size, size_t blo
 // device (queued on the context's stream).  stage (may be empty): per chunk of requests [c0, c0 + m), queued on `st` behind the chunk's hashing and before its
 // block trees: what the verdicts of that chunk read beside the roots.  verdicts: queued on `st` behind the chunk's block trees; `fresh`
 // holds the chunk's m block roots (32-byte rows, request c0 + i at row i), verdict[i] receives 0 for a match, anything else for a
-// mismatch.  Everything the callbacks allocate must outlive the call (it ends with the stream drained).
+// mismatch.  cells (may be empty): a device-side source of the candidates, in place of `data`, which may then be NULL: per chunk it queues
+// on `st` whatever fills d_cells with the m x block_size bytes of requests [c0, c0 + m); the chunk is hashed behind it on the context's
+// stream, as a small pageable chunk is behind its upload.  Everything the callbacks allocate must outlive the call (it ends with the
+// stream drained).
 struct RepairJudge {
   std::function<int(size_t chunk)> begin;
+  std::function<int(size_t c0, size_t m, uint8_t* d_cells, hipStream_t st)> cells;
   std::function<int(size_t c0, size_t m, hipStream_t st)> stage;
   std::function<int(const uint8_t* fresh, size_t c0, size_t m, uint32_t* verdict, hipStream_t st)> verdicts;
 };
 int repair_check_with(cp2_ctx* ctx, size_t cell_size, size_t block_size, const uint8_t* data, size_t n, uint32_t* status, const RepairJudge& judge);
+// Block proofs out of a device node buffer (block_proofs.cpp; cp2_dataset_block_proofs and cp2_fill_block_proofs): `rows` (host) names
+// depth + 1 rows of `nodes` per request, its block root and then its siblings bottom first, BLOCK_PROOF_NO_ROW for zeros.  A row at or past
+// n_rows: CP2_ERR_INVALID with the error text `outside`, before any device work.  Otherwise one gather and one download, split into
+// block_roots (n x 32 bytes, may be NULL) and paths (n x depth x 32 bytes, may be NULL).
+int gather_block_proofs(cp2_ctx* ctx, const void* nodes, size_t n_rows, const std::vector<uint64_t>& rows, size_t depth, const char* outside,
+                        uint8_t* block_roots, uint8_t* paths);
 // the requests whose status is CP2_REPAIR_MATCH written into "<base><slot>.dat", grouped by file in ascending offset order, each file synced
 // once.  The first file that cannot be opened, written or synced: CP2_ERR_IO, *err "cannot write <file>: <reason>", its matched requests and
 // those of every later file CP2_REPAIR_UNWRITTEN.  *n_written counts the blocks of the files written and synced, `written` their stamps.

@@ -86,6 +86,8 @@ void path_rows(const cp2_slot_trees* t, size_t slot, uint64_t cell, size_t max_d
 // merged paths (padded to max_depth, + leaf hashes) of n (slot-in-batch, cell) pairs of a batch in one gather
 int trees_paths_multi(cp2_slot_trees* t, const uint64_t* slot_idx, const uint64_t* cell_idx, size_t n, size_t max_depth, uint8_t* out, uint8_t* leaf_hashes);
 std::string slot_file_name(const std::string& base, uint64_t slot);
+// does the file at `path` start with these eight bytes?  (proof_input.cpp; false for a file that cannot be opened, too)
+bool file_has_magic(const char* path, const char* magic8);
 bool is_pow2(uint64_t x);
 
 // Persisted form of what a compact / roots-only dataset keeps (proof_input.cpp): the kept layers of `n_slots` local slots plus what

@@ -2,10 +2,18 @@
 // walked over random sessions, every answer compared with a direct restatement kept here: the layout's offsets and size, the round trip
 // (1 block per slot, bitmaps that are no multiple of 64 bits, empty and full sessions, absent rows zeroed whatever they held), every
 // truncation point and every single flipped byte of a small file refused, each differing field named, the blocks a short or missing file
-// drops, and the read plan (each present block once, ascending per file, chunks of the stated size).  Built with AddressSanitizer + UBSan.
-// No GPU.
+// drops, and the read plan (each present block once, ascending per file, chunks of the stated size).  Then the two readers the re-check and
+// cp2_fill_adopt share, against REAL slot files in a scratch directory: fill_slot_files_cover (absent, empty, whole and ragged files; a path
+// component that is a file; a name too long to stat) and fill_read_chunk (every chunk of a random plan byte for byte, into a buffer of
+// exactly a chunk; files removed, replaced by a directory or cut short after the plan was made).  Built with AddressSanitizer + UBSan.  No GPU.
+//   g++ -std=c++17 -pthread -fsanitize=address,undefined -I<csrc> fill_checkpoint_check.cpp -o check && ./check <sessions> <scratch dir>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
+#include <memory>
 #include <random>
 #include <set>
 #include <string>
@@ -65,8 +73,100 @@ static bool same_meta(const FillCkptMeta& a, const FillCkptMeta& b) {
          a.n_local == b.n_local && a.src == b.src && a.seed == b.seed && a.file_base == b.file_base && a.roots == b.roots;
 }
 
+// ---- the two readers against real files ---------------------------------------------------------------------------------------------------
+static void put_file(const std::string& name, const std::vector<uint8_t>& bytes) {
+  FILE* fh = std::fopen(name.c_str(), "wb");
+  CHECK(fh && (bytes.empty() || std::fwrite(bytes.data(), 1, bytes.size(), fh) == bytes.size()), "cannot write %s", name.c_str());
+  if (fh) std::fclose(fh);
+}
+
+static void slot_files_check(const std::string& dir, int rounds) {
+  for (int round = 0; round < rounds; ++round) {
+    const size_t bs = (size_t)pick(1, 64);
+    const uint64_t n_blocks = pick(1, 9), n_local = pick(1, 6), first = pick(0, 6), total = n_local * n_blocks;
+    const std::string base = dir + "/slot";
+    // each file: absent, empty, a whole number of blocks, or that and a partial tail
+    std::vector<std::vector<uint8_t>> bytes(n_local);
+    std::vector<bool> there(n_local);
+    std::vector<uint64_t> want(n_local), whole;
+    for (uint64_t s = 0; s < n_local; ++s) {
+      const int kind = (int)pick(0, 3);
+      there[s] = kind != 0;
+      size_t size = kind < 2 ? 0 : (size_t)pick(1, n_blocks) * bs;
+      if (kind == 3 && bs > 1) size = size - bs + (size_t)pick(1, bs - 1);       // 0 .. n_blocks - 1 whole blocks and a tail
+      bytes[s].resize(size);
+      for (auto& b : bytes[s]) b = (uint8_t)rng();
+      want[s] = size / bs;
+      if (there[s]) put_file(fill_slot_file_name(base, first + s), bytes[s]);
+    }
+    std::string bad;
+    CHECK(fill_slot_files_cover(base, first, n_local, bs, &whole, &bad) && whole == want, "round %d: the whole blocks of the files", round);
+
+    // a presence bitmap of what the files cover, every chunk byte for byte; the buffer is exactly a chunk, so an overrun is ASan's
+    std::vector<uint64_t> bits((total + 63) / 64, 0);
+    for (uint64_t g = 0; g < total; ++g)
+      if (g % n_blocks < whole[g / n_blocks] && (rng() & 1)) bits[g >> 6] |= 1ULL << (g & 63);
+    const size_t chunk = (size_t)pick(1, 9);
+    const FillReadPlan rp = fill_read_plan(bits, total, n_blocks, chunk);
+    std::unique_ptr<uint8_t[]> host(new uint8_t[chunk * bs]);
+    for (size_t k = 0; k < rp.n_chunks(); ++k) {
+      std::memset(host.get(), 0xA5, chunk * bs);
+      int e = -1;
+      CHECK(fill_read_chunk(rp, k, base, first, bs, host.get(), &bad, &e), "round %d: chunk %zu cannot be read: %s", round, k, slot_file_error(bad, e).c_str());
+      for (size_t i = rp.chunk_begin(k); i < rp.chunk_end(k); ++i)
+        CHECK(std::memcmp(host.get() + (i - rp.chunk_begin(k)) * bs, &bytes[rp.g[i] / n_blocks][(rp.g[i] % n_blocks) * bs], bs) == 0,
+              "round %d: chunk %zu: entry %zu holds other bytes", round, k, i);
+    }
+
+    // after the plan was made.  A file removed cannot be opened; a directory in its place opens and fails to read (EISDIR); the lowest such
+    // file of the chunk is the one named.  A file cut short reads as the read rule has it: zeros from its end on, and no error -- the device
+    // then finds another root.
+    if (rp.n_chunks()) {
+      const size_t k = (size_t)pick(0, rp.n_chunks() - 1);
+      const std::vector<FillReadPlan::Run> runs = rp.runs(k);
+      const FillReadPlan::Run& cut = runs[(size_t)pick(0, runs.size() - 1)];
+      const std::string cut_name = fill_slot_file_name(base, first + cut.local);
+      const size_t keep = (size_t)(rp.g[cut.i0] % n_blocks) * bs + (size_t)pick(0, bs - 1);      // inside the run's first block
+      CHECK(truncate(cut_name.c_str(), (off_t)keep) == 0, "round %d: cannot cut %s", round, cut_name.c_str());
+      int e = -1;
+      CHECK(fill_read_chunk(rp, k, base, first, bs, host.get(), &bad, &e), "round %d: a file cut short is an error", round);
+      for (size_t i = cut.i0; i < cut.i1; ++i)
+        for (size_t j = 0; j < bs; ++j) {
+          const size_t at = (size_t)(rp.g[i] % n_blocks) * bs + j;
+          CHECK(host[(i - rp.chunk_begin(k)) * bs + j] == (at < keep ? bytes[cut.local][at] : 0), "round %d: chunk %zu: byte %zu of a file cut at %zu", round, k, at, keep);
+        }
+      const size_t lo = (size_t)pick(0, runs.size() - 1), hi = (size_t)pick(lo, runs.size() - 1);  // two files fail (or one): the lower is named
+      const bool dir_lo = rng() & 1;
+      for (size_t r : std::set<size_t>{lo, hi}) {
+        const std::string name = fill_slot_file_name(base, first + runs[r].local);
+        CHECK(unlink(name.c_str()) == 0, "round %d: cannot remove %s", round, name.c_str());
+        there[runs[r].local] = false;
+      }
+      const std::string lo_name = fill_slot_file_name(base, first + runs[lo].local);
+      if (dir_lo) CHECK(mkdir(lo_name.c_str(), 0700) == 0, "round %d: cannot make the directory %s", round, lo_name.c_str());
+      e = -1;
+      bad.clear();
+      CHECK(!fill_read_chunk(rp, k, base, first, bs, host.get(), &bad, &e) && bad == lo_name && e == (dir_lo ? EISDIR : 0),
+            "round %d: chunk %zu: '%s' errno %d reported, '%s' %s expected", round, k, bad.c_str(), e, lo_name.c_str(), dir_lo ? "EISDIR" : "not opened");
+      if (dir_lo) rmdir(lo_name.c_str());
+    }
+    for (uint64_t s = 0; s < n_local; ++s)
+      if (there[s]) unlink(fill_slot_file_name(base, first + s).c_str());
+  }
+  // a path component that is a regular file: ENOTDIR, absent like ENOENT; a name no stat takes: an error that names the first file
+  std::vector<uint64_t> whole;
+  std::string bad;
+  put_file(dir + "/plain", {1, 2, 3});
+  CHECK(fill_slot_files_cover(dir + "/plain/slot", 3, 4, 1, &whole, &bad) && whole == std::vector<uint64_t>(4, 0), "files under a regular file are not absent");
+  unlink((dir + "/plain").c_str());
+  const std::string longer = dir + "/" + std::string(PATH_MAX, 'x');
+  CHECK(!fill_slot_files_cover(longer, 3, 4, 1, &whole, &bad) && bad == fill_slot_file_name(longer, 3), "a name longer than PATH_MAX: '%zu' bytes reported", bad.size());
+  CHECK(slot_file_error(bad, 0) == "cannot open " + bad, "the text of a file that cannot be looked at");
+}
+
 int main(int argc, char** argv) {
-  const int rounds = argc > 1 ? std::atoi(argv[1]) : 500;
+  if (argc < 3) { std::printf("usage: fill_checkpoint_check <sessions> <scratch dir>\n"); return 2; }
+  const int rounds = std::atoi(argv[1]);
   std::string err;
 
   // ---- round trips ------------------------------------------------------------------------------------------------------------------------
@@ -230,6 +330,8 @@ int main(int argc, char** argv) {
     if (file) want.seed += 1; else want.file_base = "elsewhere";
     CHECK(fill_ckpt_differs(c.meta, want).empty(), "source %d: a field of the other source is compared", file);
   }
+
+  slot_files_check(argv[2], rounds);
 
   std::printf("fill checkpoint ok: %d sessions, %d failures\n", rounds, failures);
   return failures ? 1 : 0;

@@ -72,10 +72,17 @@ def test_null_arguments_are_refused_and_outputs_untouched(pkg):
 def test_fill_checkpoint_with_sanitizers(tmp_path):
     """csrc/fill_checkpoint.hpp over 500 random sessions: the round trip (1 block per slot, bitmaps that are no multiple of 64 bits, empty and
     full sessions, absent rows zeroed), every truncation point and every flipped byte of a small file refused, each differing field named,
-    short and missing files, the read plan (each present block once, ascending per file), FillPlan::restore and ::drop."""
+    short and missing files, the read plan (each present block once, ascending per file), FillPlan::restore and ::drop.  Then its two
+    readers against real slot files in a scratch directory, 500 random geometries: the whole blocks each file holds (absent, empty, whole and
+    ragged files, ENOTDIR as absence, ENAMETOOLONG as an error naming the file) and every chunk of a read plan byte for byte into a buffer
+    of exactly a chunk; a file removed or replaced by a directory after the plan was made is an error naming the lowest such file and its
+    errno, a file cut short reads as zeros past its end."""
     exe = str(tmp_path / "fill_checkpoint_check")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+    scratch = tmp_path / "files"
+    scratch.mkdir()
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-pthread", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                            "-I" + os.path.join(PKG_DIR, "csrc"), "-o", exe, os.path.join(ROOT, "tests", "host_check", "fill_checkpoint_check.cpp")])
-    r = subprocess.run([exe, "500"], capture_output=True, text=True, timeout=600)
+    r = subprocess.run([exe, "500", str(scratch)], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "fill checkpoint ok" in r.stdout and ", 0 failures" in r.stdout, r.stdout
+    assert list(scratch.iterdir()) == []

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import fill_adopt_models as D
-from test_gpu_fill import add
+from test_gpu_fill import Source, add, build_compact
 from test_gpu_fill_anchored import N_SLOTS, World, last_error
 
 pytestmark = pytest.mark.gpu
@@ -228,3 +228,52 @@ def test_refusals_leave_the_outputs_untouched(pkg, sctx, tmp_path):
     filled.free()
     f.free()
     w.free()
+
+
+# ---- 8: many chunks -----------------------------------------------------------------------------------------------------------------------------------
+def test_many_chunks_damage_on_both_sides_of_a_chunk_edge(pkg, monkeypatch, tmp_path):
+    """test_gpu_fill_resume.py's test_many_chunks_fake_and_files for adopt.  1 MiB of staging and 64 KiB blocks: chunks of 8 blocks, 5 slots of
+    4 blocks, so the 20 absent blocks are read in two full chunks and a last one of 4.  One flipped byte in entries 7 and 8 of the read plan,
+    (slot 1, block 3) and (slot 2, block 0), the two sides of the first chunk edge: nothing below a slot root is known, so exactly those two
+    slots yield nothing."""
+    monkeypatch.setenv("CODEX_P2_STAGE_MB", "1")
+    ctx = pkg.Context(0)
+    cfgd = dict(maxDepth=16, maxLog2NSlots=3, cellSize=64, blockSize=65536, nSlots=5, nCells=4096, nSamples=3, seed=77)
+    cfg = pkg.make_config(**cfgd)
+    built = build_compact(ctx, cfg)
+    roots = built.local_roots()
+    src = Source(ctx, cfg, built, 0, 5)
+    nb = src.nb
+    assert nb == 4 and len(src.pairs) == 20
+    base = str(tmp_path / "slot")
+    fcfg = pkg.make_config(file=base, **cfgd)                                            # the same bytes in slot files: the same roots
+    f = ctx.fill(fcfg, roots)
+    status, n_new = add(f, src, src.pairs)
+    assert (status == pkg.FILL_NEW).all() and n_new == 20
+    f.free()                                                                             # unsaved: the files hold the true bytes, nothing else is left
+    victims = [src.pairs[7], src.pairs[8]]                                               # the plan's order: ascending (slot, block)
+    assert victims == [(1, 3), (2, 0)]
+    for s, b in victims:
+        with open("%s%d.dat" % (base, s), "r+b") as fh:
+            fh.seek(b * cfg.block_size + 65535 - 100 * s)
+            byte = fh.read(1)
+            fh.seek(-1, os.SEEK_CUR)
+            fh.write(bytes([byte[0] ^ 0x80]))
+
+    g = ctx.fill(fcfg, roots)
+    g.keep_nodes()
+    damaged = {1: [3], 2: [0]}
+    want = {s: D.Slot(nb).adopt(range(nb), damaged=damaged.get(s, ())) for s in range(5)}
+    assert want[1] == [] and want[2] == [] and all(want[s] == list(range(nb)) for s in (0, 3, 4))
+    assert g.adopt() == (20, 12) and sum(len(v) for v in want.values()) == 12
+    missing = missing_of(g)
+    assert missing == [(s, b) for s in (1, 2) for b in range(nb)] == [(s, b) for s in range(5) for b in range(nb) if b not in want[s]]
+    assert g.adopt() == (8, 0)                                                           # read again, and still nothing vouches for them
+
+    status, n_new = add(g, src, missing)                                                 # from the source, with their proofs: NEW, and written over
+    assert (status == pkg.FILL_NEW).all() and n_new == 8
+    filled = g.finish()
+    assert filled.local_roots().tobytes() == roots.tobytes() and filled.scrub()[2] == 0
+    for h in (filled, g, built):
+        h.free()
+    ctx.close()
