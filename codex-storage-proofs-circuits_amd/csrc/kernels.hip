@@ -5,8 +5,8 @@
 //   k_compress_layer  a7  merkle/bn254.nim:24-58 (one tree layer, many trees at once)    96 B / node
 //   k_sponge2_felts   a3  Sponge.hs:30-43 over field elements (sampling, generic byte strings)
 //   k_gen_fake_cells  a10 slot.nim:22-32
-//   k_gather_rows         path / cell gather for proof inputs (merkle.nim:21-42 does this on the host)
-//   k_sample_many, k_gather_addr, k_gen_fake_cells_many   the same across datasets (proof_many.cpp)
+//   k_gather_rows         path / cell gather for proof inputs (merkle.nim:21-42 does this on the host; gather_body)
+//   k_sample_many, k_gather_addr, k_gen_fake_cells_many   the same across datasets (proof_many.cpp); k_gather_addr over gather_body too
 //   k_verify_samples      what SampleAndProve accepts: sample_cells.circom:58-148, single_cell.circom:30-73, merkle.circom:44-114
 //   k_scrub_compare       a rebuilt layer against the kept one, mismatch bitmap + per-workgroup counts (scrub.cpp)
 //   k_scrub_compare_many  the same with the kept rows of every item behind an address table (many datasets in one batch)
@@ -444,20 +444,29 @@ __global__ void __launch_bounds__(TPB) k_sample_paths(TreeGeom g, const uint4* _
 }
 
 // ------------------------------------------------------------------------------------------------
-// Gather nrows rows of row_bytes bytes: out[r] = src[index[r] * row_bytes ...]; rows whose index is
-// ~0 are zero-filled (the reference pads paths with zero, merkle.nim:33-34, types.nim:27-37).
+// Gather nrows rows of row_bytes bytes in words of W, shared by k_gather_rows and k_gather_addr: out row r = the row at src_of(r), zeros
+// where that is null (the reference pads paths with zero, merkle.nim:33-34, types.nim:27-37).  Grid-stride over the words.
+template <typename W, typename Src>
+__device__ __forceinline__ void gather_body(size_t nrows, size_t row_bytes, uint8_t* __restrict__ out, Src src_of) {
+  const size_t words_per_row = row_bytes / sizeof(W);
+  size_t t = (size_t)blockIdx.x * TPB + threadIdx.x;
+  const size_t stride = (size_t)gridDim.x * TPB;
+  for (; t < nrows * words_per_row; t += stride) {
+    const size_t r = t / words_per_row, w = t - r * words_per_row;
+    const W* from = reinterpret_cast<const W*>(src_of(r));
+    W v = 0;
+    if (from) v = from[w];
+    reinterpret_cast<W*>(out + r * row_bytes)[w] = v;
+  }
+}
+
+// Row index[r] of src; ~0 is none.
 __global__ void __launch_bounds__(TPB) k_gather_rows(const uint8_t* __restrict__ src, const uint64_t* __restrict__ index,
                                                        size_t nrows, size_t row_bytes, uint8_t* __restrict__ out) {
-  const size_t words_per_row = row_bytes / 4;
-  size_t t = (size_t)blockIdx.x * TPB + threadIdx.x;
-  size_t stride = (size_t)gridDim.x * TPB;
-  for (; t < nrows * words_per_row; t += stride) {
-    size_t r = t / words_per_row, w = t - r * words_per_row;
-    uint64_t idx = index[r];
-    uint32_t v = 0;
-    if (idx != ~0ULL) v = reinterpret_cast<const uint32_t*>(src + idx * row_bytes)[w];
-    reinterpret_cast<uint32_t*>(out + r * row_bytes)[w] = v;
-  }
+  gather_body<uint32_t>(nrows, row_bytes, out, [=](size_t r) -> const uint8_t* {
+    const uint64_t idx = index[r];
+    return idx != ~0ULL ? src + idx * row_bytes : nullptr;
+  });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -519,20 +528,11 @@ __global__ void __launch_bounds__(TPB) k_sample_many(const ManyReq* __restrict__
   for (; d < md; ++d) r[d] = 0;                                       // padMerkleProof
 }
 
-// Rows of row_bytes bytes from absolute device addresses (W: the widest word the row length allows); address 0 is a row of zeros.
+// The row at the absolute device address addr[r] (W: the widest word the row length allows); 0 is none.
 template <typename W>
 __global__ void __launch_bounds__(TPB) k_gather_addr(const uint64_t* __restrict__ addr, size_t nrows, size_t row_bytes,
                                                        uint8_t* __restrict__ out) {
-  const size_t words_per_row = row_bytes / sizeof(W);
-  size_t t = (size_t)blockIdx.x * TPB + threadIdx.x;
-  const size_t stride = (size_t)gridDim.x * TPB;
-  for (; t < nrows * words_per_row; t += stride) {
-    const size_t r = t / words_per_row, w = t - r * words_per_row;
-    const uint64_t a = addr[r];
-    W v = 0;
-    if (a) v = reinterpret_cast<const W*>(a)[w];
-    reinterpret_cast<W*>(out + r * row_bytes)[w] = v;
-  }
+  gather_body<W>(nrows, row_bytes, out, [=](size_t r) { return reinterpret_cast<const uint8_t*>(addr[r]); });
 }
 
 // genFakeCell (slot.nim:22-32) with a seed per group of `per` rows: row i is cell firsts[i / per] + i % per of the slot seeded
@@ -1349,13 +1349,14 @@ hipError_t launch_sample_paths(const TreeGeom& g, const void* nodes, const void*
   return hipGetLastError();
 }
 
+// the gathers' grid: one lane per word up to 4096 workgroups, round the grid-stride loop above that
+static inline unsigned gather_grid(size_t words) { return words > (size_t)4096 * TPB ? 4096u : grid_for(words); }
+
 hipError_t launch_gather_rows(const void* src, const uint64_t* index, size_t nrows, size_t row_bytes, void* out, hipStream_t st) {
   if (nrows == 0) return hipSuccess;
   // the kernel moves whole 32-bit words: a row length or a pointer that is no multiple of four is refused, not truncated
   if ((row_bytes & 3) != 0 || ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(out)) & 3) != 0) return hipErrorInvalidValue;
-  size_t work = nrows * (row_bytes / 4);
-  unsigned grid = work > (size_t)4096 * TPB ? 4096u : grid_for(work);
-  CP2K_LAUNCH(k_gather_rows, dim3(grid), dim3(TPB), 0, st, (const uint8_t*)src, index, nrows, row_bytes, (uint8_t*)out);
+  CP2K_LAUNCH(k_gather_rows, dim3(gather_grid(nrows * (row_bytes / 4))), dim3(TPB), 0, st, (const uint8_t*)src, index, nrows, row_bytes, (uint8_t*)out);
   return hipGetLastError();
 }
 
@@ -1370,8 +1371,7 @@ hipError_t launch_sample_many(const ManyReq* reqs, const TreeGeom* geoms, size_t
 hipError_t launch_gather_addr(const uint64_t* addr, size_t nrows, size_t row_bytes, void* out, hipStream_t st) {
   if (nrows == 0 || row_bytes == 0) return hipSuccess;
   const bool words = (row_bytes & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0;   // (the callers' addresses are row multiples)
-  const size_t work = nrows * (words ? row_bytes / 4 : row_bytes);
-  const unsigned grid = work > (size_t)4096 * TPB ? 4096u : grid_for(work);
+  const unsigned grid = gather_grid(nrows * (words ? row_bytes / 4 : row_bytes));
   if (words) CP2K_LAUNCH(k_gather_addr<uint32_t>, dim3(grid), dim3(TPB), 0, st, addr, nrows, row_bytes, (uint8_t*)out);
   else CP2K_LAUNCH(k_gather_addr<uint8_t>, dim3(grid), dim3(TPB), 0, st, addr, nrows, row_bytes, (uint8_t*)out);
   return hipGetLastError();

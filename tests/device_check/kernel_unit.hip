@@ -42,6 +42,11 @@ int ku_gather_addr(const uint64_t* addr, size_t nrows, size_t row_bytes, void* o
   return (int)cp2k::launch_gather_addr(addr, nrows, row_bytes, out, nullptr);
 }
 
+int ku_gen_fake_cells(uint64_t seed0, uint64_t cells_per_slot, uint64_t first, const uint64_t* list, size_t n_cells, size_t cell_size, void* out,
+                      uint64_t units_per_slot, uint64_t first_unit) {
+  return (int)cp2k::launch_gen_fake_cells(seed0, cells_per_slot, first, list, n_cells, cell_size, out, nullptr, units_per_slot, first_unit);
+}
+
 int ku_gen_fake_cells_many(const uint64_t* seeds, const uint64_t* firsts, uint64_t per, size_t n_rows, size_t cell_size, void* out) {
   return (int)cp2k::launch_gen_fake_cells_many(seeds, firsts, per, n_rows, cell_size, out, nullptr);
 }

@@ -1,7 +1,7 @@
 """Plain references, and the case plans, for the kernels that tests/test_gpu_kernel_units.py runs one launcher at a time.
 
-The models restate in Python and numpy what csrc/kernels.hpp documents for k_scrub_compare, k_sample_paths, k_sample_many and the two
-block-path kernels; none of them shares code with the product.  tests/test_kernel_models_cpu.py holds them against
+The models restate in Python and numpy what csrc/kernels.hpp documents for k_scrub_compare, k_sample_paths, k_sample_many, the two
+block-path kernels and the index mapping of k_gen_fake_cells; none of them shares code with the product.  tests/test_kernel_models_cpu.py holds them against
 oracle/poseidon2_ref.py on small trees and checks that every edge the GPU module claims is really in its plan; the plans are plain
 functions, so that check needs no GPU.
 
@@ -270,6 +270,58 @@ def fake_group(g):
 
 def fake_many_plan():
     return [(per, n, cs, a) for per in FAKE_PER for n in FAKE_ROWS for cs in FAKE_SIZES for a in FAKE_OFFSETS]
+
+
+def fake_cell_of(g, cells_per_slot, units_per_slot, first_unit):
+    """(slot, idx) of global cell g as launch_gen_fake_cells documents it: the cell is cell idx of the slot seeded seed0 + 1001 * slot.
+    cells_per_slot == 0: one slot, or with units the batch's unit 0 alone.  units_per_slot > 1: g / cells_per_slot counts units of cells_per_slot cells from first_unit on,
+    units_per_slot of them to a slot; with units_per_slot <= 1 first_unit is not read."""
+    slot, idx = divmod(g, cells_per_slot) if cells_per_slot else (0, g)
+    if units_per_slot > 1:
+        slot, unit_in_slot = divmod(first_unit + slot, units_per_slot)
+        idx += unit_in_slot * cells_per_slot
+    return slot, idx
+
+
+FAKE_SINGLE_ROWS = (1, 63, 64, 65, 257)
+FAKE_SINGLE_OFFSETS = (0, 4)
+FAKE_SINGLE_CPS = (0, 1, 3, 64)
+FAKE_SINGLE_FIRSTS = (0, 7, (1 << 32) - 2)
+FAKE_SINGLE_UNITS = tuple((ups, fu) for ups in (1, 2, 4) for fu in (0, 5))
+FakeSingleCase = collections.namedtuple("FakeSingleCase", "no n cell_size offset cells_per_slot first units_per_slot first_unit listed seed0")
+
+
+def fake_is_wide(cell_size, offset):
+    """the write-out through LDS: whole 128-byte lines into a 16-byte-aligned pointer (offset: the pointer's, mod 16)"""
+    return cell_size % 128 == 0 and offset % 16 == 0
+
+
+def fake_single_plan():
+    """Every index mapping -- cells_per_slot x first x (units_per_slot, first_unit), as a range and as a list -- twice: once through
+    the wide write-out and once byte by byte.  Not the full product: the shapes (rows, cell_size, offset) and the seeds are taken in
+    rotation, so every shape and every mapping runs, and a given mapping meets one wide and one narrow shape."""
+    shapes = [(n, cs, a) for cs in FAKE_SIZES for a in FAKE_SINGLE_OFFSETS for n in FAKE_SINGLE_ROWS]
+    wide = [s for s in shapes if fake_is_wide(s[1], s[2])]
+    narrow = [s for s in shapes if not fake_is_wide(s[1], s[2])]
+    mappings = [(cps, first, ups, fu, listed) for cps in FAKE_SINGLE_CPS for first in FAKE_SINGLE_FIRSTS for ups, fu in FAKE_SINGLE_UNITS
+                for listed in (False, True)]
+    cases = []
+    for i, m in enumerate(mappings):
+        for shape in (wide[i % len(wide)], narrow[i % len(narrow)]):
+            cases.append(FakeSingleCase(len(cases), *shape, *m, FAKE_GROUP_SEEDS[(i + i // 5) % 5]))
+    return cases
+
+
+def fake_single_cells(case):
+    """The global cell of each lane: first + t, or a list that is not monotone, repeats an entry and jumps between slots and units."""
+    if not case.listed:
+        return [case.first + t for t in range(case.n)]
+    rng = np.random.default_rng([0xFA4E, case.no])
+    cells = [case.first + int(x) for x in rng.integers(0, 6 * max(case.cells_per_slot, 1) + 5, size=case.n)]
+    if case.n >= 3:
+        cells[0] = cells[2] = case.first + 5 * max(case.cells_per_slot, 1) + 1
+        cells[1] = case.first
+    return cells
 
 
 WALK_N_BLOCKS = tuple(range(1, 18)) + (31, 32, 33)

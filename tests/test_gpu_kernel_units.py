@@ -1,4 +1,4 @@
-"""GPU suite: the compare, sampling, gather, layer, path-walk and proof-input verify kernels one launcher at a time.
+"""GPU suite: the compare, sampling, gather, layer, fake-cell, path-walk and proof-input verify kernels one launcher at a time.
 
 The feature tests (scrub, repair, proof_many, block proofs, fill) reach these kernels only behind hosts that validate every request, so
 the kernels there see nothing but well-formed hashes.  Here each cp2k::launch_* is called directly, through the forwarders of
@@ -21,14 +21,15 @@ accepted input mutated in turn, the top walk over every (nSlots, slotIndex), fie
 regions are 0xFF bytes.  What it owes, byte for byte, is tests/circuit_verdict.py; the plan's own expectations are held against that
 model by the CPU suite.  Each ok buffer lies between guards, and the four input arrays are read back after every launch.
 
-Counts and times, printed by each test ("[kernel units] ...") and by test_summary.  On an MI355X the module ran in 4.5 s, 1.5 s of
+Counts and times, printed by each test ("[kernel units] ...") and by test_summary.  On an MI355X the module ran in 6.1 s, 1.5 s of
 it loading the libraries: scrub compare 320 cases 0.4 s, repair compare 36 cases 0.01 s, sample paths / sample many 176 cases (37 776
 lanes through each kernel) 0.4 s, compact sampling 20 cases 0.01 s, gather rows 28 cases 0.2 s, gather addr 149 cases 0.3 s, compress
-layer 240 cases 0.3 s, fake cells with many seeds 270 cases 0.1 s, block path roots 2547 requests 0.02 s (0.16 s before it for the
-oracle's trees and the model's verdicts), block path commit 2816 requests 0.01 s.  Those are 6602 cases.  The k_verify_samples plan adds
+layer 240 cases 0.3 s, fake cells with many seeds 270 cases 0.1 s, the fake cells' index mapping 288 cases 0.1 s, block path roots 2547
+requests 0.02 s (0.16 s before it for the oracle's trees and the model's verdicts), block path commit 2816 requests 0.01 s.  Those are
+6890 cases.  The k_verify_samples plan adds
 3241 inputs (7990 lanes in 19 launches: five geometries 144 / 105 / 248 / 261 / 374 inputs, top walks 1 / 5 / 92 / 1520 / 92, edges,
 layouts and refused shapes 399); building it and taking the model's verdicts costs about 8 s of pure Python on the host, most of it in
-the 2048-byte geometry (2.6 s) and in the model's first pass.  The summary line: "9843 cases, 0 skipped"."""
+the 2048-byte geometry (2.6 s) and in the model's first pass.  The summary line: "10131 cases, 0 skipped"."""
 import ctypes
 import os
 import subprocess
@@ -92,6 +93,7 @@ def ku(pkg):
             "ku_sample_many": [vp, vp, sz, u32, u32, vp, vp, vp],
             "ku_gather_rows": [vp, vp, sz, sz, vp],
             "ku_gather_addr": [vp, sz, sz, vp],
+            "ku_gen_fake_cells": [u64, u64, u64, vp, sz, sz, vp, u64, u64],
             "ku_gen_fake_cells_many": [vp, vp, u64, sz, sz, vp],
             "ku_compress_layer": [vp, vp, sz, sz, i32, sz, sz],
             "ku_block_path_roots": [vp, vp, vp, vp, u64, u32, sz, vp, vp],
@@ -541,6 +543,44 @@ def test_gen_fake_cells_many_every_write_out_path(ku, torch_, oracle, capsys):
     report(capsys, "fake cells, many seeds", len(plan), bad, t0)
 
 
+# ---- k_gen_fake_cells ----------------------------------------------------------------------------------------------------------------------
+def test_gen_fake_cells_index_mapping_and_write_out(ku, torch_, oracle, capsys):
+    """Lane t makes global cell list[t] or first + t; kernel_models.fake_cell_of says which cell of which slot that is, the C oracle what
+    that cell holds under the seed seed0 + 1001 * slot (mod 2^64).  The output lies as in the test above: 64 guard bytes before it, a
+    whole workgroup's cells of room after it.  n_cells == 0 and cell_size == 0 are no work: success, nothing touched."""
+    torch, t0, bad, plan = torch_, time.time(), [], K.fake_single_plan()
+    C, _ = oracle
+    cell_of = {}
+    for c in plan:
+        what = "gen_fake_cells n=%d cell_size=%d out offset=%d cells_per_slot=%d first=%d units=%d/%d %s seed0=%d" % (
+            c.n, c.cell_size, c.offset, c.cells_per_slot, c.first, c.units_per_slot, c.first_unit, "list" if c.listed else "range", c.seed0)
+        cells = K.fake_single_cells(c)
+        want = np.empty((c.n, c.cell_size), dtype=np.uint8)
+        for t, g in enumerate(cells):
+            slot, idx = K.fake_cell_of(g, c.cells_per_slot, c.units_per_slot, c.first_unit)
+            key = ((c.seed0 + 1001 * slot) % (1 << 64), idx, c.cell_size)
+            if key not in cell_of:
+                cell_of[key] = C.gen_fake_cells(key[0], idx, 1, c.cell_size)[0]
+            want[t] = cell_of[key]
+        d_list = up(torch, np.array(cells, dtype=np.uint64)) if c.listed else None
+        buf = Out(torch, c.n * c.cell_size, offset=c.offset - (FRONT - 64), back=256 * c.cell_size + 256)
+        assert buf.lo == 64 + c.offset and buf.ptr % 16 == c.offset
+        status = ku.ku_gen_fake_cells(c.seed0, c.cells_per_slot, c.first, d_list.data_ptr() if c.listed else None, c.n, c.cell_size, buf.ptr,
+                                      c.units_per_slot, c.first_unit)
+        if status != 0:
+            bad.append("%s: status %d" % (what, status))
+            continue
+        buf.check(want, what, bad, c.cell_size, lambda t: " (global cell %d = cell %d of slot %d)" % ((cells[t],) + K.fake_cell_of(
+            cells[t], c.cells_per_slot, c.units_per_slot, c.first_unit)[::-1]))
+    buf = Out(torch, 4 * 128, offset=-(FRONT - 64), back=256 * 128 + 256)
+    for n, cs in ((0, 128), (4, 0), (0, 0)):
+        status = ku.ku_gen_fake_cells(12417, 3, 7, None, n, cs, buf.ptr, 2, 5)
+        if status != 0:
+            bad.append("gen_fake_cells n=%d cell_size=%d: status %d" % (n, cs, status))
+    buf.check(buf.prefill(), "gen_fake_cells without work", bad)
+    report(capsys, "fake cells, index mapping", len(plan), bad, t0)
+
+
 # ---- k_block_path_roots, k_block_path_commit ---------------------------------------------------------------------------------------------
 def walk_requests(C, n_blocks):
     """The requests of K.walk_plan(n_blocks) over one random tree: (plan, fresh, paths, pairs, slot_roots, depth, expected verdicts)."""
@@ -722,7 +762,8 @@ def test_summary():
     walk = sum(len(K.walk_plan(n)) for n in K.WALK_N_BLOCKS)
     want = {"scrub compare": len(K.scrub_plan()), "repair compare": len(K.repair_plan()), "sample paths / sample many": len(K.sample_plan()),
             "sample many, compact": len(K.compact_plan()), "gather rows": len(K.gather_rows_plan()), "gather addr": len(K.gather_addr_plan()),
-            "compress layer": len(K.layer_plan()), "fake cells, many seeds": len(K.fake_many_plan()), "block path roots": walk}
+            "compress layer": len(K.layer_plan()), "fake cells, many seeds": len(K.fake_many_plan()), "fake cells, index mapping": len(K.fake_single_plan()),
+            "block path roots": walk}
     want.update({verify_name(gi): len(K.verify_geometry_launch(gi).items) for gi in range(len(K.VERIFY_GEOMS))})
     want.update({"verify samples, top walk m=%d ns=%d" % (m, ns): len(K.verify_top_launch(m, ns).items) for m, ns in VERIFY_TOP_RUNS})
     want["verify samples, edges, layouts, refused"] = K.verify_plan_cases([K.verify_edge_launch()] + K.verify_layout_launches() + [K.verify_refused_launch()])

@@ -206,6 +206,46 @@ def test_layer_plan():
     assert any(s == 257 and m % 2 == 1 and i > m and o > (m + 1) // 2 for m, s, b, i, o in plan)        # many segments, an odd tail in each, gaps
 
 
+def test_fake_cell_of_walks_the_units_of_a_dataset_in_order():
+    """A dataset's cells listed unit by unit -- units_per_slot units of cells_per_slot cells to a slot -- from unit first_unit on are what
+    fake_cell_of gives for g = 0, 1, ...; without units the same with one unit to a slot, first_unit unread."""
+    for cps in (1, 3, 64):
+        for ups in (1, 2, 4):
+            units = [(u // ups, (u % ups) * cps + i) for u in range(12) for i in range(cps)]
+            for fu in (0, 5):
+                start = fu if ups > 1 else 0
+                assert [K.fake_cell_of(g, cps, ups, fu) for g in range(6 * cps)] == units[start * cps:(start + 6) * cps]
+    # cells_per_slot == 0: every cell lies in the batch's unit 0, cell g of it
+    assert [K.fake_cell_of(g, 0, ups, 5) for g in (0, 9, 1 << 40) for ups in (1, 2, 4)] == [(s, g) for g in (0, 9, 1 << 40) for s in (0, 2, 1)]
+
+
+def test_fake_single_plan():
+    plan = K.fake_single_plan()
+    assert 200 <= len(plan) <= 400 and [c.no for c in plan] == list(range(len(plan)))
+    shapes = {(c.n, c.cell_size, c.offset) for c in plan}
+    assert shapes == {(n, cs, a) for n in (1, 63, 64, 65, 257) for cs in (1, 127, 128, 2048, 2049) for a in (0, 4)}
+    for wide in (True, False):                                   # every mapping through both write-outs
+        got = {(c.cells_per_slot, c.first, c.units_per_slot, c.first_unit, c.listed) for c in plan if K.fake_is_wide(c.cell_size, c.offset) == wide}
+        assert got == {(cps, f, ups, fu, ls) for cps in (0, 1, 3, 64) for f in (0, 7, (1 << 32) - 2) for ups in (1, 2, 4) for fu in (0, 5)
+                       for ls in (False, True)}
+    assert {(c.seed0, c.cells_per_slot) for c in plan} == {(s, cps) for s in K.FAKE_GROUP_SEEDS for cps in (0, 1, 3, 64)}
+    wraps = edges = unit_edges = 0
+    for c in plan:
+        cells = K.fake_single_cells(c)
+        where = [K.fake_cell_of(g, c.cells_per_slot, c.units_per_slot, c.first_unit) for g in cells]
+        assert len(cells) == c.n and all(0 <= g < (1 << 64) for g in cells)
+        if c.listed and c.n >= 3:                                # not monotone, a repeat, and (more than one slot) a jump back and forth
+            assert cells[0] > cells[1] < cells[2] and cells[0] == cells[2]
+            assert c.cells_per_slot == 0 or where[0][0] != where[1][0]
+        if not c.listed and c.cells_per_slot and c.n >= 63:      # a run crosses a slot edge inside its first wave
+            crosses = len({s for s, _ in where[:64]}) > 1
+            assert crosses or c.cells_per_slot == 64
+            edges += crosses
+            unit_edges += c.units_per_slot > 1 and any(a[0] == b[0] and b[1] % c.cells_per_slot == 0 for a, b in zip(where[:64], where[1:64]))
+        wraps += any(c.seed0 + 1001 * s >= (1 << 64) for s, _ in where)
+    assert wraps >= 10 and edges >= 50 and unit_edges >= 20
+
+
 def test_fake_many_plan():
     plan = K.fake_many_plan()
     assert set(plan) == {(p, n, c, a) for p in (1, 3, 100) for n in (1, 63, 64, 65, 257, 301) for c in (1, 127, 128, 2048, 2049) for a in (0, 4, 1)}
@@ -473,7 +513,7 @@ def test_check_library_builds_and_forwards_to_the_product(pkg):
     libcodex_p2.so, whose code objects are therefore the ones that run."""
     subprocess.check_call(["make", "-C", PKG_DIR, "../tests/device_check/libkernel_unit.so"], stdout=subprocess.DEVNULL)
     lib = os.path.join(ROOT, "tests", "device_check", "libkernel_unit.so")
-    launchers = ("scrub_compare", "repair_compare", "sample_paths", "sample_many", "gather_rows", "gather_addr", "gen_fake_cells_many",
+    launchers = ("scrub_compare", "repair_compare", "sample_paths", "sample_many", "gather_rows", "gather_addr", "gen_fake_cells", "gen_fake_cells_many",
                  "compress_layer", "block_path_roots", "block_path_commit", "verify_samples")
     mine, wanted, product = dynamic_symbols(lib, True), dynamic_symbols(lib, False), dynamic_symbols(pkg.LIB_PATH, True)
     assert {"ku_" + n for n in launchers} | {"ku_sizeof_tree_geom", "ku_sizeof_many_req", "ku_sizeof_verify_geom", "ku_scrub_tile"} <= mine
