@@ -223,6 +223,8 @@ def load_library():
         "cp2_dataset_block_proofs": (i32, [vp, vp, sz, vp, vp]),
         "cp2_blocks_verify": (i32, [vp, sz, sz, sz, vp, sz, vp, vp, vp, sz, vp, vp]),
         "cp2_dataset_repair_blocks_proved": (i32, [vp, vp, vp, vp, sz, i32, cp, vp, ctypes.POINTER(sz)]),
+        "cp2_datasets_read_blocks": (i32, [vp, vp, sz, vp, sz, i32, vp, vp, vp, vp, vp, ctypes.POINTER(sz)]),
+        "cp2_dataset_read_blocks": (i32, [vp, vp, sz, i32, vp, vp, vp, vp, ctypes.POINTER(sz)]),
         "cp2_fill_begin": (i32, [vp, ctypes.POINTER(Config), u64, u64, vp, pvp]),
         "cp2_fill_add": (i32, [vp, vp, vp, vp, sz, vp, ctypes.POINTER(sz)]),
         "cp2_fill_missing": (i32, [vp, vp, sz, ctypes.POINTER(u64)]),
@@ -580,6 +582,33 @@ class Context:
                  "cp2_datasets_scrub_many")
         return gran[:n].copy(), bad[:min(cap, nb.value)].copy(), counts[:n].copy(), nb.value
 
+    def read_blocks(self, datasets, requests, check_only=False, want_data=True, want_paths=True, data=None):
+        """cp2_datasets_read_blocks: the blocks named by requests (uint64[n, 3]: index into datasets, slot, block) read from the slot files,
+        checked on the device against the block roots the datasets keep and returned with their proofs.  data: an array of n x blockSize
+        bytes to read into (caller-pinned memory is read in place), else one is made unless want_data is False (which needs check_only).
+        Returns (data: uint8[n, blockSize] or None, block_roots: uint8[n, 32], paths: uint8[sum of depths, 32] or None, path_off:
+        uint64[n + 1] or None, status: uint32[n] of READ_*, n_ok); DAMAGED rows of data are zeros."""
+        rq = np.ascontiguousarray(np.asarray(requests, dtype=np.uint64).reshape(-1, 3))
+        n, nd = rq.shape[0], len(datasets)
+        hs = (ctypes.c_void_p * max(nd, 1))(*[d.h for d in datasets])
+        bs = int(datasets[0].cfg.block_size) if nd else 0
+        if data is None and want_data:
+            data = np.empty((n, bs), dtype=np.uint8)
+        roots = np.empty((n, 32), dtype=np.uint8)
+        paths = off = None
+        if want_paths:
+            depth = [d.block_proof_depth for d in datasets]
+            total = sum(depth[int(k)] for k in rq[:, 0] if int(k) < nd)
+            paths = np.empty((total, 32), dtype=np.uint8)
+            off = np.zeros(n + 1, dtype=np.uint64)
+        status = np.empty(n, dtype=np.uint32)
+        ok = ctypes.c_size_t()
+        dp = None if data is None else ctypes.c_void_p(data.ctypes.data if isinstance(data, np.ndarray) else int(data))
+        self._ck(self.L.cp2_datasets_read_blocks(self.h, hs, nd, _p(rq), n, READ_CHECK_ONLY if check_only else 0, dp, _p(roots),
+                                                 _p(paths) if want_paths else None, _p(off) if want_paths else None, _p(status), ctypes.byref(ok)),
+                 "cp2_datasets_read_blocks")
+        return data, roots, paths, off, status, ok.value
+
     def export_proof_inputs_many(self, requests, paths=None, threads=1, batch=0):
         """cp2_proof_inputs_export_many: generate + serialise (+ write paths[i] where it is not None) as a pipeline; returns the
         total text bytes."""
@@ -688,6 +717,8 @@ def _repair(fn, h, block_size, slot_block, data, check_only, cache_path, ck, whe
     return status, written.value
 
 
+READ_CHECK_ONLY = 1                               # CP2_READ_* (include/codex_p2.h): the flag and the verdicts of the verified read-back
+READ_OK, READ_DAMAGED = 0, 1
 BLOCK_MATCH, BLOCK_MISMATCH = 0, 1                # CP2_BLOCK_* (include/codex_p2.h): the verdicts of cp2_blocks_verify
 
 
@@ -846,6 +877,23 @@ class Dataset:
         self.ctx._ck(self.ctx.L.cp2_dataset_block_proofs(self.h, _p(sb) if n else None, n, _p(roots) if n else None, _p(paths) if n else None),
                      "cp2_dataset_block_proofs")
         return roots, paths
+
+    def read_blocks(self, slot_block, check_only=False, want_data=True, want_paths=True, data=None):
+        """cp2_dataset_read_blocks: Context.read_blocks over this dataset alone, (slot, block) pairs.  Returns (data: uint8[n, blockSize] or
+        None, block_roots: uint8[n, 32], paths: uint8[n, depth, 32] or None, status: uint32[n] of READ_*, n_ok)."""
+        sb = np.ascontiguousarray(np.asarray(slot_block, dtype=np.uint64).reshape(-1, 2))
+        n, depth = sb.shape[0], self.block_proof_depth
+        if data is None and want_data:
+            data = np.empty((n, int(self.cfg.block_size)), dtype=np.uint8)
+        roots = np.empty((n, 32), dtype=np.uint8)
+        paths = np.empty((n, depth, 32), dtype=np.uint8) if want_paths else None
+        status = np.empty(n, dtype=np.uint32)
+        ok = ctypes.c_size_t()
+        dp = None if data is None else ctypes.c_void_p(data.ctypes.data if isinstance(data, np.ndarray) else int(data))
+        self.ctx._ck(self.ctx.L.cp2_dataset_read_blocks(self.h, _p(sb), n, READ_CHECK_ONLY if check_only else 0, dp, _p(roots),
+                                                        _p(paths) if want_paths else None, _p(status), ctypes.byref(ok)),
+                     "cp2_dataset_read_blocks")
+        return data, roots, paths, status, ok.value
 
     def repair_blocks_proved(self, slot_block, data, paths, check_only=False, cache_path=None):
         """cp2_dataset_repair_blocks_proved: repair_blocks with the Merkle path (uint8[n, depth, 32]) of every candidate, checked against the

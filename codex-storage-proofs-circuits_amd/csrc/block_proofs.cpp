@@ -84,18 +84,27 @@ int cp2i::gather_block_proofs(cp2_ctx* ctx, const void* nodes, size_t n_rows, co
       return CP2_ERR_INVALID;
     }
   const size_t per = depth + 1, n = rows.size() / per;
-  DevBuf d_rows, d_out;
-  CP2_TRY(d_rows.scratch(ctx, rows.size() * 8));
-  CP2_TRY(d_out.scratch(ctx, rows.size() * 32));
+  // the one gather is by address (k_gather_addr): a row index is an address once the buffer is named
+  std::vector<uint64_t> addr(rows.size());
+  for (size_t r = 0; r < rows.size(); ++r) addr[r] = rows[r] == BLOCK_PROOF_NO_ROW ? 0 : (uint64_t)reinterpret_cast<uintptr_t>(nodes) + rows[r] * 32;
   std::vector<uint8_t> out(rows.size() * 32);
-  CP2_HIP(ctx, hipMemcpyAsync(d_rows.p, rows.data(), rows.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-  CP2_HIP(ctx, cp2k::launch_gather_rows(nodes, static_cast<const uint64_t*>(d_rows.p), rows.size(), 32, d_out.p, ctx->stream));
-  CP2_HIP(ctx, hipMemcpyAsync(out.data(), d_out.p, out.size(), hipMemcpyDeviceToHost, ctx->stream));
-  CP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  CP2_TRY(gather_rows_by_addr(ctx, addr, out.data()));
   for (size_t i = 0; i < n; ++i) {
     if (block_roots) std::memcpy(block_roots + i * 32, &out[i * per * 32], 32);
     if (paths) std::memcpy(paths + i * depth * 32, &out[(i * per + 1) * 32], depth * 32);
   }
+  return CP2_OK;
+}
+
+int cp2i::gather_rows_by_addr(cp2_ctx* ctx, const std::vector<uint64_t>& addr, uint8_t* out) {
+  if (addr.empty()) return CP2_OK;
+  DevBuf d_addr, d_out;
+  CP2_TRY(d_addr.scratch(ctx, addr.size() * 8));
+  CP2_TRY(d_out.scratch(ctx, addr.size() * 32));
+  CP2_HIP(ctx, hipMemcpyAsync(d_addr.p, addr.data(), addr.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+  CP2_HIP(ctx, cp2k::launch_gather_addr(static_cast<const uint64_t*>(d_addr.p), addr.size(), 32, d_out.p, ctx->stream));
+  CP2_HIP(ctx, hipMemcpyAsync(out, d_out.p, addr.size() * 32, hipMemcpyDeviceToHost, ctx->stream));
+  CP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return CP2_OK;
 }
 

@@ -11,6 +11,7 @@
 //   k_scrub_compare       a rebuilt layer against the kept one, mismatch bitmap + per-workgroup counts (scrub.cpp)
 //   k_scrub_compare_many  the same with the kept rows of every item behind an address table (many datasets in one batch)
 //   k_repair_compare      candidate block roots against the kept rows they would replace, one verdict per request (repair.cpp)
+//   k_repair_compare_addr the same with the kept row of every request at an absolute address (read_blocks.cpp: many datasets)
 //   k_block_path_roots    a13 candidate block roots walked up their Merkle paths to the slot root, merkle.nim:51-74 (block_proofs.cpp)
 //   k_block_path_commit   the same walk; a proved block root is also stored into layer 0 of a fill session's compact buffer (fill.cpp)
 //   k_block_path_commit_nodes   the same walk; a proved path's 2 x depth + 1 nodes are stored where the session's tree has them (fill.cpp)
@@ -668,19 +669,36 @@ __global__ void __launch_bounds__(TPB) k_scrub_compare_many(const uint4* __restr
 
 // ------------------------------------------------------------------------------------------------
 // Block repair (repair.cpp): lane i takes request i's freshly built block root (fresh row i, the roots of a chunk are one contiguous
-// layer) and the kept row the dataset holds for that block (row rows[i] of the kept node buffer, computed on the host from the
-// dataset's layout), two 16-byte loads a side, and writes one verdict word: 0 the roots are equal, 1 they differ.  A row at or past
-// kept_rows (never: the host validated every request) is a mismatch and is not read.
-__global__ void __launch_bounds__(TPB) k_repair_compare(const uint4* __restrict__ fresh, const uint4* __restrict__ kept, size_t kept_rows,
-                                                          const uint64_t* __restrict__ rows, size_t n, uint32_t* __restrict__ verdict) {
+// layer) and the kept row the dataset holds for that block, two 16-byte loads a side, and writes one verdict word: 0 the roots are
+// equal, 1 they differ.  No atomics, no LDS, no permutation.  The index form and the address form share this body; kept_of(i) is the
+// kept row of request i, or null (never: the host validated every request), which is a mismatch and is not read.
+template <typename Kept>
+__device__ __forceinline__ void repair_compare_body(const uint4* __restrict__ fresh, size_t n, uint32_t* __restrict__ verdict, Kept kept_of) {
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
-  const uint64_t r = rows[i];
+  const uint4* k = kept_of(i);
   uint32_t v = 1;
-  if (r < kept_rows) {
-    v = rows_equal(fresh[2 * i], fresh[2 * i + 1], kept[2 * r], kept[2 * r + 1]) ? 0u : 1u;
-  }
+  if (k) v = rows_equal(fresh[2 * i], fresh[2 * i + 1], k[0], k[1]) ? 0u : 1u;
   verdict[i] = v;
+}
+
+// The kept row is row rows[i] of the kept node buffer, computed on the host from the dataset's layout; a row at or past kept_rows is none.
+__global__ void __launch_bounds__(TPB) k_repair_compare(const uint4* __restrict__ fresh, const uint4* __restrict__ kept, size_t kept_rows,
+                                                          const uint64_t* __restrict__ rows, size_t n, uint32_t* __restrict__ verdict) {
+  repair_compare_body(fresh, n, verdict, [=](size_t i) -> const uint4* {
+    const uint64_t r = rows[i];
+    return r < kept_rows ? kept + 2 * r : nullptr;
+  });
+}
+
+// Reading blocks back across datasets (read_blocks.cpp): the kept row of request i is the 32 bytes at the absolute device address
+// kept_addr[i], 16-byte aligned like every 32-byte row (k_scrub_compare_many's table, one entry per request instead of one per item);
+// 0 is none.  The fresh side is coalesced (64 lanes, 2 KiB in a run); the kept side is one 32-byte row wherever the request points, 8
+// bytes of table beside it.  Where the time of a read-back goes is not here: a block costs 1119 permutations in k_hash_cells and the
+// block-tree layer launches before its root reaches this kernel, which moves 72 bytes and writes 4 for it.
+__global__ void __launch_bounds__(TPB) k_repair_compare_addr(const uint4* __restrict__ fresh, const uint64_t* __restrict__ kept_addr, size_t n,
+                                                               uint32_t* __restrict__ verdict) {
+  repair_compare_body(fresh, n, verdict, [=](size_t i) { return reinterpret_cast<const uint4*>(kept_addr[i]); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1414,6 +1432,14 @@ hipError_t launch_repair_compare(const void* fresh, const void* kept, size_t kep
   CP2K_LAUNCH(k_repair_compare, dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, st, (const uint4*)fresh, (const uint4*)kept, kept_rows, rows, n,
               verdict);
   return hipGetLastError();
+}
+
+hipError_t launch_repair_compare_addr(const void* fresh, const uint64_t* kept_addr, size_t n, uint32_t* verdict, hipStream_t st, size_t slice) {
+  if (n == 0) return hipSuccess;
+  if (!fresh || !kept_addr || !verdict) return hipErrorInvalidValue;
+  return for_slices(n, [&](size_t i0, size_t m) {
+    hipLaunchKernelGGL(k_repair_compare_addr, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)fresh + 2 * i0, kept_addr + i0, m, verdict + i0);
+  }, slice && slice < MAX_ITEMS ? slice : MAX_ITEMS);
 }
 
 hipError_t launch_block_path_roots(const void* fresh, const void* paths, const uint64_t* root_block, const void* slot_roots, uint64_t n_blocks,

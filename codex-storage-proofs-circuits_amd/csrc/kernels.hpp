@@ -71,6 +71,10 @@ hipError_t launch_scrub_compare_many(const void* fresh, size_t fstride, const ui
 // Block repair (repair.cpp): verdict[i] = 0 when the 32-byte row i of `fresh` equals row rows[i] of `kept` (kept_rows rows), else 1.
 hipError_t launch_repair_compare(const void* fresh, const void* kept, size_t kept_rows, const uint64_t* rows, size_t n, uint32_t* verdict,
                                  hipStream_t st);
+// The same with the kept row of request i at the absolute device address kept_addr[i] (device table, n entries; 16-byte aligned; 0 is
+// none: a mismatch, not read), so that one launch serves the requests of many datasets (read_blocks.cpp).  Launched in slices of at
+// most `slice` requests (0: what one grid holds; the tests pass small ones).
+hipError_t launch_repair_compare_addr(const void* fresh, const uint64_t* kept_addr, size_t n, uint32_t* verdict, hipStream_t st, size_t slice = 0);
 
 // Block proofs (block_proofs.cpp, k_block_path_roots): request i < n = the 32-byte row i of `fresh` (a candidate's block root), the pair
 // root_block[2 i], root_block[2 i + 1] (index into slot_roots, block of the slot; validated by the host) and `depth` canonical siblings

@@ -73,7 +73,7 @@ int cp2i::repair_check_with(cp2_ctx* ctx, size_t cell_size, size_t block_size, c
   }
   // requests per chunk: half the context's staging in candidate bytes (the node buffer of a chunk holds about as much again)
   const size_t chunk = std::max<size_t>(1, std::min<size_t>(n, (ctx->stage_bytes / 2) / block_size));
-  const bool pinned = !judge.cells && host_array_pinned(data, n * block_size, PIECE_BYTES);
+  const bool pinned = !judge.cells && (judge.host ? judge.host_pinned : host_array_pinned(data, n * block_size, PIECE_BYTES));
   DevBuf d_verdict, d_nodes, d_cells;                // (device buffers go after every stream has drained: DevBuf::release)
   if (judge.begin) CP2_TRY(judge.begin(chunk));
   CP2_TRY(d_verdict.scratch(ctx, n * 4));
@@ -99,7 +99,8 @@ int cp2i::repair_check_with(cp2_ctx* ctx, size_t cell_size, size_t block_size, c
   const size_t piece = std::max<size_t>(1, PIECE_BYTES / block_size) * block_size;
   for (size_t c0 = 0; c0 < n; c0 += chunk) {
     const size_t m = std::min(chunk, n - c0), bytes = m * block_size;
-    const uint8_t* src = data ? data + c0 * block_size : nullptr;
+    const uint8_t* src = data && !judge.host ? data + c0 * block_size : nullptr;
+    if (judge.host && !judge.cells) CP2_TRY(judge.host(c0, m, &src));
     if (pinned) {
       // the copy engine reads the caller's memory in place, piece by piece; each piece is hashed as soon as it has landed, the pieces
       // alternating between the context's two hashing streams.  Nothing of this chunk starts before the previous one is compared.

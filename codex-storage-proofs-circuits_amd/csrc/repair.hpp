@@ -34,10 +34,15 @@ int repair_check(cp2_ctx* ctx, const RepairKept& k, size_t cell_size, size_t blo
 // holds the chunk's m block roots (32-byte rows, request c0 + i at row i), verdict[i] receives 0 for a match, anything else for a
 // mismatch.  cells (may be empty): a device-side source of the candidates, in place of `data`, which may then be NULL: per chunk it queues
 // on `st` whatever fills d_cells with the m x block_size bytes of requests [c0, c0 + m); the chunk is hashed behind it on the context's
-// stream, as a small pageable chunk is behind its upload.  Everything the callbacks allocate must outlive the call (it ends with the
-// stream drained).
+// stream, as a small pageable chunk is behind its upload.  host (may be empty): a host-side source that produces the candidates chunk by
+// chunk, in place of `data`, which is then not looked at: called once per chunk, in order, before anything of the chunk is queued, it
+// sets *src to the m x block_size bytes of requests [c0, c0 + m), which stay valid and unchanged until the chunk after the next is asked
+// for; host_pinned says whether the copy engines read every such *src in place (read_blocks.cpp reads slot files one chunk ahead).
+// Everything the callbacks allocate must outlive the call (it ends with the stream drained).
 struct RepairJudge {
   std::function<int(size_t chunk)> begin;
+  std::function<int(size_t c0, size_t m, const uint8_t** src)> host;
+  bool host_pinned = false;
   std::function<int(size_t c0, size_t m, uint8_t* d_cells, hipStream_t st)> cells;
   std::function<int(size_t c0, size_t m, hipStream_t st)> stage;
   std::function<int(const uint8_t* fresh, size_t c0, size_t m, uint32_t* verdict, hipStream_t st)> verdicts;
@@ -49,6 +54,9 @@ int repair_check_with(cp2_ctx* ctx, size_t cell_size, size_t block_size, const u
 // block_roots (n x 32 bytes, may be NULL) and paths (n x depth x 32 bytes, may be NULL).
 int gather_block_proofs(cp2_ctx* ctx, const void* nodes, size_t n_rows, const std::vector<uint64_t>& rows, size_t depth, const char* outside,
                         uint8_t* block_roots, uint8_t* paths);
+// The gather under it, by absolute device address (read_blocks.cpp: the rows of many datasets in one launch): out (host, addr.size() x 32
+// bytes) row r = the 32 bytes at addr[r], zeros for 0.  One upload of the table, one k_gather_addr, one download; the stream is drained.
+int gather_rows_by_addr(cp2_ctx* ctx, const std::vector<uint64_t>& addr, uint8_t* out);
 // the requests whose status is CP2_REPAIR_MATCH written into "<base><slot>.dat", grouped by file in ascending offset order, each file synced
 // once.  The first file that cannot be opened, written or synced: CP2_ERR_IO, *err "cannot write <file>: <reason>", its matched requests and
 // those of every later file CP2_REPAIR_UNWRITTEN.  *n_written counts the blocks of the files written and synced, `written` their stamps.

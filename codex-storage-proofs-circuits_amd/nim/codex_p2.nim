@@ -86,6 +86,13 @@ proc cp2_multi_dataset_repair_blocks(ds: Cp2MultiDataset, slotBlock: ptr uint64,
 # (rootBlock = n x (index into slotRoots, block), status = n x CP2_BLOCK_*), and repair with a path beside every candidate
 proc cp2_block_proof_depth(cellSize, blockSize, nCells: csize_t): csize_t {.importc.}
 proc cp2_dataset_block_proofs(ds: Cp2Dataset, slotBlock: ptr uint64, n: csize_t, blockRoots, paths: ptr byte): cint {.importc.}
+# verified read-back: listed blocks read from the slot files, checked against the kept block roots and returned with their proofs;
+# req = n x (index into ds, slot, block), flags CP2_READ_CHECK_ONLY (data may then be nil), status = n x CP2_READ_* (0 ok, 1 damaged),
+# paths packed with pathOff (n + 1 rows) in the many-dataset form, n x depth x 32 in the single one
+proc cp2_datasets_read_blocks(ctx: Cp2Ctx, ds: ptr Cp2Dataset, nDs: csize_t, req: ptr uint64, n: csize_t, flags: cint, data, blockRoots,
+                              paths: ptr byte, pathOff: ptr uint64, status: ptr uint32, nOk: ptr csize_t): cint {.importc.}
+proc cp2_dataset_read_blocks(ds: Cp2Dataset, slotBlock: ptr uint64, n: csize_t, flags: cint, data, blockRoots, paths: ptr byte,
+                             status: ptr uint32, nOk: ptr csize_t): cint {.importc.}
 proc cp2_blocks_verify(ctx: Cp2Ctx, cellSize, blockSize, nCells: csize_t, slotRoots: ptr byte, nRoots: csize_t, rootBlock: ptr uint64,
                        data, paths: ptr byte, n: csize_t, status: ptr uint32, blockRoots: ptr byte): cint {.importc.}
 proc cp2_dataset_repair_blocks_proved(ds: Cp2Dataset, slotBlock: ptr uint64, data, paths: ptr byte, n: csize_t, flags: cint,

@@ -46,7 +46,8 @@ extern "C" {
  *                cp2_dataset_repair_blocks_proved (block proofs), cp2_fill_begin, cp2_fill_add, cp2_fill_missing, cp2_fill_finish and
  *                cp2_fill_free (fill sessions), cp2_fill_save and cp2_fill_resume (fill checkpoints), cp2_fill_keep_nodes and
  *                cp2_fill_block_proofs (fill sessions that serve), cp2_fill_anchors and cp2_fill_add_anchored (anchored fill adds),
- *                cp2_fill_adopt (adopting blocks from disk), cp2_fill_save_nodes and cp2_fill_resume_nodes (checkpoints with nodes).
+ *                cp2_fill_adopt (adopting blocks from disk), cp2_fill_save_nodes and cp2_fill_resume_nodes (checkpoints with nodes),
+ *                cp2_datasets_read_blocks and cp2_dataset_read_blocks (verified read-back of listed blocks).
  *                MINOR stays 2 until the release that carries them: the bump to 1.3 goes in its own commit with that release.         */
 #define CP2_ABI_VERSION_MAJOR 1
 #define CP2_ABI_VERSION_MINOR 2
@@ -613,6 +614,58 @@ int cp2_blocks_verify(cp2_ctx* ctx, size_t cell_size, size_t block_size, size_t 
 int cp2_dataset_repair_blocks_proved(cp2_dataset* ds, const uint64_t* slot_block /* n x 2: dataset slot, block of the slot */,
                                      const uint8_t* data /* n x block_size */, const uint8_t* paths /* n x depth x 32 */, size_t n,
                                      int flags, const char* cache_path, uint32_t* status /* n */, size_t* n_written);
+
+/* ---- verified read-back: listed blocks read from disk, checked against the kept block roots, returned with their proofs ---------------
+ * cp2_dataset_block_proofs hands out a block's root and path but none of its bytes; a node that answers a peer would read the 64 KiB
+ * itself and ship them unchecked, under a good proof, whatever happened to the sector since the last scrub.  cp2_datasets_read_blocks
+ * reads the listed blocks, hashes each to its block root on the device, compares it with the root the dataset keeps, and returns bytes,
+ * root and path together -- for the blocks of many datasets in one pass, which is also the spot scrub a node can afford every period
+ * (a few random blocks of every slot it holds).  cp2_dataset_read_blocks is the same pass with one dataset, on that dataset's context.
+ *   Requests   req (n x 3 uint64: index into ds, dataset slot inside that dataset's local range, block of the slot < its nBlocks), in any
+ *              order; the same triple may repeat (two peers may ask for the same block), each repeat with its own row and verdict; a
+ *              dataset may be listed twice in ds.  The datasets all belong to ctx and share cell_size and block_size; they may differ
+ *              in n_cells, n_slots, local range, source, base name, seed and residency (every node kept, or compact).
+ *   Data       row i of data (n x blockSize) = the blockSize bytes of request i, read from "<file_base><slot>.dat" at block x blockSize
+ *              under the builders' read rule: what lies past the end of the file reads as zeros (a truncated file's tail blocks come
+ *              back DAMAGED, as a scrub reports them), a read that fails is an error.  Reads are buffered preads, spread over the
+ *              context's ingestion threads (cp2_set_ingest), one chunk ahead of the device; O_DIRECT and the mapped mode are not used.
+ *              Each block is read once, into its row, and uploaded from there: the bytes hashed are the bytes returned.  The data path
+ *              is repair's: chunks of half the context's staging, a caller-pinned data read in place by the copy engines, a pageable
+ *              one through the pinned ring.  After the verdicts every DAMAGED row is overwritten with zeros.  Fake-source datasets
+ *              regenerate their blocks on the device and download them; they are always OK.
+ *   Check only With CP2_READ_CHECK_ONLY data may be NULL: the blocks pass through two pooled pinned chunk buffers, so memory is bounded
+ *              by the chunk whatever n is.  A non-NULL data with the flag is still filled.
+ *   Proofs     block_roots[i] (n x 32, may be NULL) and the path of request i are what cp2_dataset_block_proofs returns for it: the
+ *              KEPT nodes, authentic whatever the disk holds, so they are returned for DAMAGED requests too (the node then knows what to
+ *              ask a peer for, and hands the answer to cp2_dataset_repair_blocks).  Many-dataset form: depths differ with n_cells, so
+ *              paths are packed -- request i's path is rows [path_off[i], path_off[i + 1]) of paths (32 bytes a row, bottom first), as
+ *              many as the cp2_block_proof_depth of its dataset; path_off has n + 1 entries.  The caller sizes paths as the sum of those
+ *              depths over the requests, computed from each dataset's configuration.  paths and path_off are given together or not at
+ *              all.  Single form: paths is n x depth x 32, cp2_dataset_block_proofs' layout, and may be NULL.
+ *   Result     status[i] = CP2_READ_OK or CP2_READ_DAMAGED; *n_ok (may be NULL) counts the former.  DAMAGED is not an error: CP2_OK.
+ *   Refused    before any device or file work, CP2_ERR_INVALID, every output untouched, the dataset or request index in
+ *              cp2_last_error: a NULL ctx (handle); with n > 0 a NULL ds, req or status; NULL data without CP2_READ_CHECK_ONLY; paths
+ *              without path_off or the reverse; an unknown flag; ds[k] NULL, of another context, of another cell_size or block_size than
+ *              ds[0], roots-only, or with kept layers that are not those of whole slot trees (the unit builds); a dataset index >=
+ *              n_ds; a slot outside the local range; a block >= nBlocks of its dataset.  n == 0: CP2_OK, *n_ok = 0.  A context whose
+ *              stream will not drain is refused (CP2_ERR_HIP).
+ *   Errors     a slot file that cannot be opened or read: CP2_ERR_IO, cp2_last_error "cannot open <file>" / "cannot read <file>:
+ *              <reason>".  status, *n_ok, block_roots, paths and path_off are untouched; data, if given, holds zeros in every row the
+ *              call had written.
+ *   Read-only  kept nodes, dataset tree, residency, cache files and slot files stay as they are; every proof input is the same before
+ *              and after.  CP2_TRACE prints one line per call (datasets, requests, chunks, bytes, seconds, GB/s, damaged). */
+#define CP2_READ_CHECK_ONLY 1        /* flag: verdicts, roots and paths only; data may be NULL */
+#define CP2_READ_OK       0          /* status: the bytes on disk hash to the kept block root; returned */
+#define CP2_READ_DAMAGED  1          /* status: they do not; the request's data row is all zeros */
+int cp2_datasets_read_blocks(cp2_ctx* ctx, cp2_dataset* const* ds, size_t n_ds,
+                             const uint64_t* req /* n x 3: index into ds, dataset slot, block of the slot */, size_t n, int flags,
+                             uint8_t* data /* n x blockSize; may be NULL with CP2_READ_CHECK_ONLY */,
+                             uint8_t* block_roots /* n x 32, may be NULL */,
+                             uint8_t* paths /* packed, may be NULL */, uint64_t* path_off /* n + 1 rows, may be NULL iff paths is */,
+                             uint32_t* status /* n */, size_t* n_ok /* may be NULL */);
+int cp2_dataset_read_blocks(cp2_dataset* ds, const uint64_t* slot_block /* n x 2: dataset slot, block of the slot */, size_t n, int flags,
+                            uint8_t* data, uint8_t* block_roots, uint8_t* paths /* n x depth x 32, may be NULL */,
+                            uint32_t* status /* n */, size_t* n_ok);
 
 /* ---- fill sessions: slots filled from proved blocks in any order into a compact dataset ----------------------------------------------
  * A node that takes on a slot holds only the manifest's slot root.  It receives the slot's network blocks from peers, in any order and
