@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "body_store.hpp"
+#include "proof_export.hpp"   // proof_shape_refusal, slot_proof_of: the host-only pieces every proof-input route shares
 #include "trees.hpp"
 
 struct cp2_dataset {
@@ -63,8 +64,17 @@ inline void canonical_felt(const uint8_t in[32], uint8_t out[32]) {
 
 // the device buffer holding the roots of the local slots (n_local x 32 bytes)
 const void* dataset_roots_dev(const cp2_dataset* ds);
-// slotProof = padMerkleProof(merkleProof(dsetTree, slotIdx), maxLog2NSlots), gen_input/bn254.nim:51,72
-void fill_slot_proof(const cp2_dataset* ds, uint64_t slot_idx, std::vector<uint8_t>& out);
+// slotProof of a slot of a dataset whose dataset tree is set (slot_proof_of, proof_export.hpp)
+inline void fill_slot_proof(const cp2_dataset* ds, uint64_t slot_idx, std::vector<uint8_t>& out) {
+  cp2i::slot_proof_of(ds->dlayers, ds->dsizes, ds->cfg.n_slots, (size_t)ds->cfg.max_log2_nslots, slot_idx, out);
+}
+// What proof_shape_refusal (proof_export.hpp) is asked about a built dataset: the depth of every slot tree of the configuration -- the
+// block tree under the tree over the block roots, what cp2_slot_trees_depth says of built trees -- and of the tree over its slot roots
+inline size_t config_slot_tree_depth(const cp2_config& c) {
+  const size_t cpb = c.block_size / c.cell_size;
+  return (cp2i::layer_sizes_of(cpb).size() - 1) + (cp2i::layer_sizes_of(c.n_cells / cpb).size() - 1);
+}
+inline size_t config_dataset_tree_depth(const cp2_config& c) { return cp2i::layer_sizes_of(c.n_slots).size() - 1; }
 
 namespace cp2i {
 // The one pass that makes proof inputs for n (dataset, slot, entropy) requests of one circuit (proof_many.cpp): every request's

@@ -250,12 +250,10 @@ inline bool fill_read_chunk(const FillReadPlan& rp, size_t k, const std::string&
   const size_t i0 = rp.chunk_begin(k);
   for (const FillReadPlan::Run& run : rp.runs(k)) {
     const std::string fname = fill_slot_file_name(base, first_slot + run.local);
-    const int fd = open(fname.c_str(), O_RDONLY | O_CLOEXEC);
-    int e = 0;
-    for (size_t i = run.i0; fd >= 0 && i < run.i1 && !e; ++i)
-      e = slot_file_read_rest(fd, host + (i - i0) * block_size, block_size, (rp.g[i] % rp.n_blocks) * block_size);
-    if (fd >= 0) close(fd);
-    if (fd < 0 || e) { *bad = fname; *err = e; return false; }
+    const int e = slot_file_read_list(fname, run.i1 - run.i0, [&](size_t) { return block_size; },
+                                      [&](size_t i) { return (rp.g[run.i0 + i] % rp.n_blocks) * block_size; },
+                                      [&](size_t i) { return host + (run.i0 + i - i0) * block_size; });
+    if (e >= 0) { *bad = fname; *err = e; return false; }
   }
   return true;
 }

@@ -16,8 +16,8 @@
 // O_DIRECT (cp2_set_ingest_direct / CP2_INGEST_DIRECT=1): slot files that are not in the page cache are read straight into the pinned
 // ring, whole 4 KiB blocks, without passing through (and evicting) the page cache; a piece whose file offset or buffer address is not
 // block aligned, the last partial block of a piece, and a file system that refuses O_DIRECT (tmpfs) are read buffered.
-// ONE READ RULE for every read of a slot file (these fills and read_file_cell, which the proof-input paths use): a read interrupted
-// (EINTR) is retried, a short read reads on, a read of 0 bytes is the end of the file -- zeros from there (slot.nim:61-66) -- and a
+// ONE READ RULE for every read of a slot file (these fills and slot_file_read_list, the reader of listed cells and blocks): a read
+// interrupted (EINTR) is retried, a short read reads on, a read of 0 bytes is the end of the file -- zeros from there (slot.nim:61-66) -- and a
 // read that fails with any other errno is an ERROR naming the file, never zeros: the reference yields no data for a file it cannot
 // read.  The O_DIRECT attempt only ever reads ahead: whatever it fails on (EINVAL included), the buffered loop reads the rest of
 // the piece, and only that loop decides whether a read failed.
@@ -66,12 +66,30 @@ inline int slot_file_read_rest(int fd, uint8_t* out, size_t n, uint64_t off, siz
   return err;
 }
 
-// cell `cell` of an open slot file (slot.nim:57-68): 0, or the errno of a failed read
+// cell `cell` of an open slot file (slot.nim:57-68): 0, or the errno of a failed read (the CPU checks' yardstick; the product reads lists)
 inline int read_file_cell(int fd, size_t cell_size, uint64_t cell, uint8_t* out) { return slot_file_read_rest(fd, out, cell_size, cell * cell_size); }
 
 // what cp2_last_error says about a slot file: err == 0 it could not be opened, otherwise a read of it failed with errno `err`
 inline std::string slot_file_error(const std::string& fname, int err) {
   return err == 0 ? "cannot open " + fname : "cannot read " + fname + ": " + std::strerror(err);
+}
+
+// ONE FILE, A LIST OF PIECES: `fname` is opened, piece c = [off_of(c), + len_of(c)) of it is read into dst_of(c) for c = 0 .. count - 1
+// by the read rule, up to the first read that fails, and the file is closed.  Every reader of listed cells or blocks goes through this
+// (the proof-input paths, the read-back of listed blocks, a fill session's re-read); the turns above read ranges, not lists.
+// Returns what slot_file_error takes: -1 all read (zeros past the end of the file), 0 the file could not be opened, else the errno of
+// the read that failed -- *bad_piece is then the piece it belonged to.  The file is opened for zero pieces, too.
+template <typename LenOf, typename OffOf, typename DstOf>
+inline int slot_file_read_list(const std::string& fname, size_t count, LenOf len_of, OffOf off_of, DstOf dst_of, size_t* bad_piece = nullptr) {
+  const int fd = open(fname.c_str(), O_RDONLY | O_CLOEXEC);
+  if (fd < 0) return 0;
+  int err = 0;
+  size_t c = 0;
+  for (; c < count && !err; ++c) err = slot_file_read_rest(fd, dst_of(c), (size_t)len_of(c), (uint64_t)off_of(c));
+  (void)close(fd);
+  if (!err) return -1;
+  if (bad_piece) *bad_piece = c - 1;
+  return err;
 }
 
 class FillPipeline {

@@ -31,6 +31,7 @@
 #include <thread>
 #include <vector>
 
+#include "proof_export.hpp"
 #include "trees.hpp"
 #include "repair.hpp"
 #include "exchange_policy.hpp"
@@ -851,15 +852,13 @@ int units_proof_inputs(cp2_multi_dataset* mds, const uint64_t* slots, size_t n, 
   cp2_multi* m = mds->m;
   for (size_t i = 0; i < n; ++i) { out[i] = nullptr; if (slots[i] >= c.n_slots) return CP2_ERR_INVALID; }
   if (n == 0) return CP2_OK;
-  if (c.n_samples && c.n_cells < 2) return CP2_ERR_INVALID;                        // extractLowBits asserts k > 0, types/bn254.nim:48
-  if (!is_pow2(c.n_cells)) return CP2_ERR_INVALID;                                 // sample/bn254.nim:19-20
   const uint64_t S = mds->units_per_slot, P = c.n_cells / S, cpb = c.block_size / c.cell_size;
   const size_t ns = c.n_samples, md = (size_t)c.max_depth, cs = c.cell_size, total = n * ns;
   size_t levels = 0;
   while (((uint64_t)1 << levels) < S) ++levels;
   const size_t depth_unit = (layer_sizes_of(cpb).size() - 1) + (layer_sizes_of(P / cpb).size() - 1);
-  if (depth_unit + levels > md) return CP2_ERR_INVALID;                            // padMerkleProof assert, types.nim:29
-  if (mds->dsizes.size() - 1 > (size_t)c.max_log2_nslots) return CP2_ERR_INVALID;  // the same for slotProof
+  const std::string refusal = proof_shape_refusal(c, depth_unit + levels, mds->dsizes.size() - 1);   // a path: inside the unit, then the levels above it
+  if (!refusal.empty()) { m->err = refusal; return CP2_ERR_INVALID; }
   cp2_ctx* ctx0 = mds->shards[0].units->ctx;
   // (the entropy is a field element, types/bn254.nim:21: the sponge takes any 32 bytes mod r, and cp2_proof_input_create stores and
   // prints the canonical residue -- so what is hashed and what is printed agree without reducing it here)
@@ -935,12 +934,9 @@ int units_proof_inputs(cp2_multi_dataset* mds, const uint64_t* slots, size_t n, 
     auto work = [&](int t) {
       for (size_t i = (size_t)t; i < n; i += (size_t)nt) {
         const std::string fname = slot_file_name(mds->file_base, slots[i]);
-        const int fd = open(fname.c_str(), O_RDONLY);
-        if (fd < 0) { failed[t] = slot_file_error(fname, 0); return; }
-        int err = 0;
-        for (size_t k = 0; k < ns && !err; ++k) err = read_file_cell(fd, cs, idx[i * ns + k], &cells[(i * ns + k) * cs]);
-        close(fd);
-        if (err) { failed[t] = slot_file_error(fname, err); return; }
+        const int err = slot_file_read_list(fname, ns, [&](size_t) { return cs; }, [&](size_t k) { return idx[i * ns + k] * cs; },
+                                            [&](size_t k) { return &cells[(i * ns + k) * cs]; });
+        if (err >= 0) { failed[t] = slot_file_error(fname, err); return; }
       }
     };
     {
@@ -963,18 +959,10 @@ int units_proof_inputs(cp2_multi_dataset* mds, const uint64_t* slots, size_t n, 
     CP2_HIP(ctx0, hipMemcpyAsync(cells.data(), d_cells.p, total * cs, hipMemcpyDeviceToHost, ctx0->stream));
     CP2_HIP(ctx0, hipStreamSynchronize(ctx0->stream));
   }
-  // ---- slotProof = padMerkleProof(merkleProof(dsetTree, slotIdx), maxLog2NSlots), gen_input/bn254.nim:51,72; the objects
-  std::vector<uint8_t> proof((size_t)c.max_log2_nslots * 32);
+  // ---- slotProof and the objects
+  std::vector<uint8_t> proof;
   for (size_t i = 0; i < n; ++i) {
-    std::fill(proof.begin(), proof.end(), 0);
-    size_t k = slots[i], mm = c.n_slots, off = 0;
-    for (size_t l = 0; l + 1 < mds->dsizes.size(); ++l) {
-      const size_t j = k ^ 1;
-      if (j < mm) std::memcpy(&proof[l * 32], &mds->dlayers[(off + j) * 32], 32);
-      off += mds->dsizes[l];
-      k >>= 1;
-      mm = (mm + 1) >> 1;
-    }
+    slot_proof_of(mds->dlayers, mds->dsizes, c.n_slots, (size_t)c.max_log2_nslots, slots[i], proof);
     int r = cp2_proof_input_create(&c, slots[i], &mds->dlayers[mds->dlayers.size() - 32], entropy, mds->slot_root(slots[i]), proof.data(), ns, &idx[i * ns],
                                    &cells[i * ns * cs], &paths[i * ns * md * 32], &leaves[i * ns * 32], out + i);
     if (r != CP2_OK) {
@@ -1011,7 +999,7 @@ int units_export(cp2_multi_dataset* mds, const uint64_t* slot_idx, size_t n, con
     std::vector<std::string> names;
     std::vector<const char*> paths;
     if (dir) {
-      for (size_t i = 0; i < k; ++i) names.push_back(std::string(dir) + "/input_" + std::to_string(slot_idx[b0 + i]) + ".json");
+      for (size_t i = 0; i < k; ++i) names.push_back(input_json_name(dir, slot_idx[b0 + i]));
       for (auto& s2 : names) paths.push_back(s2.c_str());
     }
     uint64_t got = 0;
@@ -1150,7 +1138,7 @@ extern "C" int cp2_multi_dataset_export_streamed(cp2_multi_dataset* mds, const c
     for (size_t s = 0; s < mds->texts.size(); ++s) {
       tot += mds->texts[s].size();
       if (!dir) continue;
-      const std::string name = std::string(dir) + "/input_" + std::to_string(s) + ".json";
+      const std::string name = input_json_name(dir, s);
       FILE* f = std::fopen(name.c_str(), "wb");
       const bool ok = f && std::fwrite(mds->texts[s].data(), 1, mds->texts[s].size(), f) == mds->texts[s].size();
       if ((f && std::fclose(f) != 0) || !ok) { mds->m->err = "cannot write " + name; return CP2_ERR_IO; }
@@ -1176,14 +1164,7 @@ extern "C" int cp2_multi_dataset_streamed_json(cp2_multi_dataset* mds, uint64_t 
   if (!mds || !text) return CP2_ERR_INVALID;
   if (mds->by_units()) {
     if (!mds->prepared || slot_idx >= mds->texts.size()) return CP2_ERR_INVALID;
-    const std::string& t = mds->texts[slot_idx];
-    char* buf = (char*)std::malloc(t.size() + 1);
-    if (!buf) return CP2_ERR_ALLOC;
-    std::memcpy(buf, t.data(), t.size());
-    buf[t.size()] = 0;
-    *text = buf;
-    if (len) *len = t.size();
-    return CP2_OK;
+    return text_to_malloc(mds->texts[slot_idx], text, len);
   }
   auto* s = mds->owner(slot_idx);
   if (!s) return CP2_ERR_INVALID;

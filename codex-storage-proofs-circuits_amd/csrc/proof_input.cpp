@@ -9,6 +9,12 @@
 // (2) cp2_dataset_build_streamed: the entropy is known up front, so the sampling / gather / download / JSON body of
 // every finished slot overlaps the hashing of the later slots, and only the lines that need ALL slot roots
 // (dataSetRoot, slotProof: gen_input/bn254.nim:49-51,72) are added at the end by cp2_dataset_export_streamed.
+//
+// What these routes share with proof_many.cpp and multi_gpu.cpp is not in here.  proof_export.hpp (host only, checked on the CPU):
+// the refusals that mirror the reference's asserts (proof_shape_refusal), slotProof, the name of an input.json, the malloc'ed text,
+// the strided formatting fan-out under cp2_proof_inputs_write_json_batch and cp2_dataset_export_streamed, and the two-stage
+// generate / format pipeline (export_in_chunks) that cp2_dataset_export_proof_inputs is one call of.  fill_pipeline.hpp: the one
+// reader of listed pieces of a slot file (slot_file_read_list) that every sampled-cell read on the host goes through.
 #include <hip/hip_runtime.h>
 
 #include <fcntl.h>
@@ -551,14 +557,9 @@ int enqueue_sampling(cp2_slot_trees* t, const cp2k::TreeGeom& g, SampleDev& d, S
   CP2_HIP(ctx, cp2k::launch_gather_rows(t->nodes.p, gcell, total, 32, d.leaves.p, st));
   CP2_HIP(ctx, hipMemcpyAsync(host.leaves.p, d.leaves.p, total * 32, hipMemcpyDeviceToHost, st));
   if (!fetch_cells) return CP2_OK;   // host-side sources: the caller reads the sampled cells itself
-  if (t->src == CellSrc::Fake) {
-    CP2_HIP(ctx, cp2k::launch_gen_fake_cells(cp2_slot_seed(t->dataset_seed, t->units_per_slot > 1 ? 0 : t->first_slot), t->n_cells, 0, gcell, total, cs,
-                                             d.cells.p, st, t->units_per_slot, t->first_slot));
-  } else if (t->src == CellSrc::Dev && t->d_cells) {
-    CP2_HIP(ctx, cp2k::launch_gather_rows(t->d_cells, gcell, total, cs, d.cells.p, st));
-  } else {
-    return CP2_ERR_INVALID;
-  }
+  if (t->src != CellSrc::Fake) return CP2_ERR_INVALID;   // a dataset's trees are Fake or File (dataset_build_trees, the match test of cached trees)
+  CP2_HIP(ctx, cp2k::launch_gen_fake_cells(cp2_slot_seed(t->dataset_seed, t->units_per_slot > 1 ? 0 : t->first_slot), t->n_cells, 0, gcell, total, cs,
+                                           d.cells.p, st, t->units_per_slot, t->first_slot));
   CP2_HIP(ctx, hipMemcpyAsync(host.cells.p, d.cells.p, total * cs, hipMemcpyDeviceToHost, st));
   return CP2_OK;
 }
@@ -570,62 +571,27 @@ int enqueue_sampling(cp2_slot_trees* t, const cp2k::TreeGeom& g, SampleDev& d, S
 // ---------------------------------------------------------------------------------------------
 // BatchStore and struct cp2_proof_input: proof_input_obj.hpp (shared with verify.cpp)
 
-// slotProof = padMerkleProof(merkleProof(dsetTree, slotIdx), maxLog2NSlots), gen_input/bn254.nim:51,72
-void fill_slot_proof(const cp2_dataset* ds, uint64_t slot_idx, std::vector<uint8_t>& out) {
-  out.assign((size_t)ds->cfg.max_log2_nslots * 32, 0);
-  size_t k = slot_idx, m = ds->cfg.n_slots, off = 0;
-  for (size_t i = 0; i + 1 < ds->dsizes.size(); ++i) {
-    size_t j = k ^ 1;
-    if (j < m) std::memcpy(&out[i * 32], &ds->dlayers[(off + j) * 32], 32);
-    off += ds->dsizes[i];
-    k >>= 1;
-    m = (m + 1) >> 1;
-  }
-}
-
-// sampled cells of the host-side sources: global index g = local_slot * n_cells + cell (slotLoadCellData, slot.nim:57-68)
-static int host_cells_global(cp2_slot_trees* t, const uint64_t* g, size_t n, uint8_t* out) {
+// The sampled cells of `n` slots of slot-file trees (slotLoadCellData, slot.nim:57-68): cells idx[r * ns .. + ns) of local slot
+// local[r] into out, in that order.  A batch of proof inputs samples hundreds of thousands of cells (4096 slots x 100): the slots are
+// spread over the context's fill threads, each taking a contiguous share and every slot's file read as one list.  The failure reported
+// is that of the lowest slot in the list.  (A dataset's trees hold whole slots -- units_per_slot 1 -- of the Fake or the File source:
+// dataset_build_trees, dataset_transient_trees and the match test of cached trees make no other.)
+static int host_cells_of_slots(cp2_slot_trees* t, const uint64_t* local, const uint64_t* idx, size_t n, size_t ns, uint8_t* out) {
   cp2_ctx* ctx = t->ctx;
   const size_t cs = t->cell_size;
-  if (t->src == CellSrc::Host) {
-    if (!t->h_cells) return CP2_ERR_INVALID;   // loaded from a cache: attach the cells first
-    for (size_t i = 0; i < n; ++i) std::memcpy(out + i * cs, t->h_cells + g[i] * cs, cs);
-    return CP2_OK;
-  }
-  if (t->src == CellSrc::File) {
-    // a batch of proof inputs samples hundreds of thousands of cells (4096 slots x 100): the reads are spread over the
-    // context's fill threads, each taking a contiguous range of the (slot-ordered) list and opening a slot file once per run
-    const int threads = (int)std::min<size_t>((size_t)fill_threads(ctx), std::max<size_t>(1, n / 256));
-    struct Run { int fd = -1; size_t slot = ~(size_t)0; std::string fname, failed; };   // per worker: the file it has open, and slot_file_error of the one it could not open or read
-    std::vector<Run> runs(threads);
-    on_threads(threads, n, [&](int w, size_t i) {
-      Run& r = runs[w];
-      const size_t slot = g[i] / t->n_cells, cell = g[i] % t->n_cells;
-      if (slot != r.slot) {
-        if (r.fd >= 0) close(r.fd);
-        r.fname = slot_file_name(t->file_base, (t->first_slot + slot) / t->units_per_slot);
-        r.fd = open(r.fname.c_str(), O_RDONLY);
-        if (r.fd < 0) { r.failed = slot_file_error(r.fname, 0); return false; }
-        r.slot = slot;
-      }
-      const int err = read_file_cell(r.fd, cs, ((t->first_slot + slot) % t->units_per_slot) * t->n_cells + cell, out + i * cs);
-      if (err) r.failed = slot_file_error(r.fname, err);
-      return !err;
-    });
-    for (const Run& r : runs)
-      if (r.fd >= 0) close(r.fd);
-    for (const Run& r : runs)
-      if (!r.failed.empty()) { ctx->err = r.failed; return CP2_ERR_IO; }
-    return CP2_OK;
-  }
-  if (t->src == CellSrc::Dev) {   // cell sizes the row gather cannot take: plain copies
-    if (!t->d_cells) return CP2_ERR_INVALID;
-    for (size_t i = 0; i < n; ++i)
-      CP2_HIP(ctx, hipMemcpyAsync(out + i * cs, t->d_cells + g[i] * cs, cs, hipMemcpyDeviceToHost, ctx->stream));
-    CP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CP2_OK;
-  }
-  return CP2_ERR_INVALID;
+  if (t->src != CellSrc::File || t->units_per_slot != 1) return CP2_ERR_INVALID;
+  const int threads = (int)std::min<size_t>((size_t)fill_threads(ctx), std::max<size_t>(1, n * ns / 256));
+  std::vector<std::string> failed(threads);   // per worker: slot_file_error of the file it could not open or read
+  on_threads(threads, n, [&](int w, size_t r) {
+    const std::string fname = slot_file_name(t->file_base, t->first_slot + local[r]);
+    const int e = slot_file_read_list(fname, ns, [&](size_t) { return cs; }, [&](size_t c) { return idx[r * ns + c] * cs; },
+                                      [&](size_t c) { return out + (r * ns + c) * cs; });
+    if (e >= 0) failed[w] = slot_file_error(fname, e);
+    return e < 0;
+  });
+  for (const std::string& f : failed)
+    if (!f.empty()) { ctx->err = f; return CP2_ERR_IO; }
+  return CP2_OK;
 }
 
 // generateProofInput (gen_input/bn254.nim:35-79) for `n` slots of the dataset at once.  Every node kept: one sampling launch, one
@@ -643,13 +609,10 @@ extern "C" int cp2_proof_inputs_generate_batch(cp2_dataset* ds, const uint64_t* 
   cp2_ctx* ctx = ds->ctx;
   for (size_t i = 0; i < n; ++i)
     if (slot_idx[i] < ds->first_slot || slot_idx[i] >= ds->first_slot + ds->n_local) return CP2_ERR_INVALID;
-  if (!is_pow2(cfg.n_cells)) return CP2_ERR_INVALID;                    // sample/bn254.nim:19-20
-  if (cfg.n_samples && cfg.n_cells < 2) return CP2_ERR_INVALID;         // extractLowBits asserts k > 0, types/bn254.nim:48
+  const std::string refusal = proof_shape_refusal(cfg, config_slot_tree_depth(cfg), config_dataset_tree_depth(cfg));
+  if (!refusal.empty()) { ctx->err = refusal; return CP2_ERR_INVALID; }
   if (!ds->trees && ds->tree_mode == 2) {                               // compact dataset: stored upper layers + the touched blocks
     if (!ds->have_roots) CP2_TRY(cp2_dataset_set_roots(ds, nullptr));
-    if (ds->dsizes.size() - 1 > (size_t)cfg.max_log2_nslots) return CP2_ERR_INVALID;   // padMerkleProof assert
-    const size_t cpb = cfg.block_size / cfg.cell_size;
-    if (layer_sizes_of(cpb).size() - 1 + ds->csizes.size() - 1 > (size_t)cfg.max_depth) return CP2_ERR_INVALID;   // padMerkleProof assert, types.nim:29
     std::vector<cp2_dataset*> same(n, ds);
     std::vector<uint8_t> entropies(n * 32);
     for (size_t i = 0; i < n; ++i) std::memcpy(&entropies[i * 32], entropy, 32);
@@ -686,15 +649,12 @@ extern "C" int cp2_proof_inputs_generate_batch(cp2_dataset* ds, const uint64_t* 
   }
   const uint64_t local_base = ds->trees ? ds->first_slot : slot_idx[0];  // index inside `t` = slot index - local_base
   if (!ds->have_roots) CP2_TRY(cp2_dataset_set_roots(ds, nullptr));
-  if (ds->dsizes.size() - 1 > (size_t)cfg.max_log2_nslots) return CP2_ERR_INVALID;   // padMerkleProof assert
-  if (cp2_slot_trees_depth(t) > (size_t)cfg.max_depth) return CP2_ERR_INVALID;        // padMerkleProof assert
   CP2_HIP(ctx, hipSetDevice(ctx->device));
   const size_t ns = cfg.n_samples, md = (size_t)cfg.max_depth, cs = cfg.cell_size, total = n * ns;
 
   StageTimer trace;
   auto store = std::make_shared<BatchStore>();
-  const bool dev_cells = t->src == CellSrc::Fake ||
-                         (t->src == CellSrc::Dev && t->d_cells && (cs & 3) == 0 && (reinterpret_cast<uintptr_t>(t->d_cells) & 3) == 0);
+  const bool dev_cells = t->src == CellSrc::Fake;   // regenerated on the device; slot files are read on the host
   if (total) {
     cp2k::TreeGeom g;
     trees_geom(t, &g);
@@ -714,12 +674,8 @@ extern "C" int cp2_proof_inputs_generate_batch(cp2_dataset* ds, const uint64_t* 
     if (dev_cells) {
       store->cells.swap(host.cells);
     } else {
-      const uint64_t* idx = static_cast<const uint64_t*>(store->idx.p);
-      std::vector<uint64_t> gcell(total);
-      for (size_t i = 0; i < n; ++i)
-        for (size_t c = 0; c < ns; ++c) gcell[i * ns + c] = local[i] * t->n_cells + idx[i * ns + c];
       store->cells_heap.resize(total * cs);
-      CP2_TRY(host_cells_global(t, gcell.data(), total, store->cells_heap.data()));
+      CP2_TRY(host_cells_of_slots(t, local.data(), static_cast<const uint64_t*>(store->idx.p), n, ns, store->cells_heap.data()));
       trace.lap("cells read on the host");
     }
   }
@@ -842,13 +798,7 @@ extern "C" int cp2_proof_input_json(const cp2_proof_input* p, char** text, size_
   if (!p || !text) return CP2_ERR_INVALID;
   std::string s;
   proof_input_text(p, s);
-  char* buf = (char*)std::malloc(s.size() + 1);
-  if (!buf) return CP2_ERR_ALLOC;
-  std::memcpy(buf, s.data(), s.size());
-  buf[s.size()] = 0;
-  *text = buf;
-  if (len) *len = s.size();
-  return CP2_OK;
+  return text_to_malloc(s, text, len);
 } catch (const std::bad_alloc&) {
   return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
 } catch (...) {
@@ -862,90 +812,29 @@ extern "C" int cp2_proof_inputs_write_json_batch(const cp2_proof_input* const* p
   if (n && !ps) return CP2_ERR_INVALID;
   for (size_t i = 0; i < n; ++i)
     if (!ps[i]) return CP2_ERR_INVALID;
-  if (threads < 1) threads = 1;
-  if ((size_t)threads > n) threads = n ? (int)n : 1;
-  std::vector<int> status(threads, CP2_OK);
-  std::vector<uint64_t> bytes(threads, 0);
-  auto work = [&](int t) {
-    try {
-      std::string s;
-      for (size_t i = t; i < n; i += threads) {
-        proof_input_text(ps[i], s);
-        bytes[t] += s.size();
-        if (paths && paths[i]) {
-          int st = write_parts(paths[i], s, std::string());
-          if (st != CP2_OK) status[t] = st;
-        }
-      }
-    } catch (...) {
-      status[t] = CP2_ERR_ALLOC;
-    }
-  };
-  {
-    Workers pool(threads - 1 > 0 ? threads - 1 : 1);   // joined by its destructor on every path out of this scope
-    for (int t = 1; t < threads; ++t) pool.submit([&, t] { work(t); });
-    work(0);
-    pool.wait_idle();
-  }
-  uint64_t tot = 0;
-  for (int t = 0; t < threads; ++t) {
-    tot += bytes[t];
-    if (status[t] != CP2_OK) return status[t];
-  }
-  if (total_bytes) *total_bytes = tot;
-  return CP2_OK;
+  std::vector<std::string> text(std::min<size_t>((size_t)std::max(threads, 1), std::max<size_t>(n, 1)));   // one per formatting thread, reused from input to input
+  return format_strided(n, threads, [&](int t, size_t i, uint64_t* bytes) {
+    proof_input_text(ps[i], text[t]);
+    *bytes += text[t].size();
+    return paths && paths[i] ? write_parts(paths[i], text[t], std::string()) : CP2_OK;
+  }, total_bytes);
 } catch (const std::bad_alloc&) {
   return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
 } catch (...) {
   return CP2_ERR_INVALID;
 }
 
-// Proof inputs for many slots of a built dataset, generated and serialised as a two-stage pipeline: while the host
-// threads turn batch k into JSON text (and write it when dir != NULL: "<dir>/input_<slot>.json"), the GPU already
-// samples and gathers batch k+1.
+// Proof inputs for many slots of a built dataset, generated and serialised as a two-stage pipeline (export_in_chunks,
+// proof_export.hpp): while the host threads turn batch k into JSON text (and write it when dir != NULL: "<dir>/input_<slot>.json"),
+// the GPU already samples and gathers batch k+1.
 extern "C" int cp2_dataset_export_proof_inputs(cp2_dataset* ds, const uint64_t* slot_idx, size_t n, const uint8_t entropy[32],
                                                const char* dir, int threads, size_t batch, uint64_t* total_bytes) try {
   if (!ds || !entropy || (n && !slot_idx)) return CP2_ERR_INVALID;
-  if (batch == 0) batch = 512;
-  if (threads < 1) threads = 1;
-  uint64_t bytes = 0;
-  int status = CP2_OK;
-  std::vector<cp2_proof_input*> cur, next;
-  auto generate = [&](size_t b0, std::vector<cp2_proof_input*>& out) -> int {
-    size_t m = std::min(batch, n - b0);
-    out.assign(m, nullptr);
-    return cp2_proof_inputs_generate_batch(ds, slot_idx + b0, m, entropy, out.data());
-  };
-  struct Release {   // whatever leaves this scope, the objects are freed
-    std::vector<cp2_proof_input*>& v;
-    ~Release() { for (auto* p : v) delete p; v.clear(); }
-  } rel_cur{cur}, rel_next{next};
-  if (n) status = generate(0, cur);
-  for (size_t b0 = 0; status == CP2_OK && b0 < n; b0 += batch) {
-    const size_t b1 = b0 + batch;
-    // names first: nothing below may throw while the producer task is in flight except into the pool's joining destructor
-    std::vector<std::string> names;
-    std::vector<const char*> paths;
-    if (dir) {
-      for (size_t i = 0; i < cur.size(); ++i) names.push_back(std::string(dir) + "/input_" + std::to_string(slot_idx[b0 + i]) + ".json");
-      for (auto& s2 : names) paths.push_back(s2.c_str());
-    }
-    int gen_status = CP2_OK, st = CP2_OK;
-    uint64_t got = 0;
-    {
-      Workers producer(1);                                   // GPU stage of the NEXT batch; joined when this scope ends
-      if (b1 < n) producer.submit([&] { gen_status = generate(b1, next); });
-      st = cp2_proof_inputs_write_json_batch(cur.data(), cur.size(), dir ? paths.data() : nullptr, threads, &got);
-    }
-    bytes += got;
-    for (auto* p : cur) delete p;
-    cur.clear();
-    if (st != CP2_OK) status = st;
-    else if (gen_status != CP2_OK) status = gen_status;
-    cur.swap(next);
-  }
-  if (total_bytes) *total_bytes = bytes;
-  return status;
+  std::vector<std::string> names(dir ? n : 0);
+  for (size_t i = 0; i < names.size(); ++i) names[i] = input_json_name(dir, slot_idx[i]);
+  return export_in_chunks(n, batch, threads, [&](size_t b0, size_t m, cp2_proof_input** out) {
+    return cp2_proof_inputs_generate_batch(ds, slot_idx + b0, m, entropy, out);
+  }, [&](size_t i) { return dir ? names[i].c_str() : nullptr; }, total_bytes);
 } catch (const std::bad_alloc&) {
   return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
 } catch (...) {
@@ -996,13 +885,10 @@ static int build_streamed_in_mode(cp2_ctx* ctx, const cp2_config* cfg, uint64_t 
   canonical_felt(entropy_in, entropy);
   *out = nullptr;
   CP2_TRY(dataset_check(cfg, first_slot, n_local));
-  if (!is_pow2(cfg->n_cells)) return CP2_ERR_INVALID;                    // sample/bn254.nim:19-20
-  if (cfg->n_samples && cfg->n_cells < 2) return CP2_ERR_INVALID;        // extractLowBits asserts k > 0, types/bn254.nim:48
   CP2_TRY(trees_check_geometry(cfg->cell_size, cfg->block_size, cfg->n_cells, n_local));
-  {
-    const size_t cpb = cfg->block_size / cfg->cell_size, depth = (layer_sizes_of(cpb).size() - 1) + (layer_sizes_of(cfg->n_cells / cpb).size() - 1);
-    if (depth > (size_t)cfg->max_depth) return CP2_ERR_INVALID;          // padMerkleProof assert, types.nim:29
-  }
+  // (the dataset tree is not asked about here: the heads, slotProof among them, are made by cp2_dataset_export_streamed, which refuses then)
+  const std::string refusal = proof_shape_refusal(*cfg, config_slot_tree_depth(*cfg), 0);
+  if (!refusal.empty()) { ctx->err = refusal; return CP2_ERR_INVALID; }
   CP2_HIP(ctx, hipSetDevice(ctx->device));
   if (threads < 1) threads = 1;
   const size_t ns = cfg->n_samples, md = (size_t)cfg->max_depth, cs = cfg->cell_size;
@@ -1064,16 +950,12 @@ static int build_streamed_in_mode(cp2_ctx* ctx, const cp2_config* cfg, uint64_t 
             if (from_file) {      // sampled cells straight from the slot file (slot.nim:57-68)
               std::vector<uint8_t> cells(ns * cs);
               const std::string fname = slot_file_name(file_base, first_slot + s);
-              int fd = open(fname.c_str(), O_RDONLY);
-              int err = 0;
-              if (fd >= 0) {
-                for (size_t c = 0; c < ns && !err; ++c) err = read_file_cell(fd, cs, idx[c], &cells[c * cs]);
-                close(fd);
-              }
-              if (fd < 0 || err) {   // reported like the classic path ("cannot open / cannot read <file>"); no body for this slot
+              const int err = slot_file_read_list(fname, ns, [&](size_t) { return cs; }, [&](size_t c) { return idx[c] * cs; },
+                                                  [&](size_t c) { return &cells[c * cs]; });
+              if (err >= 0) {   // reported like the classic path ("cannot open / cannot read <file>"); no body for this slot
                 task_status.store(CP2_ERR_IO);
                 std::lock_guard<std::mutex> lk(io_mu);
-                if (io_error.empty()) io_error = slot_file_error(fname, fd < 0 ? 0 : err);
+                if (io_error.empty()) io_error = slot_file_error(fname, err);
                 have = false;
               } else {
                 text_body(body, cfgv, ns, cells.data(), paths);
@@ -1236,44 +1118,18 @@ extern "C" int cp2_dataset_export_streamed(cp2_dataset* ds, const char* dir, int
   if (!ds || !ds->prepared) return CP2_ERR_INVALID;
   if (!ds->have_roots) CP2_TRY(cp2_dataset_set_roots(ds, nullptr));
   if (ds->dsizes.size() - 1 > (size_t)ds->cfg.max_log2_nslots) return CP2_ERR_INVALID;   // padMerkleProof assert
-  if (threads < 1) threads = 1;
+  struct Scratch { std::string head; std::vector<uint8_t> proof; };
   const size_t n = ds->n_local;
-  if ((size_t)threads > n) threads = (int)n;
-  std::vector<int> status(threads, CP2_OK);
-  std::vector<uint64_t> bytes(threads, 0);
-  auto work = [&](int t) {
-    try {
-      std::string head;
-      std::vector<uint8_t> proof;
-      for (size_t s = t; s < n; s += threads) {
-        const uint64_t slot = ds->first_slot + s;
-        head.clear();
-        fill_slot_proof(ds, slot, proof);
-        text_head(head, ds->cfg, slot, &ds->dlayers[ds->dlayers.size() - 32], ds->prep_entropy, &ds->dlayers[slot * 32], proof.data());
-        bytes[t] += head.size() + ds->bodies.size[s];
-        if (dir) {
-          std::string name = std::string(dir) + "/input_" + std::to_string(slot) + ".json";
-          int st = write_head_and_body(name.c_str(), head, ds->bodies, s);
-          if (st != CP2_OK) status[t] = st;
-        }
-      }
-    } catch (...) {
-      status[t] = CP2_ERR_ALLOC;
-    }
-  };
-  {
-    Workers pool(threads > 1 ? threads - 1 : 1);
-    for (int t = 1; t < threads; ++t) pool.submit([&, t] { work(t); });
-    work(0);
-    pool.wait_idle();
-  }
-  uint64_t tot = 0;
-  for (int t = 0; t < threads; ++t) {
-    tot += bytes[t];
-    if (status[t] != CP2_OK) return status[t];
-  }
-  if (total_bytes) *total_bytes = tot;
-  return CP2_OK;
+  std::vector<Scratch> scratch(std::min<size_t>((size_t)std::max(threads, 1), n));   // one per formatting thread, reused from slot to slot
+  return format_strided(n, threads, [&](int t, size_t s, uint64_t* bytes) {
+    std::string& head = scratch[t].head;
+    const uint64_t slot = ds->first_slot + s;
+    head.clear();
+    fill_slot_proof(ds, slot, scratch[t].proof);
+    text_head(head, ds->cfg, slot, &ds->dlayers[ds->dlayers.size() - 32], ds->prep_entropy, &ds->dlayers[slot * 32], scratch[t].proof.data());
+    *bytes += head.size() + ds->bodies.size[s];
+    return dir ? write_head_and_body(input_json_name(dir, slot).c_str(), head, ds->bodies, s) : CP2_OK;
+  }, total_bytes);
 } catch (const std::bad_alloc&) {
   return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
 } catch (...) {
@@ -1291,13 +1147,7 @@ extern "C" int cp2_dataset_streamed_json(cp2_dataset* ds, uint64_t slot_idx, cha
   fill_slot_proof(ds, slot_idx, proof);
   text_head(head, ds->cfg, slot_idx, &ds->dlayers[ds->dlayers.size() - 32], ds->prep_entropy, &ds->dlayers[slot_idx * 32], proof.data());
   CP2_TRY(ds->bodies.append(slot_idx - ds->first_slot, head));
-  char* buf = (char*)std::malloc(head.size() + 1);
-  if (!buf) return CP2_ERR_ALLOC;
-  std::memcpy(buf, head.data(), head.size());
-  buf[head.size()] = 0;
-  *text = buf;
-  if (len) *len = head.size();
-  return CP2_OK;
+  return text_to_malloc(head, text, len);
 } catch (const std::bad_alloc&) {
   return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
 } catch (...) {

@@ -20,10 +20,11 @@
 //
 // The engine behind both entry points (cp2i::prove_requests, dataset_obj.hpp) is also the compact branch of
 // cp2_proof_inputs_generate_batch (proof_input.cpp): n requests on one dataset under one entropy, error texts without the request.
+//
+// Shared with the one-dataset routes, and not in here: the shape refusals validate() passes on (proof_shape_refusal) and the two-stage
+// pipeline cp2_proof_inputs_export_many is one call of (export_in_chunks), both in proof_export.hpp; the reader of the touched blocks
+// and of the sampled cells of a slot file (slot_file_read_list, fill_pipeline.hpp).
 #include <hip/hip_runtime.h>
-
-#include <fcntl.h>
-#include <unistd.h>
 
 #include <algorithm>
 #include <cstring>
@@ -76,14 +77,9 @@ int validate(cp2_ctx* ctx, cp2_dataset* const* ds, const uint64_t* slot_idx, siz
                                 std::to_string(d->first_slot + d->n_local - 1) + ")");
     if (!d->have_roots && !(d->first_slot == 0 && d->n_local == c.n_slots))
       return refuse(ctx, i, "its dataset has no dataset tree: not all of its slots are local and cp2_dataset_set_roots was never called");
-    if (!is_pow2(c.n_cells) || (c.n_samples && c.n_cells < 2))   // sample/bn254.nim:19-20, types/bn254.nim:48
-      return refuse(ctx, i, "nCells " + std::to_string(c.n_cells) + " is not a power of two >= 2");
-    const size_t cpb = c.block_size / c.cell_size;
-    if (depth_of(cpb) + depth_of(c.n_cells / cpb) > (size_t)c.max_depth)   // padMerkleProof assert, types.nim:29
-      return refuse(ctx, i, "its slot tree is deeper than maxDepth");
-    if (depth_of(c.n_slots) > (size_t)c.max_log2_nslots)
-      return refuse(ctx, i, "its dataset tree is deeper than maxLog2NSlots");
-    if (!d->trees && d->tree_mode == 2 && d->csizes.size() - 1 != depth_of(c.n_cells / cpb))
+    const std::string shape = proof_shape_refusal(c, config_slot_tree_depth(c), config_dataset_tree_depth(c));
+    if (!shape.empty()) return refuse(ctx, i, shape);
+    if (!d->trees && d->tree_mode == 2 && d->csizes.size() - 1 != depth_of(c.n_cells / (c.block_size / c.cell_size)))
       return refuse(ctx, i, "its compact layers do not match its configuration");
   }
   return CP2_OK;
@@ -214,18 +210,13 @@ int run_pass(cp2_ctx* ctx, const std::vector<const Req*>& rq, size_t n_rf, size_
         const size_t q0 = CF + k * ns;                                     // compact lane of the request's first counter
         const Req* r = rq[nr + q0 / ns];
         const std::string fname = slot_file_name(r->ds->file_base, r->slot);
-        const int fd = open(fname.c_str(), O_RDONLY);
-        if (fd < 0) { failed[w] = who(named, r) + "slot " + std::to_string(r->slot) + ": " + slot_file_error(fname, 0); return false; }
-        int err = 0;
-        size_t c = 0;
-        for (; c < ns && !err; ++c) err = slot_file_read_rest(fd, h_blocks.u8() + (q0 - CF + c) * bs, bs, blk[q0 + c] * bs);
-        close(fd);
-        if (err) {
-          failed[w] = who(named, r) + "block " + std::to_string(blk[q0 + c - 1]) + " of slot " + std::to_string(r->slot) +
+        size_t bad = 0;
+        const int err = slot_file_read_list(fname, ns, [&](size_t) { return bs; }, [&](size_t c) { return blk[q0 + c] * bs; },
+                                            [&](size_t c) { return h_blocks.u8() + (q0 - CF + c) * bs; }, &bad);
+        if (err >= 0)
+          failed[w] = who(named, r) + (err ? "block " + std::to_string(blk[q0 + bad]) + " of slot " : std::string("slot ")) + std::to_string(r->slot) +
                       ": " + slot_file_error(fname, err);
-          return false;
-        }
-        return true;
+        return err < 0;
       });
       for (const auto& f : failed)
         if (!f.empty()) { ctx->err = f; return CP2_ERR_IO; }
@@ -288,14 +279,11 @@ int run_pass(cp2_ctx* ctx, const std::vector<const Req*>& rq, size_t n_rf, size_
       on_threads(fill_threads(ctx), n_rfile, [&](int w, size_t k) {
         const Req* r = rq[n_rf + k];
         const std::string fname = slot_file_name(r->ds->file_base, r->slot);
-        const int fd = open(fname.c_str(), O_RDONLY);
-        if (fd < 0) { failed[w] = who(named, r) + slot_file_error(fname, 0); return false; }
-        int err = 0;
         const size_t p0 = (n_rf + k) * ns;
-        for (size_t c = 0; c < ns && !err; ++c) err = read_file_cell(fd, cs, idx[p0 + c], store->cells.u8() + (p0 + c) * cs);
-        close(fd);
-        if (err) { failed[w] = who(named, r) + slot_file_error(fname, err); return false; }
-        return true;
+        const int err = slot_file_read_list(fname, ns, [&](size_t) { return cs; }, [&](size_t c) { return idx[p0 + c] * cs; },
+                                            [&](size_t c) { return store->cells.u8() + (p0 + c) * cs; });
+        if (err >= 0) failed[w] = who(named, r) + slot_file_error(fname, err);
+        return err < 0;
       });
       for (const auto& f : failed)
         if (!f.empty()) { ctx->err = f; return CP2_ERR_IO; }
@@ -380,8 +368,9 @@ extern "C" int cp2_proof_inputs_generate_many(cp2_ctx* ctx, cp2_dataset* const* 
   return CP2_ERR_INVALID;
 }
 
-// The same, serialised (and written where paths[i] != NULL) as cp2_dataset_export_proof_inputs does it: while the host threads turn
-// chunk k into JSON text, the device already samples and gathers chunk k+1.
+// The same, serialised (and written where paths[i] != NULL) as cp2_dataset_export_proof_inputs does it, by the same pipeline
+// (export_in_chunks, proof_export.hpp): while the host threads turn chunk k into JSON text, the device already samples and gathers
+// chunk k+1.
 extern "C" int cp2_proof_inputs_export_many(cp2_ctx* ctx, cp2_dataset* const* ds, const uint64_t* slot_idx, const uint8_t* entropies, size_t n,
                                             const char* const* paths, int threads, size_t batch, uint64_t* total_bytes) try {
   if (!ctx) return CP2_ERR_INVALID;
@@ -393,39 +382,9 @@ extern "C" int cp2_proof_inputs_export_many(cp2_ctx* ctx, cp2_dataset* const* ds
   if (n == 0) return CP2_OK;
   CP2_REFUSE_STUCK(ctx);
   CP2_TRY(prepare(ctx, ds, slot_idx, n));
-  if (batch == 0) batch = 512;
-  if (threads < 1) threads = 1;
-  uint64_t bytes = 0;
-  int status = CP2_OK;
-  std::vector<cp2_proof_input*> cur, next;
-  auto generate = [&](size_t b0, std::vector<cp2_proof_input*>& o) -> int {
-    const size_t m = std::min(batch, n - b0);
-    o.assign(m, nullptr);
-    return prove_requests(ctx, ds + b0, slot_idx + b0, entropies + 32 * b0, m, b0, true, o.data());
-  };
-  struct Release {   // whatever leaves this scope, the objects are freed
-    std::vector<cp2_proof_input*>& v;
-    ~Release() { for (auto* p : v) cp2_proof_input_free(p); v.clear(); }
-  } rel_cur{cur}, rel_next{next};
-  status = generate(0, cur);
-  for (size_t b0 = 0; status == CP2_OK && b0 < n; b0 += batch) {
-    const size_t b1 = b0 + batch;
-    int gen_status = CP2_OK, st = CP2_OK;
-    uint64_t got = 0;
-    {
-      Workers producer(1);                                   // device stage of the NEXT chunk; joined when this scope ends
-      if (b1 < n) producer.submit([&] { gen_status = generate(b1, next); });
-      st = cp2_proof_inputs_write_json_batch(cur.data(), cur.size(), paths ? paths + b0 : nullptr, threads, &got);
-    }
-    bytes += got;
-    for (auto* p : cur) cp2_proof_input_free(p);
-    cur.clear();
-    if (st != CP2_OK) status = st;
-    else if (gen_status != CP2_OK) status = gen_status;
-    cur.swap(next);
-  }
-  if (total_bytes) *total_bytes = bytes;
-  return status;
+  return export_in_chunks(n, batch, threads, [&](size_t b0, size_t m, cp2_proof_input** out) {
+    return prove_requests(ctx, ds + b0, slot_idx + b0, entropies + 32 * b0, m, b0, true, out);
+  }, [&](size_t i) { return paths ? paths[i] : nullptr; }, total_bytes);
 } catch (const std::bad_alloc&) {
   return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
 } catch (...) {

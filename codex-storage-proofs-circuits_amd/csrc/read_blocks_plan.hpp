@@ -216,15 +216,9 @@ inline bool read_blocks_read_chunk(const ReadPlan& p, size_t k, const std::vecto
   std::vector<int> failed(ng, -1);                    // per group: -1 fine, else the errno (0: open)
   on_threads(threads, ng, [&](int, size_t j) {
     const ReadGroup& g = p.groups[g0 + j];
-    const std::string fname = fill_slot_file_name(ds[g.ds].base, g.slot);
-    const int fd = open(fname.c_str(), O_RDONLY | O_CLOEXEC);
-    if (fd < 0) { failed[j] = 0; return true; }
-    for (size_t q = g.begin; q < g.end && failed[j] < 0; ++q) {
-      const size_t i = p.order[q];
-      const int e = slot_file_read_rest(fd, row_of(i), block_size, req[3 * i + 2] * (uint64_t)block_size);
-      if (e) failed[j] = e;
-    }
-    (void)close(fd);
+    failed[j] = slot_file_read_list(fill_slot_file_name(ds[g.ds].base, g.slot), g.end - g.begin, [&](size_t) { return block_size; },
+                                    [&](size_t q) { return req[3 * p.order[g.begin + q] + 2] * (uint64_t)block_size; },
+                                    [&](size_t q) { return row_of(p.order[g.begin + q]); });
     return true;
   });
   for (size_t j = 0; j < ng; ++j)

@@ -226,6 +226,38 @@ def test_export_writes_the_per_call_texts(pkg, mctx, datasets, tmp_path):
     assert mctx.export_proof_inputs_many([]) == 0
 
 
+@pytest.mark.parametrize("files", [False, True], ids=["fake", "files"])
+@pytest.mark.parametrize("mode", [1, 2, 0])
+def test_dataset_export_in_chunks_is_the_batch_call_and_export_many(pkg, mctx, tmp_path, mode, files):
+    """Dataset.export_proof_inputs over 9 of 11 slots with batch=4 -- chunks of 4, 4 and 1, the second and third generated while the
+    one before is formatted -- writes byte for byte what one cp2_proof_inputs_generate_batch call gives for the same slots, from either
+    source and whatever the dataset keeps; cp2_proof_inputs_export_many over the same requests under the same entropy writes the same
+    files (keep-trees modes 1 and 2), and the byte totals agree."""
+    base = None
+    if files:
+        base = str(tmp_path / "slot")
+        write_slot_files(base, 11, 64, 256, 31)
+    ds = build(pkg, mctx, pkg.make_config(nSlots=11, nCells=64, cellSize=256, blockSize=2048, nSamples=5, file=base), mode)
+    slots, entropy = [10, 0, 3, 1, 7, 2, 9, 5, 4], R_MOD + 987654321
+    want = [p.json() for p in ds.proof_inputs(slots, entropy)]
+    out = tmp_path / "out"
+    out.mkdir()
+    total = ds.export_proof_inputs(slots, entropy, str(out), threads=3, batch=4)
+    assert total == sum(len(w) for w in want)
+    assert sorted(os.listdir(out)) == sorted("input_%d.json" % s for s in slots)
+    for s, w in zip(slots, want):
+        assert open(out / ("input_%d.json" % s)).read() == w, s
+    assert ds.export_proof_inputs(slots, entropy, None, threads=2, batch=4) == total   # serialise only
+    if mode in (1, 2):
+        many = tmp_path / "many"
+        many.mkdir()
+        paths = [str(many / ("input_%d.json" % s)) for s in slots]
+        assert mctx.export_proof_inputs_many([(ds, s, entropy) for s in slots], paths, threads=3, batch=4) == total
+        for s, p in zip(slots, paths):
+            assert open(p, "rb").read() == open(out / ("input_%d.json" % s), "rb").read(), s
+    ds.free()
+
+
 CHUNK_CHILD = r"""
 import json, sys
 sys.path.insert(0, %(root)r)

@@ -68,6 +68,46 @@ def test_fill_pipeline_against_real_files_asan_ubsan_and_tsan(tmp_path):
         assert "read rule ok: 16 pipe cases" in r.stdout and "7 cell-reader cases" in r.stdout, (name, r.stdout)
 
 
+def test_proof_export_pieces_asan_ubsan_and_tsan(tmp_path):
+    """What the proof-input routes share (csrc/proof_export.hpp, and slot_file_read_list of csrc/fill_pipeline.hpp), compiled from the
+    product's own headers with stand-ins for the generate and format steps: the reader of listed pieces against real files and through
+    an injected reader (status, failing piece, zeros past the end, no descriptor left open), the two-stage export pipeline (chunk
+    sequence, byte total, which status wins, no object alive at return on any way out), the strided fan-out and the shape refusals.
+    Built with AddressSanitizer + UBSan and again with ThreadSanitizer.  Then slotProof for every slot of dataset trees over 1, 2, 3, 5,
+    8 and 11 slot roots against the oracle's padMerkleProof(merkleProof(..)).  No GPU, no HIP."""
+    import random
+    import sys
+    sys.path.insert(0, ROOT)
+    from oracle import poseidon2_ref as ref
+    src = os.path.join(ROOT, "tests", "host_check", "proof_export_check.cpp")
+    inc = "-I" + os.path.join(ROOT, "codex-storage-proofs-circuits_amd", "csrc")
+    exes = {}
+    for name, flags in (("asan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]), ("tsan", ["-fsanitize=thread"])):
+        exe = exes[name] = str(tmp_path / ("proof_export_" + name))
+        subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-pthread", "-Wall", *flags, inc, "-o", exe, src])
+        scratch = tmp_path / ("files_" + name)
+        scratch.mkdir()
+        r = subprocess.run([exe, "run", str(scratch)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (name, r.stdout[-2000:], r.stderr[-4000:])
+        assert "proof export check ok" in r.stdout and "ThreadSanitizer" not in r.stderr, (name, r.stdout, r.stderr[-2000:])
+        for part in ("read list ok: 7 file cases, 6 injected cases", "export pipeline ok: 18 cases", "strided fan-out ok", "shape refusals ok"):
+            assert part in r.stdout, (name, part, r.stdout)
+    rnd = random.Random(20261019)
+    max_log2 = 8
+    for n_slots in (1, 2, 3, 5, 8, 11):
+        layers = ref.merkle_tree([rnd.randrange(ref.R_MOD) for _ in range(n_slots)])
+        blob = tmp_path / ("tree_%d.bin" % n_slots)
+        blob.write_bytes(b"".join(x.to_bytes(8, "little") for x in [n_slots, max_log2, len(layers)] + [len(l) for l in layers]) +
+                         b"".join(v.to_bytes(32, "little") for l in layers for v in l))
+        r = subprocess.run([exes["asan"], "slotproof", str(blob)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (n_slots, r.stdout[-2000:], r.stderr[-4000:])
+        got = r.stdout.split()
+        assert len(got) == n_slots
+        for slot, line in enumerate(got):
+            want = ref.pad_merkle_proof(ref.merkle_proof(layers, slot), max_log2)["merklePath"]
+            assert bytes.fromhex(line) == b"".join(v.to_bytes(32, "little") for v in want), (n_slots, slot)
+
+
 def _build_text_check(pkg, tmp_path, sanitize=("-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"), name="host_text_check"):
     libdir = os.path.dirname(pkg.LIB_PATH)
     exe = str(tmp_path / name)
