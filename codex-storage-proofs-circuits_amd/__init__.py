@@ -217,6 +217,7 @@ def load_library():
         "cp2_dataset_scrub": (i32, [vp, u64, u64, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_int)]),
         "cp2_multi_dataset_scrub": (i32, [vp, u64, u64, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_int)]),
         "cp2_datasets_scrub_many": (i32, [vp, vp, sz, vp, sz, ctypes.POINTER(sz), vp, vp]),
+        "cp2_datasets_build_many": (i32, [vp, vp, vp, sz, vp]),
         "cp2_dataset_repair_blocks": (i32, [vp, vp, vp, sz, i32, cp, vp, ctypes.POINTER(sz)]),
         "cp2_multi_dataset_repair_blocks": (i32, [vp, vp, vp, sz, i32, cp, vp, ctypes.POINTER(sz)]),
         "cp2_block_proof_depth": (sz, [sz, sz, sz]),
@@ -581,6 +582,20 @@ class Context:
         self._ck(self.L.cp2_datasets_scrub_many(self.h, hs, n, _p(bad) if cap else None, cap, ctypes.byref(nb), _p(counts), _p(gran)),
                  "cp2_datasets_scrub_many")
         return gran[:n].copy(), bad[:min(cap, nb.value)].copy(), counts[:n].copy(), nb.value
+
+    def build_many(self, requests):
+        """cp2_datasets_build_many: one Dataset per (cfg, first_slot, n_local) request, all built in one pass; each is what
+        Context.dataset(cfg, first_slot, n_local) returns under the same kept mode.  All of them, or an error and none."""
+        requests = list(requests)
+        n = len(requests)
+        cfgs = (Config * max(n, 1))()
+        ranges = np.zeros((max(n, 1), 2), dtype=np.uint64)
+        for i, (cfg, first_slot, n_local) in enumerate(requests):
+            cfgs[i] = cfg                          # (a copy of the struct; the request keeps the base name it points to alive)
+            ranges[i] = (first_slot, n_local)
+        out = (ctypes.c_void_p * max(n, 1))()
+        self._ck(self.L.cp2_datasets_build_many(self.h, cfgs, _p(ranges), n, out), "cp2_datasets_build_many")
+        return [Dataset.adopt(self, r[0], ctypes.c_void_p(out[i]), int(r[1]), int(r[2])) for i, r in enumerate(requests)]
 
     def read_blocks(self, datasets, requests, check_only=False, want_data=True, want_paths=True, data=None):
         """cp2_datasets_read_blocks: the blocks named by requests (uint64[n, 3]: index into datasets, slot, block) read from the slot files,

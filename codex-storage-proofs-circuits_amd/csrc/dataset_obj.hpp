@@ -3,6 +3,7 @@
 #pragma once
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -37,6 +38,9 @@ struct cp2_dataset {
   bool prepared = false;
   uint8_t prep_entropy[32] = {};
   BodyStore bodies;
+  // cp2_datasets_build_many: what this dataset keeps (`trees->nodes`, `compact` or `local_roots`, then a borrowed view) is a slice of an
+  // allocation shared with other datasets of the same call; the allocation goes with the last of them
+  std::shared_ptr<cp2i::DevBuf> arena;
   ~cp2_dataset() { cp2_slot_trees_free(trees); }
 };
 
@@ -75,6 +79,20 @@ inline size_t config_slot_tree_depth(const cp2_config& c) {
   return (cp2i::layer_sizes_of(cpb).size() - 1) + (cp2i::layer_sizes_of(c.n_cells / cpb).size() - 1);
 }
 inline size_t config_dataset_tree_depth(const cp2_config& c) { return cp2i::layer_sizes_of(c.n_slots).size() - 1; }
+
+// What cp2_datasets_build_many (build_many.cpp) shares with cp2_dataset_build (proof_input.cpp): the request checks, the object, the
+// named mode (0 / 1 / 2; -1 with the context's error set: CODEX_P2_KEEP_TREES is malformed; -2: automatic), the automatic choice over
+// totals, the sizes the choice and the batches go by, one build attempt in a given mode and the step down after an allocation failure.
+int dataset_check(const cp2_config* cfg, uint64_t first_slot, uint64_t n_local);
+cp2_dataset* dataset_new(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local);
+int dataset_named_mode(cp2_ctx* ctx, bool* automatic);
+int dataset_mode_that_fits(cp2_ctx* ctx, unsigned __int128 data, unsigned __int128 nodes_all, unsigned __int128 compact_all,
+                           unsigned __int128 in_flight);
+size_t compact_bytes(const cp2_config& c, size_t n_slots);
+size_t dataset_kept_layout(cp2_dataset* ds, int mode);   // compact / roots only: sets tree_mode, csizes and coff; the bytes of what is kept
+size_t transient_batch_slots(const cp2_ctx* ctx, const cp2_config& c, uint64_t n_local);
+int dataset_build_in_mode(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local, int mode, cp2_dataset** out);
+bool step_down(cp2_ctx* ctx, int* mode, const char* what);
 
 namespace cp2i {
 // The one pass that makes proof inputs for n (dataset, slot, entropy) requests of one circuit (proof_many.cpp): every request's

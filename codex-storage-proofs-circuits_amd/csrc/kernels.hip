@@ -12,6 +12,7 @@
 //   k_scrub_compare_many  the same with the kept rows of every item behind an address table (many datasets in one batch)
 //   k_repair_compare      candidate block roots against the kept rows they would replace, one verdict per request (repair.cpp)
 //   k_repair_compare_addr the same with the kept row of every request at an absolute address (read_blocks.cpp: many datasets)
+//   k_scatter_rows_addr   a batch's layer written to where every item's dataset keeps it, through an address table (build_many.cpp)
 //   k_block_path_roots    a13 candidate block roots walked up their Merkle paths to the slot root, merkle.nim:51-74 (block_proofs.cpp)
 //   k_block_path_commit   the same walk; a proved block root is also stored into layer 0 of a fill session's compact buffer (fill.cpp)
 //   k_block_path_commit_nodes   the same walk; a proved path's 2 x depth + 1 nodes are stored where the session's tree has them (fill.cpp)
@@ -665,6 +666,28 @@ __global__ void __launch_bounds__(TPB) k_scrub_compare_many(const uint4* __restr
     for (int w = 0; w < TPB / 64; ++w) s += wave_count[w];
     counts[blockIdx.x] = s;
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Building many datasets in one pass (build_many.cpp): the mirror image of k_scrub_compare_many, a WRITE through an address table.  Row g
+// of the launch is row g % rows of item g / rows: the 32 bytes at src + (item * sstride + row) * 32 go to dst_addr[item] + row * 32,
+// dst_addr holding one absolute device address per item -- row 0 of what that item's dataset keeps of this layer, 16-byte aligned like
+// every 32-byte row; 0 = the item keeps nothing here, its rows are neither read nor written.  One lane per row, two 16-byte loads and two
+// 16-byte stores; consecutive lanes take consecutive rows, so with a layer-major source and rows >= 64 a wave reads and writes whole
+// contiguous runs and one table entry.  No LDS, no atomics; nothing but the rows is written.  A launch covers rows [g0, g0 + m).
+__global__ void __launch_bounds__(TPB) k_scatter_rows_addr(const uint4* __restrict__ src, size_t sstride, const uint64_t* __restrict__ dst_addr,
+                                                             size_t rows, size_t g0, size_t m) {
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= m) return;
+  const size_t g = g0 + i;
+  const size_t item = g / rows, r = g - item * rows;
+  const uint64_t a = dst_addr[item];
+  if (a == 0) return;
+  const size_t so = item * sstride + r;
+  const uint4 v0 = src[2 * so], v1 = src[2 * so + 1];
+  uint4* d = reinterpret_cast<uint4*>(a) + 2 * r;
+  d[0] = v0;
+  d[1] = v1;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1423,6 +1446,15 @@ hipError_t launch_scrub_compare_many(const void* fresh, size_t fstride, const ui
   CP2K_LAUNCH(k_scrub_compare_many, dim3((unsigned)groups), dim3(TPB), 0, st, (const uint4*)fresh, fstride, kept_addr, rows, total,
               (unsigned long long*)bits, counts);
   return hipGetLastError();
+}
+
+hipError_t launch_scatter_rows_addr(const void* src, size_t sstride, const uint64_t* dst_addr, size_t rows, size_t n_items, hipStream_t st,
+                                    size_t slice) {
+  if (n_items == 0 || rows == 0) return hipSuccess;
+  if (!src || !dst_addr || sstride < rows) return hipErrorInvalidValue;
+  return for_slices(rows * n_items, [&](size_t g0, size_t m) {
+    hipLaunchKernelGGL(k_scatter_rows_addr, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)src, sstride, dst_addr, rows, g0, m);
+  }, slice && slice < MAX_ITEMS ? slice : MAX_ITEMS);
 }
 
 hipError_t launch_repair_compare(const void* fresh, const void* kept, size_t kept_rows, const uint64_t* rows, size_t n, uint32_t* verdict,

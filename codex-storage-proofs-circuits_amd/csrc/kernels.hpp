@@ -68,6 +68,14 @@ hipError_t launch_scrub_compare(const void* fresh, size_t fstride, const void* k
 hipError_t launch_scrub_compare_many(const void* fresh, size_t fstride, const uint64_t* kept_addr, size_t rows, size_t n_items, uint64_t* bits,
                                      uint32_t* counts, hipStream_t st);
 
+// Building many datasets in one pass (build_many.cpp): the write through an address table.  Row g < rows * n_items is row g % rows of item
+// g / rows and is copied from src + (item * sstride + row) * 32 to dst_addr[item] + row * 32; dst_addr (device, n_items entries) holds
+// absolute device addresses, 16-byte aligned; 0 = the item keeps nothing here (its rows are neither read nor written).  Nothing outside
+// the rows is written.  Launched in slices of at most `slice` rows (0: what one grid holds; the tests pass small ones).
+// hipErrorInvalidValue, nothing launched: src or dst_addr NULL with work to do, sstride < rows.  rows == 0 or n_items == 0: no work.
+hipError_t launch_scatter_rows_addr(const void* src, size_t sstride, const uint64_t* dst_addr, size_t rows, size_t n_items, hipStream_t st,
+                                    size_t slice = 0);
+
 // Block repair (repair.cpp): verdict[i] = 0 when the 32-byte row i of `fresh` equals row rows[i] of `kept` (kept_rows rows), else 1.
 hipError_t launch_repair_compare(const void* fresh, const void* kept, size_t kept_rows, const uint64_t* rows, size_t n, uint32_t* verdict,
                                  hipStream_t st);

@@ -49,14 +49,14 @@ using namespace cp2text;
 // ---------------------------------------------------------------------------------------------
 // struct cp2_dataset and canonical_felt: dataset_obj.hpp (shared with proof_many.cpp)
 
-static int dataset_check(const cp2_config* cfg, uint64_t first_slot, uint64_t n_local) {
+int dataset_check(const cp2_config* cfg, uint64_t first_slot, uint64_t n_local) {
   if (n_local == 0 || first_slot > cfg->n_slots || n_local > cfg->n_slots - first_slot) return CP2_ERR_INVALID;   // (no wrap-around)
   if (cfg->max_depth < 0 || cfg->max_log2_nslots < 0) return CP2_ERR_INVALID;
   if (cfg->file_base && cfg->cell_size > SLOT_FILE_MAX_CELL) return CP2_ERR_INVALID;   // slot.nim:60-61
   return CP2_OK;
 }
 
-static cp2_dataset* dataset_new(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local) {
+cp2_dataset* dataset_new(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local) {
   cp2_dataset* ds = new (std::nothrow) cp2_dataset();
   if (!ds) return nullptr;
   ds->ctx = ctx;
@@ -93,7 +93,7 @@ static int dataset_transient_trees(const cp2_dataset* ds, size_t s0, size_t n, c
 }
 
 // bytes of the compact part (block roots and up) of n_slots slot trees
-static size_t compact_bytes(const cp2_config& c, size_t n_slots) {
+size_t compact_bytes(const cp2_config& c, size_t n_slots) {
   size_t per_slot = 0;
   for (size_t m : layer_sizes_of(c.n_cells / (c.block_size / c.cell_size))) per_slot += m;
   return n_slots * per_slot * 32;
@@ -108,12 +108,12 @@ static size_t compact_bytes(const cp2_config& c, size_t n_slots) {
 
 // Slots per batch of a transient (compact / roots-only) build: half a staging chunk of nodes (1 GiB by default: 4 slots of 8 GiB), at
 // least one slot.  The pipelined build holds two such node buffers, together one staging chunk's worth.
-static size_t transient_batch_slots(const cp2_ctx* ctx, const cp2_config& c, uint64_t n_local) {
+size_t transient_batch_slots(const cp2_ctx* ctx, const cp2_config& c, uint64_t n_local) {
   const size_t per_slot = std::max<size_t>(1, trees_node_bytes(1, c.cell_size, c.block_size, c.n_cells));
   return std::max<size_t>(1, std::min<size_t>(n_local, (ctx->stage_bytes / 2) / per_slot));
 }
 
-static int dataset_tree_mode(cp2_ctx* ctx, const cp2_config& c, uint64_t n_local, bool* automatic = nullptr) {
+int dataset_named_mode(cp2_ctx* ctx, bool* automatic) {
   if (automatic) *automatic = false;
   int mode = ctx->keep_trees;
   if (mode < 0 && !env_keep_trees(&mode)) {
@@ -122,6 +122,14 @@ static int dataset_tree_mode(cp2_ctx* ctx, const cp2_config& c, uint64_t n_local
   }
   if (mode >= 0) return mode;
   if (automatic) *automatic = true;
+  return -2;
+}
+
+// The automatic choice over totals: `data` bytes of slot data, `nodes_all` bytes when every node is kept, `compact_all` when the compact
+// layers are, `in_flight` the node buffers of two transient batches.  One dataset (dataset_tree_mode) or the sum over the datasets of one
+// cp2_datasets_build_many call (build_many.cpp), which share one staging and one pair of batches.
+int dataset_mode_that_fits(cp2_ctx* ctx, unsigned __int128 data, unsigned __int128 nodes_all, unsigned __int128 compact_all,
+                           unsigned __int128 in_flight) {
   if (const char* t = std::getenv("CODEX_P2_TEST_OPTIMISTIC"))   // test-only: start at "every node" without looking, so that the step-down chain is what finds the mode that fits
     if (*t == '1') return 1;
   size_t free_b = ctx->mem_allowance;
@@ -129,26 +137,38 @@ static int dataset_tree_mode(cp2_ctx* ctx, const cp2_config& c, uint64_t n_local
   // What a build holds at its peak: what it keeps + the builders' staging (two chunks of at most `stage_bytes`, never more than the
   // data itself) + for the transient modes the node buffers of two batches in flight + headroom (sampling scratch, the dataset tree)
   typedef unsigned __int128 u128;
-  const u128 data = (u128)n_local * c.n_cells * c.cell_size;
   const u128 staging = 2 * std::min<u128>(data, ctx->stage_bytes), headroom = std::min<u128>(data, (u128)1 << 30);
-  const u128 nodes_all = (u128)trees_node_bytes(1, c.cell_size, c.block_size, c.n_cells) * n_local;
-  const u128 in_flight = 2 * (u128)trees_node_bytes(transient_batch_slots(ctx, c, n_local), c.cell_size, c.block_size, c.n_cells);
   const u128 room = (u128)free_b * 9 / 10;
   if (nodes_all + staging + headroom <= room) return 1;
-  if ((u128)compact_bytes(c, 1) * n_local + in_flight + staging + headroom <= room) return 2;
+  if (compact_all + in_flight + staging + headroom <= room) return 2;
   return 0;
 }
 
-// compact / roots-only datasets: room for what stays of the local slots
-static int dataset_alloc_kept(cp2_dataset* ds, int mode) {
+static int dataset_tree_mode(cp2_ctx* ctx, const cp2_config& c, uint64_t n_local, bool* automatic = nullptr) {
+  const int named = dataset_named_mode(ctx, automatic);
+  if (named != -2) return named;
+  typedef unsigned __int128 u128;
+  const u128 data = (u128)n_local * c.n_cells * c.cell_size;
+  const u128 nodes_all = (u128)trees_node_bytes(1, c.cell_size, c.block_size, c.n_cells) * n_local;
+  const u128 in_flight = 2 * (u128)trees_node_bytes(transient_batch_slots(ctx, c, n_local), c.cell_size, c.block_size, c.n_cells);
+  return dataset_mode_that_fits(ctx, data, nodes_all, (u128)compact_bytes(c, 1) * n_local, in_flight);
+}
+
+// compact / roots-only datasets: room for what stays of the local slots (dataset_kept_layout: the mode, the layout and its bytes)
+size_t dataset_kept_layout(cp2_dataset* ds, int mode) {
   ds->tree_mode = mode;
-  if (mode == 0) return ds->local_roots.alloc(ds->ctx, ds->n_local * 32);
+  if (mode == 0) return ds->n_local * 32;
   const cp2_config& c = ds->cfg;
   ds->csizes = layer_sizes_of(c.n_cells / (c.block_size / c.cell_size));
   ds->coff.clear();
   size_t off = 0;
   for (size_t m : ds->csizes) { ds->coff.push_back(off); off += ds->n_local * m; }
-  return ds->compact.alloc(ds->ctx, off * 32);
+  return off * 32;
+}
+
+static int dataset_alloc_kept(cp2_dataset* ds, int mode) {
+  const size_t bytes = dataset_kept_layout(ds, mode);
+  return mode == 0 ? ds->local_roots.alloc(ds->ctx, bytes) : ds->compact.alloc(ds->ctx, bytes);
 }
 
 // ... and what stays of a finished batch `t` (local slots [base, base + t->n_slots)): its roots, or its layers from the block roots up.
@@ -220,7 +240,7 @@ static int dataset_build_transient(cp2_dataset* ds, int mode, bool allocated = f
 
 // One mode down after an allocation failure of an automatically chosen mode: everything of the failed attempt is gone by now (the
 // dataset object, its trees), the context's cached scratch goes too, and the trace / the error text say what happened.
-static bool step_down(cp2_ctx* ctx, int* mode, const char* what) {
+bool step_down(cp2_ctx* ctx, int* mode, const char* what) {
   if (*mode == 0) return false;
   const int next = *mode == 1 ? 2 : 0;
   (void)cp2_trim(ctx);
@@ -231,6 +251,16 @@ static bool step_down(cp2_ctx* ctx, int* mode, const char* what) {
   ctx->err.clear();
   *mode = next;
   return true;
+}
+
+// one attempt in a given mode: *out, or nothing of the attempt left
+int dataset_build_in_mode(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local, int mode, cp2_dataset** out) {
+  *out = nullptr;
+  std::unique_ptr<cp2_dataset> ds(dataset_new(ctx, cfg, first_slot, n_local));
+  if (!ds) return CP2_ERR_ALLOC;
+  CP2_TRY(mode == 1 ? dataset_build_trees(ds.get(), 0, nullptr) : dataset_build_transient(ds.get(), mode));
+  *out = ds.release();
+  return CP2_OK;
 }
 
 static int dataset_build(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local, bool always_keep_trees, cp2_dataset** out) {
@@ -244,14 +274,8 @@ static int dataset_build(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slo
   int mode = always_keep_trees ? 1 : dataset_tree_mode(ctx, *cfg, n_local, &automatic);
   if (mode < 0) return CP2_ERR_INVALID;
   for (;;) {
-    std::unique_ptr<cp2_dataset> ds(dataset_new(ctx, cfg, first_slot, n_local));
-    if (!ds) return CP2_ERR_ALLOC;
-    const int st = mode == 1 ? dataset_build_trees(ds.get(), 0, nullptr) : dataset_build_transient(ds.get(), mode);
-    if (st == CP2_OK) {
-      *out = ds.release();
-      return CP2_OK;
-    }
-    ds.reset();                                   // (frees what the failed attempt holds before anything else is tried)
+    const int st = dataset_build_in_mode(ctx, cfg, first_slot, n_local, mode, out);   // (a failed attempt holds nothing by now)
+    if (st == CP2_OK) return CP2_OK;
     if (st != CP2_ERR_ALLOC || !automatic || !step_down(ctx, &mode, "dataset build")) return st;
   }
 }

@@ -78,7 +78,7 @@ cp2i::BuildScratch::~BuildScratch() {
   if (ctx->aux2_stream) (void)hipStreamSynchronize(ctx->aux2_stream);
 }
 
-static int trees_layout(cp2_slot_trees* t, cp2i::DevBuf* borrow_from = nullptr) {
+int trees_layout(cp2_slot_trees* t, cp2i::DevBuf* borrow_from) {
   t->bsizes = layer_sizes_of(t->cpb);
   t->tsizes = layer_sizes_of(t->nblocks);
   if (t->bsizes.size() > (size_t)cp2k::TreeGeom::MAX_LAYERS || t->tsizes.size() > (size_t)cp2k::TreeGeom::MAX_LAYERS) return CP2_ERR_INVALID;
@@ -123,7 +123,7 @@ void cp2i::trees_geom(const cp2_slot_trees* t, cp2k::TreeGeom* g) {
   for (size_t k = 0; k < t->tsizes.size(); ++k) { g->toff[k] = t->toff[k]; g->tsz[k] = t->tsizes[k]; }
 }
 
-static cp2_slot_trees* trees_new(cp2_ctx* ctx, size_t n_slots, size_t cell_size, size_t block_size, size_t n_cells) {
+cp2_slot_trees* trees_new(cp2_ctx* ctx, size_t n_slots, size_t cell_size, size_t block_size, size_t n_cells) {
   cp2_slot_trees* t = new (std::nothrow) cp2_slot_trees();
   if (!t) return nullptr;
   t->ctx = ctx;

@@ -29,6 +29,12 @@ struct cp2_slot_trees {
   std::string file_base;
 };
 
+// An empty batch object of this geometry, and its layout: layer sizes and offsets for its n_slots, then the node buffer -- allocated
+// (pooled when pooled_nodes is set), or, with borrow_from, a view of that buffer (grown from the context's scratch pool when too small).
+// The builders (slot_trees.cpp) start with these; build_many.cpp makes the every-node trees of its datasets with them.
+cp2_slot_trees* trees_new(cp2_ctx* ctx, size_t n_slots, size_t cell_size, size_t block_size, size_t n_cells);
+int trees_layout(cp2_slot_trees* t, cp2i::DevBuf* borrow_from = nullptr);
+
 namespace cp2i {
 
 constexpr uint64_t NO_ROW = ~0ULL;
