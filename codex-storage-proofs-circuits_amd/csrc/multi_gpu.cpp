@@ -27,6 +27,8 @@
 #include <memory>
 #include <mutex>
 #include <new>
+#include <numeric>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -250,7 +252,10 @@ struct cp2_multi_dataset {
   cp2_multi* m = nullptr;
   cp2_config cfg{};
   std::string file_base;
-  struct Shard { int dev = 0; uint64_t first = 0, count = 0; cp2_dataset* ds = nullptr; cp2_slot_trees* units = nullptr; };
+  struct Shard {
+    int dev = 0; uint64_t first = 0, count = 0; cp2_dataset* ds = nullptr; cp2_slot_trees* units = nullptr;
+    cp2_ctx* ctx() const { return ds ? cp2_dataset_ctx(ds) : units->ctx; }
+  };
   std::vector<Shard> shards;                 // ranges count slots (by slots) or units (by units)
   uint64_t units_per_slot = 1;               // S; 1 = by slots
   // by units: host copies of the upper layers (layer k of ALL slots contiguous: n_slots * (S >> k) elements) and the dataset tree
@@ -265,6 +270,7 @@ struct cp2_multi_dataset {
     for (auto& s : shards) { cp2_dataset_free(s.ds); cp2_slot_trees_free(s.units); }
   }
   bool by_units() const { return units_per_slot > 1; }
+  size_t levels() const { size_t k = 0; while (((uint64_t)1 << k) < units_per_slot) ++k; return k; }   // log2 S: the layers above a unit's root
   Shard* owner(uint64_t item) {              // the shard holding slot `item` (by slots) or unit `item` (by units)
     for (auto& s : shards)
       if (item >= s.first && item < s.first + s.count) return &s;
@@ -293,6 +299,37 @@ template <typename F> int for_each_shard(size_t n, F f) {
   return CP2_OK;
 }
 
+// for_each_shard where a failing shard says why: f(i, why).  m->err = the text of the lowest shard that gave one.
+template <typename F> int for_each_shard_named(cp2_multi* m, size_t n, F f) {
+  std::vector<std::string> errs(n);
+  const int st = for_each_shard(n, [&](size_t i) -> int { return f(i, errs[i]); });
+  if (st != CP2_OK) for (auto& e : errs) if (!e.empty()) { m->err = e; break; }
+  return st;
+}
+
+// "device D, slots|units a..z: <the context's error, else the status by name>"
+std::string shard_failure(const cp2_multi_dataset* mds, const cp2_multi_dataset::Shard& s, uint64_t a, uint64_t z, cp2_ctx* ctx, int status) {
+  return "device " + std::to_string(mds->m->devices[s.dev]) + (mds->by_units() ? ", units " : ", slots ") + std::to_string(a) + ".." + std::to_string(z) +
+         ": " + (*cp2_last_error(ctx) ? cp2_last_error(ctx) : cp2_strerror(status));
+}
+
+// the host threads divided over the shards, f(i, threads of shard i, its bytes) on every shard, the bytes summed
+template <typename F> int for_each_shard_summing(size_t world, int threads, uint64_t* total_bytes, F f) {
+  const int per = std::max(1, threads / (int)world);
+  std::vector<uint64_t> bytes(world, 0);
+  const int st = for_each_shard(world, [&](size_t i) -> int { return f(i, per, &bytes[i]); });
+  if (total_bytes) *total_bytes = std::accumulate(bytes.begin(), bytes.end(), (uint64_t)0);
+  return st;
+}
+
+// the files cp2_multi_dataset_build_cached gives shard `shard` of `world`: its tree file and, by slots, the kept-nodes file beside it
+std::vector<std::string> shard_cache_paths(const char* cache_path, uint64_t units_per_slot, size_t shard, size_t world) {
+  const std::string of = ".shard" + std::to_string(shard) + "of" + std::to_string(world);
+  if (units_per_slot > 1) return {std::string(cache_path) + ".units" + std::to_string(units_per_slot) + of};
+  const std::string tree = world == 1 ? std::string(cache_path) : cache_path + of;
+  return {tree, tree + ".kept"};
+}
+
 struct DeviceRestore {   // the caller's current device is left as it was found
   int dev = -1;
   DeviceRestore() { if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = -1; } }
@@ -302,13 +339,12 @@ struct DeviceRestore {   // the caller's current device is left as it was found
 // One shard's contribution to the exchange: `count` roots in device memory of `ctx`, rows [first, first + count) of the whole.
 struct RootsPart { cp2_ctx* ctx; const void* d_roots; uint64_t first, count; };
 // What the exchange leaves behind: all n roots on EVERY device (dev[i], in memory owned by this object), or in host memory.
-struct Exchanged {
+// timed_out (exchange_policy.hpp): given up with work still queued on the participating streams, NOT a failed or mis-verified
+// exchange -- nothing more may be enqueued on those streams (a retry through host memory would wait on them for ever)
+struct Exchanged : ExchangeOutcome {
   std::vector<DevBuf> gath, all;
   std::vector<const void*> dev;
   std::vector<uint8_t> host;
-  bool on_device = false;
-  bool timed_out = false;   // the exchange was given up with work still queued on the participating streams: NOT a failed or mis-verified
-                            // exchange -- nothing more may be enqueued on those streams (a retry through host memory would wait on them for ever)
   // work that may still be reading or writing these buffers could not be waited for (it timed out): they must never go back to
   // a pool or to the device's allocator -- they are dropped from the books instead (a leak, said so in the error message)
   void abandon() {
@@ -325,6 +361,23 @@ double exchange_timeout_s() {
   bool set = false;
   if (env_decimal("CODEX_P2_EXCHANGE_TIMEOUT_S", &v, &set) && set) return (double)v;
   return 120.0;
+}
+
+// every participating stream drained without a bound; a failed copy or kernel is reported by its context
+int sync_parts(const std::vector<RootsPart>& parts) {
+  for (auto& p : parts) {
+    CP2_HIP(p.ctx, hipSetDevice(p.ctx->device));
+    CP2_HIP(p.ctx, hipStreamSynchronize(p.ctx->stream));
+  }
+  return CP2_OK;
+}
+
+// CODEX_P2_TEST_EXCHANGE_FAULT (test-only, include/codex_p2.h): read where it acts, anything else is no fault
+enum class ExchangeFault { None, HangInit, HangCollective, Corrupt };
+ExchangeFault exchange_test_fault() {
+  const char* e = std::getenv("CODEX_P2_TEST_EXCHANGE_FAULT");
+  const std::string v = e ? e : "";
+  return v == "hang_init" ? ExchangeFault::HangInit : v == "hang_collective" ? ExchangeFault::HangCollective : v == "corrupt" ? ExchangeFault::Corrupt : ExchangeFault::None;
 }
 
 // Waits until every participating context's stream has drained.  Bounded: false when `timeout_s` (> 0) passed first.
@@ -377,9 +430,8 @@ bool comm_init_all(Rccl& r, const std::vector<int>& devices, size_t world, doubl
   st->comms.assign(world, nullptr);
   st->devices.assign(devices.begin(), devices.begin() + (long)world);
   std::thread th([st, &r] {
-    if (const char* fault = std::getenv("CODEX_P2_TEST_EXCHANGE_FAULT"))      // test-only: a communicator creation that never returns
-      if (std::strcmp(fault, "hang_init") == 0)
-        for (;;) std::this_thread::sleep_for(std::chrono::seconds(3600));
+    if (exchange_test_fault() == ExchangeFault::HangInit)                     // test-only: a communicator creation that never returns
+      for (;;) std::this_thread::sleep_for(std::chrono::seconds(3600));
     ncclResult_t e = r.CommInitAll(st->comms.data(), (int)st->comms.size(), st->devices.data());
     std::lock_guard<std::mutex> lk(st->mu);
     st->result = e;
@@ -410,13 +462,14 @@ bool comm_init_all(Rccl& r, const std::vector<int>& devices, size_t world, doubl
 // librccl loads; host memory otherwise; by name also plain device-to-device copies (CP2_GATHER_COPY: the RCCL path's buffers,
 // layout and compaction with the collective written out as peer copies -- no library, any mix of devices).  One shard and no
 // RCCL by name: nothing moves.  `force_host`: the automatic mode's second attempt after a device path failed its verification.
-int exchange_roots(cp2_multi* m, const std::vector<RootsPart>& parts, uint64_t n, Exchanged& ex, bool force_host = false) {
+int exchange_roots(cp2_multi* m, const std::vector<RootsPart>& parts, uint64_t n, Exchanged& ex, bool force_host) {
   const size_t world = parts.size();
   ex.dev.assign(world, nullptr);
   if (world == 1 && m->gather != CP2_GATHER_RCCL) {   // (RCCL asked for by name: a communicator of one rank, as a self-test of the path)
     m->gather_note = "none (one shard: nothing to exchange)";
     ex.dev[0] = parts[0].d_roots;
     ex.on_device = true;
+    ex.moved = false;
     return CP2_OK;
   }
   DeviceRestore restore;
@@ -475,10 +528,7 @@ int exchange_roots(cp2_multi* m, const std::vector<RootsPart>& parts, uint64_t n
     } else {
       // the same all-gather written out as world x (world - 1) peer copies: every shard's row block, once it is staged, into the
       // same place of every other context's buffer, on the RECEIVING context's stream (what consumes it there follows in order)
-      for (auto& p : parts) {
-        CP2_HIP(p.ctx, hipSetDevice(p.ctx->device));
-        CP2_HIP(p.ctx, hipStreamSynchronize(p.ctx->stream));
-      }
+      CP2_TRY(sync_parts(parts));
       for (size_t i = 0; i < world; ++i) {
         cp2_ctx* ctx = parts[i].ctx;
         CP2_HIP(ctx, hipSetDevice(ctx->device));
@@ -501,26 +551,23 @@ int exchange_roots(cp2_multi* m, const std::vector<RootsPart>& parts, uint64_t n
                                     hipMemcpyDeviceToDevice, ctx->stream));
       ex.dev[i] = ex.all[i].p;
     }
-    if (const char* fault = std::getenv("CODEX_P2_TEST_EXCHANGE_FAULT")) {
-      // test-only: overwrite one byte of the first row in every context's gathered copy -- what a wrong rank-to-device mapping or a
-      // misplaced block would look like to the verification that follows the exchange (tests/test_gpu_round5.py)
-      if (std::strcmp(fault, "corrupt") == 0)
-        for (size_t i = 0; i < world; ++i) {
-          cp2_ctx* ctx = parts[i].ctx;
-          CP2_HIP(ctx, hipSetDevice(ctx->device));
-          CP2_HIP(ctx, hipMemsetAsync(const_cast<uint8_t*>(static_cast<const uint8_t*>(ex.dev[i])) + 5, 0x5a, 1, ctx->stream));
-        }
-    }
-    if (const char* fault = std::getenv("CODEX_P2_TEST_EXCHANGE_FAULT")) {
-      // test-only: a collective that does not complete in time -- a host function that sleeps for the time-out and five seconds more on
-      // every participating stream (bounded: the streams do drain in the end, the device itself is never made to spin)
-      if (std::strcmp(fault, "hang_collective") == 0)
-        for (auto& p : parts) {
-          CP2_HIP(p.ctx, hipSetDevice(p.ctx->device));
-          CP2_HIP(p.ctx, hipLaunchHostFunc(p.ctx->stream, [](void* ms) { std::this_thread::sleep_for(std::chrono::milliseconds((long)(intptr_t)ms)); },
-                                           reinterpret_cast<void*>((intptr_t)((timeout_s > 0 ? timeout_s : 1) * 1000 + 5000))));
-        }
-    }
+    const ExchangeFault fault = exchange_test_fault();
+    // test-only: overwrite one byte of the first row in every context's gathered copy -- what a wrong rank-to-device mapping or a
+    // misplaced block would look like to the verification that follows the exchange (tests/test_gpu_round5.py)
+    if (fault == ExchangeFault::Corrupt)
+      for (size_t i = 0; i < world; ++i) {
+        cp2_ctx* ctx = parts[i].ctx;
+        CP2_HIP(ctx, hipSetDevice(ctx->device));
+        CP2_HIP(ctx, hipMemsetAsync(const_cast<uint8_t*>(static_cast<const uint8_t*>(ex.dev[i])) + 5, 0x5a, 1, ctx->stream));
+      }
+    // test-only: a collective that does not complete in time -- a host function that sleeps for the time-out and five seconds more on
+    // every participating stream (bounded: the streams do drain in the end, the device itself is never made to spin)
+    if (fault == ExchangeFault::HangCollective)
+      for (auto& p : parts) {
+        CP2_HIP(p.ctx, hipSetDevice(p.ctx->device));
+        CP2_HIP(p.ctx, hipLaunchHostFunc(p.ctx->stream, [](void* ms) { std::this_thread::sleep_for(std::chrono::milliseconds((long)(intptr_t)ms)); },
+                                         reinterpret_cast<void*>((intptr_t)((timeout_s > 0 ? timeout_s : 1) * 1000 + 5000))));
+      }
     // the exchange is COMPLETE when this returns: a context's buffers are read by its peers (RCCL kernels, peer copies), so none
     // of them may go back to its pool on the strength of its own stream alone
     if (!drain_streams(parts, timeout_s)) {
@@ -533,10 +580,7 @@ int exchange_roots(cp2_multi* m, const std::vector<RootsPart>& parts, uint64_t n
       if (use_rccl) { Rccl::get().abandoned = true; Rccl::get().why = "an all-gather did not complete in time"; m->comms.clear(); m->comm_world = 0; }
       return CP2_ERR_HIP;
     }
-    for (auto& p : parts) {                       // a failed copy or kernel shows up here, not in the next unrelated call
-      CP2_HIP(p.ctx, hipSetDevice(p.ctx->device));
-      CP2_HIP(p.ctx, hipStreamSynchronize(p.ctx->stream));
-    }
+    CP2_TRY(sync_parts(parts));                   // a failed copy or kernel shows up here, not in the next unrelated call
     guard.done = true;
     ex.on_device = true;
     return CP2_OK;
@@ -553,91 +597,68 @@ int exchange_roots(cp2_multi* m, const std::vector<RootsPart>& parts, uint64_t n
   return CP2_OK;
 }
 
+// exchange_until_verified (exchange_policy.hpp: when a device path is retried through host memory) over exchange_roots: install(ex)
+// and verify(bad) see what the latest exchange left behind; its buffers live until the next one
+template <typename Install, typename Verify>
+int exchange_verified(cp2_multi* m, const std::vector<RootsPart>& parts, uint64_t n, Install install, Verify verify) {
+  std::optional<Exchanged> ex;
+  return exchange_until_verified(
+      m->gather, parts.size(), m->gather_note, m->err,
+      [&](bool force_host) { ex.emplace(); ex->status = exchange_roots(m, parts, n, *ex, force_host); return ExchangeOutcome(*ex); },
+      [&](const ExchangeOutcome&) -> int { return install(*ex); }, [&](const ExchangeOutcome&, std::string& bad) -> int { return verify(bad); },
+      [](const std::string& line) { if (std::getenv("CP2_TRACE")) std::fprintf(stderr, "[cp2 trace] %s\n", line.c_str()); });
+}
+
 // by slots: the exchange, then the dataset tree on every device -- and a check that costs one 32-byte-per-slot download per
 // shard: (1) every device finds ITS OWN roots at its own rows of the list it was handed, (2) every device computed the same
 // dataset root.  Together: every device holds the same list and every block of it is where its owner put it, i.e. the exchange
-// did what it is for -- whatever carried it.  A wrong rank-to-device mapping, a misplaced block of the padded layout or a peer
-// that delivered stale memory gives CP2_ERR_HIP here, never a wrong dataSetRoot in an input.json.  In the automatic mode a
-// device path that fails the check is retried once through host memory.
+// did what it is for -- whatever carried it (also a one-rank communicator asked for by name: the RCCL path's self-test).  A wrong
+// rank-to-device mapping, a misplaced block of the padded layout or a peer that delivered stale memory gives CP2_ERR_HIP here,
+// never a wrong dataSetRoot in an input.json.
 int gather_roots_and_build_trees(cp2_multi_dataset* mds) {
-  cp2_multi* m = mds->m;
-  const size_t world = mds->shards.size();
+  auto& shards = mds->shards;
+  const size_t world = shards.size();
   std::vector<RootsPart> parts;
-  for (auto& s : mds->shards) parts.push_back({cp2_dataset_ctx(s.ds), cp2_dataset_local_roots_dev(s.ds), s.first, s.count});
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    Exchanged ex;
-    int st = exchange_roots(m, parts, mds->cfg.n_slots, ex, attempt == 1);
-    if (st != CP2_OK) {
-      if (exchange_may_retry_on_host(st, ex.timed_out, m->gather, world, attempt)) {   // the device path broke (NOT: timed out): host memory carries 1 MiB just as well
-        const std::string first = m->err;
-        m->err.clear();
-        Exchanged ex2;
-        st = exchange_roots(m, parts, mds->cfg.n_slots, ex2, true);
-        if (st != CP2_OK) { m->err = first; return st; }
-        m->gather_note += " [first attempt: " + first + "]";
-        CP2_TRY(for_each_shard(world, [&](size_t i) -> int { return cp2_dataset_set_roots(mds->shards[i].ds, ex2.host.data()); }));
-        attempt = 1;
-      } else {
-        return st;
-      }
-    } else {
-      CP2_TRY(for_each_shard(world, [&](size_t i) -> int {
-        return ex.on_device ? cp2_dataset_set_roots_dev(mds->shards[i].ds, ex.dev[i]) : cp2_dataset_set_roots(mds->shards[i].ds, ex.host.data());
-      }));
-    }
-    if (m->gather_note.rfind("none", 0) == 0) return CP2_OK;   // nothing moved
-    // ---- verification (also of a one-rank communicator asked for by name: the RCCL path's self-test)
+  for (auto& s : shards) parts.push_back({s.ctx(), cp2_dataset_local_roots_dev(s.ds), s.first, s.count});
+  auto install = [&](const Exchanged& ex) {
+    return for_each_shard(world, [&](size_t i) -> int {
+      return ex.on_device ? cp2_dataset_set_roots_dev(shards[i].ds, ex.dev[i]) : cp2_dataset_set_roots(shards[i].ds, ex.host.data());
+    });
+  };
+  auto verify = [&](std::string& bad) -> int {
     std::vector<char> in_place(world, 1);
     std::vector<std::array<uint8_t, 32>> roots(world);
     CP2_TRY(for_each_shard(world, [&](size_t i) -> int {
       bool ok = false;
-      CP2_TRY(dataset_own_roots_in_place(mds->shards[i].ds, &ok));
+      CP2_TRY(dataset_own_roots_in_place(shards[i].ds, &ok));
       in_place[i] = ok ? 1 : 0;
-      return cp2_dataset_root(mds->shards[i].ds, roots[i].data());
+      return cp2_dataset_root(shards[i].ds, roots[i].data());
     }));
-    std::string bad;
     for (size_t i = 0; i < world && bad.empty(); ++i) {
-      if (!in_place[i]) bad = "the device of shard " + std::to_string(i) + " does not find its own slot roots at rows " + std::to_string(mds->shards[i].first) + ".." +
-                              std::to_string(mds->shards[i].first + mds->shards[i].count) + " of the gathered list";
+      if (!in_place[i]) bad = "the device of shard " + std::to_string(i) + " does not find its own slot roots at rows " + std::to_string(shards[i].first) + ".." +
+                              std::to_string(shards[i].first + shards[i].count) + " of the gathered list";
       else if (roots[i] != roots[0]) bad = "shards 0 and " + std::to_string(i) + " computed different dataset roots from the gathered list";
     }
-    if (bad.empty()) return CP2_OK;
-    if (attempt == 0 && m->gather == CP2_GATHER_AUTO && ex.on_device) {
-      if (std::getenv("CP2_TRACE")) std::fprintf(stderr, "[cp2 trace] exchange verification FAILED (%s: %s): once more through host memory\n", m->gather_note.c_str(), bad.c_str());
-      continue;
-    }
-    m->err = "exchange verification failed (" + m->gather_note + "): " + bad;
-    return CP2_ERR_HIP;
-  }
-  return CP2_ERR_HIP;   // not reached
+    return CP2_OK;
+  };
+  return exchange_verified(mds->m, parts, mds->cfg.n_slots, install, verify);
 }
 
 // by units: the exchange of unit roots, then -- once, on the first device -- the log2 S upper layers of every slot tree
 // (inner layers of gen_input/bn254.nim:29's tree: keys 0, never the bottom rule) and the dataset tree over the slot roots.
 // Verified like the exchange of slot roots: every shard finds its own unit roots at its rows of the list the first device built from.
 int gather_unit_roots_and_build_upper(cp2_multi_dataset* mds) {
-  cp2_multi* m = mds->m;
   const uint64_t S = mds->units_per_slot, n_slots = mds->cfg.n_slots, n_units = n_slots * S;
   std::vector<RootsPart> parts;
-  for (auto& s : mds->shards) parts.push_back({s.units->ctx, cp2_slot_trees_roots_dev(s.units), s.first, s.count});
-  for (auto& p : parts) {                          // the unit trees are complete before their roots travel
-    CP2_HIP(p.ctx, hipSetDevice(p.ctx->device));
-    CP2_HIP(p.ctx, hipStreamSynchronize(p.ctx->stream));
-  }
+  for (auto& s : mds->shards) parts.push_back({s.ctx(), cp2_slot_trees_roots_dev(s.units), s.first, s.count});
+  CP2_TRY(sync_parts(parts));                      // the unit trees are complete before their roots travel
   DeviceRestore restore;
   cp2_ctx* ctx = parts[0].ctx;
-  size_t levels = 0;
-  while (((uint64_t)1 << levels) < S) ++levels;
+  const size_t levels = mds->levels();
   size_t total = 0;
   mds->upper_off.clear();
   for (size_t k = 0; k <= levels; ++k) { mds->upper_off.push_back(total); total += n_slots * (S >> k); }
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    Exchanged ex;
-    int st = exchange_roots(m, parts, n_units, ex, attempt == 1);
-    if (st != CP2_OK) {
-      if (exchange_may_retry_on_host(st, ex.timed_out, m->gather, parts.size(), attempt)) { m->gather_note += " [failed: " + m->err + "]"; m->err.clear(); continue; }
-      return st;
-    }
+  auto install = [&](const Exchanged& ex) -> int {
     CP2_HIP(ctx, hipSetDevice(ctx->device));
     DevBuf up, dtree;
     CP2_TRY(up.scratch(ctx, total * 32));
@@ -655,9 +676,10 @@ int gather_unit_roots_and_build_upper(cp2_multi_dataset* mds) {
     CP2_HIP(ctx, hipMemcpyAsync(mds->upper.data(), up.p, total * 32, hipMemcpyDeviceToHost, ctx->stream));
     CP2_HIP(ctx, hipMemcpyAsync(mds->dlayers.data(), dtree.p, dtotal * 32, hipMemcpyDeviceToHost, ctx->stream));
     CP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (parts.size() == 1) return CP2_OK;
-    // every shard's own unit roots against rows [first, first + count) of what the first device built from
-    std::string bad;
+    return CP2_OK;
+  };
+  // every shard's own unit roots against rows [first, first + count) of what the first device built from
+  auto verify = [&](std::string& bad) -> int {
     std::vector<uint8_t> own;
     for (size_t i = 0; i < parts.size() && bad.empty(); ++i) {
       own.resize(parts[i].count * 32);
@@ -668,15 +690,9 @@ int gather_unit_roots_and_build_upper(cp2_multi_dataset* mds) {
         bad = "the unit roots of shard " + std::to_string(i) + " are not at rows " + std::to_string(parts[i].first) + ".." + std::to_string(parts[i].first + parts[i].count) +
               " of the list the first device received";
     }
-    if (bad.empty()) return CP2_OK;
-    if (attempt == 0 && m->gather == CP2_GATHER_AUTO && ex.on_device) {
-      if (std::getenv("CP2_TRACE")) std::fprintf(stderr, "[cp2 trace] exchange verification FAILED (%s: %s): once more through host memory\n", m->gather_note.c_str(), bad.c_str());
-      continue;
-    }
-    m->err = "exchange verification failed (" + m->gather_note + "): " + bad;
-    return CP2_ERR_HIP;
-  }
-  return CP2_ERR_HIP;   // not reached
+    return CP2_OK;
+  };
+  return exchange_verified(mds->m, parts, n_units, install, verify);
 }
 
 double imbalance(uint64_t items, uint64_t world) { return (double)((items + world - 1) / world * world) / (double)items; }
@@ -763,8 +779,6 @@ int multi_build(cp2_multi* m, const cp2_config* cfg, BuildKind kind, const uint8
     mds->shards[r].dev = (int)r;
     cp2_shard_range(cfg->n_slots * S, (int)r, (int)world, &mds->shards[r].first, &mds->shards[r].count);
   }
-  const int per = std::max(1, threads / (int)world);
-  std::vector<std::string> errs(world);
   // what every device has free NOW, before any shard allocates, shared out among the contexts placed on it: each context's
   // automatic residency choice plans with its share (0: the device did not answer, the context asks for itself)
   std::vector<size_t> allowance(world, 0);
@@ -777,18 +791,18 @@ int multi_build(cp2_multi* m, const cp2_config* cfg, BuildKind kind, const uint8
     }
   }
   StageTimer trace;
-  int st = for_each_shard(world, [&](size_t i) -> int {
+  CP2_TRY(for_each_shard_named(m, world, [&](size_t i, std::string& why) -> int {
     auto& s = mds->shards[i];
     int cst = CP2_OK;
     cp2_ctx* ctx = m->ctx_of(s.dev, &cst);
-    if (!ctx) { errs[i] = "device " + std::to_string(m->devices[s.dev]) + ": " + cp2_strerror(cst); return cst; }
+    if (!ctx) { why = "device " + std::to_string(m->devices[s.dev]) + ": " + cp2_strerror(cst); return cst; }
     ctx->mem_allowance = allowance[i];
     struct AllowanceReset { cp2_ctx* c; ~AllowanceReset() { c->mem_allowance = 0; } } allowance_reset{ctx};
     int r = CP2_OK;
     if (S > 1) {
       // cached: this shard's unit trees from "<cache>.units<S>.shard<i>of<world>" when that file is intact and describes exactly
       // these units of this data (cp2_slot_trees_load checks the checksum and, for slot files, their sizes and mtimes)
-      const std::string path = kind == BuildKind::Cached ? std::string(cache_path) + ".units" + std::to_string(S) + ".shard" + std::to_string(i) + "of" + std::to_string(world) : std::string();
+      const std::string path = kind == BuildKind::Cached ? shard_cache_paths(cache_path, S, i, world)[0] : std::string();
       if (kind == BuildKind::Cached && cp2_slot_trees_load(ctx, path.c_str(), &s.units) == CP2_OK) {
         const cp2_slot_trees* t = s.units;
         const bool match = t->n_slots == s.count && t->first_slot == s.first && t->units_per_slot == S && t->cell_size == cfg->cell_size &&
@@ -802,28 +816,22 @@ int multi_build(cp2_multi* m, const cp2_config* cfg, BuildKind kind, const uint8
                          : cp2_slot_trees_build_fake_units(ctx, cfg->seed, S, s.first, s.count, cfg->cell_size, cfg->block_size, cfg->n_cells / S, &s.units);
       if (r == CP2_OK && kind == BuildKind::Cached) r = cp2_slot_trees_save(s.units, path.c_str());
     } else if (kind == BuildKind::Streamed) {
-      r = cp2_dataset_build_streamed(ctx, &mds->cfg, s.first, s.count, entropy, per, group_slots, &s.ds);
+      r = cp2_dataset_build_streamed(ctx, &mds->cfg, s.first, s.count, entropy, std::max(1, threads / (int)world), group_slots, &s.ds);
     } else if (kind == BuildKind::Cached) {
-      const std::string path = world == 1 ? std::string(cache_path) : std::string(cache_path) + ".shard" + std::to_string(i) + "of" + std::to_string(world);
-      r = cp2_dataset_build_cached(ctx, &mds->cfg, s.first, s.count, path.c_str(), &s.ds);
+      r = cp2_dataset_build_cached(ctx, &mds->cfg, s.first, s.count, shard_cache_paths(cache_path, 1, i, world)[0].c_str(), &s.ds);
     } else {
       r = cp2_dataset_build(ctx, &mds->cfg, s.first, s.count, &s.ds);
     }
-    if (r != CP2_OK) errs[i] = "device " + std::to_string(m->devices[s.dev]) + (S > 1 ? ", units " : ", slots ") + std::to_string(s.first) + ".." +
-                               std::to_string(s.first + s.count) + ": " + (*cp2_last_error(ctx) ? cp2_last_error(ctx) : cp2_strerror(r));
+    if (r != CP2_OK) why = shard_failure(mds.get(), s, s.first, s.first + s.count, ctx, r);
     return r;
-  });
-  if (st != CP2_OK) {
-    for (auto& e : errs) if (!e.empty()) { m->err = e; break; }
-    return st;
-  }
+  }));
   trace.lap((std::string(S > 1 ? "unit trees on " : "slot trees on ") + std::to_string(world) + " device context(s)").c_str());
-  st = S > 1 ? gather_unit_roots_and_build_upper(mds.get()) : gather_roots_and_build_trees(mds.get());
+  const int st = S > 1 ? gather_unit_roots_and_build_upper(mds.get()) : gather_roots_and_build_trees(mds.get());
   trace.lap(("slot roots exchanged: " + m->gather_note).c_str());
   if (st != CP2_OK) {
     if (m->err.empty())
       for (auto& s : mds->shards) {
-        const char* e = cp2_last_error(s.ds ? cp2_dataset_ctx(s.ds) : s.units->ctx);
+        const char* e = cp2_last_error(s.ctx());
         if (e && *e) { m->err = e; break; }
       }
     return st;
@@ -854,8 +862,7 @@ int units_proof_inputs(cp2_multi_dataset* mds, const uint64_t* slots, size_t n, 
   if (n == 0) return CP2_OK;
   const uint64_t S = mds->units_per_slot, P = c.n_cells / S, cpb = c.block_size / c.cell_size;
   const size_t ns = c.n_samples, md = (size_t)c.max_depth, cs = c.cell_size, total = n * ns;
-  size_t levels = 0;
-  while (((uint64_t)1 << levels) < S) ++levels;
+  const size_t levels = mds->levels();
   const size_t depth_unit = (layer_sizes_of(cpb).size() - 1) + (layer_sizes_of(P / cpb).size() - 1);
   const std::string refusal = proof_shape_refusal(c, depth_unit + levels, mds->dsizes.size() - 1);   // a path: inside the unit, then the levels above it
   if (!refusal.empty()) { m->err = refusal; return CP2_ERR_INVALID; }
@@ -894,8 +901,7 @@ int units_proof_inputs(cp2_multi_dataset* mds, const uint64_t* slots, size_t n, 
     if (!sh) return CP2_ERR_INVALID;
     by_shard[(size_t)(sh - mds->shards.data())].push_back(p);
   }
-  std::vector<std::string> errs(world);
-  int st = for_each_shard(world, [&](size_t w) -> int {
+  CP2_TRY(for_each_shard_named(m, world, [&](size_t w, std::string& why) -> int {
     const auto& mine = by_shard[w];
     if (mine.empty()) return CP2_OK;
     auto& sh = mds->shards[w];
@@ -908,18 +914,14 @@ int units_proof_inputs(cp2_multi_dataset* mds, const uint64_t* slots, size_t n, 
     }
     std::vector<uint8_t> up(k * depth_unit * 32), lf(k * 32);
     int r = trees_paths_multi(sh.units, unit_local.data(), cell_local.data(), k, depth_unit, up.data(), lf.data());
-    if (r != CP2_OK) { errs[w] = cp2_last_error(sh.units->ctx); return r; }
+    if (r != CP2_OK) { why = cp2_last_error(sh.ctx()); return r; }
     for (size_t j = 0; j < k; ++j) {
       const size_t p = mine[j];
       std::memcpy(&paths[p * md * 32], &up[j * depth_unit * 32], depth_unit * 32);                          // merkleProof inside the unit
       std::memcpy(&leaves[p * 32], &lf[j * 32], 32);
     }
     return CP2_OK;
-  });
-  if (st != CP2_OK) {
-    for (auto& e : errs) if (!e.empty()) { m->err = e; break; }
-    return st;
-  }
+  }));
   for (size_t p = 0; p < total; ++p) {                                              // ... and above the unit, from the upper layers
     const uint64_t slot = slots[p / ns], q = idx[p] / P;
     for (size_t lv = 0; lv < levels; ++lv) {
@@ -1114,16 +1116,10 @@ extern "C" int cp2_multi_dataset_export_proof_inputs(cp2_multi_dataset* mds, con
     if (!s) return CP2_ERR_INVALID;
     part[(size_t)(s - mds->shards.data())].push_back(slot_idx[i]);
   }
-  const int per = std::max(1, threads / (int)world);
-  std::vector<uint64_t> bytes(world, 0);
-  int st = for_each_shard(world, [&](size_t i) -> int {
+  return for_each_shard_summing(world, threads, total_bytes, [&](size_t i, int per, uint64_t* bytes) -> int {
     if (part[i].empty()) return CP2_OK;
-    return cp2_dataset_export_proof_inputs(mds->shards[i].ds, part[i].data(), part[i].size(), entropy, dir, per, batch, &bytes[i]);
+    return cp2_dataset_export_proof_inputs(mds->shards[i].ds, part[i].data(), part[i].size(), entropy, dir, per, batch, bytes);
   });
-  uint64_t tot = 0;
-  for (uint64_t b : bytes) tot += b;
-  if (total_bytes) *total_bytes = tot;
-  return st;
 } catch (const std::bad_alloc&) {
   return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
 } catch (...) {
@@ -1146,14 +1142,9 @@ extern "C" int cp2_multi_dataset_export_streamed(cp2_multi_dataset* mds, const c
     if (total_bytes) *total_bytes = tot;
     return CP2_OK;
   }
-  const size_t world = mds->shards.size();
-  const int per = std::max(1, threads / (int)world);
-  std::vector<uint64_t> bytes(world, 0);
-  int st = for_each_shard(world, [&](size_t i) { return cp2_dataset_export_streamed(mds->shards[i].ds, dir, per, &bytes[i]); });
-  uint64_t tot = 0;
-  for (uint64_t b : bytes) tot += b;
-  if (total_bytes) *total_bytes = tot;
-  return st;
+  return for_each_shard_summing(mds->shards.size(), threads, total_bytes, [&](size_t i, int per, uint64_t* bytes) {
+    return cp2_dataset_export_streamed(mds->shards[i].ds, dir, per, bytes);
+  });
 } catch (const std::bad_alloc&) {
   return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
 } catch (...) {
@@ -1199,27 +1190,17 @@ extern "C" int cp2_multi_dataset_scrub(cp2_multi_dataset* mds, uint64_t first_sl
   const size_t world = mds->shards.size();
   std::vector<std::vector<uint64_t>> got(world);
   std::vector<uint64_t> count(world, 0);
-  std::vector<std::string> errs(world);
   DeviceRestore restore;
-  const int st = for_each_shard(world, [&](size_t i) -> int {
+  CP2_TRY(for_each_shard_named(m, world, [&](size_t i, std::string& why) -> int {
     auto& s = mds->shards[i];
     const uint64_t a = std::max(first_slot * S, s.first), z = std::min((first_slot + n_slots) * S, s.first + s.count);   // slots or units
     if (a >= z) return CP2_OK;
-    cp2_ctx* ctx = s.ds ? cp2_dataset_ctx(s.ds) : s.units->ctx;
     int r = CP2_OK;
     if (s.ds) {
       r = dataset_scrub(s.ds, a, z - a, level, cap, got[i], &count[i]);
     } else {
       const cp2_slot_trees* t = s.units;
-      ScrubSrc src;
-      src.from_file = t->src == CellSrc::File;
-      src.file_base = t->file_base;
-      src.seed = t->dataset_seed;
-      src.cell_size = t->cell_size;
-      src.block_size = t->block_size;
-      src.n_cells = t->n_cells;
-      src.units_per_slot = S;
-      r = scrub_items(ctx, src, a, z - a, CP2_SCRUB_CELL, t->nodes.u8() + (t->boff[0] + (a - s.first) * t->n_cells) * 32, t->n_cells, cap,
+      r = scrub_items(t->ctx, scrub_src_of(t, S), a, z - a, CP2_SCRUB_CELL, t->nodes.u8() + (t->boff[0] + (a - s.first) * t->n_cells) * 32, t->n_cells, cap,
                       got[i], &count[i]);
       for (size_t j = 0; r == CP2_OK && j < got[i].size(); j += 2) {   // (unit, cell of the unit) -> (slot, cell of the slot)
         const uint64_t u = got[i][j];
@@ -1227,15 +1208,9 @@ extern "C" int cp2_multi_dataset_scrub(cp2_multi_dataset* mds, uint64_t first_sl
         got[i][j + 1] += (u % S) * t->n_cells;
       }
     }
-    if (r != CP2_OK)
-      errs[i] = "device " + std::to_string(m->devices[s.dev]) + (S > 1 ? ", units " : ", slots ") + std::to_string(a) + ".." + std::to_string(z) +
-                ": " + (*cp2_last_error(ctx) ? cp2_last_error(ctx) : cp2_strerror(r));
+    if (r != CP2_OK) why = shard_failure(mds, s, a, z, s.ctx(), r);
     return r;
-  });
-  if (st != CP2_OK) {
-    for (auto& e : errs) if (!e.empty()) { m->err = e; break; }
-    return st;
-  }
+  }));
   uint64_t total = 0;
   size_t k = 0;
   for (size_t i = 0; i < world; ++i) {
@@ -1281,10 +1256,9 @@ extern "C" int cp2_multi_dataset_repair_blocks(cp2_multi_dataset* mds, const uin
     if (n_written) *n_written = 0;
     return CP2_OK;
   }
-  auto ctx_of = [&](size_t k) { return mds->shards[k].ds ? cp2_dataset_ctx(mds->shards[k].ds) : mds->shards[k].units->ctx; };
-  for (size_t k = 0; k < world; ++k)
-    if (ctx_of(k)->stuck) {
-      m->err = "device " + std::to_string(m->devices[mds->shards[k].dev]) + ": this context takes no further work: a multi-device exchange timed out";
+  for (auto& s : mds->shards)
+    if (s.ctx()->stuck) {
+      m->err = "device " + std::to_string(m->devices[s.dev]) + ": this context takes no further work: a multi-device exchange timed out";
       return CP2_ERR_HIP;
     }
   const auto t0 = std::chrono::steady_clock::now();
@@ -1303,13 +1277,11 @@ extern "C" int cp2_multi_dataset_repair_blocks(cp2_multi_dataset* mds, const uin
                            : repair_row_full(s.units->boff.back(), s.units->bsizes.back(), s.units->nblocks, u.unit - s.first, u.block));
   }
   std::vector<uint32_t> st(n);
-  std::vector<std::string> errs(world);
   DeviceRestore restore;
-  const int rc = for_each_shard(world, [&](size_t k) -> int {
+  CP2_TRY(for_each_shard_named(m, world, [&](size_t k, std::string& why) -> int {
     const std::vector<size_t>& q = reqs[k];
     if (q.empty()) return CP2_OK;
     auto& s = mds->shards[k];
-    cp2_ctx* ctx = ctx_of(k);
     RepairKept kept = s.ds ? repair_dataset_kept(s.ds) : RepairKept{s.units->nodes.u8(), s.units->nodes.bytes / 32};
     // the shard's candidates: read where they are when its requests are one run of the caller's array (q ascends), else gathered
     const uint8_t* p = data + q.front() * c.block_size;
@@ -1320,19 +1292,11 @@ extern "C" int cp2_multi_dataset_repair_blocks(cp2_multi_dataset* mds, const uin
       p = gathered.data();
     }
     std::vector<uint32_t> v(q.size());
-    const int r = repair_check(ctx, kept, c.cell_size, c.block_size, p, rows[k].data(), q.size(), v.data());
-    if (r != CP2_OK) {
-      errs[k] = "device " + std::to_string(m->devices[s.dev]) + (S > 1 ? ", units " : ", slots ") + std::to_string(s.first) + ".." +
-                std::to_string(s.first + s.count) + ": " + (*cp2_last_error(ctx) ? cp2_last_error(ctx) : cp2_strerror(r));
-      return r;
-    }
+    const int r = repair_check(s.ctx(), kept, c.cell_size, c.block_size, p, rows[k].data(), q.size(), v.data());
+    if (r != CP2_OK) { why = shard_failure(mds, s, s.first, s.first + s.count, s.ctx(), r); return r; }
     for (size_t j = 0; j < q.size(); ++j) st[q[j]] = v[j];
     return CP2_OK;
-  });
-  if (rc != CP2_OK) {
-    for (auto& e : errs) if (!e.empty()) { m->err = e; break; }
-    return rc;
-  }
+  }));
   size_t written_n = 0, restamped = 0;
   int r = CP2_OK;
   if (!(flags & CP2_REPAIR_CHECK_ONLY)) {
@@ -1340,13 +1304,8 @@ extern "C" int cp2_multi_dataset_repair_blocks(cp2_multi_dataset* mds, const uin
     r = repair_write(mds->file_base, c.block_size, slot_block, data, n, st.data(), &written_n, &written, &err);
     for (size_t k = 0; cache_path && !written.empty() && k < world; ++k) {   // the names cp2_multi_dataset_build_cached gives the shards' caches
       const auto& s = mds->shards[k];
-      const std::string of = ".shard" + std::to_string(k) + "of" + std::to_string(world);
-      std::vector<std::string> paths;
-      if (S > 1) paths = {std::string(cache_path) + ".units" + std::to_string(S) + of};
-      else if (world == 1) paths = {std::string(cache_path), std::string(cache_path) + ".kept"};
-      else paths = {std::string(cache_path) + of, std::string(cache_path) + of + ".kept"};
       std::string rerr;
-      const int rs = repair_restamp_caches(paths, c, s.count, c.n_cells / S, s.first, S, mds->file_base, written, &restamped, &rerr);
+      const int rs = repair_restamp_caches(shard_cache_paths(cache_path, S, k, world), c, s.count, c.n_cells / S, s.first, S, mds->file_base, written, &restamped, &rerr);
       if (r == CP2_OK && rs != CP2_OK) { r = rs; err = rerr; }
     }
   }

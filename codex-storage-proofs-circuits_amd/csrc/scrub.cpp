@@ -204,6 +204,13 @@ int cp2i::scrub_items(cp2_ctx* ctx, const ScrubSrc& src, uint64_t item0, uint64_
   return scrub_loop(ctx, items, ks, n_items, level, cap, bad, n_bad, nullptr);
 }
 
+ScrubSrc cp2i::scrub_src_of(const cp2_slot_trees* t, uint64_t units_per_slot) {
+  return {t->src == CellSrc::File, t->file_base, t->dataset_seed, t->cell_size, t->block_size, t->n_cells, units_per_slot};
+}
+ScrubSrc cp2i::scrub_src_of(const cp2_dataset* ds) {
+  return {ds->from_file, ds->file_base, ds->cfg.seed, ds->cfg.cell_size, ds->cfg.block_size, ds->cfg.n_cells, 1};
+}
+
 int cp2i::dataset_scrub_level(const cp2_dataset* ds) {
   return ds->trees ? CP2_SCRUB_CELL : (ds->tree_mode == 2 ? CP2_SCRUB_BLOCK : CP2_SCRUB_SLOT);
 }
@@ -213,18 +220,10 @@ int cp2i::dataset_scrub(cp2_dataset* ds, uint64_t first_slot, uint64_t n, int le
   if (level > dataset_scrub_level(ds) || first_slot < ds->first_slot || first_slot - ds->first_slot > ds->n_local ||
       n > ds->n_local - (first_slot - ds->first_slot))
     return CP2_ERR_INVALID;
-  const cp2_config& c = ds->cfg;
-  ScrubSrc src;
-  src.from_file = ds->from_file;
-  src.file_base = ds->file_base;
-  src.seed = c.seed;
-  src.cell_size = c.cell_size;
-  src.block_size = c.block_size;
-  src.n_cells = c.n_cells;
   const uint64_t local = first_slot - ds->first_slot;
   size_t kstride = 1;
   const uint8_t* kept = kept_layer(ds, level, local, &kstride);   // of the first slot scrubbed
-  return scrub_items(ds->ctx, src, first_slot, n, level, kept, kstride, cap, bad, n_bad);
+  return scrub_items(ds->ctx, scrub_src_of(ds), first_slot, n, level, kept, kstride, cap, bad, n_bad);
 }
 
 extern "C" int cp2_dataset_scrub(cp2_dataset* ds, uint64_t first_slot, uint64_t n_slots, uint64_t* bad, size_t cap, size_t* n_bad,

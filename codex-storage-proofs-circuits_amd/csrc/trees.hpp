@@ -132,6 +132,8 @@ struct ScrubSrc {
   size_t cell_size = 0, block_size = 0, n_cells = 0;   // n_cells: per item
   uint64_t units_per_slot = 1;
 };
+ScrubSrc scrub_src_of(const cp2_slot_trees* t, uint64_t units_per_slot);   // the units of `t`
+ScrubSrc scrub_src_of(const cp2_dataset* ds);                              // the slots of `ds`
 int scrub_items(cp2_ctx* ctx, const ScrubSrc& src, uint64_t item0, uint64_t n, int level, const uint8_t* kept, size_t kstride, size_t cap,
                 std::vector<uint64_t>& bad, uint64_t* n_bad);
 // the finest level a dataset keeps: CP2_SCRUB_CELL (every node), _BLOCK (compact) or _SLOT (roots only)

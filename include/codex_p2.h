@@ -101,8 +101,8 @@ int cp2_device_is_native(const cp2_ctx* ctx);
  *                        the hash launches of the streamed builds hold every workgroup slot instead of leaving room; parsed strictly)
  *   CODEX_P2_TEST_OPTIMISTIC     "1": the automatic residency choice starts at "every node" without looking at the device, so that
  *                        the step-down chain is what finds the mode that fits (anything else: ignored)
- *   CODEX_P2_TEST_EXCHANGE_FAULT "hang_init" | "hang_collective" | "init" | "collective" | "corrupt": the multi-device exchange of
- *                        slot roots stalls, fails or delivers wrong rows at that point (cp2_multi_*; anything else: ignored)
+ *   CODEX_P2_TEST_EXCHANGE_FAULT "hang_init" | "hang_collective" | "corrupt": the multi-device exchange of slot roots stalls at
+ *                        that point or delivers wrong rows (cp2_multi_*; anything else: ignored)
  * and the A/B knobs of the measurement tools, read leniently (anything but the value named means "off"): CP2_STREAM_SERIAL=1,
  * CP2_STREAM_RAMP=0, CP2_HASH_BLOCK=64, CP2_INGEST_COPY_STREAM=1 (the ingestion pipe's uploads on a stream of their own, as until
  * round 6, instead of on the chunk's own hashing stream), CP2_TRACE (any value: stage timings on stderr). */

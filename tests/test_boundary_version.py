@@ -99,3 +99,19 @@ def test_exchange_never_retries_through_host_memory_after_a_timeout(tmp_path):
     subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-I" + os.path.join(PKG_DIR, "csrc"), "-o", exe, str(src)])
     r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0 and "policy ok (2 combinations retried)" in r.stdout, (r.stdout, r.stderr)
+
+
+def test_exchange_loop_walked_over_every_outcome_with_sanitizers(tmp_path):
+    """exchange_until_verified (csrc/exchange_policy.hpp), the one loop around the exchange of slot roots and of unit roots: stand-in
+    exchange / install / verify callables over gather mode x shards x first exchange x second exchange x install x verify (1008 runs)
+    under AddressSanitizer + UBSan, each against the table written out in tests/host_check/exchange_loop_check.cpp -- how often each
+    callable ran and with which force_host, nothing after a time-out, no install or verify on a failed exchange, verification skipped
+    only when nothing moved, the status, the error text, the note's " [first attempt: " suffix, never more than two exchanges.  A second
+    exchange happens in 36 runs: 24 after a failed exchange (automatic mode, 2 or 8 shards, CP2_ERR_HIP, no time-out) and 12 after a
+    device path failed its check in the automatic mode."""
+    exe = str(tmp_path / "exchange_loop_check")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-I" + os.path.join(PKG_DIR, "csrc"), "-o", exe, os.path.join(ROOT, "tests", "host_check", "exchange_loop_check.cpp")])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    assert "exchange loop ok: 1008 runs, 36 with a second exchange, 91 ending in a failed verification" in r.stdout, r.stdout

@@ -401,3 +401,73 @@ def test_multi_equals_single_context(pkg, sctx, tmp_path):
             md.free()
     finally:
         m.close()
+
+
+def traced(capfd, f):
+    """f() with CP2_TRACE set: (its result, what the library wrote to stderr meanwhile)"""
+    os.environ["CP2_TRACE"] = "1"
+    capfd.readouterr()
+    try:
+        out = f()
+    finally:
+        del os.environ["CP2_TRACE"]
+    return out, capfd.readouterr().err
+
+
+def test_multi_repair_restamps_the_caches_the_cached_build_wrote(pkg, tmp_path, capfd):
+    """cp2_multi_dataset_repair_blocks with cache_path, two contexts on one device, by whole slots and cut by units: the shard caches it
+    restamps are the files cp2_multi_dataset_build_cached wrote (one function names them for both), so after bit rot and its repair the
+    next cached build finds the same files and nothing else, loads them (same inode, same mtime as after the restamp) and reads no slot
+    file.  By slots the shards' tree caches get a compact build's ".kept" files beside them first: both names are restamped, and both a
+    compact and an every-node build load afterwards."""
+    slot, blk = 4, 9
+    m = pkg.Multi([0, 0])
+
+    def multi_build(cfg, cache, mode):
+        for i in range(2):
+            m.ctx(i).set_keep_trees(mode)
+        try:
+            return traced(capfd, lambda: m.dataset(cfg, cache=cache))
+        finally:
+            for i in range(2):
+                m.ctx(i).set_keep_trees(-1)
+
+    try:
+        m.set_policy(pkg.GATHER_AUTO, 1)
+        for split in (1, 0):
+            d = tmp_path / ("cut%d" % split)
+            d.mkdir()
+            base = str(d / "slot")
+            data = write_files(base, n_slots=7)
+            cfg = config(pkg, base, n_slots=7)
+            cache = str(d / "c.cp2")
+            caches = lambda: sorted(f for f in os.listdir(d) if f.startswith("c.cp2"))
+            stats = lambda: {f: (os.stat(d / f).st_ino, os.stat(d / f).st_mtime_ns) for f in caches()}
+            m.set_split(split)
+            md, err = multi_build(cfg, cache, 1)
+            assert "slot files:" in err, err                         # the first build read the slot files
+            assert len(md.shards()) == 2
+            if split == 1:
+                assert md.units_per_slot == 1
+                md.free()
+                md, err = multi_build(cfg, cache, 2)                 # compact beside the tree caches: rebuilt once, saved as ".kept"
+                assert "slot files:" in err and md.units_per_slot == 1
+                names = ["c.cp2.shard0of2", "c.cp2.shard0of2.kept", "c.cp2.shard1of2", "c.cp2.shard1of2.kept"]
+            else:
+                assert md.units_per_slot == 2                        # 7 slots over 2 contexts: the plan cuts every slot in two
+                names = ["c.cp2.units2.shard0of2", "c.cp2.units2.shard1of2"]
+            assert caches() == names
+            flip_keep_mtime(base, slot, blk * BS + 77)
+            assert blocks_of(*md.scrub()[:2]) == [(slot, blk)]
+            status, n_written = md.repair_blocks([(slot, blk)], candidates(data, [(slot, blk)]), cache_path=cache)
+            assert list(status) == [pkg.REPAIR_MATCH] and n_written == 1
+            md.free()
+            after_repair = stats()
+            for mode in ((2, 1) if split == 1 else (1,)):
+                md, err = multi_build(cfg, cache, mode)
+                assert caches() == names and stats() == after_repair   # the same files, none written again
+                assert "slot files:" not in err, err                 # ... and loaded: no slot file was read
+                assert (md.units_per_slot > 1) == (split == 0) and md.scrub()[2] == 0
+                md.free()
+    finally:
+        m.close()
