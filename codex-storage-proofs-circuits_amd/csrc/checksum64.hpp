@@ -1,4 +1,4 @@
-// The checksum of the library's own files: the tree cache and the kept form (slot_trees.cpp), fill checkpoints (fill_checkpoint.hpp).
+// The checksum of the library's own files: the tree cache and the kept form (cache_file.hpp, cache_file.cpp), fill checkpoints (fill_checkpoint.hpp).
 // No HIP in here.
 #pragma once
 #include <cstddef>

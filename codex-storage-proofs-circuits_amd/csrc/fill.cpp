@@ -99,18 +99,6 @@ namespace {
 cp2_fill_session* session(void* f) { return static_cast<cp2_fill_session*>(f); }
 const cp2_fill_session* session(const void* f) { return static_cast<const cp2_fill_session*>(f); }
 
-// the kept form of the session's layers, under the name and with the contents cp2_dataset_build_cached writes for a compact dataset: a
-// tree cache at the path stays, the kept form goes beside it
-int save_kept(const cp2_fill_session* f, const char* cache_path) {
-  const cp2_config& c = f->cfg;
-  KeptMeta meta;
-  meta.n_slots = f->plan.n_local; meta.cell_size = c.cell_size; meta.block_size = c.block_size; meta.n_cells = c.n_cells;
-  meta.src = (uint64_t)(f->from_file ? CellSrc::File : CellSrc::Fake); meta.dataset_seed = c.seed; meta.first_slot = f->plan.first_slot;
-  meta.mode = 2; meta.file_base = f->file_base;
-  const std::string path = file_has_magic(cache_path, "CP2TREE3") ? std::string(cache_path) + ".kept" : std::string(cache_path);
-  return kept_save(f->ctx, path.c_str(), meta, f->compact.p, f->plan.rows * 32);
-}
-
 // the session's buffer handed over without a copy
 void hand_over(DevBuf& from, DevBuf& to) {
   to.release();
@@ -364,9 +352,11 @@ extern "C" int cp2_fill_finish(void* fill, const char* cache_path, cp2_dataset**
       ctx->err = "fill: the tree over the kept block roots of slot " + std::to_string(plan.first_slot + s) + " does not end in the stated slot root";
       return CP2_ERR_IO;
     }
-  // the kept form, with the stamps of the slot files as they stand: cp2_dataset_build_cached loads it instead of rebuilding
+  // the kept form, under the name and with the contents cp2_dataset_build_cached writes for a compact dataset (it loads this instead of
+  // rebuilding), with the stamps of the slot files as they stand
   if (cache_path) {
-    const int st = save_kept(f, cache_path);
+    const int st = kept_save(ctx, kept_cache_path(cache_path).c_str(), kept_meta(f->cfg, f->plan.first_slot, f->plan.n_local, f->from_file, f->file_base, 2),
+                             f->compact.p, f->plan.rows * 32);
     if (st != CP2_OK) {
       if (ctx->err.empty()) ctx->err = std::string("fill: cannot write the kept layers to ") + cache_path;
       return st;
@@ -413,31 +403,14 @@ FillCkptMeta session_meta(const cp2_fill_session* f) {
   return m;
 }
 
-bool write_all(int fd, const uint8_t* p, size_t n) {
-  while (n) {
-    const ssize_t w = write(fd, p, n);
-    if (w < 0 && errno == EINTR) continue;
-    if (w <= 0) return false;
-    p += w; n -= (size_t)w;
-  }
-  return true;
-}
-
 // a checkpoint's bytes at `path`: written beside it, synced and renamed, so that an older checkpoint there stays whole until the new one is
 int write_checkpoint_file(cp2_ctx* ctx, const char* path, const std::vector<uint8_t>& buf) {
-  const std::string tmp = std::string(path) + ".tmp." + std::to_string((long)getpid());
-  const int fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_NOFOLLOW | O_CLOEXEC, 0644);
-  if (fd < 0) {
-    ctx->err = "fill: cannot create checkpoint " + tmp + ": " + std::strerror(errno);
-    return CP2_ERR_IO;
-  }
-  const char* what = nullptr;
-  if (!write_all(fd, buf.data(), buf.size()) || fsync(fd) != 0) what = std::strerror(errno);
-  if (close(fd) != 0 && !what) what = std::strerror(errno);
-  if (!what && std::rename(tmp.c_str(), path) != 0) what = std::strerror(errno);
-  if (what) {                                         // an older checkpoint at `path` stays as it is
-    ctx->err = "fill: cannot write checkpoint " + std::string(path) + " (through " + tmp + "): " + what;
-    std::remove(tmp.c_str());
+  TmpFile tmp(path);
+  const bool made = tmp.ok(), done = made && pwrite_all(tmp.fd(), buf.data(), buf.size(), 0) && tmp.commit(true);
+  const std::string why = std::strerror(errno);       // of the step that failed, before anything else can set it
+  if (!done) {                                         // an older checkpoint at `path` stays as it is
+    ctx->err = made ? "fill: cannot write checkpoint " + std::string(path) + " (through " + tmp.tmp_name() + "): " + why
+                    : "fill: cannot create checkpoint " + tmp.tmp_name() + ": " + why;
     return CP2_ERR_IO;
   }
   return CP2_OK;
@@ -453,7 +426,7 @@ int read_checkpoint_file(cp2_ctx* ctx, const char* path, HeadOk head_ok, Parse p
     ctx->err = "fill: cannot open checkpoint " + name + ": " + std::strerror(errno);
     return CP2_ERR_IO;
   }
-  struct Closer { int fd; ~Closer() { close(fd); } } closer{fd};
+  const FdCloser closer{fd};
   struct stat sb;
   if (fstat(fd, &sb) != 0) {
     ctx->err = "fill: cannot stat checkpoint " + name + ": " + std::strerror(errno);

@@ -301,15 +301,6 @@ extern "C" int cp2_dataset_build(cp2_ctx* ctx, const cp2_config* cfg, uint64_t f
 //   * saving never overwrites a tree cache ("CP2TREE3") with the smaller kept form: that goes to "<cache_path>.kept" beside it,
 //     and loading looks there too.
 // To pin the representation, pin the mode: cp2_set_keep_trees / CODEX_P2_KEEP_TREES.
-bool cp2i::file_has_magic(const char* path, const char* magic8) {
-  char m[8] = {};
-  const int fd = open(path, O_RDONLY | O_CLOEXEC);
-  if (fd < 0) return false;
-  const bool ok = pread(fd, m, 8, 0) == 8 && std::memcmp(m, magic8, 8) == 0;
-  close(fd);
-  return ok;
-}
-
 namespace {
 
 // the kept form of `mode` (2 compact, 0 roots) from `path`: CP2_OK with *out set, CP2_ERR_IO when the file is not that, other errors as they come
@@ -318,28 +309,19 @@ int load_kept_dataset(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, 
   std::unique_ptr<cp2_dataset> ds(dataset_new(ctx, cfg, first_slot, n_local));
   if (!ds) return CP2_ERR_ALLOC;
   CP2_TRY(dataset_alloc_kept(ds.get(), mode));
-  KeptMeta meta;
-  meta.n_slots = n_local; meta.cell_size = cfg->cell_size; meta.block_size = cfg->block_size; meta.n_cells = cfg->n_cells;
-  meta.src = (uint64_t)(ds->from_file ? CellSrc::File : CellSrc::Fake); meta.dataset_seed = cfg->seed; meta.first_slot = first_slot;
-  meta.mode = (uint64_t)mode; meta.file_base = ds->file_base;
   void* buf = mode == 2 ? ds->compact.p : ds->local_roots.p;
   const size_t bytes = mode == 2 ? compact_bytes(*cfg, n_local) : (size_t)n_local * 32;
-  CP2_TRY(kept_load(ctx, path, meta, buf, bytes));
+  CP2_TRY(kept_load(ctx, path, kept_meta(*cfg, first_slot, n_local, ds->from_file, ds->file_base, mode), buf, bytes));
   *out = ds.release();
   return CP2_OK;
 }
 
 int save_kept_dataset(cp2_dataset* ds, const char* cache_path) {
   const cp2_config& c = ds->cfg;
-  KeptMeta meta;
-  meta.n_slots = ds->n_local; meta.cell_size = c.cell_size; meta.block_size = c.block_size; meta.n_cells = c.n_cells;
-  meta.src = (uint64_t)(ds->from_file ? CellSrc::File : CellSrc::Fake); meta.dataset_seed = c.seed; meta.first_slot = ds->first_slot;
-  meta.mode = (uint64_t)ds->tree_mode; meta.file_base = ds->file_base;
   const void* buf = ds->tree_mode == 2 ? ds->compact.p : ds->local_roots.p;
   const size_t bytes = ds->tree_mode == 2 ? compact_bytes(c, ds->n_local) : (size_t)ds->n_local * 32;
-  // a tree cache at the path is the richer representation: it stays, the kept form goes beside it
-  const std::string path = file_has_magic(cache_path, "CP2TREE3") ? std::string(cache_path) + ".kept" : std::string(cache_path);
-  return kept_save(ds->ctx, path.c_str(), meta, buf, bytes);
+  return kept_save(ds->ctx, kept_cache_path(cache_path).c_str(), kept_meta(c, ds->first_slot, ds->n_local, ds->from_file, ds->file_base, ds->tree_mode),
+                   buf, bytes);
 }
 
 }  // namespace

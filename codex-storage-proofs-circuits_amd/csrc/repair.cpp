@@ -192,9 +192,12 @@ int cp2i::repair_write(const std::string& base, size_t block_size, const uint64_
 int cp2i::repair_restamp_caches(const std::vector<std::string>& paths, const cp2_config& cfg, uint64_t n_items, size_t n_cells, uint64_t first_item,
                                 uint64_t units_per_slot, const std::string& base, const std::vector<FileStamp>& written, size_t* restamped,
                                 std::string* err) {
+  CacheHead want;                                       // the items a cache must describe for its stamps to follow the writes
+  want.n_items = n_items; want.cell_size = cfg.cell_size; want.block_size = cfg.block_size; want.n_cells = n_cells;
+  want.src = (uint64_t)CellSrc::File; want.first_item = first_item; want.units_per_slot = units_per_slot; want.base = base;
   for (const std::string& p : paths) {
     size_t r = 0;
-    CP2_TRY(cache_restamp(p.c_str(), n_items, cfg.cell_size, cfg.block_size, n_cells, first_item, units_per_slot, base, written, &r, err));
+    CP2_TRY(cache_restamp(p.c_str(), want, written, &r, err));
     *restamped += r;
   }
   return CP2_OK;

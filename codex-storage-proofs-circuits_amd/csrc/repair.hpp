@@ -62,7 +62,7 @@ int gather_rows_by_addr(cp2_ctx* ctx, const std::vector<uint64_t>& addr, uint8_t
 // those of every later file CP2_REPAIR_UNWRITTEN.  *n_written counts the blocks of the files written and synced, `written` their stamps.
 int repair_write(const std::string& base, size_t block_size, const uint64_t* slot_block, const uint8_t* data, size_t n, uint32_t* status,
                  size_t* n_written, std::vector<FileStamp>* written, std::string* err);
-// cache_restamp (trees.hpp) over each of `paths`; *restamped accumulates
+// cache_restamp (cache_file.hpp) over each of `paths`; *restamped accumulates
 int repair_restamp_caches(const std::vector<std::string>& paths, const cp2_config& cfg, uint64_t n_items, size_t n_cells, uint64_t first_item,
                           uint64_t units_per_slot, const std::string& base, const std::vector<FileStamp>& written, size_t* restamped,
                           std::string* err);

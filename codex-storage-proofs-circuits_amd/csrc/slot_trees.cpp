@@ -1,5 +1,5 @@
 // Slot trees behind the C ABI (include/codex_p2.h): builders for the four cell sources, the streaming
-// ingestion pipe, the persisted-tree cache and path lookup.
+// ingestion pipe and path lookup (the persisted-tree cache: cache_file.cpp).
 //
 // Mirrors reference/nim/proof_input/src/gen_input/bn254.nim:21-33 (buildSlotTreeFull), blocks/bn254.nim:60-67
 // (networkBlockTree), slot.nim:57-73 (slot data), merkle.nim:21-42,86-100 + types.nim:27-37 (paths).  All hashing
@@ -14,22 +14,18 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
-#include <mutex>
 #include <new>
 #include <string>
 #include <vector>
 
 #include "trees.hpp"
-#include "checksum64.hpp"
 #include "fake_turns.hpp"
 #include "ingest_turns.hpp"
 #include "fill_pipeline.hpp"
-#include "repair_plan.hpp"
 
 using namespace cp2i;
 
@@ -310,13 +306,11 @@ extern "C" int cp2_slot_trees_build_fake(cp2_ctx* ctx, uint64_t dataset_seed, ui
 // Units: `n_units` consecutive pieces of `cells_per_unit` cells, unit u = cells [(u % units_per_slot) * cells_per_unit, ...) of
 // slot u / units_per_slot.  The root of a unit is the node of that slot's tree (gen_input/bn254.nim:21-30) above its cells
 // (cells_per_unit / cellsPerBlock >= 2 blocks, a power of two, so that the unit's layers ARE layers of the slot tree).
-namespace {
-bool unit_geometry_ok(uint64_t units_per_slot, size_t cell_size, size_t block_size, size_t cells_per_unit) {
+bool cp2i::unit_geometry_ok(uint64_t units_per_slot, size_t cell_size, size_t block_size, size_t cells_per_unit) {
   if (!is_pow2(units_per_slot) || cell_size == 0 || block_size < cell_size) return false;
   const size_t nb = cells_per_unit / (block_size / cell_size);
   return nb >= 2 && is_pow2(nb);
 }
-}  // namespace
 extern "C" int cp2_slot_trees_build_fake_units(cp2_ctx* ctx, uint64_t dataset_seed, uint64_t units_per_slot, uint64_t first_unit,
                                                size_t n_units, size_t cell_size, size_t block_size, size_t cells_per_unit,
                                                cp2_slot_trees** out) try {
@@ -1000,411 +994,6 @@ extern "C" int cp2_set_ingest(cp2_ctx* ctx, int fill_threads, int ring_depth, si
   return CP2_OK;
 } catch (...) {
   return CP2_ERR_INVALID;
-}
-
-// ---- persisted slot trees ---------------------------------------------------
-// File = header + data-source description + every node of the layer-major buffer (canonical 32-byte elements).
-// A later run with new entropy then needs only 2 permutations per sample plus gathers instead of re-hashing every
-// slot (the reference re-hashes all slots per run AND the proving slot once per sample, gen_input/bn254.nim:42,57).
-// The file is written to "<path>.tmp.<pid>" and renamed into place; it carries a checksum of the nodes and, for the
-// SlotFile source, size + mtime of every slot file so that a cache is never reused over changed data.
-namespace {
-struct TreeFileHeader {
-  char magic[8];            // "CP2TREE3"
-  uint64_t n_slots, cell_size, block_size, n_cells;   // a batch of units: units and the cells of one unit (trees.hpp)
-  uint64_t units_per_slot;  // 1: whole slots
-  uint64_t src;             // CellSrc
-  uint64_t dataset_seed, first_slot;
-  uint64_t file_base_len;   // bytes following the header
-  uint64_t n_stamps;        // (size, mtime_ns) pairs following the base name: one per slot for CellSrc::File
-  uint64_t n_nodes;
-  uint64_t node_checksum;
-};
-
-// ring-slot flags shared between the streaming thread and its I/O worker
-struct SlotFlags {
-  static constexpr int K = 3;
-  std::mutex mu;
-  std::condition_variable cv;
-  bool flag[K] = {false, false, false};
-  bool failed = false;
-  void set(int r, bool v) { { std::lock_guard<std::mutex> lk(mu); flag[r] = v; } cv.notify_all(); }
-  void fail() { { std::lock_guard<std::mutex> lk(mu); failed = true; } cv.notify_all(); }
-  // waits until flag[r] == v; false if the worker reported a failure
-  bool wait(int r, bool v) {
-    std::unique_lock<std::mutex> lk(mu);
-    cv.wait(lk, [&] { return failed || flag[r] == v; });
-    return !failed;
-  }
-};
-constexpr size_t CACHE_CHUNK = (size_t)64 << 20;
-
-bool pwrite_all(int fd, const uint8_t* p, size_t n, off_t off) {
-  while (n) {
-    ssize_t w = pwrite(fd, p, n, off);
-    if (w <= 0) return false;
-    p += w; n -= (size_t)w; off += w;
-  }
-  return true;
-}
-bool pread_all(int fd, uint8_t* p, size_t n, off_t off) {
-  while (n) {
-    ssize_t r = pread(fd, p, n, off);
-    if (r <= 0) return false;
-    p += r; n -= (size_t)r; off += r;
-  }
-  return true;
-}
-
-// (size, mtime in ns) of the slot file behind each slot (each unit: several units then stamp the same file); a missing file
-// stamps as (~0, ~0)
-std::vector<uint64_t> file_stamps(const std::string& base, uint64_t first_slot, size_t n_slots, uint64_t units_per_slot = 1) {
-  std::vector<uint64_t> v(2 * n_slots);
-  for (size_t s = 0; s < n_slots; ++s) {
-    struct stat sb;
-    if (stat(slot_file_name(base, (first_slot + s) / units_per_slot).c_str(), &sb) == 0) {
-      v[2 * s] = (uint64_t)sb.st_size;
-      v[2 * s + 1] = (uint64_t)sb.st_mtim.tv_sec * 1000000000ULL + (uint64_t)sb.st_mtim.tv_nsec;
-    } else {
-      v[2 * s] = v[2 * s + 1] = ~0ULL;
-    }
-  }
-  return v;
-}
-}  // namespace
-
-// The nodes stream device -> pinned ring -> file in 64 MiB chunks: the download of chunk i+1, the checksum of chunk i and the
-// write of chunk i-1 overlap, and no host copy of the whole node buffer exists (8 GiB for 32 768 slots of 2^12 cells).
-extern "C" int cp2_slot_trees_save(cp2_slot_trees* t, const char* path) try {
-  if (!t || !path) return CP2_ERR_INVALID;
-  cp2_ctx* ctx = t->ctx;
-  CP2_HIP(ctx, hipSetDevice(ctx->device));
-  TreeFileHeader h{};
-  std::memcpy(h.magic, "CP2TREE3", 8);
-  h.units_per_slot = t->units_per_slot;
-  h.n_slots = t->n_slots; h.cell_size = t->cell_size; h.block_size = t->block_size; h.n_cells = t->n_cells;
-  h.src = (uint64_t)t->src; h.dataset_seed = t->dataset_seed; h.first_slot = t->first_slot;
-  h.file_base_len = t->file_base.size();
-  std::vector<uint64_t> stamps;
-  if (t->src == CellSrc::File) stamps = file_stamps(t->file_base, t->first_slot, t->n_slots, t->units_per_slot);
-  h.n_stamps = stamps.size() / 2;
-  h.n_nodes = t->nodes.bytes / 32;
-  const size_t total = t->nodes.bytes;
-  const std::string tmp = std::string(path) + ".tmp." + std::to_string((long)getpid());
-  const int fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_NOFOLLOW | O_CLOEXEC, 0644);
-  if (fd < 0) { ctx->err = "cannot create " + tmp; return CP2_ERR_IO; }
-  struct FdGuard { int fd; std::string tmp; bool keep = false; ~FdGuard() { if (fd >= 0) close(fd); if (!keep) std::remove(tmp.c_str()); } } guard{fd, tmp};
-  const off_t data_off = (off_t)(sizeof h + h.file_base_len + stamps.size() * 8);
-  bool ok = (h.file_base_len == 0 || pwrite_all(fd, reinterpret_cast<const uint8_t*>(t->file_base.data()), h.file_base_len, sizeof h)) &&
-            (stamps.empty() || pwrite_all(fd, reinterpret_cast<const uint8_t*>(stamps.data()), stamps.size() * 8, (off_t)(sizeof h + h.file_base_len)));
-  if (!ok) return CP2_ERR_IO;
-  CP2_HIP(ctx, hipStreamSynchronize(ctx->stream));                  // the trees are complete
-  if (ctx->aux_stream) CP2_HIP(ctx, hipStreamSynchronize(ctx->aux_stream));
-  Checksum64 sum;
-  {
-    constexpr int K = SlotFlags::K;
-    PinBuf pin[K];
-    hipEvent_t ev[K] = {};
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < K; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } ev_guard{ev};
-    const size_t chunk = std::min(CACHE_CHUNK, std::max<size_t>(total, 32));
-    for (int r = 0; r < K; ++r) {
-      CP2_TRY(pin[r].alloc(ctx, chunk));
-      CP2_HIP(ctx, hipEventCreateWithFlags(&ev[r], hipEventDisableTiming));
-    }
-    SlotFlags busy;                                                 // flag[r]: the writer still reads pin[r]
-    const size_t n_chunks = (total + chunk - 1) / chunk;
-    int st = CP2_OK;
-    {
-      Workers writer(1);                                            // joins before the pinned blocks go back to the pool
-      auto finish_chunk = [&](size_t c) -> int {                    // landed -> checksum -> hand to the writer
-        const int r = (int)(c % K);
-        const size_t m = std::min(chunk, total - c * chunk);
-        CP2_HIP(ctx, hipEventSynchronize(ev[r]));
-        sum.update(pin[r].u8(), m);
-        busy.set(r, true);
-        const uint8_t* src = pin[r].u8();
-        const off_t off = data_off + (off_t)(c * chunk);
-        writer.submit([&busy, r, fd, src, m, off] {
-          if (pwrite_all(fd, src, m, off)) busy.set(r, false);
-          else busy.fail();
-        });
-        return CP2_OK;
-      };
-      for (size_t c = 0; c < n_chunks && st == CP2_OK; ++c) {
-        const int r = (int)(c % K);
-        const size_t m = std::min(chunk, total - c * chunk);
-        if (!busy.wait(r, false)) { st = CP2_ERR_IO; break; }       // chunk c - K has left pin[r]
-        hipError_t e = hipMemcpyAsync(pin[r].p, t->nodes.u8() + c * chunk, m, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipEventRecord(ev[r], ctx->stream);
-        if (e != hipSuccess) { ctx->err = std::string("cache download: ") + hipGetErrorString(e); st = CP2_ERR_HIP; break; }
-        if (c > 0) st = finish_chunk(c - 1);                        // overlaps the download just enqueued
-      }
-      if (st == CP2_OK && n_chunks) st = finish_chunk(n_chunks - 1);
-      writer.wait_idle();
-      (void)hipStreamSynchronize(ctx->stream);
-      if (st == CP2_OK && busy.failed) st = CP2_ERR_IO;
-    }
-    if (st != CP2_OK) return st;
-  }
-  h.node_checksum = sum.finish();
-  if (!pwrite_all(fd, reinterpret_cast<const uint8_t*>(&h), sizeof h, 0)) return CP2_ERR_IO;
-  if (close(fd) != 0) { guard.fd = -1; return CP2_ERR_IO; }
-  guard.fd = -1;
-  if (std::rename(tmp.c_str(), path) != 0) return CP2_ERR_IO;
-  guard.keep = true;
-  return CP2_OK;
-} catch (const std::bad_alloc&) {
-  return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
-} catch (...) {
-  return CP2_ERR_INVALID;
-}
-
-// file -> pinned ring -> device in 64 MiB chunks: the read of chunk i+1, the checksum of chunk i and the upload of chunk i-1
-// overlap.  The nodes reach the device before the checksum is known; a mismatch discards them.
-extern "C" int cp2_slot_trees_load(cp2_ctx* ctx, const char* path, cp2_slot_trees** out) try {
-  if (!ctx || !path || !out) return CP2_ERR_INVALID;
-  *out = nullptr;
-  const int fd = open(path, O_RDONLY);
-  if (fd < 0) return CP2_ERR_IO;
-  struct Closer { int fd; ~Closer() { close(fd); } } closer{fd};
-  TreeFileHeader h{};
-  // every header field is bounded before anything is sized from it
-  if (!pread_all(fd, reinterpret_cast<uint8_t*>(&h), sizeof h, 0) || std::memcmp(h.magic, "CP2TREE3", 8) != 0 || h.file_base_len > 4096 ||
-      trees_check_geometry(h.cell_size, h.block_size, h.n_cells, h.n_slots) != CP2_OK || h.src > (uint64_t)CellSrc::File ||
-      h.units_per_slot == 0 || (h.units_per_slot > 1 && !unit_geometry_ok(h.units_per_slot, h.cell_size, h.block_size, h.n_cells)) ||
-      (h.n_stamps != 0 && h.n_stamps != h.n_slots) || (h.src == (uint64_t)CellSrc::File) != (h.n_stamps != 0)) {
-    ctx->err = std::string("not a slot-tree cache of this version: ") + path;
-    return CP2_ERR_IO;
-  }
-  {   // the stamps the header announces are in the file before anything is sized from their count
-    struct stat sb;
-    if (fstat(fd, &sb) != 0 || h.n_stamps > ((uint64_t)1 << 40) || (uint64_t)sb.st_size < sizeof h + h.file_base_len + 16 * h.n_stamps) {
-      ctx->err = std::string("slot-tree cache is truncated: ") + path;
-      return CP2_ERR_IO;
-    }
-  }
-  std::string base(h.file_base_len, '\0');
-  if (h.file_base_len && !pread_all(fd, reinterpret_cast<uint8_t*>(&base[0]), h.file_base_len, sizeof h)) return CP2_ERR_IO;
-  std::vector<uint64_t> stamps(2 * h.n_stamps);
-  if (!stamps.empty() && !pread_all(fd, reinterpret_cast<uint8_t*>(stamps.data()), stamps.size() * 8, (off_t)(sizeof h + h.file_base_len))) return CP2_ERR_IO;
-  if (h.src == (uint64_t)CellSrc::File && stamps != file_stamps(base, h.first_slot, h.n_slots, h.units_per_slot)) {
-    ctx->err = std::string("slot files changed since the cache was written: ") + path;
-    return CP2_ERR_IO;   // size or mtime of a slot file differs: the trees no longer describe the data
-  }
-  const off_t data_off = (off_t)(sizeof h + h.file_base_len + stamps.size() * 8);
-  if (hipSetDevice(ctx->device) != hipSuccess) return CP2_ERR_HIP;
-  std::unique_ptr<cp2_slot_trees> t(trees_new(ctx, h.n_slots, h.cell_size, h.block_size, h.n_cells));
-  if (!t) return CP2_ERR_ALLOC;
-  t->src = (CellSrc)h.src;
-  t->dataset_seed = h.dataset_seed;
-  t->first_slot = h.first_slot;
-  t->units_per_slot = h.units_per_slot;
-  t->file_base = base;
-  CP2_TRY(trees_layout(t.get()));
-  if (t->nodes.bytes / 32 != h.n_nodes) return CP2_ERR_IO;
-  {
-    struct stat sb;
-    if (fstat(fd, &sb) != 0 || (uint64_t)sb.st_size != (uint64_t)data_off + t->nodes.bytes) {
-      ctx->err = std::string("slot-tree cache is truncated: ") + path;
-      return CP2_ERR_IO;
-    }
-  }
-  const size_t total = t->nodes.bytes;
-  Checksum64 sum;
-  {
-    constexpr int K = SlotFlags::K;
-    PinBuf pin[K];
-    hipEvent_t ev[K] = {};
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < K; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } ev_guard{ev};
-    const size_t chunk = std::min(CACHE_CHUNK, std::max<size_t>(total, 32));
-    for (int r = 0; r < K; ++r) {
-      CP2_TRY(pin[r].alloc(ctx, chunk));
-      CP2_HIP(ctx, hipEventCreateWithFlags(&ev[r], hipEventDisableTiming));
-      CP2_HIP(ctx, hipEventRecord(ev[r], ctx->stream));
-    }
-    SlotFlags ready;                                                // flag[r]: pin[r] holds the chunk the main thread waits for
-    const size_t n_chunks = (total + chunk - 1) / chunk;
-    int st = CP2_OK;
-    {
-      Workers reader(1);
-      size_t submitted = 0;
-      auto submit_read = [&](size_t c) -> int {                     // pin[c % K] is free once the upload of chunk c - K has finished
-        const int r = (int)(c % K);
-        CP2_HIP(ctx, hipEventSynchronize(ev[r]));
-        uint8_t* dst = pin[r].u8();
-        const size_t m = std::min(chunk, total - c * chunk);
-        const off_t off = data_off + (off_t)(c * chunk);
-        reader.submit([&ready, r, fd, dst, m, off] {
-          if (pread_all(fd, dst, m, off)) ready.set(r, true);
-          else ready.fail();
-        });
-        return CP2_OK;
-      };
-      for (size_t c = 0; c < n_chunks && st == CP2_OK; ++c) {
-        while (st == CP2_OK && submitted < n_chunks && submitted < c + K) st = submit_read(submitted++);
-        if (st != CP2_OK) break;
-        const int r = (int)(c % K);
-        const size_t m = std::min(chunk, total - c * chunk);
-        if (!ready.wait(r, true)) { st = CP2_ERR_IO; break; }
-        ready.set(r, false);
-        sum.update(pin[r].u8(), m);
-        hipError_t e = hipMemcpyAsync(t->nodes.u8() + c * chunk, pin[r].p, m, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipEventRecord(ev[r], ctx->stream);
-        if (e != hipSuccess) { ctx->err = std::string("cache upload: ") + hipGetErrorString(e); st = CP2_ERR_HIP; }
-      }
-      reader.wait_idle();
-      if (hipStreamSynchronize(ctx->stream) != hipSuccess && st == CP2_OK) st = CP2_ERR_HIP;
-    }
-    if (st != CP2_OK) return st;
-  }
-  if (sum.finish() != h.node_checksum) {
-    ctx->err = std::string("slot-tree cache is corrupt (checksum): ") + path;
-    return CP2_ERR_IO;
-  }
-  *out = t.release();
-  return CP2_OK;
-} catch (const std::bad_alloc&) {
-  return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
-} catch (...) {
-  return CP2_ERR_INVALID;
-}
-
-// ---- persisted compact layers / roots (what a dataset that does not keep every node keeps) ------------------------------------
-// Same discipline as the tree cache above: written to "<path>.tmp.<pid>" and renamed, a checksum over the payload, size + mtime of
-// every slot file for the SlotFile source.  The payload moves through one pinned 64 MiB buffer, chunk by chunk.
-namespace {
-struct KeptFileHeader {
-  char magic[8];            // "CP2KEPT1"
-  uint64_t n_slots, cell_size, block_size, n_cells, src, dataset_seed, first_slot, mode;
-  uint64_t file_base_len, n_stamps, payload_bytes, checksum;
-};
-}  // namespace
-
-int cp2i::kept_save(cp2_ctx* ctx, const char* path, const KeptMeta& m, const void* d_buf, size_t bytes) {
-  CP2_HIP(ctx, hipSetDevice(ctx->device));
-  KeptFileHeader h{};
-  std::memcpy(h.magic, "CP2KEPT1", 8);
-  h.n_slots = m.n_slots; h.cell_size = m.cell_size; h.block_size = m.block_size; h.n_cells = m.n_cells;
-  h.src = m.src; h.dataset_seed = m.dataset_seed; h.first_slot = m.first_slot; h.mode = m.mode;
-  h.file_base_len = m.file_base.size();
-  std::vector<uint64_t> stamps;
-  if (m.src == (uint64_t)CellSrc::File) stamps = file_stamps(m.file_base, m.first_slot, m.n_slots);
-  h.n_stamps = stamps.size() / 2;
-  h.payload_bytes = bytes;
-  const std::string tmp = std::string(path) + ".tmp." + std::to_string((long)getpid());
-  const int fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_NOFOLLOW | O_CLOEXEC, 0644);
-  if (fd < 0) { ctx->err = "cannot create " + tmp; return CP2_ERR_IO; }
-  struct FdGuard { int fd; std::string tmp; bool keep = false; ~FdGuard() { if (fd >= 0) close(fd); if (!keep) std::remove(tmp.c_str()); } } guard{fd, tmp};
-  off_t off = (off_t)sizeof h;
-  if (h.file_base_len && !pwrite_all(fd, reinterpret_cast<const uint8_t*>(m.file_base.data()), h.file_base_len, off)) return CP2_ERR_IO;
-  off += (off_t)h.file_base_len;
-  if (!stamps.empty() && !pwrite_all(fd, reinterpret_cast<const uint8_t*>(stamps.data()), stamps.size() * 8, off)) return CP2_ERR_IO;
-  off += (off_t)(stamps.size() * 8);
-  PinBuf pin;
-  CP2_TRY(pin.alloc(ctx, std::min(CACHE_CHUNK, std::max<size_t>(bytes, 32))));
-  Checksum64 sum;
-  for (size_t at = 0; at < bytes; at += CACHE_CHUNK) {
-    const size_t n = std::min(CACHE_CHUNK, bytes - at);
-    CP2_HIP(ctx, hipMemcpyAsync(pin.p, static_cast<const uint8_t*>(d_buf) + at, n, hipMemcpyDeviceToHost, ctx->stream));
-    CP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    sum.update(pin.u8(), n);
-    if (!pwrite_all(fd, pin.u8(), n, off + (off_t)at)) return CP2_ERR_IO;
-  }
-  h.checksum = sum.finish();
-  if (!pwrite_all(fd, reinterpret_cast<const uint8_t*>(&h), sizeof h, 0)) return CP2_ERR_IO;
-  if (close(fd) != 0) { guard.fd = -1; return CP2_ERR_IO; }
-  guard.fd = -1;
-  if (std::rename(tmp.c_str(), path) != 0) return CP2_ERR_IO;
-  guard.keep = true;
-  return CP2_OK;
-}
-
-int cp2i::kept_load(cp2_ctx* ctx, const char* path, const KeptMeta& w, void* d_buf, size_t bytes) {
-  const int fd = open(path, O_RDONLY);
-  if (fd < 0) return CP2_ERR_IO;
-  struct Closer { int fd; ~Closer() { close(fd); } } closer{fd};
-  KeptFileHeader h{};
-  if (!pread_all(fd, reinterpret_cast<uint8_t*>(&h), sizeof h, 0) || std::memcmp(h.magic, "CP2KEPT1", 8) != 0 || h.file_base_len > 4096) return CP2_ERR_IO;
-  if (h.n_slots != w.n_slots || h.cell_size != w.cell_size || h.block_size != w.block_size || h.n_cells != w.n_cells || h.src != w.src ||
-      h.first_slot != w.first_slot || h.mode != w.mode || h.payload_bytes != bytes || h.file_base_len != w.file_base.size() ||
-      (w.src == (uint64_t)CellSrc::Fake && h.dataset_seed != w.dataset_seed) || (h.n_stamps != 0 && h.n_stamps != h.n_slots) ||
-      (h.src == (uint64_t)CellSrc::File) != (h.n_stamps != 0))
-    return CP2_ERR_IO;
-  off_t off = (off_t)sizeof h;
-  std::string base(h.file_base_len, '\0');
-  if (h.file_base_len && !pread_all(fd, reinterpret_cast<uint8_t*>(&base[0]), h.file_base_len, off)) return CP2_ERR_IO;
-  if (base != w.file_base) return CP2_ERR_IO;
-  off += (off_t)h.file_base_len;
-  std::vector<uint64_t> stamps(2 * h.n_stamps);
-  if (!stamps.empty() && !pread_all(fd, reinterpret_cast<uint8_t*>(stamps.data()), stamps.size() * 8, off)) return CP2_ERR_IO;
-  off += (off_t)(stamps.size() * 8);
-  if (h.src == (uint64_t)CellSrc::File && stamps != file_stamps(base, h.first_slot, h.n_slots)) return CP2_ERR_IO;   // the slot files changed
-  struct stat sb;
-  if (fstat(fd, &sb) != 0 || (uint64_t)sb.st_size != (uint64_t)off + bytes) return CP2_ERR_IO;                          // truncated / appended
-  if (hipSetDevice(ctx->device) != hipSuccess) return CP2_ERR_HIP;
-  PinBuf pin;
-  CP2_TRY(pin.alloc(ctx, std::min(CACHE_CHUNK, std::max<size_t>(bytes, 32))));
-  Checksum64 sum;
-  for (size_t at = 0; at < bytes; at += CACHE_CHUNK) {
-    const size_t n = std::min(CACHE_CHUNK, bytes - at);
-    if (!pread_all(fd, pin.u8(), n, off + (off_t)at)) return CP2_ERR_IO;
-    sum.update(pin.u8(), n);
-    CP2_HIP(ctx, hipMemcpyAsync(static_cast<uint8_t*>(d_buf) + at, pin.p, n, hipMemcpyHostToDevice, ctx->stream));
-    CP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return sum.finish() == h.checksum ? CP2_OK : CP2_ERR_IO;
-}
-
-// ---- stamps of a cache after a block repair (repair.cpp) ---------------------------------------------------------------------------
-int cp2i::cache_restamp(const char* path, uint64_t n_items, size_t cell_size, size_t block_size, size_t n_cells, uint64_t first_item,
-                        uint64_t units_per_slot, const std::string& base, const std::vector<FileStamp>& written, size_t* restamped,
-                        std::string* err) {
-  *restamped = 0;
-  const int fd = open(path, O_RDWR | O_NOFOLLOW | O_CLOEXEC);
-  if (fd < 0) return CP2_OK;                                      // no cache there: nothing to keep valid
-  struct Closer { int fd; ~Closer() { close(fd); } } closer{fd};
-  char magic[8] = {};
-  if (!pread_all(fd, reinterpret_cast<uint8_t*>(magic), 8, 0)) return CP2_OK;
-  uint64_t stamps_at = 0, n_stamps = 0, base_len = 0;
-  if (std::memcmp(magic, "CP2TREE3", 8) == 0) {
-    TreeFileHeader h{};
-    if (!pread_all(fd, reinterpret_cast<uint8_t*>(&h), sizeof h, 0)) return CP2_OK;
-    if (h.n_slots != n_items || h.cell_size != cell_size || h.block_size != block_size || h.n_cells != n_cells || h.src != (uint64_t)CellSrc::File ||
-        h.first_slot != first_item || h.units_per_slot != units_per_slot || h.file_base_len != base.size() || h.n_stamps != n_items)
-      return CP2_OK;
-    stamps_at = sizeof h + h.file_base_len;
-    n_stamps = h.n_stamps;
-    base_len = h.file_base_len;
-  } else if (std::memcmp(magic, "CP2KEPT1", 8) == 0) {
-    KeptFileHeader h{};
-    if (!pread_all(fd, reinterpret_cast<uint8_t*>(&h), sizeof h, 0)) return CP2_OK;
-    if (units_per_slot != 1 || h.n_slots != n_items || h.cell_size != cell_size || h.block_size != block_size || h.n_cells != n_cells ||
-        h.src != (uint64_t)CellSrc::File || h.first_slot != first_item || h.file_base_len != base.size() || h.n_stamps != n_items)
-      return CP2_OK;
-    stamps_at = sizeof h + h.file_base_len;
-    n_stamps = h.n_stamps;
-    base_len = h.file_base_len;
-  } else {
-    return CP2_OK;
-  }
-  std::string got(base_len, '\0');
-  if (base_len && !pread_all(fd, reinterpret_cast<uint8_t*>(&got[0]), base_len, (off_t)(stamps_at - base_len))) return CP2_OK;
-  if (got != base) return CP2_OK;
-  std::vector<uint64_t> stamps(2 * n_stamps);
-  if (!pread_all(fd, reinterpret_cast<uint8_t*>(stamps.data()), stamps.size() * 8, (off_t)stamps_at)) return CP2_OK;
-  const std::vector<size_t> changed = repair_restamp(stamps, first_item, units_per_slot, written);
-  if (changed.empty()) return CP2_OK;
-  for (size_t i : changed)
-    if (!pwrite_all(fd, reinterpret_cast<const uint8_t*>(&stamps[2 * i]), 16, (off_t)(stamps_at + 16 * i))) {
-      *err = std::string("cannot restamp ") + path + ": " + std::strerror(errno);
-      return CP2_ERR_IO;
-    }
-  if (fdatasync(fd) != 0) {
-    *err = std::string("cannot sync ") + path + ": " + std::strerror(errno);
-    return CP2_ERR_IO;
-  }
-  *restamped = changed.size();
-  return CP2_OK;
 }
 
 // trees loaded from a cache that were built from caller memory have no cell source until one is attached

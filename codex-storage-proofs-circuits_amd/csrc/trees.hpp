@@ -1,4 +1,4 @@
-// Slot-tree batch shared by slot_trees.cpp and proof_input.cpp (not installed).
+// Slot-tree batch shared by slot_trees.cpp, cache_file.cpp and proof_input.cpp (not installed).
 #pragma once
 #include <functional>
 #include <string>
@@ -7,8 +7,7 @@
 #include "internal.hpp"
 #include "kernels.hpp"
 #include "fill_pipeline.hpp"   // the slot-file read rule: read_file_cell, slot_file_error
-
-enum class CellSrc { Fake, Dev, Host, File };
+#include "cache_file.hpp"      // CellSrc; the cache files' heads, stamps and tmp-file writer (host side)
 
 struct cp2_slot_trees {
   cp2_ctx* ctx = nullptr;
@@ -60,6 +59,8 @@ struct BuildScratch {
 };
 
 int trees_check_geometry(size_t cell_size, size_t block_size, size_t n_cells, size_t n_slots);
+// slots cut into units_per_slot > 1 units of cells_per_unit cells: a power of two of units, each a power of two >= 2 of whole blocks
+bool unit_geometry_ok(uint64_t units_per_slot, size_t cell_size, size_t block_size, size_t cells_per_unit);
 // fake-data or slot-file trees; `group` = how many finished slots to batch per layer pass / callback (0: all at the end)
 // units_per_slot > 1: first_slot / n_slots / n_cells count UNITS and the cells of one unit (cp2_slot_trees above)
 // pooled_nodes: the node buffer comes from (and goes back to) the context's scratch pool instead of hipMalloc / hipFree
@@ -92,29 +93,13 @@ void path_rows(const cp2_slot_trees* t, size_t slot, uint64_t cell, size_t max_d
 // merged paths (padded to max_depth, + leaf hashes) of n (slot-in-batch, cell) pairs of a batch in one gather
 int trees_paths_multi(cp2_slot_trees* t, const uint64_t* slot_idx, const uint64_t* cell_idx, size_t n, size_t max_depth, uint8_t* out, uint8_t* leaf_hashes);
 std::string slot_file_name(const std::string& base, uint64_t slot);
-// does the file at `path` start with these eight bytes?  (proof_input.cpp; false for a file that cannot be opened, too)
-bool file_has_magic(const char* path, const char* magic8);
 bool is_pow2(uint64_t x);
 
-// Persisted form of what a compact / roots-only dataset keeps (proof_input.cpp): the kept layers of `n_slots` local slots plus what
-// they were built from.  kept_load fills the device buffer and returns CP2_OK only when the file is intact and describes exactly
-// `want` (and, for the SlotFile source, slot files of unchanged size and mtime); anything else is CP2_ERR_IO and means "rebuild".
-struct KeptMeta {
-  uint64_t n_slots = 0, cell_size = 0, block_size = 0, n_cells = 0, src = 0, dataset_seed = 0, first_slot = 0, mode = 0;
-  std::string file_base;
-};
-int kept_save(cp2_ctx* ctx, const char* path, const KeptMeta& meta, const void* d_buf, size_t bytes);
-int kept_load(cp2_ctx* ctx, const char* path, const KeptMeta& want, void* d_buf, size_t bytes);
-
-// Block repair (repair.cpp): the per-item (size, mtime_ns) stamps of the cache file at `path` -- a tree cache ("CP2TREE3") or a kept
-// file ("CP2KEPT1") -- that describes exactly these items of slot-file data (magic, geometry, SlotFile source, first item, units per
-// slot, base name): the stamps of items whose file this call wrote are set to the file's stat after the writes, where they equalled its
-// stat before the first write (repair_restamp, repair_plan.hpp), with pwrite and fdatasync in place.  Stamps sit outside the checksum.
-// *restamped = how many stamps changed; a file that does not describe these items is left alone (CP2_OK, 0).  CP2_ERR_IO when a file
-// that does describe them cannot be rewritten.
-struct FileStamp;
-int cache_restamp(const char* path, uint64_t n_items, size_t cell_size, size_t block_size, size_t n_cells, uint64_t first_item,
-                  uint64_t units_per_slot, const std::string& base, const std::vector<FileStamp>& written, size_t* restamped, std::string* err);
+// Persisted form of what a compact / roots-only dataset keeps (cache_file.cpp, beside the tree cache; its head: kept_meta, cache_file.hpp).
+// kept_load fills the device buffer and returns CP2_OK only when the file is intact and describes exactly `want` (and, for the SlotFile
+// source, slot files of unchanged size and mtime); anything else is CP2_ERR_IO and means "rebuild".
+int kept_save(cp2_ctx* ctx, const char* path, CacheHead meta, const void* d_buf, size_t bytes);
+int kept_load(cp2_ctx* ctx, const char* path, const CacheHead& want, void* d_buf, size_t bytes);
 
 // After cp2_dataset_set_roots*: do rows [first_slot, first_slot + n_local) of the dataset tree's bottom layer hold THIS dataset's own
 // slot roots?  One small download.  The multi-device exchange is verified with it (multi_gpu.cpp).

@@ -187,3 +187,38 @@ def test_body_store_workers_with_thread_sanitizer(pkg, tmp_path):
     spill.mkdir()
     r = subprocess.run([exe, "store", str(spill)], capture_output=True, timeout=600)
     assert r.returncode == 0 and b"body store ok" in r.stdout and b"ThreadSanitizer" not in r.stderr, (r.returncode, r.stderr[-3000:])
+
+
+def test_cache_file_heads_restamp_and_tmp_writer_with_sanitizers(tmp_path):
+    """The host side of the library's cache files (csrc/cache_file.hpp: the tree cache and the kept form share one head reader, one head
+    image, one restamp and one tmp-file writer) against REAL files in a scratch directory, under AddressSanitizer + UBSan: the byte image
+    of both formats against the layout restated in the check and back through cache_head_read; every refusal a one-field damage of a good
+    file (other versions' magics, a base name of 4097 bytes, stamps that are neither none nor one per item, stamps without the slot-file
+    source and the reverse, more than 2^40 stamps, files cut inside the header and inside base name or stamps, for both formats);
+    cache_restamp over real files (only the 16 bytes of each changed stamp differ, a cache of other items is left byte for byte); the
+    tmp-file writer (commit with and without fsync, no commit, a link at the tmp name).  Then the golden files, written on the GPU by the
+    commit before this module existed: each parsed, its head giving its own bytes back, its payload under its checksum, and its fields
+    those of the configuration that wrote it.  No GPU, no HIP."""
+    import json
+    golden = os.path.join(ROOT, "tests", "golden", "cache_files")
+    exe = str(tmp_path / "cache_file_check")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-pthread", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-I" + os.path.join(ROOT, "codex-storage-proofs-circuits_amd", "csrc"), "-o", exe,
+                           os.path.join(ROOT, "tests", "host_check", "cache_file_check.cpp")])
+    scratch = tmp_path / "files"
+    scratch.mkdir()
+    r = subprocess.run([exe, str(scratch), golden], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-4000:]
+    assert "cache file check ok: 75 refusals, 28 restamp cases, 8 tmp-file cases" in r.stdout, r.stdout
+    assert os.listdir(scratch) == [], "the check left files behind"
+    c = json.load(open(os.path.join(golden, "config.json")))["config"]
+    nodes = {"tree_3slots.cp2": None, "kept_mode2.cp2": 2, "kept_mode0.cp2": 0}
+    lines = {l.split()[1].rstrip(":"): dict(kv.split("=") for kv in l.split()[2:]) for l in r.stdout.splitlines() if l.startswith("golden ")}
+    assert sorted(lines) == sorted(nodes)
+    for name, mode in nodes.items():
+        h = lines[name]
+        assert h["format"] == ("tree" if mode is None else "kept") and int(h["mode"]) == (mode or 0), (name, h)
+        assert [int(h[k]) for k in ("n_items", "cell_size", "block_size", "n_cells", "units_per_slot", "src", "seed", "first_item", "base", "stamps")] == \
+            [c["nSlots"], c["cellSize"], c["blockSize"], c["nCells"], 1, 0, c["seed"], 0, 0, 0], (name, h)
+        assert os.path.getsize(os.path.join(golden, name)) == 104 + int(h["payload"]) < 16384
+    assert int(lines["kept_mode0.cp2"]["payload"]) == 32 * c["nSlots"]
