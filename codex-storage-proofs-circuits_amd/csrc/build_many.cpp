@@ -4,10 +4,10 @@
 // pipe (rings, events, a copy stream set up and torn down), a sliver of a hash launch and a drain of the device: 5.7 ms a dataset of 8
 // MiB, 27 times what the same files cost as the slots of one dataset (profiles/scrub_many_rate.txt).  The read side of one pass over the
 // slots of many datasets exists since cp2_datasets_scrub_many: trees_build_file_list builds a batch from a table of file names, and the
-// scrub's batch loop (scrub.cpp) drives it with a BuildScratch, two node buffers and two address tables.  This is its mirror image on the
-// write side.  Where the scrub COMPARES a batch's fresh layer with the kept layers through a table of addresses, the build WRITES the
-// batch's layers through one: one k_scatter_rows_addr launch per kept layer, whatever number of datasets the batch's items belong to
-// (dataset_keep_from_batch, proof_input.cpp, is one hipMemcpyAsync per layer into ONE dataset's layout: 4096 x 8 tiny copies here).
+// batch loop (batch_loop.hpp; DESIGN.md, "The batch loop") drives it.  This is the scrub's mirror image on the write side.  Where the
+// scrub COMPARES a batch's fresh layer with the kept layers through a table of addresses, the build WRITES the batch's layers through
+// one: one k_scatter_rows_addr launch per kept layer, whatever number of datasets the batch's items belong to (dataset_keep_from_batch,
+// proof_input.cpp, is one hipMemcpyAsync per layer into ONE dataset's layout: 4096 x 8 tiny copies here).
 //
 // The plan -- classes, items, batches, the row of every kept layer in a batch and in a request's buffer, the address tables -- is
 // build_many_plan.hpp (host only).  What the datasets keep lives in ARENAS: device allocations shared by consecutive requests of the call
@@ -95,75 +95,55 @@ int allocate(cp2_ctx* ctx, const cp2_config* cfgs, const std::vector<BuildReques
   return CP2_OK;
 }
 
-// One class through the batch loop (scrub_loop's shape, scrub.cpp): one BuildScratch, two node buffers used alternately, two pinned
-// and two device address tables of kept layers x batch entries, table b rewritten for batch k + 2 only after batch k's event; in the
-// builder's SlotsDone hook -- on the stream the batch's layer passes ran on -- the table's upload, then one k_scatter_rows_addr launch
-// per kept layer.  No HIP call per dataset anywhere in here.
+// One class through the batch loop: two pinned and two device address tables of kept layers x batch entries, table b rewritten for
+// batch k + 2 only after batch k's event, like node buffer b; in the builder's SlotsDone hook -- on the stream the batch's layer passes
+// ran on -- the table's upload, then one k_scatter_rows_addr launch per kept layer.  No HIP call per dataset anywhere in here.
 int build_class(cp2_ctx* ctx, const BuildClass& k, int mode, const std::vector<BuildRequest>& req, const std::vector<std::string>& names,
                 const std::vector<uint64_t>& base) {
   const BuildLayers L = build_many_layers(k.cell_size, k.block_size, k.n_cells, mode);
   const size_t n_items = k.n_items(), batch = k.batch, nl = L.n();
   if (n_items == 0) return CP2_OK;
   const int n_bufs = n_items > batch ? 2 : 1;
-  DevBuf d_addr[2];                             // (declared before the scratch: they go after it has drained the streams)
+  DevBuf d_addr[2];                             // (declared before the device: they go after its scratch has drained the streams)
   PinBuf h_addr[2];
   for (int b = 0; b < n_bufs; ++b) {
     CP2_TRY(d_addr[b].scratch(ctx, nl * batch * 8));
     CP2_TRY(h_addr[b].alloc(ctx, nl * batch * 8));
   }
-  int st = CP2_OK;
-  {
-    BuildScratch scratch;                       // drains the context's streams before its buffers go, whatever path leaves this scope
-    hipEvent_t kept[2] = {nullptr, nullptr};
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 2; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } ev_guard{kept};
-    for (int i = 0; i < 2; ++i) CP2_HIP(ctx, hipEventCreateWithFlags(&kept[i], hipEventDisableTiming));
-    size_t kb = 0;
-    for (size_t s0 = 0; st == CP2_OK && s0 < n_items; s0 += batch, ++kb) {
-      const size_t n = std::min(batch, n_items - s0);
-      const int b = (int)(kb & 1);
-      if (kb >= 2 && hipEventSynchronize(kept[b]) != hipSuccess) { (void)hipGetLastError(); ctx->err = "build many: a batch failed on the device"; st = CP2_ERR_HIP; break; }
-      // (table b's last upload landed with batch kb - 2)
-      if (!build_many_addr_table(k, L, req, base.data(), s0, n, static_cast<uint64_t*>(h_addr[b].p))) {
+  const ItemSource src{true, std::string(), 0, k.cell_size, k.block_size, (size_t)k.n_cells, 1, names.data(), names.size()};
+  // the builder calls this once, with every slot of the batch, on the stream its layer passes ran on (group 0: one pass at the end)
+  const auto keep = [&](const BatchStep& s, cp2_slot_trees* t, size_t a, size_t z, hipStream_t ls) -> int {
+    const size_t b = (size_t)s.b, n = s.n;
+    if (a != 0 || z != n || t->n_slots != n) { ctx->err = "build many: a batch's layers were built in parts"; return CP2_ERR_INVALID; }
+    const size_t below = mode == 1 ? t->bsizes.size() - 1 : 0;             // kept layers below the block roots
+    if (nl != (mode == 0 ? 1 : below + t->tsizes.size())) { ctx->err = "build many: the plan and the batch disagree about the kept layers"; return CP2_ERR_INVALID; }
+    CP2_HIP(ctx, hipMemcpyAsync(d_addr[b].p, h_addr[b].p, nl * n * 8, hipMemcpyHostToDevice, ls));
+    for (size_t layer = 0; layer < nl; ++layer) {
+      const size_t src_row = (size_t)build_many_src_row(L, layer, n);
+      // the plan's row against the batch's own layout: a write through a wrong row is a fault, not a wrong answer
+      const size_t big = mode == 0 ? t->tsizes.size() - 1 : layer - below;
+      const size_t have = layer < below ? t->boff[layer] : t->toff[big];
+      const size_t rows = layer < below ? t->nblocks * t->bsizes[layer] : t->tsizes[big];
+      if (src_row != have || rows != L.rows[layer] || (src_row + n * rows) * 32 > t->nodes.bytes) {
+        ctx->err = "build many: the plan and the batch disagree about a layer";
+        return CP2_ERR_INVALID;
+      }
+      CP2_HIP(ctx, cp2k::launch_scatter_rows_addr(t->nodes.u8() + src_row * 32, rows, static_cast<const uint64_t*>(d_addr[b].p) + layer * n, rows, n, ls));
+    }
+    return CP2_OK;
+  };
+  BatchDevice dev;
+  CP2_TRY(dev.init(ctx));
+  return batch_loop(dev, "build many", ctx->err, n_items, batch,
+      [&](const BatchStep& s) -> int {   // (table b's last upload landed with batch k - 2)
+        if (build_many_addr_table(k, L, req, base.data(), s.s0, s.n, static_cast<uint64_t*>(h_addr[s.b].p))) return CP2_OK;
         ctx->err = "build many: a kept row outside its request's buffer";
-        st = CP2_ERR_INVALID;
-        break;
-      }
-      // the builder calls this once, with every slot of the batch, on the stream its layer passes ran on (group 0: one pass at the end)
-      SlotsDone keep = [&, b, n](cp2_slot_trees* t, size_t a, size_t z, hipStream_t ls) -> int {
-        if (a != 0 || z != n || t->n_slots != n) { ctx->err = "build many: a batch's layers were built in parts"; return CP2_ERR_INVALID; }
-        const size_t below = mode == 1 ? t->bsizes.size() - 1 : 0;             // kept layers below the block roots
-        if (nl != (mode == 0 ? 1 : below + t->tsizes.size())) { ctx->err = "build many: the plan and the batch disagree about the kept layers"; return CP2_ERR_INVALID; }
-        CP2_HIP(ctx, hipMemcpyAsync(d_addr[b].p, h_addr[b].p, nl * n * 8, hipMemcpyHostToDevice, ls));
-        for (size_t layer = 0; layer < nl; ++layer) {
-          const size_t src = (size_t)build_many_src_row(L, layer, n);
-          // the plan's row against the batch's own layout: a write through a wrong row is a fault, not a wrong answer
-          const size_t big = mode == 0 ? t->tsizes.size() - 1 : layer - below;
-          const size_t have = layer < below ? t->boff[layer] : t->toff[big];
-          const size_t rows = layer < below ? t->nblocks * t->bsizes[layer] : t->tsizes[big];
-          if (src != have || rows != L.rows[layer] || (src + n * rows) * 32 > t->nodes.bytes) {
-            ctx->err = "build many: the plan and the batch disagree about a layer";
-            return CP2_ERR_INVALID;
-          }
-          CP2_HIP(ctx, cp2k::launch_scatter_rows_addr(t->nodes.u8() + src * 32, rows, static_cast<const uint64_t*>(d_addr[b].p) + layer * n, rows, n, ls));
-        }
-        return CP2_OK;
-      };
-      cp2_slot_trees* t = nullptr;
-      st = trees_build_file_list(ctx, names.data() + s0, n, k.cell_size, k.block_size, (size_t)k.n_cells, 0, keep, &t, true, &scratch, b);
-      hipStream_t tail = scratch.tail_stream ? scratch.tail_stream : ctx->stream;
-      if (st == CP2_OK && hipEventRecord(kept[b], tail) != hipSuccess) { ctx->err = "hipEventRecord failed"; st = CP2_ERR_HIP; }
-      cp2_slot_trees_free(t);                   // (the batch's nodes are the scratch's: nothing is waited for here)
-    }
-    if (st == CP2_OK) {                         // everything landed (a failed launch or copy shows up here)
-      if (hipStreamSynchronize(ctx->stream) != hipSuccess || (ctx->aux_stream && hipStreamSynchronize(ctx->aux_stream) != hipSuccess) ||
-          (ctx->aux2_stream && hipStreamSynchronize(ctx->aux2_stream) != hipSuccess)) {
-        (void)hipGetLastError();
-        ctx->err = "build many: a batch failed on the device";
-        st = CP2_ERR_HIP;
-      }
-    }
-  }
-  return st;
+        return CP2_ERR_INVALID;
+      },
+      [&](const BatchStep& s, hipStream_t* tail) -> int {
+        return dev.build(src, s.s0, s.n, 0, [&](cp2_slot_trees* t, size_t a, size_t z, hipStream_t ls) { return keep(s, t, a, z, ls); }, s.b, tail);
+      },
+      [](const BatchStep&, hipStream_t) -> int { return CP2_OK; }, [](const BatchStep&) {});
 }
 
 // one attempt in `mode`: every dataset of the call in built.ds, or an error (the caller frees what the attempt made)
@@ -196,11 +176,8 @@ int call_mode(cp2_ctx* ctx, const std::vector<BuildRequest>& req, const BuildPla
     data += (u128)r.n_local * r.n_cells * r.cell_size;
     nodes_all += (u128)kept_bytes(r, 1);
     compact_all += (u128)kept_bytes(r, 2);
-    if (!r.from_file) {
-      cp2_config c{};
-      c.cell_size = r.cell_size; c.block_size = r.block_size; c.n_cells = r.n_cells;
-      in_flight = std::max<u128>(in_flight, 2 * (u128)trees_node_bytes(transient_batch_slots(ctx, c, r.n_local), r.cell_size, r.block_size, r.n_cells));
-    }
+    if (!r.from_file)
+      in_flight = std::max<u128>(in_flight, 2 * (u128)trees_node_bytes(trees_batch_items(ctx, r.cell_size, r.block_size, r.n_cells, r.n_local), r.cell_size, r.block_size, r.n_cells));
   }
   for (const BuildClass& k : plan.classes)
     in_flight = std::max<u128>(in_flight, 2 * (u128)trees_node_bytes(k.batch, k.cell_size, k.block_size, (size_t)k.n_cells));

@@ -13,6 +13,8 @@
 #include <string>
 #include <vector>
 
+#include "batch_loop.hpp"   // batch_items
+
 namespace cp2i {
 
 // what the plan knows of one request (already validated: block_size a multiple of cell_size, n_cells a multiple of cells per block)
@@ -73,12 +75,6 @@ inline uint64_t build_many_dst_row(const BuildLayers& L, size_t layer, uint64_t 
   return n_local * L.dst_prefix[layer] + local * L.rows[layer];
 }
 
-// transient_batch_slots' rule: half a staging chunk of nodes, at least one item, no more than there are
-inline size_t build_many_batch(size_t stage_bytes, uint64_t item_rows, uint64_t n_items) {
-  const uint64_t per_item = std::max<uint64_t>(1, item_rows * 32);
-  return (size_t)std::max<uint64_t>(1, std::min<uint64_t>(n_items, (stage_bytes / 2) / per_item));
-}
-
 struct BuildClass {
   size_t cell_size = 0, block_size = 0;
   uint64_t n_cells = 0;
@@ -113,7 +109,7 @@ inline BuildPlan build_many_plan(const std::vector<BuildRequest>& req, size_t st
     for (uint64_t s = 0; s < r.n_local; ++s) { k->request.push_back(i); k->local.push_back(s); }
   }
   for (auto& k : p.classes) {
-    k.batch = build_many_batch(stage_bytes, build_many_layers(k.cell_size, k.block_size, k.n_cells, 1).item_rows, k.n_items());
+    k.batch = batch_items(stage_bytes, build_many_layers(k.cell_size, k.block_size, k.n_cells, 1).item_rows * 32, k.n_items());   // every build's rule
     p.n_items += k.n_items();
     p.n_batches += k.n_batches();
   }

@@ -380,18 +380,13 @@ int stream_map(cp2_ctx* ctx, const uint8_t* in, size_t in_item, uint8_t* out, si
   struct Ring {
     cp2_ctx* ctx;
     hipStream_t up = nullptr, down = nullptr;
-    hipEvent_t e_up[MAX_DEPTH] = {}, e_k[MAX_DEPTH] = {}, e_down[MAX_DEPTH] = {};
+    Event e_up[MAX_DEPTH], e_k[MAX_DEPTH], e_down[MAX_DEPTH];   // (members go after the destructor's body: after its drain)
     PinBuf pin_in[MAX_DEPTH], pin_out[MAX_DEPTH];
     DevBuf d_in[MAX_DEPTH], d_out[MAX_DEPTH];
-    ~Ring() {   // drain everything before the buffers go back to the pools
+    ~Ring() {   // drain everything before the events go and the buffers go back to the pools
       if (up) (void)hipStreamSynchronize(up);
       (void)hipStreamSynchronize(ctx->stream);
       if (down) (void)hipStreamSynchronize(down);
-      for (int r = 0; r < MAX_DEPTH; ++r) {
-        if (e_up[r]) (void)hipEventDestroy(e_up[r]);
-        if (e_k[r]) (void)hipEventDestroy(e_k[r]);
-        if (e_down[r]) (void)hipEventDestroy(e_down[r]);
-      }
       if (up) (void)hipStreamDestroy(up);
       if (down) (void)hipStreamDestroy(down);
     }
@@ -404,9 +399,9 @@ int stream_map(cp2_ctx* ctx, const uint8_t* in, size_t in_item, uint8_t* out, si
   const bool direct = host_range_pinned(in, n * in_item, ((size_t)1 << 20) * in_item) && host_range_pinned(out, n * out_item, ((size_t)1 << 20) * out_item);
   const size_t chunk = direct ? (size_t)1 << 20 : CHUNK;
   for (int r = 0; r < DEPTH; ++r) {
-    CP2_HIP(ctx, hipEventCreateWithFlags(&ring.e_up[r], hipEventDisableTiming));
-    CP2_HIP(ctx, hipEventCreateWithFlags(&ring.e_k[r], hipEventDisableTiming));
-    CP2_HIP(ctx, hipEventCreateWithFlags(&ring.e_down[r], hipEventDisableTiming));
+    CP2_TRY(ring.e_up[r].create(ctx));
+    CP2_TRY(ring.e_k[r].create(ctx));
+    CP2_TRY(ring.e_down[r].create(ctx));
     if (!direct) {
       CP2_TRY(ring.pin_in[r].alloc(ctx, chunk * in_item));
       CP2_TRY(ring.pin_out[r].alloc(ctx, chunk * out_item));

@@ -90,7 +90,6 @@ int dataset_mode_that_fits(cp2_ctx* ctx, unsigned __int128 data, unsigned __int1
                            unsigned __int128 in_flight);
 size_t compact_bytes(const cp2_config& c, size_t n_slots);
 size_t dataset_kept_layout(cp2_dataset* ds, int mode);   // compact / roots only: sets tree_mode, csizes and coff; the bytes of what is kept
-size_t transient_batch_slots(const cp2_ctx* ctx, const cp2_config& c, uint64_t n_local);
 int dataset_build_in_mode(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local, int mode, cp2_dataset** out);
 bool step_down(cp2_ctx* ctx, int* mode, const char* what);
 

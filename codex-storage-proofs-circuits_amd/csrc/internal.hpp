@@ -176,6 +176,19 @@ namespace cp2i {
     if (s__ != CP2_OK) return s__;    \
   } while (0)
 
+// RAII event without timing.  Members and locals go in reverse order of declaration: an Event declared AFTER the buffers (or the scratch,
+// or the ring) it guards is destroyed BEFORE they drain their streams and go -- an event that is still pending then is released by the
+// runtime once it has completed --; one declared before them outlives their drain.
+struct Event {
+  hipEvent_t e = nullptr;
+  Event() = default;
+  Event(const Event&) = delete;
+  Event& operator=(const Event&) = delete;
+  ~Event() { if (e) (void)hipEventDestroy(e); }
+  int create(cp2_ctx* ctx) { CP2_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming)); return CP2_OK; }
+  operator hipEvent_t() const { return e; }
+};
+
 // host threads for slot-file reads outside the ingestion pipe (on_threads, workers.hpp): cp2_set_ingest's fill threads, 8 by default
 inline int fill_threads(const cp2_ctx* ctx) { return ctx->ingest_threads > 0 ? ctx->ingest_threads : 8; }
 

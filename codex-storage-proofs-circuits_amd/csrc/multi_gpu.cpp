@@ -1200,7 +1200,7 @@ extern "C" int cp2_multi_dataset_scrub(cp2_multi_dataset* mds, uint64_t first_sl
       r = dataset_scrub(s.ds, a, z - a, level, cap, got[i], &count[i]);
     } else {
       const cp2_slot_trees* t = s.units;
-      r = scrub_items(t->ctx, scrub_src_of(t, S), a, z - a, CP2_SCRUB_CELL, t->nodes.u8() + (t->boff[0] + (a - s.first) * t->n_cells) * 32, t->n_cells, cap,
+      r = scrub_items(t->ctx, item_source_of(t, S), a, z - a, CP2_SCRUB_CELL, t->nodes.u8() + (t->boff[0] + (a - s.first) * t->n_cells) * 32, t->n_cells, cap,
                       got[i], &count[i]);
       for (size_t j = 0; r == CP2_OK && j < got[i].size(); j += 2) {   // (unit, cell of the unit) -> (slot, cell of the slot)
         const uint64_t u = got[i][j];

@@ -69,11 +69,12 @@ cp2_dataset* dataset_new(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slo
   return ds;
 }
 
+ItemSource cp2i::item_source_of(const cp2_dataset* ds) {
+  return {ds->from_file, ds->file_base, ds->cfg.seed, ds->cfg.cell_size, ds->cfg.block_size, ds->cfg.n_cells, 1};
+}
+
 static int dataset_build_trees(cp2_dataset* ds, size_t group, const SlotsDone& done) {
-  const cp2_config& c = ds->cfg;
-  if (ds->from_file)
-    return trees_build_files(ds->ctx, ds->file_base, ds->first_slot, ds->n_local, c.cell_size, c.block_size, c.n_cells, group, done, &ds->trees);
-  return trees_build_fake(ds->ctx, c.seed, ds->first_slot, ds->n_local, c.cell_size, c.block_size, c.n_cells, group, done, &ds->trees);
+  return build_items(ds->ctx, item_source_of(ds), ds->first_slot, ds->n_local, group, done, &ds->trees);
 }
 
 // the device buffer holding the roots of the local slots (n_local x 32 bytes)
@@ -86,10 +87,7 @@ const void* dataset_roots_dev(const cp2_dataset* ds) {
 // the trees of `n` local slots starting at local index `s0`, in pooled scratch (roots-only datasets: batches of the build, and
 // the one slot a proof input is made for)
 static int dataset_transient_trees(const cp2_dataset* ds, size_t s0, size_t n, cp2_slot_trees** out) {
-  const cp2_config& c = ds->cfg;
-  if (ds->from_file)
-    return trees_build_files(ds->ctx, ds->file_base, ds->first_slot + s0, n, c.cell_size, c.block_size, c.n_cells, 0, nullptr, out, 1, true);
-  return trees_build_fake(ds->ctx, c.seed, ds->first_slot + s0, n, c.cell_size, c.block_size, c.n_cells, 0, nullptr, out, 1, true);
+  return build_items(ds->ctx, item_source_of(ds), ds->first_slot + s0, n, 0, nullptr, out, true);
 }
 
 // bytes of the compact part (block roots and up) of n_slots slot trees
@@ -106,11 +104,9 @@ size_t compact_bytes(const cp2_config& c, size_t n_slots) {
 // chosen here (then dataset_build may step down when the allocation fails after all) or named by the caller (never changed).
 #define CP2_TRY_MODE(call) do { if ((call) != CP2_OK) return 1; } while (0)   /* the device does not answer: plan as if everything fits */
 
-// Slots per batch of a transient (compact / roots-only) build: half a staging chunk of nodes (1 GiB by default: 4 slots of 8 GiB), at
-// least one slot.  The pipelined build holds two such node buffers, together one staging chunk's worth.
-size_t transient_batch_slots(const cp2_ctx* ctx, const cp2_config& c, uint64_t n_local) {
-  const size_t per_slot = std::max<size_t>(1, trees_node_bytes(1, c.cell_size, c.block_size, c.n_cells));
-  return std::max<size_t>(1, std::min<size_t>(n_local, (ctx->stage_bytes / 2) / per_slot));
+// Slots per batch of a transient (compact / roots-only) build: every batch loop's rule (batch_items, batch_loop.hpp)
+static size_t transient_batch_slots(const cp2_ctx* ctx, const cp2_config& c, uint64_t n_local) {
+  return trees_batch_items(ctx, c.cell_size, c.block_size, c.n_cells, n_local);
 }
 
 int dataset_named_mode(cp2_ctx* ctx, bool* automatic) {
@@ -186,54 +182,29 @@ static int dataset_keep_from_batch(cp2_dataset* ds, const cp2_slot_trees* t, siz
   return CP2_OK;
 }
 
-// compact / roots-only build: batches of at most ~1 GiB of nodes (transient_batch_slots: 4 slots of 8 GiB; at least one slot), every
-// batch a normal builder call; what the mode keeps is copied out, the rest is overwritten by the batch after next.
-//
-// The batches PIPELINE, from either source (BuildScratch: two node buffers used alternately, staging -- or, for slot files, the whole
-// ingestion pipe -- that outlives a builder call, nothing synchronised per batch).  A batch ends with its tree-layer passes -- 22 launches for 2^22-cell slots, the top 16 of them one lone
-// permutation latency each -- and the copy-out of what is kept, all on the context's THIRD stream; the next batch's generation and
-// hashing go on alternating between the first two meanwhile, so the device does not drain between batches and the tail of a
-// batch's last hash launch has the next batch's first one beside it (round 4 synchronised and freed here).  Node buffer b is handed
-// to batch k + 2 once batch k's copy-out has completed (an event; long past by then).  (Until round 6 slot files went batch by batch, a new
-// pipe set up and drained for each: "bound by the storage" is true of cold files, not of files in the page cache.)
+// compact / roots-only build: batches of transient_batch_slots slots, every batch a normal builder call; what the mode keeps is copied
+// out, the rest is overwritten by the batch after next.  The batches PIPELINE, from either source, through the batch loop
+// (batch_loop.hpp; DESIGN.md, "The batch loop").  A batch ends with its tree-layer passes -- 22 launches for 2^22-cell slots, the top
+// 16 of them one lone permutation latency each -- and the copy-out of what is kept, all on the context's THIRD stream; the next batch's
+// generation and hashing go on alternating between the first two meanwhile, so the device does not drain between batches and the tail
+// of a batch's last hash launch has the next batch's first one beside it.
 static int dataset_build_transient(cp2_dataset* ds, int mode, bool allocated = false) {
   cp2_ctx* ctx = ds->ctx;
-  const cp2_config& c = ds->cfg;
-  const size_t batch = transient_batch_slots(ctx, c, ds->n_local);
+  const size_t batch = transient_batch_slots(ctx, ds->cfg, ds->n_local);
   if (!allocated) CP2_TRY(dataset_alloc_kept(ds, mode));
-  const char* what = mode == 2 ? "compact" : "roots-only";
+  const std::string what = mode == 2 ? "compact build" : "roots-only build";
+  const ItemSource src = item_source_of(ds);
   StageTimer trace;
-  int st = CP2_OK;
   {
-    BuildScratch scratch;                       // drains the context's streams before its buffers go, whatever path leaves this scope
-    hipEvent_t kept[2] = {nullptr, nullptr};
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 2; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } ev_guard{kept};
-    for (int i = 0; i < 2; ++i) CP2_HIP(ctx, hipEventCreateWithFlags(&kept[i], hipEventDisableTiming));
-    size_t k = 0;
-    for (size_t s0 = 0; st == CP2_OK && s0 < ds->n_local; s0 += batch, ++k) {
-      const size_t n = std::min(batch, (size_t)ds->n_local - s0);
-      const int b = (int)(k & 1);
-      if (k >= 2 && hipEventSynchronize(kept[b]) != hipSuccess) { ctx->err = std::string(what) + " build: a batch failed on the device"; st = CP2_ERR_HIP; break; }
-      cp2_slot_trees* t = nullptr;
-      st = ds->from_file ? trees_build_files(ctx, ds->file_base, ds->first_slot + s0, n, c.cell_size, c.block_size, c.n_cells, 0, nullptr, &t, 1, true, &scratch, b)
-                         : trees_build_fake(ctx, c.seed, ds->first_slot + s0, n, c.cell_size, c.block_size, c.n_cells, 0, nullptr, &t, 1, true, &scratch, b);
-      hipStream_t tail = scratch.tail_stream ? scratch.tail_stream : ctx->stream;
-      if (st == CP2_OK) st = dataset_keep_from_batch(ds, t, s0, tail);    // follows the batch's layer passes on their stream (the context's third)
-      if (st == CP2_OK && hipEventRecord(kept[b], tail) != hipSuccess) { ctx->err = "hipEventRecord failed"; st = CP2_ERR_HIP; }
-      cp2_slot_trees_free(t);                                             // (the batch's nodes are the scratch's: nothing is waited for here)
-      if (trace.on && ((k % 32) == 31 || s0 + n == ds->n_local))
-        std::fprintf(stderr, "[cp2 trace] %s build: %zu of %llu slots enqueued\n", what, s0 + n, (unsigned long long)ds->n_local);
-    }
-    if (st == CP2_OK) {                         // everything landed (a failed launch or copy shows up here)
-      if (hipStreamSynchronize(ctx->stream) != hipSuccess || (ctx->aux_stream && hipStreamSynchronize(ctx->aux_stream) != hipSuccess) ||
-          (ctx->aux2_stream && hipStreamSynchronize(ctx->aux2_stream) != hipSuccess)) {
-        (void)hipGetLastError();
-        ctx->err = std::string(what) + " build: a batch failed on the device";
-        st = CP2_ERR_HIP;
-      }
-    }
+    BatchDevice dev;
+    CP2_TRY(dev.init(ctx));
+    CP2_TRY(batch_loop(dev, what.c_str(), ctx->err, (size_t)ds->n_local, batch, [](const BatchStep&) -> int { return CP2_OK; },
+        [&](const BatchStep& s, hipStream_t* tail) -> int { return dev.build(src, ds->first_slot + s.s0, s.n, 0, nullptr, s.b, tail); },
+        [&](const BatchStep& s, hipStream_t tail) -> int { return dataset_keep_from_batch(ds, dev.batch, s.s0, tail); },   // behind the batch's layer passes
+        [&](const BatchStep& s) {
+          if (trace.on) std::fprintf(stderr, "[cp2 trace] %s: %zu of %llu slots enqueued\n", what.c_str(), s.s0 + s.n, (unsigned long long)ds->n_local);
+        }));
   }
-  if (st != CP2_OK) return st;
   trace.lap(mode == 2 ? "compact build (block layers dropped)" : "roots-only build (trees dropped)");
   return CP2_OK;
 }
@@ -861,9 +832,8 @@ struct StreamRing {
   static constexpr int MAX_DEPTH = 8;
   int depth = 4;
   SampleHost host[MAX_DEPTH];
-  hipEvent_t landed[MAX_DEPTH] = {};
+  Event landed[MAX_DEPTH];                         // (after host[], which drain their stream themselves: the events go first, as they always have)
   size_t s0[MAX_DEPTH] = {}, s1[MAX_DEPTH] = {};   // slot range parked in host[r]
-  ~StreamRing() { for (auto e : landed) if (e) (void)hipEventDestroy(e); }   // host[] drain their stream themselves
   // body tasks still reading host[r]: the build thread sleeps on the condition variable until a ring slot is free
   void begin(int r, size_t n) { std::lock_guard<std::mutex> lk(mu); pending[r] = n; }
   void task_done(int r) {
@@ -918,12 +888,11 @@ static int build_streamed_in_mode(cp2_ctx* ctx, const cp2_config* cfg, uint64_t 
   ring.depth = from_file ? StreamRing::MAX_DEPTH : 4;
   for (int r = 0; r < ring.depth; ++r) {
     CP2_TRY(ring.host[r].init(ctx, group_slots, ns, md, cs, !from_file));
-    CP2_HIP(ctx, hipEventCreateWithFlags(&ring.landed[r], hipEventDisableTiming));
+    CP2_TRY(ring.landed[r].create(ctx));
   }
   CP2_HIP(ctx, hipMemcpyAsync(dev.entropy.p, entropy, 32, hipMemcpyHostToDevice, aux));
-  hipEvent_t trees_ready = nullptr;
-  CP2_HIP(ctx, hipEventCreateWithFlags(&trees_ready, hipEventDisableTiming));
-  struct EvGuard { hipEvent_t e; ~EvGuard() { (void)hipEventDestroy(e); } } ev_guard{trees_ready};
+  Event trees_ready;
+  CP2_TRY(trees_ready.create(ctx));
 
   std::atomic<int> task_status{CP2_OK};
   std::mutex io_mu;
@@ -1039,49 +1008,34 @@ static int build_streamed_in_mode(cp2_ctx* ctx, const cp2_config* cfg, uint64_t 
       batch = std::max(group_slots, batch / group_slots * group_slots);
       st = dataset_alloc_kept(dsp, tree_mode);
       {
-        // The batches PIPELINE, fake data and slot files alike (BuildScratch: two node buffers used alternately, nothing synchronised per batch).  A
-        // batch's tail -- the layer passes of its last group, that group's sampling, gathers and downloads, the copy-out of what
-        // is kept: all on the third stream -- runs while the next batch's generation and hashing already occupy the two hashing
-        // streams (round 4 drained the device here: 816 s against 806 s for the roots alone over 32 TiB).  Node buffer b goes to
-        // batch k + 2 once batch k's copy-out and last sampling have completed.
-        BuildScratch scratch;                                    // drains the context's streams before its buffers go
-        hipStream_t layer_stream = nullptr;
-        if (st == CP2_OK) st = aux_stream(ctx, &layer_stream, 1);
-        hipEvent_t done_ev[2] = {nullptr, nullptr}, sampled[2] = {nullptr, nullptr};
-        struct EvGuard { hipEvent_t* a; hipEvent_t* b; ~EvGuard() { for (int i = 0; i < 2; ++i) { if (a[i]) (void)hipEventDestroy(a[i]); if (b[i]) (void)hipEventDestroy(b[i]); } } } ev_guard2{done_ev, sampled};
-        for (int i = 0; i < 2 && st == CP2_OK; ++i)
-          if (hipEventCreateWithFlags(&done_ev[i], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&sampled[i], hipEventDisableTiming) != hipSuccess) {
-            ctx->err = "hipEventCreate failed";
-            st = CP2_ERR_HIP;
-          }
-        size_t k = 0;
-        for (size_t base = 0; st == CP2_OK && base < n_local; base += batch, ++k) {
-          const size_t nb = std::min(batch, (size_t)n_local - base);
-          const int b = (int)(k & 1);
-          if (k >= 2 && hipEventSynchronize(done_ev[b]) != hipSuccess) { ctx->err = "streamed build: a batch failed on the device"; st = CP2_ERR_HIP; break; }
-          slot_base = base;
-          have_geom = false;                                     // node offsets are those of THIS batch's layout
-          cp2_slot_trees* t = nullptr;
-          st = from_file ? trees_build_files(ctx, file_base, first_slot + base, nb, cfgv.cell_size, cfgv.block_size, cfgv.n_cells, group_slots, on_done, &t, 1, true, &scratch, b)
-                         : trees_build_fake(ctx, cfgv.seed, first_slot + base, nb, cfgv.cell_size, cfgv.block_size, cfgv.n_cells, group_slots, on_done, &t, 1, true, &scratch, b);
-          layer_stream = scratch.tail_stream ? scratch.tail_stream : layer_stream;         // where the builder put the batch's layer passes (the third stream)
-          if (st == CP2_OK) st = dataset_keep_from_batch(dsp, t, base, layer_stream);     // follows the batch's last layer pass on that stream
-          if (st == CP2_OK && (hipEventRecord(sampled[b], aux) != hipSuccess || hipStreamWaitEvent(layer_stream, sampled[b], 0) != hipSuccess ||
-                               hipEventRecord(done_ev[b], layer_stream) != hipSuccess)) {
-            ctx->err = "streamed build: event bookkeeping failed";
-            st = CP2_ERR_HIP;
-          }
-          cp2_slot_trees_free(t);                                // (the batch's nodes are the scratch's: nothing is waited for here)
-          if (trace.on && ((k % 32) == 31 || base + nb == n_local))
-            std::fprintf(stderr, "[cp2 trace] streamed %s build: %zu of %llu slots enqueued\n", tree_mode == 2 ? "compact" : "roots-only", base + nb, (unsigned long long)n_local);
-        }
-        while (st == CP2_OK && consumed < n_groups) { st = consume(consumed); ++consumed; }
+        // The batches PIPELINE, fake data and slot files alike, through the batch loop (batch_loop.hpp).  A batch's tail -- the layer passes
+        // of its last group, that group's sampling, gathers and downloads, the copy-out of what is kept: all on the third stream -- runs
+        // while the next batch's generation and hashing already occupy the two hashing streams.  Node buffer b goes to batch k + 2 once
+        // batch k's copy-out and last sampling have completed: the tail waits for `sampled` before the loop records its event on it.
+        BatchDevice batches;
+        Event sampled[2];                                        // (after the device, like its own events: gone before its scratch drains)
+        const ItemSource src = item_source_of(dsp);
+        const std::string what = std::string("streamed ") + (tree_mode == 2 ? "compact" : "roots-only") + " build";
+        if (st == CP2_OK) st = batches.init(ctx);
+        for (int i = 0; i < 2 && st == CP2_OK; ++i) st = sampled[i].create(ctx);
+        if (st == CP2_OK)
+          st = batch_loop(batches, "streamed build", ctx->err, (size_t)n_local, batch,
+              [&](const BatchStep& s) -> int { slot_base = s.s0; have_geom = false; return CP2_OK; },   // node offsets are those of THIS batch's layout
+              [&](const BatchStep& s, hipStream_t* tail) -> int { return batches.build(src, first_slot + s.s0, s.n, group_slots, on_done, s.b, tail); },
+              [&](const BatchStep& s, hipStream_t tail) -> int {
+                CP2_TRY(dataset_keep_from_batch(dsp, batches.batch, s.s0, tail));   // follows the batch's last layer pass on that stream
+                if (hipEventRecord(sampled[s.b], aux) != hipSuccess || hipStreamWaitEvent(tail, sampled[s.b], 0) != hipSuccess) {
+                  ctx->err = "streamed build: event bookkeeping failed";
+                  return CP2_ERR_HIP;
+                }
+                // the last batch: the passes still parked go to the workers now, so that their formatting overlaps the loop's drain
+                while (s.last && consumed < n_groups) { CP2_TRY(consume(consumed)); ++consumed; }
+                return CP2_OK;
+              },
+              [&](const BatchStep& s) {
+                if (trace.on) std::fprintf(stderr, "[cp2 trace] %s: %zu of %llu slots enqueued\n", what.c_str(), s.s0 + s.n, (unsigned long long)n_local);
+              });
         pool.wait_idle();
-        if (st == CP2_OK && (hipStreamSynchronize(ctx->stream) != hipSuccess || hipStreamSynchronize(layer_stream) != hipSuccess || hipStreamSynchronize(aux) != hipSuccess)) {
-          (void)hipGetLastError();
-          ctx->err = "streamed build: a batch failed on the device";
-          st = CP2_ERR_HIP;
-        }
       }
       trace.lap("trees + bodies, batch by batch (trees dropped)");
     }

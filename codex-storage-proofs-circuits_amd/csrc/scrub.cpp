@@ -3,12 +3,12 @@
 //
 // A storage node keeps a slot's trees -- every node, the compact layers or the roots -- and proves every period from the touched blocks
 // alone; nothing on that path reads the rest of the slot.  A scrub re-reads the selected slots from the dataset's source and hashes them
-// exactly as the compact / roots-only builds do (dataset_build_transient, proof_input.cpp): batches of about half a staging chunk of nodes
-// in a BuildScratch, two node buffers used alternately, nothing synchronised per batch.  Where the build copies out what it keeps, the
-// scrub compares instead: the builder's SlotsDone hook -- on the stream the batch's layer passes ran on -- launches k_scrub_compare over the
-// fresh layer and the kept one (the fresh layer never leaves the device) and downloads one count per 4096 rows into pinned memory.  When
-// batch k's node buffer is handed to batch k + 2 the host reads batch k's counts and downloads bitmap words only for tiles with a
-// mismatch; batches are decoded in order, so the report comes out sorted by (item, row) with no sort anywhere.
+// exactly as the compact / roots-only builds do, batch by batch through the batch loop (batch_loop.hpp; DESIGN.md, "The batch loop").
+// Where the build copies out what it keeps, the scrub compares instead: the builder's SlotsDone hook -- on the stream the batch's layer
+// passes ran on -- launches k_scrub_compare over the fresh layer and the kept one (the fresh layer never leaves the device) and downloads
+// one count per 4096 rows into pinned memory.  When batch k's node buffer is handed to batch k + 2 the host reads batch k's counts and
+// downloads bitmap words only for tiles with a mismatch; batches are decoded in order, so the report comes out sorted by (item, row)
+// with no sort anywhere.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -26,49 +26,40 @@ using namespace cp2i;
 
 namespace {
 
-// The batch loop, shared by scrub_items (one dataset) and cp2_datasets_scrub_many (the slots of many datasets as one run of items).
-// Two things differ between them, and nothing else:
-//   the ITEM source   item i is unit item0 + i of `src` (slot files "<base><k>.dat" or the fake source), or -- a name table -- the whole
-//                     file (*names)[i];
+// One run of items through the batch loop, shared by scrub_items (one dataset) and cp2_datasets_scrub_many (the slots of many datasets
+// as one run of items).  Two things differ between them, and nothing else:
+//   the ITEM source   item i is unit item0 + i of `src` (slot files "<base><k>.dat" or the fake source), or -- `src` has a name table,
+//                     item0 is 0 -- the whole file names[i];
 //   the KEPT source   the kept layer of item i starts at base + i * stride * 32, or -- an address table -- at the device address
 //                     addr[i].  A batch's slice of the table goes into one of two pinned host tables, is uploaded to one of two device
 //                     tables on the stream the compare runs on, just before it, and is read by k_scrub_compare_many; table b is
-//                     rewritten for batch k + 2 only after batch k's `landed` event, like node buffer b: a table outlives its copy.
+//                     rewritten for batch k + 2 only after batch k's event, like node buffer b: a table outlives its copy.
 // Mismatches come out as (item0 + i, row) pairs in order, at most `cap`; *n_bad counts all.  item_counts (may be null; n_items entries,
 // zeroed by the caller) receives the mismatches of every item, complete whatever `cap` is: every tile with a mismatch is decoded then.
-struct ScrubItemSource {
-  const ScrubSrc* src = nullptr;
-  uint64_t item0 = 0;
-  const std::vector<std::string>* names = nullptr;
-};
 struct ScrubKeptSource {
   const uint8_t* base = nullptr;
   size_t stride = 0;
   const uint64_t* addr = nullptr;
 };
 
-int scrub_loop(cp2_ctx* ctx, const ScrubItemSource& items, const ScrubKeptSource& keptsrc, uint64_t n_items, int level, size_t cap,
+int scrub_loop(cp2_ctx* ctx, const ItemSource& src, uint64_t item0, const ScrubKeptSource& keptsrc, uint64_t n_items, int level, size_t cap,
                std::vector<uint64_t>& bad, uint64_t* n_bad, uint64_t* item_counts, size_t* n_batches = nullptr) {
-  const ScrubSrc& src = *items.src;
-  const uint64_t item0 = items.item0;
   const uint8_t* kept = keptsrc.base;
   const uint64_t* addr = keptsrc.addr;
   const size_t kstride = addr ? 0 : keptsrc.stride;
   *n_bad = 0;
   if (n_items == 0) return CP2_OK;
   if ((!kept && !addr) || src.cell_size == 0 || src.block_size < src.cell_size) return CP2_ERR_INVALID;
-  if (items.names && (!src.from_file || items.names->size() != n_items)) return CP2_ERR_INVALID;
+  if (src.names && (!src.from_file || src.n_names != n_items || item0 != 0)) return CP2_ERR_INVALID;
   CP2_REFUSE_STUCK(ctx);
   CP2_HIP(ctx, hipSetDevice(ctx->device));
   const size_t nblocks = src.n_cells / (src.block_size / src.cell_size);
   const size_t rows = level == CP2_SCRUB_CELL ? src.n_cells : (level == CP2_SCRUB_BLOCK ? nblocks : 1);
   if (rows == 0 || (!addr && kstride < rows)) return CP2_ERR_INVALID;
-  // batches as the compact build cuts them (transient_batch_slots, proof_input.cpp): half a staging chunk of nodes, at least one item
-  const size_t per_item = std::max<size_t>(1, trees_node_bytes(1, src.cell_size, src.block_size, src.n_cells));
-  const size_t batch = std::max<size_t>(1, std::min<size_t>(n_items, (ctx->stage_bytes / 2) / per_item));
+  const size_t batch = trees_batch_items(ctx, src.cell_size, src.block_size, src.n_cells, n_items);   // as the compact build cuts them
   const size_t groups = cp2k::scrub_groups(batch * rows);
   const int n_bufs = n_items > batch ? 2 : 1;
-  DevBuf d_bits[2], d_counts[2];               // (declared before the scratch: they go after it has drained the streams)
+  DevBuf d_bits[2], d_counts[2];               // (declared before the device: they go after its scratch has drained the streams)
   DevBuf d_addr[2];
   PinBuf h_counts[2], h_addr[2];
   for (int b = 0; b < n_bufs; ++b) {
@@ -107,65 +98,43 @@ int scrub_loop(cp2_ctx* ctx, const ScrubItemSource& items, const ScrubKeptSource
     }
     return CP2_OK;
   };
-  int st = CP2_OK;
+  // the builder calls this once, with every slot of the batch, on the stream its layer passes ran on (group 0: one pass at the end)
+  const auto compare = [&](const BatchStep& s, cp2_slot_trees* t, size_t a, size_t z, hipStream_t ls) -> int {
+    const size_t b = (size_t)s.b, n = s.n;
+    if (a != 0 || z != n) { ctx->err = "scrub: a batch's layers were built in parts"; return CP2_ERR_INVALID; }
+    const size_t off = level == CP2_SCRUB_CELL ? t->boff[0] : (level == CP2_SCRUB_BLOCK ? t->toff[0] : t->toff.back());
+    const size_t fstride = level == CP2_SCRUB_CELL ? t->n_cells : (level == CP2_SCRUB_BLOCK ? t->tsizes[0] : 1);
+    if (addr) {
+      CP2_HIP(ctx, hipMemcpyAsync(d_addr[b].p, h_addr[b].p, n * 8, hipMemcpyHostToDevice, ls));
+      CP2_HIP(ctx, cp2k::launch_scrub_compare_many(t->nodes.u8() + off * 32, fstride, static_cast<const uint64_t*>(d_addr[b].p), rows, n,
+                                                   static_cast<uint64_t*>(d_bits[b].p), static_cast<uint32_t*>(d_counts[b].p), ls));
+    } else {
+      CP2_HIP(ctx, cp2k::launch_scrub_compare(t->nodes.u8() + off * 32, fstride, kept + s.s0 * kstride * 32, kstride, rows, n,
+                                              static_cast<uint64_t*>(d_bits[b].p), static_cast<uint32_t*>(d_counts[b].p), ls));
+    }
+    CP2_HIP(ctx, hipMemcpyAsync(h_counts[b].p, d_counts[b].p, cp2k::scrub_groups(n * rows) * 4, hipMemcpyDeviceToHost, ls));
+    return CP2_OK;
+  };
+  size_t k = 0;
   {
-    BuildScratch scratch;                       // drains the context's streams before its buffers go, whatever path leaves this scope
-    hipEvent_t landed[2] = {nullptr, nullptr};
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 2; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } ev_guard{landed};
-    for (int i = 0; i < 2; ++i) CP2_HIP(ctx, hipEventCreateWithFlags(&landed[i], hipEventDisableTiming));
-    size_t k = 0;
-    for (uint64_t s0 = 0; st == CP2_OK && s0 < n_items; s0 += batch, ++k) {
-      const size_t n = (size_t)std::min<uint64_t>(batch, n_items - s0);
-      const int b = (int)(k & 1);
-      if (k >= 2) {
-        if (hipEventSynchronize(landed[b]) != hipSuccess) { (void)hipGetLastError(); ctx->err = "scrub: a batch failed on the device"; st = CP2_ERR_HIP; break; }
-        st = collect(b);
-        if (st != CP2_OK) break;
-      }
-      const uint8_t* kept_b = addr ? nullptr : kept + s0 * kstride * 32;
-      if (addr) std::copy(addr + s0, addr + s0 + n, static_cast<uint64_t*>(h_addr[b].p));   // (table b's last copy landed with batch k - 2)
-      // the builder calls this once, with every slot of the batch, on the stream its layer passes ran on (group 0: one pass at the end)
-      SlotsDone compare = [&, b, n, kept_b](cp2_slot_trees* t, size_t a, size_t z, hipStream_t ls) -> int {
-        if (a != 0 || z != n) { ctx->err = "scrub: a batch's layers were built in parts"; return CP2_ERR_INVALID; }
-        const size_t off = level == CP2_SCRUB_CELL ? t->boff[0] : (level == CP2_SCRUB_BLOCK ? t->toff[0] : t->toff.back());
-        const size_t fstride = level == CP2_SCRUB_CELL ? t->n_cells : (level == CP2_SCRUB_BLOCK ? t->tsizes[0] : 1);
-        if (addr) {
-          CP2_HIP(ctx, hipMemcpyAsync(d_addr[b].p, h_addr[b].p, n * 8, hipMemcpyHostToDevice, ls));
-          CP2_HIP(ctx, cp2k::launch_scrub_compare_many(t->nodes.u8() + off * 32, fstride, static_cast<const uint64_t*>(d_addr[b].p), rows, n,
-                                                       static_cast<uint64_t*>(d_bits[b].p), static_cast<uint32_t*>(d_counts[b].p), ls));
-        } else {
-          CP2_HIP(ctx, cp2k::launch_scrub_compare(t->nodes.u8() + off * 32, fstride, kept_b, kstride, rows, n, static_cast<uint64_t*>(d_bits[b].p),
-                                                  static_cast<uint32_t*>(d_counts[b].p), ls));
-        }
-        CP2_HIP(ctx, hipMemcpyAsync(h_counts[b].p, d_counts[b].p, cp2k::scrub_groups(n * rows) * 4, hipMemcpyDeviceToHost, ls));
-        return CP2_OK;
-      };
-      cp2_slot_trees* t = nullptr;
-      st = items.names  ? trees_build_file_list(ctx, items.names->data() + s0, n, src.cell_size, src.block_size, src.n_cells, 0, compare, &t, true,
-                                                &scratch, b)
-           : src.from_file ? trees_build_files(ctx, src.file_base, item0 + s0, n, src.cell_size, src.block_size, src.n_cells, 0, compare, &t,
-                                             src.units_per_slot, true, &scratch, b)
-                         : trees_build_fake(ctx, src.seed, item0 + s0, n, src.cell_size, src.block_size, src.n_cells, 0, compare, &t,
-                                            src.units_per_slot, true, &scratch, b);
-      hipStream_t tail = scratch.tail_stream ? scratch.tail_stream : ctx->stream;
-      if (st == CP2_OK && hipEventRecord(landed[b], tail) != hipSuccess) { ctx->err = "hipEventRecord failed"; st = CP2_ERR_HIP; }
-      cp2_slot_trees_free(t);                   // (the batch's nodes are the scratch's: nothing is waited for here)
-      if (st == CP2_OK) { pending[b].live = true; pending[b].s0 = s0; pending[b].n = n; }
-    }
-    if (st == CP2_OK) {                         // everything landed (a failed launch or copy shows up here)
-      if (hipStreamSynchronize(ctx->stream) != hipSuccess || (ctx->aux_stream && hipStreamSynchronize(ctx->aux_stream) != hipSuccess) ||
-          (ctx->aux2_stream && hipStreamSynchronize(ctx->aux2_stream) != hipSuccess)) {
-        (void)hipGetLastError();
-        ctx->err = "scrub: a batch failed on the device";
-        st = CP2_ERR_HIP;
-      }
-    }
-    if (st == CP2_OK) st = collect((int)(k & 1));          // the older of the two batches still pending first
-    if (st == CP2_OK) st = collect((int)((k + 1) & 1));
+    BatchDevice dev;
+    CP2_TRY(dev.init(ctx));
+    CP2_TRY(batch_loop(dev, "scrub", ctx->err, n_items, batch,
+        [&](const BatchStep& s) -> int {   // batch k - 2 has landed: its report, then table b is free for this batch's slice
+          CP2_TRY(collect(s.b));
+          if (addr) std::copy(addr + s.s0, addr + s.s0 + s.n, static_cast<uint64_t*>(h_addr[s.b].p));
+          return CP2_OK;
+        },
+        [&](const BatchStep& s, hipStream_t* tail) -> int {
+          return dev.build(src, item0 + s.s0, s.n, 0, [&](cp2_slot_trees* t, size_t a, size_t z, hipStream_t ls) { return compare(s, t, a, z, ls); }, s.b, tail);
+        },
+        [&](const BatchStep& s, hipStream_t) -> int { pending[s.b] = {true, s.s0, s.n}; return CP2_OK; },
+        [](const BatchStep&) {}, &k));
+    CP2_TRY(collect((int)(k & 1)));             // the older of the two batches still pending first
+    CP2_TRY(collect((int)((k + 1) & 1)));
   }
-  if (st != CP2_OK) return st;
   *n_bad = total;
-  if (n_batches) *n_batches = (size_t)((n_items + batch - 1) / batch);
+  if (n_batches) *n_batches = k;
   return CP2_OK;
 }
 
@@ -190,25 +159,12 @@ const uint8_t* kept_layer(const cp2_dataset* ds, int level, uint64_t local, size
 
 }  // namespace
 
-int cp2i::scrub_items(cp2_ctx* ctx, const ScrubSrc& src, uint64_t item0, uint64_t n_items, int level, const uint8_t* kept, size_t kstride,
+int cp2i::scrub_items(cp2_ctx* ctx, const ItemSource& src, uint64_t item0, uint64_t n_items, int level, const uint8_t* kept, size_t kstride,
                       size_t cap, std::vector<uint64_t>& bad, uint64_t* n_bad) {
   *n_bad = 0;
   if (n_items == 0) return CP2_OK;
   if (!kept) return CP2_ERR_INVALID;
-  ScrubItemSource items;
-  items.src = &src;
-  items.item0 = item0;
-  ScrubKeptSource ks;
-  ks.base = kept;
-  ks.stride = kstride;
-  return scrub_loop(ctx, items, ks, n_items, level, cap, bad, n_bad, nullptr);
-}
-
-ScrubSrc cp2i::scrub_src_of(const cp2_slot_trees* t, uint64_t units_per_slot) {
-  return {t->src == CellSrc::File, t->file_base, t->dataset_seed, t->cell_size, t->block_size, t->n_cells, units_per_slot};
-}
-ScrubSrc cp2i::scrub_src_of(const cp2_dataset* ds) {
-  return {ds->from_file, ds->file_base, ds->cfg.seed, ds->cfg.cell_size, ds->cfg.block_size, ds->cfg.n_cells, 1};
+  return scrub_loop(ctx, src, item0, {kept, kstride, nullptr}, n_items, level, cap, bad, n_bad, nullptr);
 }
 
 int cp2i::dataset_scrub_level(const cp2_dataset* ds) {
@@ -223,7 +179,7 @@ int cp2i::dataset_scrub(cp2_dataset* ds, uint64_t first_slot, uint64_t n, int le
   const uint64_t local = first_slot - ds->first_slot;
   size_t kstride = 1;
   const uint8_t* kept = kept_layer(ds, level, local, &kstride);   // of the first slot scrubbed
-  return scrub_items(ds->ctx, scrub_src_of(ds), first_slot, n, level, kept, kstride, cap, bad, n_bad);
+  return scrub_items(ds->ctx, item_source_of(ds), first_slot, n, level, kept, kstride, cap, bad, n_bad);
 }
 
 extern "C" int cp2_dataset_scrub(cp2_dataset* ds, uint64_t first_slot, uint64_t n_slots, uint64_t* bad, size_t cap, size_t* n_bad,
@@ -270,7 +226,7 @@ extern "C" int cp2_dataset_scrub(cp2_dataset* ds, uint64_t first_slot, uint64_t 
 namespace {
 
 struct ManyClass {
-  ScrubSrc src;
+  ItemSource src;                         // (its name table: `names` below, set when the class runs)
   int level = 0;
   std::vector<size_t> request;            // per item
   std::vector<uint64_t> slot;             // per item: the dataset's slot number
@@ -321,16 +277,14 @@ int scrub_many(cp2_ctx* ctx, cp2_dataset* const* ds, size_t n, size_t cap, std::
   std::vector<uint64_t> got;
   for (const ManyClass& k : classes) {
     if (k.names.empty()) continue;
-    ScrubItemSource items;
-    items.src = &k.src;
-    items.names = &k.names;
-    ScrubKeptSource ks;
-    ks.addr = k.addr.data();
+    ItemSource src = k.src;
+    src.names = k.names.data();
+    src.n_names = k.names.size();
     std::vector<uint64_t> per_item(k.names.size(), 0);
     uint64_t count = 0;
     got.clear();
     size_t batches = 0;
-    CP2_TRY(scrub_loop(ctx, items, ks, k.names.size(), k.level, cap, got, &count, per_item.data(), &batches));
+    CP2_TRY(scrub_loop(ctx, src, 0, {nullptr, 0, k.addr.data()}, k.names.size(), k.level, cap, got, &count, per_item.data(), &batches));
     *n_batches += batches;
     *total += count;
     for (size_t j = 0; j < per_item.size(); ++j) counts[k.request[j]] += per_item[j];

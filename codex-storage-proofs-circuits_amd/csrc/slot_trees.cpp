@@ -74,6 +74,19 @@ cp2i::BuildScratch::~BuildScratch() {
   if (ctx->aux2_stream) (void)hipStreamSynchronize(ctx->aux2_stream);
 }
 
+ItemSource cp2i::item_source_of(const cp2_slot_trees* t, uint64_t units_per_slot) {
+  return {t->src == CellSrc::File, t->file_base, t->dataset_seed, t->cell_size, t->block_size, t->n_cells, units_per_slot};
+}
+
+int cp2i::build_items(cp2_ctx* ctx, const ItemSource& src, uint64_t s0, size_t n, size_t group, const SlotsDone& done, cp2_slot_trees** out,
+                      bool pooled_nodes, BuildScratch* scratch, int node_slot) {
+  const size_t cs = src.cell_size, bs = src.block_size, nc = src.n_cells;
+  if (src.names && (!src.from_file || s0 > src.n_names || n > src.n_names - s0)) return CP2_ERR_INVALID;
+  if (src.names) return trees_build_file_list(ctx, src.names + s0, n, cs, bs, nc, group, done, out, pooled_nodes, scratch, node_slot);
+  if (src.from_file) return trees_build_files(ctx, src.file_base, s0, n, cs, bs, nc, group, done, out, src.units_per_slot, pooled_nodes, scratch, node_slot);
+  return trees_build_fake(ctx, src.seed, s0, n, cs, bs, nc, group, done, out, src.units_per_slot, pooled_nodes, scratch, node_slot);
+}
+
 int trees_layout(cp2_slot_trees* t, cp2i::DevBuf* borrow_from) {
   t->bsizes = layer_sizes_of(t->cpb);
   t->tsizes = layer_sizes_of(t->nblocks);

@@ -4,6 +4,7 @@
 #include <string>
 #include <vector>
 
+#include "batch_loop.hpp"
 #include "internal.hpp"
 #include "kernels.hpp"
 #include "fill_pipeline.hpp"   // the slot-file read rule: read_file_cell, slot_file_error
@@ -47,8 +48,8 @@ using SlotsDone = std::function<int(cp2_slot_trees* t, size_t s0, size_t s1, hip
 // draining the device between them: two staging buffers for generated cells and two node buffers used alternately.  With it
 // trees_build_fake returns with its work ENQUEUED (nothing synchronised, the batch's nodes a borrowed view of nodes[node_slot]):
 // the next batch's generation and hashing start on the context's two hashing streams while this batch's layer passes and
-// copy-outs still run on the third.  The owner waits for whatever reads nodes[b] before it hands slot b to another batch, and drains the
-// context's streams before the scratch goes (its destructor does).
+// copy-outs still run on the third.  The owner (BatchDevice below, driven by batch_loop.hpp) waits for whatever reads nodes[b] before it
+// hands slot b to another batch, and drains the context's streams before the scratch goes (its destructor does).
 struct BuildScratch {
   cp2_ctx* ctx = nullptr;
   DevBuf stage[2], nodes[2];
@@ -80,13 +81,63 @@ int trees_build_files(cp2_ctx* ctx, const std::string& base, uint64_t first_slot
 int trees_build_file_list(cp2_ctx* ctx, const std::string* names, size_t n_names, size_t cell_size, size_t block_size, size_t n_cells,
                           size_t group, const SlotsDone& done, cp2_slot_trees** out, bool pooled_nodes = false,
                           BuildScratch* scratch = nullptr, int node_slot = 0);
-inline int trees_build_file_list(cp2_ctx* ctx, const std::vector<std::string>& names, size_t cell_size, size_t block_size, size_t n_cells,
-                                 size_t group, const SlotsDone& done, cp2_slot_trees** out, bool pooled_nodes = false,
-                                 BuildScratch* scratch = nullptr, int node_slot = 0) {
-  return trees_build_file_list(ctx, names.data(), names.size(), cell_size, block_size, n_cells, group, done, out, pooled_nodes, scratch, node_slot);
-}
+// Where a run of items comes from: item i is unit i of the fake source (`seed`) or of the slot files "<file_base><k>.dat", the units
+// counted as cp2_slot_trees says (units_per_slot, n_cells per item) -- or, with a name table, the whole file names[i] (from_file,
+// units_per_slot 1; the table is the caller's and outlives every call).  build_items builds items [s0, s0 + n) of it: THE call of the
+// three builders above outside slot_trees.cpp, their arguments as described there.
+struct ItemSource {
+  bool from_file = false;
+  std::string file_base;
+  uint64_t seed = 0;                   // dataset seed (fake source)
+  size_t cell_size = 0, block_size = 0, n_cells = 0;   // n_cells: per item
+  uint64_t units_per_slot = 1;
+  const std::string* names = nullptr;  // the name table, n_names entries (null: none)
+  size_t n_names = 0;
+};
+ItemSource item_source_of(const cp2_slot_trees* t, uint64_t units_per_slot);   // the units of `t`
+ItemSource item_source_of(const cp2_dataset* ds);                              // the slots of `ds`
+int build_items(cp2_ctx* ctx, const ItemSource& src, uint64_t s0, size_t n, size_t group, const SlotsDone& done, cp2_slot_trees** out,
+                bool pooled_nodes = false, BuildScratch* scratch = nullptr, int node_slot = 0);
+
+// The device of the batch loop (batch_loop.hpp): the scratch, the two events "whatever reads node buffer b has completed", the drain of
+// the context's streams.  A failed wait or drain clears the runtime's sticky error: the loop reports it, it must not resurface from a
+// later hipGetLastError().  The events are declared after the scratch and so go first; the scratch then drains the streams before its
+// buffers go, whatever path leaves the owner's scope.  What the owner keeps beside it for the batches in flight (tables, counts) is
+// declared BEFORE the device and so goes after that drain.
+struct BatchDevice {
+  using Tail = hipStream_t;
+  cp2_ctx* ctx = nullptr;
+  BuildScratch scratch;
+  Event landed[2];
+  cp2_slot_trees* batch = nullptr;     // the batch of the current step, its nodes a view of scratch.nodes[b]: freeing it waits for nothing
+  ~BatchDevice() { release(); }
+  int init(cp2_ctx* c) { ctx = c; CP2_TRY(landed[0].create(c)); return landed[1].create(c); }
+  int wait(int b) { return cleared(hipEventSynchronize(landed[b]) == hipSuccess); }
+  int record(int b, hipStream_t tail) {
+    if (hipEventRecord(landed[b], tail) == hipSuccess) return CP2_OK;
+    ctx->err = "hipEventRecord failed";
+    return CP2_ERR_HIP;
+  }
+  int drain() {                        // everything landed (a failed launch or copy shows up here)
+    return cleared(hipStreamSynchronize(ctx->stream) == hipSuccess && (!ctx->aux_stream || hipStreamSynchronize(ctx->aux_stream) == hipSuccess) &&
+                   (!ctx->aux2_stream || hipStreamSynchronize(ctx->aux2_stream) == hipSuccess));
+  }
+  void release() { cp2_slot_trees_free(batch); batch = nullptr; }
+  // items [s0, s0 + n) of `src` into node buffer b, enqueued; *tail = the stream the batch's layer passes ended on (the context's third)
+  int build(const ItemSource& src, uint64_t s0, size_t n, size_t group, const SlotsDone& done, int b, hipStream_t* tail) {
+    const int st = build_items(ctx, src, s0, n, group, done, &batch, true, &scratch, b);
+    *tail = scratch.tail_stream ? scratch.tail_stream : ctx->stream;
+    return st;
+  }
+  static int cleared(bool ok) { if (!ok) (void)hipGetLastError(); return ok ? CP2_OK : CP2_ERR_HIP; }
+};
+
 // bytes of the node buffer of a batch of n_slots slots of this geometry (all layers, 32 bytes per node)
 size_t trees_node_bytes(size_t n_slots, size_t cell_size, size_t block_size, size_t n_cells);
+// items per batch of the batch loop for this geometry (batch_items, batch_loop.hpp, over the context's staging chunk)
+inline size_t trees_batch_items(const cp2_ctx* ctx, size_t cell_size, size_t block_size, size_t n_cells, uint64_t n_items) {
+  return batch_items(ctx->stage_bytes, trees_node_bytes(1, cell_size, block_size, n_cells), n_items);
+}
 void trees_geom(const cp2_slot_trees* t, cp2k::TreeGeom* g);
 // node-row indices of the merged path of `cell` in slot `slot` (host twin of k_sample_paths' row arithmetic)
 void path_rows(const cp2_slot_trees* t, size_t slot, uint64_t cell, size_t max_depth, uint64_t* rows);
@@ -105,21 +156,12 @@ int kept_load(cp2_ctx* ctx, const char* path, const CacheHead& want, void* d_buf
 // slot roots?  One small download.  The multi-device exchange is verified with it (multi_gpu.cpp).
 int dataset_own_roots_in_place(cp2_dataset* ds, bool* ok);
 
-// Scrub (scrub.cpp): items (whole slots, or units of a slot cut by units_per_slot) rebuilt batch by batch in a BuildScratch from their
+// Scrub (scrub.cpp): items (whole slots, or units of a slot cut by units_per_slot) rebuilt batch by batch (batch_loop.hpp) from their
 // source, and the fresh layer of `level` (CP2_SCRUB_CELL: cell hashes, _BLOCK: block roots, _SLOT: item roots) compared on the device
 // with the kept one.  The kept layer of items [item0, item0 + n) starts at `kept` (32-byte rows) with `kstride` rows per item.
 // Mismatches are appended to `bad` as (item, row) pairs in that order, at most `cap` of them; *n_bad counts all.  Reads the kept
 // layer only.
-struct ScrubSrc {
-  bool from_file = false;
-  std::string file_base;
-  uint64_t seed = 0;                   // dataset seed (fake source)
-  size_t cell_size = 0, block_size = 0, n_cells = 0;   // n_cells: per item
-  uint64_t units_per_slot = 1;
-};
-ScrubSrc scrub_src_of(const cp2_slot_trees* t, uint64_t units_per_slot);   // the units of `t`
-ScrubSrc scrub_src_of(const cp2_dataset* ds);                              // the slots of `ds`
-int scrub_items(cp2_ctx* ctx, const ScrubSrc& src, uint64_t item0, uint64_t n, int level, const uint8_t* kept, size_t kstride, size_t cap,
+int scrub_items(cp2_ctx* ctx, const ItemSource& src, uint64_t item0, uint64_t n, int level, const uint8_t* kept, size_t kstride, size_t cap,
                 std::vector<uint64_t>& bad, uint64_t* n_bad);
 // the finest level a dataset keeps: CP2_SCRUB_CELL (every node), _BLOCK (compact) or _SLOT (roots only)
 int dataset_scrub_level(const cp2_dataset* ds);

@@ -196,23 +196,16 @@ extern "C" int cp2_proof_inputs_verify(cp2_ctx* ctx, const cp2_proof_input* cons
   struct Slot {
     PinBuf host;
     DevBuf dev;
-    hipEvent_t done = nullptr;
+    Event done;                 // (after the buffers: it goes before they wait for the stream and go back to the pool)
     size_t first = 0, count = 0;
     bool busy = false;
   };
   Slot slots[2];
-  struct EvGuard {
-    Slot* s;
-    ~EvGuard() {
-      for (int k = 0; k < 2; ++k)
-        if (s[k].done) (void)hipEventDestroy(s[k].done);
-    }
-  } ev_guard{slots};
   const int n_slots = n > chunk ? 2 : 1;
   for (int k = 0; k < n_slots; ++k) {
     CP2_TRY(slots[k].host.alloc(ctx, slot_bytes));
     CP2_TRY(slots[k].dev.scratch(ctx, slot_bytes));
-    CP2_HIP(ctx, hipEventCreateWithFlags(&slots[k].done, hipEventDisableTiming));
+    CP2_TRY(slots[k].done.create(ctx));
   }
   // offsets inside a slot for a chunk of q inputs (all 32-byte multiples up to the verdict bytes)
   auto offs = [&](size_t q, size_t* o_head, size_t* o_cells, size_t* o_paths, size_t* o_ok) {

@@ -271,6 +271,28 @@ def test_many_turns_and_batches_same_report(pkg, tmp_path, direct):
         ref.close()
 
 
+@pytest.mark.parametrize("mode", [2, 0])
+def test_fake_source_through_four_batches_the_last_one_short(pkg, oracle, mode):
+    """The fake source through the batch loop (csrc/batch_loop.hpp) with both node buffers handed on and a short last batch: 1 MiB of
+    staging cuts 7 slots of 2^12 cells into batches of 2, 2, 2 and 1 -- for the compact / roots-only build, whose roots are the
+    oracle's, and for the scrub after it, which finds nothing."""
+    C, _ = oracle
+    os.environ["CODEX_P2_STAGE_MB"] = "1"
+    try:
+        small = pkg.Context(0)
+    finally:
+        del os.environ["CODEX_P2_STAGE_MB"]
+    try:
+        ds = build(small, config(pkg, n_cells=4096, n_slots=7, seed=77), mode)
+        want = np.stack([C.fake_slot_root(C.slot_seed(77, s), CS, CS * CPB, 4096, 4) for s in range(7)])
+        assert np.array_equal(ds.local_roots(), want)
+        g, bad, n = ds.scrub()
+        assert (g, n, bad.shape) == (LEVEL[mode], 0, (0, 2))
+        ds.free()
+    finally:
+        small.close()
+
+
 def test_multi_merged_report_equals_single_context(pkg, sctx, tmp_path):
     """Three contexts on one device, by whole slots (each shard compact) and cut by units (cells of the slot, not of the unit)."""
     base = str(tmp_path / "slot")

@@ -222,3 +222,20 @@ def test_cache_file_heads_restamp_and_tmp_writer_with_sanitizers(tmp_path):
             [c["nSlots"], c["cellSize"], c["blockSize"], c["nCells"], 1, 0, c["seed"], 0, 0, 0], (name, h)
         assert os.path.getsize(os.path.join(golden, name)) == 104 + int(h["payload"]) < 16384
     assert int(lines["kept_mode0.cp2"]["payload"]) == 32 * c["nSlots"]
+
+
+def test_batch_loop_over_a_modelled_device_with_sanitizers(tmp_path):
+    """THE loop of the batch-by-batch builds (csrc/batch_loop.hpp: the compact / roots-only build, the batched streamed build, the scrub
+    and build many run through it) with a stand-in device that models the two node buffers, under AddressSanitizer + UBSan: 0..9 items
+    in batches of 1..4, no failure or one of wait / reuse / build / after / record / drain failing at every batch with each of four
+    statuses.  No build and no reuse ever sees a buffer whose event has not been waited for; wait(b) exactly from the third batch on
+    and before reuse; reuse, build, after, record in that order with the batch's own (s0, n, b) and tail; the ranges tile the items;
+    every batch object released exactly once; nothing after the first failure but that release; one drain, only when all went well;
+    status, error text and batch count; progress after batches 31, 63 and the last of 70.  No GPU, no HIP."""
+    exe = str(tmp_path / "batch_loop_check")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-I" + os.path.join(ROOT, "codex-storage-proofs-circuits_amd", "csrc"), "-o", exe,
+                           os.path.join(ROOT, "tests", "host_check", "batch_loop_check.cpp")])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-4000:]
+    assert r.stdout.splitlines()[-1] == "batch loop ok: 2013 runs, 1972 of them with a failing step, 5673 batches, 3 progress lines in the run of 70", r.stdout
