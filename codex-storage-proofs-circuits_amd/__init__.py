@@ -218,6 +218,7 @@ def load_library():
         "cp2_multi_dataset_scrub": (i32, [vp, u64, u64, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_int)]),
         "cp2_datasets_scrub_many": (i32, [vp, vp, sz, vp, sz, ctypes.POINTER(sz), vp, vp]),
         "cp2_datasets_build_many": (i32, [vp, vp, vp, sz, vp]),
+        "cp2_datasets_set_roots_many": (i32, [vp, vp, vp, sz, vp]),
         "cp2_dataset_repair_blocks": (i32, [vp, vp, vp, sz, i32, cp, vp, ctypes.POINTER(sz)]),
         "cp2_multi_dataset_repair_blocks": (i32, [vp, vp, vp, sz, i32, cp, vp, ctypes.POINTER(sz)]),
         "cp2_block_proof_depth": (sz, [sz, sz, sz]),
@@ -596,6 +597,28 @@ class Context:
         out = (ctypes.c_void_p * max(n, 1))()
         self._ck(self.L.cp2_datasets_build_many(self.h, cfgs, _p(ranges), n, out), "cp2_datasets_build_many")
         return [Dataset.adopt(self, r[0], ctypes.c_void_p(out[i]), int(r[1]), int(r[2])) for i, r in enumerate(requests)]
+
+    def set_roots_many(self, datasets, roots=None):
+        """cp2_datasets_set_roots_many: the dataset tree of every Dataset of this context in one pass; each is left as
+        Dataset.set_roots(roots[i]) leaves it.  roots: None, or one entry per dataset (None, or n_slots x 32 bytes).  Returns own:
+        uint8[n], 1 where the dataset's own rows of its roots equal the roots it built.  All of them, or an error and none."""
+        datasets = list(datasets)
+        n = len(datasets)
+        hs = (ctypes.c_void_p * max(n, 1))(*[d.h for d in datasets])
+        ptrs, keep = None, []
+        if roots is not None:
+            roots = list(roots)
+            assert len(roots) == n
+            ptrs = (ctypes.c_void_p * max(n, 1))()
+            for i, r in enumerate(roots):
+                if r is not None:
+                    a = np.ascontiguousarray(_u8(r).reshape(-1, 32))
+                    assert a.shape[0] == datasets[i].cfg.n_slots
+                    keep.append(a)
+                    ptrs[i] = a.ctypes.data
+        own = np.zeros(max(n, 1), dtype=np.uint8)
+        self._ck(self.L.cp2_datasets_set_roots_many(self.h, hs, ptrs, n, _p(own)), "cp2_datasets_set_roots_many")
+        return own[:n].copy()
 
     def read_blocks(self, datasets, requests, check_only=False, want_data=True, want_paths=True, data=None):
         """cp2_datasets_read_blocks: the blocks named by requests (uint64[n, 3]: index into datasets, slot, block) read from the slot files,

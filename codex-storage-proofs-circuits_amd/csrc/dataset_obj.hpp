@@ -100,4 +100,8 @@ namespace cp2i {
 // comes in through this, and a roots-only request goes back out through cp2_proof_inputs_generate_batch, one slot at a time.
 int prove_requests(cp2_ctx* ctx, cp2_dataset* const* ds, const uint64_t* slot_idx, const uint8_t* entropies, size_t n, size_t at0,
                    bool named, cp2_proof_input** out);
+// The dataset trees of n datasets of one context in one pass (set_roots_many.cpp): what cp2_dataset_set_roots(ds[i], all_roots[i]) leaves
+// behind for every i, or no dataset changed.  Already validated by the caller: no dataset twice, and where all_roots or all_roots[i] is
+// NULL every slot of ds[i] is local.  own (n, may be NULL): whether request i's own rows of the roots equal its built roots.
+int set_roots_pass(cp2_ctx* ctx, cp2_dataset* const* ds, const uint8_t* const* all_roots, size_t n, uint8_t* own);
 }  // namespace cp2i

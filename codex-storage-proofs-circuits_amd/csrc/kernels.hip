@@ -3,6 +3,7 @@
 //   k_permute_batch   a1  Permutation.hs:40-45                       192 algorithmic B / permutation
 //   k_hash_cells      a5  blocks/bn254.nim:23-29 (= Slot.hs:222-270 + Sponge.hs:30-43)   cellSize+32 B / cell
 //   k_compress_layer  a7  merkle/bn254.nim:24-58 (one tree layer, many trees at once)    96 B / node
+//   k_compress_layer_ragged   the same layer for trees of different leaf counts, tree-major, through a prefix table (set_roots_many.cpp)
 //   k_sponge2_felts   a3  Sponge.hs:30-43 over field elements (sampling, generic byte strings)
 //   k_gen_fake_cells  a10 slot.nim:22-32
 //   k_gather_rows         path / cell gather for proof inputs (merkle.nim:21-42 does this on the host; gather_body)
@@ -117,6 +118,44 @@ __global__ void __launch_bounds__(TPB) k_compress_layer(const uint4* __restrict_
   s.z = key_fe((bottom ? 1u : 0u) + (pair ? 0u : 2u));
   p2::permute(s, qtab);
   store_fe_canonical(out + 2 * (seg * out_seg_stride + j), s.x);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The same layer for trees of DIFFERENT leaf counts (set_roots_many.cpp: the dataset trees of many datasets).  The trees lie tree-major in
+// `rows`: tree r owns its layers, bottom first, from row tree_tab[2 r], over tree_tab[2 r + 1] leaves (set_roots_plan.hpp).  Level `level`
+// of the trees that still have one: lane t belongs to the first of the cnt entries whose prefix (the running sum of the entries' layer
+// level + 1 sizes) is > t -- found in `trips` steps whatever t is, 2^trips >= cnt, so a wave's lanes stay together -- and is node
+// j = t - (the prefix before it) of tree tree_of[entry].  It reads rows of layer `level` and writes one row of layer level + 1 of the same
+// tree: disjoint sets, nothing else is written.  Per node k_compress_layer's rule, unchanged.  LDS is the QTab only; no atomics.
+// The register bound names k_compress_layer's 5 waves per SIMD: left alone the allocator settles at 127 VGPRs and 4 waves, with it at
+// 73 and no scratch (profiles/set_roots_many_kernel_resources.txt).
+__global__ void __launch_bounds__(TPB, 5) k_compress_layer_ragged(uint4* __restrict__ rows, const uint64_t* __restrict__ tree_tab,
+                                                                 const uint64_t* __restrict__ prefix, const uint32_t* __restrict__ tree_of,
+                                                                 uint32_t cnt, uint32_t trips, uint32_t level, size_t work) {
+  __shared__ fr::QTab qtab;
+  fr::qtab_fill(qtab, threadIdx.x, TPB);
+  __syncthreads();
+  const size_t t = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (t >= work) return;
+  uint32_t lo = 0;
+  for (uint32_t s = trips; s-- > 0;) {
+    const uint32_t mid = lo + (1u << s);
+    if (mid < cnt && prefix[mid - 1] <= t) lo = mid;
+  }
+  const size_t j = t - (lo ? prefix[lo - 1] : 0);
+  const uint32_t r = tree_of[lo];
+  const uint64_t n = tree_tab[2 * (size_t)r + 1];
+  uint64_t off = tree_tab[2 * (size_t)r];                      // of layer `level`: the tree's first row + the layers below
+  for (uint32_t i = 0; i < level; ++i) off += ((n - 1) >> i) + 1;
+  const uint64_t m_in = ((n - 1) >> level) + 1;
+  const uint4* src = rows + 2 * (off + 2 * j);
+  const bool pair = (2 * j + 1 < m_in);
+  State s;
+  s.x = load_fe_canonical(src);
+  s.y = pair ? load_fe_canonical(src + 2) : fr::fe_zero();
+  s.z = key_fe((level == 0 ? 1u : 0u) + (pair ? 0u : 2u));
+  p2::permute(s, qtab);
+  store_fe_canonical(rows + 2 * (off + m_in + j), s.x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1296,6 +1335,32 @@ hipError_t launch_compress_layer(const void* in, void* out, size_t m_in, size_t 
   CP2K_LAUNCH(k_compress_layer, dim3(grid_for(m_out * nseg)), dim3(TPB), 0, st, (const uint4*)in, (uint4*)out,
                      m_in, m_out, nseg, bottom ? 1u : 0u, in_seg_stride, out_seg_stride);
   return hipGetLastError();
+}
+
+hipError_t launch_compress_layers_ragged(void* rows, const uint64_t* tree_tab, const uint64_t* prefix, const uint32_t* tree_of,
+                                         const uint64_t* level_off, const uint64_t* level_cnt, const uint64_t* level_work, size_t n_levels,
+                                         hipStream_t st) {
+  size_t work = 0;
+  if (n_levels && (!level_off || !level_cnt || !level_work)) return hipErrorInvalidValue;
+  for (size_t k = 0; k < n_levels; ++k) {
+    if (level_work[k] && (level_cnt[k] == 0 || level_cnt[k] > 0xffffffffull || !fits_one_grid(level_work[k]))) return hipErrorInvalidValue;
+    work += level_work[k];
+  }
+  if (work == 0) return hipSuccess;
+  if (!rows || !tree_tab || !prefix || !tree_of || n_levels > 63) return hipErrorInvalidValue;
+  if ((reinterpret_cast<uintptr_t>(rows) & 15) || (reinterpret_cast<uintptr_t>(tree_tab) & 7) || (reinterpret_cast<uintptr_t>(prefix) & 7) ||
+      (reinterpret_cast<uintptr_t>(tree_of) & 3))
+    return hipErrorInvalidValue;
+  for (size_t k = 0; k < n_levels; ++k) {                    // in order on st: level k + 1 reads what level k wrote
+    if (level_work[k] == 0) continue;
+    uint32_t trips = 0;
+    while (((uint64_t)1 << trips) < level_cnt[k]) ++trips;
+    CP2K_LAUNCH(k_compress_layer_ragged, dim3(grid_for(level_work[k])), dim3(TPB), 0, st, (uint4*)rows, tree_tab, prefix + level_off[k],
+                tree_of + level_off[k], (uint32_t)level_cnt[k], trips, (uint32_t)k, (size_t)level_work[k]);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 hipError_t launch_compress_pairs(const void* xy, uint32_t key, void* out, size_t n, hipStream_t st) {

@@ -22,6 +22,15 @@ hipError_t launch_permute_batch(const void* in, void* out, size_t n, hipStream_t
 // one Merkle layer of nseg trees; segment strides are in field elements
 hipError_t launch_compress_layer(const void* in, void* out, size_t m_in, size_t nseg, bool bottom,
                                  size_t in_seg_stride, size_t out_seg_stride, hipStream_t st);
+// Every layer of many trees of different leaf counts, tree-major in `rows` (16-byte aligned), one launch per level in order on st
+// (k_compress_layer_ragged; the tables are set_roots_plan.hpp's).  Device: tree_tab (first row and leaf count of tree r at [2 r],
+// [2 r + 1]), prefix and tree_of (per level k the entries [level_off[k], + level_cnt[k]): the trees that have a layer k + 1 and the
+// running sum of those layers' sizes).  Host: level_off, level_cnt, level_work (the lanes of level k: its last prefix), n_levels entries
+// each.  The leaves are read, every other row of every tree is written, nothing else.  hipErrorInvalidValue, nothing launched: a NULL
+// or misaligned pointer with work to do, a level with work and no entries, more than 63 levels.  No work at any level: success, no launch.
+hipError_t launch_compress_layers_ragged(void* rows, const uint64_t* tree_tab, const uint64_t* prefix, const uint32_t* tree_of,
+                                         const uint64_t* level_off, const uint64_t* level_cnt, const uint64_t* level_work, size_t n_levels,
+                                         hipStream_t st);
 // n pairs (x, y) of canonical elements -> compress(x, y, key), key in {0,1,2,3}
 hipError_t launch_compress_pairs(const void* xy, uint32_t key, void* out, size_t n, hipStream_t st);
 hipError_t launch_sponge2_felts(const void* felts, size_t nf, size_t nitems, void* out, hipStream_t st);

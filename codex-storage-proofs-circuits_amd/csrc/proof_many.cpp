@@ -110,8 +110,12 @@ int check_roots(cp2_ctx* ctx, cp2_dataset* const* ds, const uint64_t* slot_idx, 
 int prepare(cp2_ctx* ctx, cp2_dataset* const* ds, const uint64_t* slot_idx, size_t n) {
   CP2_TRY(validate(ctx, ds, slot_idx, n));
   CP2_HIP(ctx, hipSetDevice(ctx->device));
+  std::vector<cp2_dataset*> bare;                                             // every slot is local (validate); a dataset once
   for (size_t i = 0; i < n; ++i)
-    if (!ds[i]->have_roots) CP2_TRY(cp2_dataset_set_roots(ds[i], nullptr));   // every slot is local (validate)
+    if (!ds[i]->have_roots) bare.push_back(ds[i]);
+  std::sort(bare.begin(), bare.end());
+  bare.erase(std::unique(bare.begin(), bare.end()), bare.end());
+  CP2_TRY(set_roots_pass(ctx, bare.data(), nullptr, bare.size(), nullptr));
   return check_roots(ctx, ds, slot_idx, n);
 }
 

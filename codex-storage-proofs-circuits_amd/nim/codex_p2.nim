@@ -78,6 +78,9 @@ proc cp2_datasets_scrub_many(ctx: Cp2Ctx, ds: ptr Cp2Dataset, n: csize_t, bad: p
                              counts: ptr uint64, granularity: ptr cint): cint {.importc.}
 # n datasets of one context built in one pass: request i = (cfgs[i], ranges[2 i], ranges[2 i + 1]), what cp2_dataset_build takes; outp = n
 proc cp2_datasets_build_many(ctx: Cp2Ctx, cfgs: ptr Cp2Config, ranges: ptr uint64, n: csize_t, outp: ptr Cp2Dataset): cint {.importc.}
+# the dataset trees of n datasets of one context in one pass: request i = (ds[i], allRoots[i]), what cp2_dataset_set_roots takes (allRoots
+# or allRoots[i] nil: the local roots are all of them); own = n (may be nil): 1 where the request's own rows equal its built roots
+proc cp2_datasets_set_roots_many(ctx: Cp2Ctx, ds: ptr Cp2Dataset, allRoots: ptr ptr byte, n: csize_t, own: ptr byte): cint {.importc.}
 # repair: candidate blocks checked against the kept block roots, the matching ones written back; slotBlock = n x (slot, block),
 # data = n x blockSize bytes, flags CP2_REPAIR_CHECK_ONLY, status = n x CP2_REPAIR_*
 proc cp2_dataset_repair_blocks(ds: Cp2Dataset, slotBlock: ptr uint64, data: ptr byte, n: csize_t, flags: cint, cachePath: cstring,

@@ -48,7 +48,7 @@ extern "C" {
  *                cp2_fill_block_proofs (fill sessions that serve), cp2_fill_anchors and cp2_fill_add_anchored (anchored fill adds),
  *                cp2_fill_adopt (adopting blocks from disk), cp2_fill_save_nodes and cp2_fill_resume_nodes (checkpoints with nodes),
  *                cp2_datasets_read_blocks and cp2_dataset_read_blocks (verified read-back of listed blocks),
- *                cp2_datasets_build_many (many datasets built in one pass).
+ *                cp2_datasets_build_many (many datasets built in one pass), cp2_datasets_set_roots_many (their dataset trees in one pass).
  *                MINOR stays 2 until the release that carries them: the bump to 1.3 goes in its own commit with that release.         */
 #define CP2_ABI_VERSION_MAJOR 1
 #define CP2_ABI_VERSION_MINOR 2
@@ -544,6 +544,32 @@ int cp2_datasets_scrub_many(cp2_ctx* ctx, cp2_dataset* const* ds, size_t n, uint
  *            GB/s, mode; items and bytes count the slot files read). */
 int cp2_datasets_build_many(cp2_ctx* ctx, const cp2_config* cfgs /* n structs */, const uint64_t* ranges /* n x 2: first_slot, n_local */,
                             size_t n, cp2_dataset** out /* n */);
+
+/* ---- set roots many: the dataset trees of n datasets of one context in ONE pass ------------------------------------------------------
+ * Between "built" and "can prove" every dataset needs the slot roots of its manifest, so that its dataset tree and slotProof exist.  One by
+ * one through cp2_dataset_set_roots every dataset pays a launch per tree level and a drain of the device: 4096 datasets of 4096 slots,
+ * 5.87 s after a build of 0.82 s (profiles/build_many_rate.txt).
+ *   Requests request i is (ds[i], all_roots[i]): what cp2_dataset_set_roots takes, all_roots[i] holding n_slots(ds[i]) x 32 bytes.
+ *            all_roots == NULL or all_roots[i] == NULL: the local roots of ds[i] are all of them.
+ *   Result   after CP2_OK dataset i is, in every observable, what cp2_dataset_set_roots(ds[i], all_roots[i]) leaves behind: cp2_dataset_root,
+ *            slotProof and the head lines of every proof input and input.json, cp2_dataset_export_streamed of a streamed build,
+ *            cp2_proof_inputs_generate_many.  A dataset that already had a tree gets the new one.
+ *   own      own[i] (own may be NULL) is 1 when rows [first_slot, first_slot + n_local) of the roots given for request i equal the roots
+ *            ds[i] built, else 0; always 1 where no roots were given.  Compared on the device in the same pass.  A difference is no error
+ *            -- cp2_dataset_set_roots accepts any roots, and cp2_proof_inputs_generate_many refuses such a request later --: the node
+ *            learns at set time that its slot does not match the manifest.
+ *   Refused  before any device work (CP2_ERR_INVALID, "request i: ..." in cp2_last_error where a request is at fault): ctx NULL; ds NULL
+ *            with n > 0; a NULL dataset; a dataset of another context; the same dataset twice; NULL roots for a dataset whose slots are
+ *            not all local.  n == 0: CP2_OK.  A context whose stream will not drain: CP2_ERR_HIP.
+ *   Errors   on every return other than CP2_OK no dataset of the call has changed (the trees wait in host staging until all are there) and
+ *            own is not written.
+ *   How      the requests go in chunks whose trees (the sum of cp2_merkle_total(n_slots) x 32 bytes) fit half the context's staging
+ *            (CODEX_P2_STAGE_MB); a request larger than that runs alone.  Per chunk: one upload of the tables and the given roots, a
+ *            device-to-device copy per tree that puts its leaves in place, one launch per tree level for all trees of the chunk whatever
+ *            their sizes, one download.  CP2_TRACE prints one line for the whole call (requests, chunks, tree rows, levels, and the
+ *            seconds of upload, levels, download and commit). */
+int cp2_datasets_set_roots_many(cp2_ctx* ctx, cp2_dataset* const* ds, const uint8_t* const* all_roots /* n pointers, may be NULL */, size_t n,
+                                uint8_t* own /* n, may be NULL */);
 
 /* ---- repair: replacement blocks checked against the kept block roots, then written back ----------------------------------------
  * A scrub names the network blocks whose data no longer hashes to what the dataset keeps; the node fetches or re-decodes them (erasure
