@@ -238,6 +238,7 @@ def load_library():
         "cp2_fill_block_proofs": (i32, [vp, vp, sz, vp, vp, vp]),
         "cp2_fill_anchors": (i32, [vp, vp, sz, vp]),
         "cp2_fill_add_anchored": (i32, [vp, vp, vp, vp, vp, sz, vp, ctypes.POINTER(sz)]),
+        "cp2_fills_add_many": (i32, [vp, vp, sz, vp, vp, vp, vp, sz, vp, vp]),
         "cp2_fill_adopt": (i32, [vp, u64, u64, i32, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
         "cp2_fill_save_nodes": (i32, [vp, cp]),
         "cp2_fill_resume_nodes": (i32, [vp, ctypes.POINTER(Config), u64, u64, vp, cp, i32, pvp, ctypes.POINTER(u64), ctypes.POINTER(u64),
@@ -1135,6 +1136,33 @@ class FillSession:
         h = ctypes.c_void_p()
         self.ctx._ck(self.ctx.L.cp2_fill_finish(self.h, cache_path.encode() if cache_path else None, ctypes.byref(h)), "cp2_fill_finish")
         return Dataset.adopt(self.ctx, self.cfg, h, self.first_slot, self.n_local)
+
+
+def fills_add_many(ctx, sessions, req, data, paths, levels=None):
+    """cp2_fills_add_many: proved blocks added to many FillSessions of `ctx` in one pass.  req: uint64[n, 3] of (index into sessions,
+    dataset slot, block); data: n x blockSize bytes; levels: uint32[n], or None when every request brings its session's whole path; paths:
+    the siblings packed in request order (None when every level is 0).  Per session the meaning of FillSession.add / add_anchored on the
+    requests that name it.  Returns (status: uint32[n] of FILL_*, n_new: list of len(sessions)); a file that cannot be written raises with
+    both in the error's `fill_status` / `n_new`."""
+    sessions = list(sessions)
+    rq = np.ascontiguousarray(np.asarray(req, dtype=np.uint64).reshape(-1, 3))
+    n, k = rq.shape[0], len(sessions)
+    d = np.ascontiguousarray(data) if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)   # (no copy: see _candidates)
+    lv = None if levels is None else np.ascontiguousarray(np.asarray(levels, dtype=np.uint32).reshape(-1))
+    if lv is not None and lv.size != n:
+        raise ValueError("fills: %d level(s) expected, got %d" % (n, lv.size))
+    p = _u8(paths) if paths is not None else np.empty(0, dtype=np.uint8)
+    hs = (ctypes.c_void_p * max(k, 1))(*[None if s is None else s.h for s in sessions])
+    status = np.empty(n, dtype=np.uint32)
+    new = (ctypes.c_size_t * max(k, 1))()
+    st = ctx.L.cp2_fills_add_many(ctx.h, hs, k, _p(rq) if n else None, _p(d) if d.size else None, _p(lv) if lv is not None and n else None,
+                                  _p(p) if p.size else None, n, _p(status) if n else None, new)
+    try:
+        ctx._ck(st, "cp2_fills_add_many")
+    except CodexP2Error as e:
+        e.fill_status, e.n_new = status, list(new)[:k]
+        raise
+    return status, list(new)[:k]
 
 
 GATHER_AUTO, GATHER_RCCL, GATHER_HOST, GATHER_COPY = 0, 1, 2, 3

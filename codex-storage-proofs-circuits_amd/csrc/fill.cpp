@@ -62,6 +62,7 @@
 #include "dataset_obj.hpp"
 #include "fill_checkpoint.hpp"
 #include "fill_plan.hpp"
+#include "fill_session.hpp"
 #include "node_ckpt_plan.hpp"
 #include "repair.hpp"
 
@@ -79,20 +80,7 @@ static_assert(BLOCK_PROOF_NO_ROW == NO_ROW, "k_gather_rows zero-fills the rows t
 static_assert(FILL_WRITE == CP2_REPAIR_MATCH && FILL_SKIP == CP2_REPAIR_MISMATCH && FILL_WRITE_FAILED == CP2_REPAIR_UNWRITTEN,
               "repair_write takes and leaves repair's statuses");
 
-// the session behind the header's opaque cp2_fill
-struct cp2_fill_session {
-  cp2_ctx* ctx = nullptr;
-  cp2_config cfg{};                     // file_base cleared: the name lives in `file_base`
-  std::string file_base;
-  bool from_file = false;
-  FillPlan plan;
-  DevBuf compact;                       // the compact layout of the local slots; becomes the dataset's buffer in finish
-  DevBuf slot_roots;                    // the stated roots, canonical: n_local x 32 bytes
-  std::vector<uint8_t> roots;           // ... and on the host, for a checkpoint
-  DevBuf layer_tab;                     // a session that keeps nodes: coff then csizes as uint64, depth + 1 entries each, uploaded once
-  DevBuf adopt_roots;                   // cp2_fill_adopt: the fresh block roots of the candidates, n_local x n_blocks rows, from the first adopt on
-  std::vector<uint64_t> adopt_have;     // ... and which of its rows hold one
-};
+// (the session behind the header's opaque cp2_fill: fill_session.hpp)
 
 namespace {
 

@@ -18,6 +18,7 @@
 //   k_block_path_commit   the same walk; a proved block root is also stored into layer 0 of a fill session's compact buffer (fill.cpp)
 //   k_block_path_commit_nodes   the same walk; a proved path's 2 x depth + 1 nodes are stored where the session's tree has them (fill.cpp)
 //   k_block_path_commit_anchored   the same walk, stopped per lane at a node the session's tree already holds (fill.cpp)
+//   k_block_path_commit_many   the anchored walk with the session taken per lane from a descriptor table (fill_many.cpp)
 //   k_block_root_recheck  re-read block roots against layer 0 of a resumed fill session; a row the disk no longer backs is zeroed (fill.cpp)
 //   k_adopt_layer, k_adopt_resolve   the tree over block roots read back from disk, judged against the nodes a fill session keeps (fill.cpp)
 //   k_nodes_restore_layer   the kept nodes a checkpoint states, authenticated top-down from the stated slot roots (fill.cpp)
@@ -1094,6 +1095,70 @@ __global__ void __launch_bounds__(TPB) k_block_path_commit_anchored(const uint4*
 }
 
 // ------------------------------------------------------------------------------------------------
+// Slot filling across many sessions (fill_many.cpp, cp2_fills_add_many): k_block_path_commit_anchored with the session taken per lane.
+// What the three kernels above take as launch arguments -- the compact buffer and its n_rows, the stated roots, the layer tables, n_blocks
+// and depth -- lane i reads from descriptor session_of[i] of `sessions` (FillManySession, kernels.hpp; the host uploads the table once per
+// call).  The request arrays are device_requests_anchored's: levels, path_off (absolute; path_base as above), (local slot, block), dest
+// and anchor_row, the rows being rows of the lane's OWN session's buffer.  The walk is walk_block_path<true> from fresh row i with j =
+// block, m = the session's n_blocks, staged into the lane's 2 x levels[i] rows of `scratch` at row 2 (path_off[i] - path_base); the result
+// is compared with the anchor row of the session's buffer, or, anchor_row[i] == UINT64_MAX, with the session's stated root of the slot.
+//   On a match only, and unless levels[i] == 0, the block root goes to row dest[i] of the session's buffer.  A session that keeps nodes
+//   (layer_tab != 0: layer_off at that address, layer_size depth + 1 entries behind it) also receives the siblings and the ancestors
+//   strictly below the anchor through keep_path_rows with ITS tables; with keep_top != 0 (a call of whole paths, which is cp2_fill_add per
+//   session) a path of the session's full depth leaves its last ancestor, the slot root's row, as k_block_path_commit_nodes does.  A session
+//   that keeps none gets the block root alone.
+//   Defensive mismatches (the host never produces them; each writes the verdict word and nothing else, not even scratch): a session index
+//   at or past n_sessions, a level above the session's depth, a level below it in a session that keeps no nodes, a slot at or past n_local,
+//   a dest or anchor row at or past n_rows.
+// No atomics; plain 16-byte loads and stores; LDS is the QTab only.  Two sessions never share a buffer, and inside one session the argument
+// of k_block_path_commit_anchored holds: identical bytes to one row, and only anchors known before the launch.  Lanes of a wave now differ
+// in DEPTH as well as in level (neighbouring requests belong to different sessions): a wave lasts as long as its longest lane, the
+// deepest session's whole path at worst.  The one staged walk serves every lane, so a lane of a session that keeps no nodes also writes
+// its 64 x levels[i] bytes of staging, which nothing reads (k_block_path_commit stages nothing).  Measured with every session plain, 4096
+// sessions x 4 whole paths of depth 4 beside 64 KiB blocks: the whole call, this traffic, the descriptor loads and the host grouping
+// included, takes 1.02 times the one-session k_block_path_commit call (profiles/fill_many_rate.txt); 256 B staged against 65 536 B hashed.
+__global__ void __launch_bounds__(TPB) k_block_path_commit_many(const uint4* __restrict__ fresh, const uint4* __restrict__ paths,
+                                                                  const FillManySession* __restrict__ sessions, uint64_t n_sessions,
+                                                                  const uint64_t* __restrict__ session_of,
+                                                                  const uint32_t* __restrict__ levels, const uint64_t* __restrict__ path_off,
+                                                                  uint64_t path_base, const uint64_t* __restrict__ slot_block,
+                                                                  const uint64_t* __restrict__ dest, const uint64_t* __restrict__ anchor_row,
+                                                                  uint32_t keep_top, size_t n, uint32_t* __restrict__ verdict, uint4* scratch) {
+  __shared__ fr::QTab qtab;
+  fr::qtab_fill(qtab, threadIdx.x, TPB);
+  __syncthreads();
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t k = session_of[i];
+  if (k >= n_sessions) {                               // (never, like everything refused below: the host validated every request)
+    verdict[i] = 1u;
+    return;
+  }
+  const FillManySession* d = sessions + k;
+  const uint64_t n_rows = d->n_rows, tab = d->layer_tab;
+  const uint32_t depth = d->depth, len = levels[i];
+  const uint64_t slot = slot_block[2 * i], blk = slot_block[2 * i + 1];
+  const uint64_t r = dest[i], target = anchor_row[i];
+  const bool stated = target == ~(uint64_t)0;
+  if (len > depth || (len < depth && tab == 0) || slot >= d->n_local || r >= n_rows || (!stated && target >= n_rows)) {
+    verdict[i] = 1u;
+    return;
+  }
+  uint4* tree = reinterpret_cast<uint4*>(d->tree);
+  const uint64_t at = path_off[i] - path_base;
+  uint4* mine = scratch + 4 * at;
+  const Fe cur = walk_block_path<true>(load_fe_canonical(fresh + 2 * i), paths + 2 * at, mine, blk, d->n_blocks, len, qtab);
+  const Fe want = load_fe_canonical(stated ? reinterpret_cast<const uint4*>(d->slot_roots) + 2 * slot : tree + 2 * target);
+  const bool keep = fe_equal(cur, want);
+  verdict[i] = keep ? 0u : 1u;
+  if (!keep || len == 0) return;
+  copy_row(tree + 2 * r, fresh + 2 * i);
+  if (tab == 0) return;
+  const uint64_t* layer_off = reinterpret_cast<const uint64_t*>(tab);
+  keep_path_rows(tree, mine, layer_off, layer_off + depth + 1, slot, blk, len, keep_top && len == depth ? len : len - 1, n_rows);
+}
+
+// ------------------------------------------------------------------------------------------------
 // Resuming a fill session (fill.cpp): k_repair_compare's comparison, with what a resumed session does about a block whose bytes on disk no
 // longer hash to the root the checkpoint kept -- as k_block_path_commit is k_block_path_roots' walk with what a session keeps of a proved
 // block.  Lane i takes the freshly built block root of re-read block i (fresh row i) and row dest[i] of `layer0`, the session's compact
@@ -1586,6 +1651,21 @@ hipError_t launch_block_path_commit_anchored(const void* fresh, const void* path
     hipLaunchKernelGGL(k_block_path_commit_anchored, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)fresh + 2 * i0, (const uint4*)paths, levels + i0,
                 path_off + i0, path_base, slot_block + 2 * i0, (const uint4*)slot_roots, dest + i0, anchor_row + i0, layer_off, layer_size, n_blocks,
                 depth, m, verdict + i0, (uint4*)tree, n_rows, (uint4*)scratch);
+  });
+}
+
+hipError_t launch_block_path_commit_many(const void* fresh, const void* paths, const FillManySession* sessions, uint64_t n_sessions,
+                                         const uint64_t* session_of, const uint32_t* levels, const uint64_t* path_off, uint64_t path_base,
+                                         const uint64_t* slot_block, const uint64_t* dest, const uint64_t* anchor_row, bool keep_top, size_t n,
+                                         uint32_t* verdict, void* scratch, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  if (!fresh || !paths || !sessions || !session_of || !levels || !path_off || !slot_block || !dest || !anchor_row || !verdict || !scratch ||
+      n_sessions == 0)
+    return hipErrorInvalidValue;
+  return for_slices(n, [&](size_t i0, size_t m) {     // path_off is absolute: `paths` and `scratch` stay where they are
+    hipLaunchKernelGGL(k_block_path_commit_many, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)fresh + 2 * i0, (const uint4*)paths, sessions,
+                n_sessions, session_of + i0, levels + i0, path_off + i0, path_base, slot_block + 2 * i0, dest + i0, anchor_row + i0,
+                keep_top ? 1u : 0u, m, verdict + i0, (uint4*)scratch);
   });
 }
 

@@ -130,6 +130,30 @@ hipError_t launch_block_path_commit_anchored(const void* fresh, const void* path
                                              uint64_t n_blocks, uint32_t depth, size_t n, uint32_t* verdict, void* tree, uint64_t n_rows,
                                              void* scratch, hipStream_t st);
 
+// Slot filling across many sessions (fill_many.cpp, k_block_path_commit_many): launch_block_path_commit_anchored with the session per
+// request.  One descriptor per session, a device table of n_sessions entries uploaded once per call: what the launchers above take as
+// launch arguments.
+struct FillManySession {
+  uint64_t tree;         // device address of the session's compact buffer ...
+  uint64_t n_rows;       // ... and its rows
+  uint64_t slot_roots;   // device address of the stated roots, canonical, n_local x 32 bytes ...
+  uint64_t n_local;      // ... and how many
+  uint64_t layer_tab;    // device address of layer_off, depth + 1 entries, layer_size behind it; 0: the session keeps no nodes
+  uint64_t n_blocks;
+  uint32_t depth;
+  uint32_t reserved;     // 0
+};
+// Request i belongs to session session_of[i]; levels, path_off / path_base, slot_block (local slot, block), dest and anchor_row as for
+// launch_block_path_commit_anchored, the rows being rows of that session's buffer, and `paths` / `scratch` packed over the whole launch.
+// verdict[i] = 0 and the stores of a match as there, into the session's buffer; a session that keeps no nodes receives the block root
+// alone.  keep_top: a path of its session's full depth also leaves its last ancestor (the slot root's row) in a session that keeps nodes,
+// as launch_block_path_commit_nodes does.  A session index >= n_sessions, a level above the session's depth, a level below it in a
+// session that keeps no nodes, a slot >= n_local and a dest or anchor row >= n_rows are mismatches that store nothing.
+hipError_t launch_block_path_commit_many(const void* fresh, const void* paths, const FillManySession* sessions, uint64_t n_sessions,
+                                         const uint64_t* session_of, const uint32_t* levels, const uint64_t* path_off, uint64_t path_base,
+                                         const uint64_t* slot_block, const uint64_t* dest, const uint64_t* anchor_row, bool keep_top, size_t n,
+                                         uint32_t* verdict, void* scratch, hipStream_t st);
+
 // Resuming a fill session (fill.cpp, k_block_root_recheck): verdict[i] = 0 when the 32-byte row i of `fresh` (the root a re-read block
 // hashed to) equals row dest[i] of `layer0` (n_rows rows), else 1 -- and then that row of layer0 is overwritten with zeros.  dest[i] >=
 // n_rows: verdict 1, nothing read or written.  The rows of one call are distinct.

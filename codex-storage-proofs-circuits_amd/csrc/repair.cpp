@@ -147,6 +147,11 @@ int cp2i::repair_check_with(cp2_ctx* ctx, size_t cell_size, size_t block_size, c
 
 int cp2i::repair_write(const std::string& base, size_t block_size, const uint64_t* slot_block, const uint8_t* data, size_t n, uint32_t* status,
                        size_t* n_written, std::vector<FileStamp>* written, std::string* err) {
+  return repair_write_rows(base, block_size, slot_block, data, nullptr, n, status, n_written, written, err);
+}
+
+int cp2i::repair_write_rows(const std::string& base, size_t block_size, const uint64_t* slot_block, const uint8_t* data, const size_t* row, size_t n,
+                            uint32_t* status, size_t* n_written, std::vector<FileStamp>* written, std::string* err) {
   std::vector<size_t> matched;
   for (size_t i = 0; i < n; ++i)
     if (status[i] == CP2_REPAIR_MATCH) matched.push_back(i);
@@ -164,7 +169,7 @@ int cp2i::repair_write(const std::string& base, size_t block_size, const uint64_
     if (fd < 0) what = std::strerror(errno);
     for (size_t k = 0; !what && k < groups[g].reqs.size(); ++k) {
       const size_t i = groups[g].reqs[k];
-      const uint8_t* p = data + i * block_size;
+      const uint8_t* p = data + (row ? row[i] : i) * block_size;
       size_t left = block_size;
       off_t off = (off_t)(slot_block[2 * i + 1] * block_size);
       while (left) {

@@ -62,6 +62,10 @@ int gather_rows_by_addr(cp2_ctx* ctx, const std::vector<uint64_t>& addr, uint8_t
 // those of every later file CP2_REPAIR_UNWRITTEN.  *n_written counts the blocks of the files written and synced, `written` their stamps.
 int repair_write(const std::string& base, size_t block_size, const uint64_t* slot_block, const uint8_t* data, size_t n, uint32_t* status,
                  size_t* n_written, std::vector<FileStamp>* written, std::string* err);
+// the same writer with request i's bytes at row row[i] of `data` (cp2_fills_add_many: one session's requests out of the call's blocks, with
+// no copy of them); row == NULL: row i
+int repair_write_rows(const std::string& base, size_t block_size, const uint64_t* slot_block, const uint8_t* data, const size_t* row, size_t n,
+                      uint32_t* status, size_t* n_written, std::vector<FileStamp>* written, std::string* err);
 // cache_restamp (cache_file.hpp) over each of `paths`; *restamped accumulates
 int repair_restamp_caches(const std::vector<std::string>& paths, const cp2_config& cfg, uint64_t n_items, size_t n_cells, uint64_t first_item,
                           uint64_t units_per_slot, const std::string& base, const std::vector<FileStamp>& written, size_t* restamped,

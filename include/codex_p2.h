@@ -48,7 +48,8 @@ extern "C" {
  *                cp2_fill_block_proofs (fill sessions that serve), cp2_fill_anchors and cp2_fill_add_anchored (anchored fill adds),
  *                cp2_fill_adopt (adopting blocks from disk), cp2_fill_save_nodes and cp2_fill_resume_nodes (checkpoints with nodes),
  *                cp2_datasets_read_blocks and cp2_dataset_read_blocks (verified read-back of listed blocks),
- *                cp2_datasets_build_many (many datasets built in one pass), cp2_datasets_set_roots_many (their dataset trees in one pass).
+ *                cp2_datasets_build_many (many datasets built in one pass), cp2_datasets_set_roots_many (their dataset trees in one pass),
+ *                cp2_fills_add_many (proved blocks added to many fill sessions in one pass).
  *                MINOR stays 2 until the release that carries them: the bump to 1.3 goes in its own commit with that release.         */
 #define CP2_ABI_VERSION_MAJOR 1
 #define CP2_ABI_VERSION_MINOR 2
@@ -933,6 +934,45 @@ int cp2_fill_add_anchored(void* f /* cp2_fill* */, const uint64_t* slot_block /*
                           const uint8_t* data /* n x blockSize */, const uint32_t* levels /* n */,
                           const uint8_t* paths /* sum(levels) x 32, packed in request order */, size_t n, uint32_t* status /* n */,
                           size_t* n_new);
+
+/* ---- proved blocks added to many fill sessions in one pass ------------------------------------------------------------------------------------
+ * A node that takes on slots of many datasets runs one session per dataset on one context, and the blocks of all of them arrive
+ * interleaved.  Every cp2_fill_add / cp2_fill_add_anchored is a pass of its own (a data-path set-up, launches that last one wave's lifetime
+ * whatever their size, a drain); across thousands of one-slot sessions a batch of arrivals is thousands of calls of a few blocks each.
+ * cp2_fills_add_many is ONE pass over the blocks of all of them: the last device step (k_block_path_commit_many) takes the session per
+ * request from a table uploaded once per call.
+ *   Sessions   fills[0 .. n_fills): sessions of `ctx` with one cell_size and block_size.  They may differ in n_cells (so in nBlocks and
+ *              depth), n_slots, local range, source (slot files or fake), file base name, seed, and in whether they keep nodes.
+ *   Requests   req: n x 3, (index into fills, dataset slot, block of the slot); data: n x blockSize.  Request i brings levels[i] siblings,
+ *              bottom first; levels == NULL: the cp2_block_proof_depth of its own session.  `paths` holds the siblings packed in request
+ *              order and may be NULL only when every level is 0.  A request whose level is its session's depth is a cp2_fill_add request
+ *              and is accepted by every session; a shorter one is a cp2_fill_add_anchored request: its session must keep nodes, and the
+ *              anchor must be known WHEN THE CALL STARTS.
+ *   Meaning    by the calls that exist.  With R_k the subsequence, in request order, of the requests that name fills[k], the call leaves
+ *              every session, every slot file and every output entry as this loop leaves them: for k in order, cp2_fill_add(fills[k],
+ *              R_k ...) when levels is NULL or fills[k] keeps no nodes, cp2_fill_add_anchored(fills[k], R_k ...) otherwise, continuing
+ *              after a call that returns CP2_ERR_IO.  NEW / DUPLICATE is decided per session by the lowest proved index of R_k; the
+ *              writer, its roll-back, CP2_FILL_UNWRITTEN and presence after the sync are cp2_fill_add's, per session; n_new[k] (n_fills
+ *              entries, may be NULL) is the number of bits set in session k.  The blocks are written from their rows of `data`, session
+ *              after session: the writes are serial.
+ *   I/O        a file that cannot be written stops that session's writing, as in cp2_fill_add; the other sessions' writes still
+ *              happen.  CP2_ERR_IO, and cp2_last_error names the first failing file in `fills` order.
+ *   Refused    all or nothing, unlike the loop: every check of every request runs before any device or file work, and a refused call
+ *              changes no session, file or output.  CP2_ERR_INVALID with the fills index or the request index in cp2_last_error: a NULL
+ *              ctx; with n > 0, NULL fills, req, data or status; fills[k] NULL, of another context, finished, or of another cell_size /
+ *              block_size than fills[0]; the same session listed twice (two writers to one file set); a session index >= n_fills;
+ *              everything cp2_fill_add or cp2_fill_add_anchored refuses for the request inside its session (a level below the depth of
+ *              a session that keeps no nodes among it); NULL paths while any level is not 0.  n == 0: CP2_OK with n_new zeroed.  A
+ *              context whose stream will not drain: CP2_ERR_HIP.
+ *   Trace      CP2_TRACE prints one line: sessions, requests, proved, new, siblings received, bytes, seconds, GB/s, seconds writing.
+ * Out of scope: cp2_multi_*; a many-session finish, save or adopt (each session's own calls, as before); spreading the file writes over
+ * threads. */
+int cp2_fills_add_many(cp2_ctx* ctx, void* const* fills /* cp2_fill* each */, size_t n_fills,
+                       const uint64_t* req /* n x 3: index into fills, dataset slot, block of the slot */,
+                       const uint8_t* data /* n x blockSize */,
+                       const uint32_t* levels /* n, or NULL: every request brings its session's whole path */,
+                       const uint8_t* paths /* packed in request order */, size_t n,
+                       uint32_t* status /* n: CP2_FILL_* */, size_t* n_new /* n_fills entries, may be NULL */);
 
 /* replaces `writeCircomMainComponent`, reference/nim/proof_input/src/cli.nim:186-204 */
 int cp2_write_circom_main(const cp2_config* cfg, const char* path);
