@@ -239,6 +239,7 @@ def load_library():
         "cp2_fill_anchors": (i32, [vp, vp, sz, vp]),
         "cp2_fill_add_anchored": (i32, [vp, vp, vp, vp, vp, sz, vp, ctypes.POINTER(sz)]),
         "cp2_fills_add_many": (i32, [vp, vp, sz, vp, vp, vp, vp, sz, vp, vp]),
+        "cp2_fills_finish_many": (i32, [vp, vp, sz, vp, vp]),
         "cp2_fill_adopt": (i32, [vp, u64, u64, i32, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
         "cp2_fill_save_nodes": (i32, [vp, cp]),
         "cp2_fill_resume_nodes": (i32, [vp, ctypes.POINTER(Config), u64, u64, vp, cp, i32, pvp, ctypes.POINTER(u64), ctypes.POINTER(u64),
@@ -1163,6 +1164,23 @@ def fills_add_many(ctx, sessions, req, data, paths, levels=None):
         e.fill_status, e.n_new = status, list(new)[:k]
         raise
     return status, list(new)[:k]
+
+
+def fills_finish_many(ctx, sessions, cache_paths=None):
+    """cp2_fills_finish_many: many complete FillSessions of `ctx` finished in one pass.  cache_paths: None, or one entry per session, each
+    a path or None.  Per session the meaning of FillSession.finish(cache_path).  Returns the compact Datasets in the order of `sessions` and
+    marks every session wrapper `finished`; all of them, or an error, no Dataset and every session as it was."""
+    sessions = list(sessions)
+    k = len(sessions)
+    if cache_paths is not None and len(cache_paths) != k:
+        raise ValueError("fills: %d cache path(s) expected, got %d" % (k, len(cache_paths)))
+    hs = (ctypes.c_void_p * max(k, 1))(*[None if s is None else s.h for s in sessions])
+    paths = None if cache_paths is None else (ctypes.c_char_p * max(k, 1))(*[None if p is None else os.fsencode(p) for p in cache_paths])
+    out = (ctypes.c_void_p * max(k, 1))()
+    ctx._ck(ctx.L.cp2_fills_finish_many(ctx.h, hs, k, paths, out), "cp2_fills_finish_many")
+    for s in sessions:
+        s.finished = True
+    return [Dataset.adopt(ctx, s.cfg, ctypes.c_void_p(out[i]), s.first_slot, s.n_local) for i, s in enumerate(sessions)]
 
 
 GATHER_AUTO, GATHER_RCCL, GATHER_HOST, GATHER_COPY = 0, 1, 2, 3

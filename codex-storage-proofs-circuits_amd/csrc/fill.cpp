@@ -87,12 +87,7 @@ namespace {
 cp2_fill_session* session(void* f) { return static_cast<cp2_fill_session*>(f); }
 const cp2_fill_session* session(const void* f) { return static_cast<const cp2_fill_session*>(f); }
 
-// the session's buffer handed over without a copy
-void hand_over(DevBuf& from, DevBuf& to) {
-  to.release();
-  to.p = from.p; to.bytes = from.bytes; to.owner = from.owner; to.home = from.home; to.borrowed = from.borrowed;
-  from.p = nullptr; from.bytes = 0; from.owner = nullptr; from.home = nullptr; from.borrowed = false;
-}
+// (a buffer handed over without a copy: hand_over, fill_session.hpp)
 
 constexpr uint64_t WHOLE_PATHS = ~(uint64_t)0;
 
@@ -351,17 +346,8 @@ extern "C" int cp2_fill_finish(void* fill, const char* cache_path, cp2_dataset**
     }
   }
   // the session's buffer becomes the compact buffer of an ordinary dataset (dataset_alloc_kept's layout), source as begun
-  std::unique_ptr<cp2_dataset> ds(new (std::nothrow) cp2_dataset());
+  std::unique_ptr<cp2_dataset> ds = fill_dataset_shell(f);
   if (!ds) return CP2_ERR_ALLOC;
-  ds->ctx = ctx;
-  ds->cfg = f->cfg;
-  ds->from_file = f->from_file;
-  ds->file_base = f->file_base;
-  ds->first_slot = plan.first_slot;
-  ds->n_local = plan.n_local;
-  ds->tree_mode = 2;
-  ds->csizes = plan.csizes;
-  ds->coff = plan.coff;
   hand_over(f->compact, ds->compact);
   plan.finished = true;
   if (std::getenv("CP2_TRACE"))

@@ -1,7 +1,9 @@
-// The session behind the header's opaque cp2_fill, shared by fill.cpp (one session's calls) and fill_many.cpp (cp2_fills_add_many, many
-// sessions in one pass).  Not installed.
+// The session behind the header's opaque cp2_fill, shared by fill.cpp (one session's calls), fill_many.cpp (cp2_fills_add_many) and
+// fill_finish_many.cpp (cp2_fills_finish_many): many sessions in one pass.  Not installed.
 #pragma once
 #include <cstdint>
+#include <memory>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -21,3 +23,31 @@ struct cp2_fill_session {
   cp2i::DevBuf adopt_roots;             // cp2_fill_adopt: the fresh block roots of the candidates, n_local x n_blocks rows, from the first adopt on
   std::vector<uint64_t> adopt_have;     // ... and which of its rows hold one
 };
+
+namespace cp2i {
+
+// a buffer handed over without a copy
+inline void hand_over(DevBuf& from, DevBuf& to) {
+  to.release();
+  to.p = from.p; to.bytes = from.bytes; to.owner = from.owner; to.home = from.home; to.borrowed = from.borrowed;
+  from.p = nullptr; from.bytes = 0; from.owner = nullptr; from.home = nullptr; from.borrowed = false;
+}
+
+// The compact dataset a complete session becomes (dataset_alloc_kept's layout, source as begun), all but its buffer: the finish calls
+// hand the session's buffer over into `compact` and mark the session finished.  nullptr: no memory.
+inline std::unique_ptr<cp2_dataset> fill_dataset_shell(const cp2_fill_session* f) {
+  std::unique_ptr<cp2_dataset> ds(new (std::nothrow) cp2_dataset());
+  if (!ds) return ds;
+  ds->ctx = f->ctx;
+  ds->cfg = f->cfg;
+  ds->from_file = f->from_file;
+  ds->file_base = f->file_base;
+  ds->first_slot = f->plan.first_slot;
+  ds->n_local = f->plan.n_local;
+  ds->tree_mode = 2;
+  ds->csizes = f->plan.csizes;
+  ds->coff = f->plan.coff;
+  return ds;
+}
+
+}  // namespace cp2i

@@ -4,6 +4,8 @@
 //   k_hash_cells      a5  blocks/bn254.nim:23-29 (= Slot.hs:222-270 + Sponge.hs:30-43)   cellSize+32 B / cell
 //   k_compress_layer  a7  merkle/bn254.nim:24-58 (one tree layer, many trees at once)    96 B / node
 //   k_compress_layer_ragged   the same layer for trees of different leaf counts, tree-major, through a prefix table (set_roots_many.cpp)
+//   k_finish_layer_many       the same layer for the slot trees of many fill sessions, each in its own layer-major buffer, with the
+//                             comparison against the stated roots on each tree's last level (fill_finish_many.cpp)
 //   k_sponge2_felts   a3  Sponge.hs:30-43 over field elements (sampling, generic byte strings)
 //   k_gen_fake_cells  a10 slot.nim:22-32
 //   k_gather_rows         path / cell gather for proof inputs (merkle.nim:21-42 does this on the host; gather_body)
@@ -157,6 +159,78 @@ __global__ void __launch_bounds__(TPB, 5) k_compress_layer_ragged(uint4* __restr
   s.z = key_fe((level == 0 ? 1u : 0u) + (pair ? 0u : 2u));
   p2::permute(s, qtab);
   store_fe_canonical(rows + 2 * (off + m_in + j), s.x);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The same layer for the slot trees of MANY FILL SESSIONS (fill_finish_many.cpp: cp2_fills_finish_many).  A session's compact buffer is
+// layer-major over its n_local slots -- layer l of slot s starts at row coff[l] + s * csizes[l], coff[l + 1] = coff[l] + n_local *
+// csizes[l], csizes[0] = n_blocks -- and every session lies in an allocation of its own, so neither kernel above fits: the lane takes its
+// session from the FillManySession table (tree, n_rows, slot_roots, n_local, n_blocks, depth; layer_tab is not read, a session that keeps
+// no nodes has none).  Level `level` over the sessions with depth > level: entry e of the level's tables is session sess_of[e] with
+// n_local * m_out lanes, m_in = csizes[level], m_out = (m_in + 1) / 2; the lane finds its entry as k_compress_layer_ragged does, in `trips`
+// uniform steps.  Inside the entry j = t - (the prefix before it), s = j / m_out, node = j - s * m_out; the layer's first row is n_local
+// times the sum of the sizes below, in closed form.  The lane reads rows off + s * m_in + 2 node (+ 1) and writes row off + n_local * m_in
+// + s * m_out + node: per level disjoint sets.  Per node k_compress_layer's rule, unchanged (a one-block slot is one level with key 3).
+//   On its session's LAST level (level + 1 == depth) the lane's row is the slot root: besides storing it, it compares the canonical words
+//   with slot_roots[s], byte for byte as k_repair_compare does, and writes verdict[voff[session] + s] = 0 or 1.  Every verdict entry has
+//   exactly one such lane, so nothing is cleared beforehand and there are no atomics.
+//   Defensive (the host never produces them): a destination row at or past n_rows is neither read for nor stored, and on the last level
+//   its verdict is 1 -- the rows of a slot ascend with the level, so a tree that leaves its buffer anywhere ends in a 1 --; a level at or
+//   past the session's depth, a session at or past n_sessions and a slot at or past n_local store nothing.
+// LDS is the QTab only.  The register bound names k_compress_layer's 5 waves per SIMD, as k_compress_layer_ragged's does
+// (profiles/fill_finish_many_kernel_resources.txt: 77 VGPRs, no scratch).  Measured over 4096 sessions x 1 slot x 4096 block roots, all 12
+// levels: 1.005 times k_compress_layer layer by layer over the same leaves (profiles/fill_finish_many_rate.txt); the search, the descriptor
+// loads and the 64-bit division stay below what a 50 k-instruction permutation shows.
+__global__ void __launch_bounds__(TPB, 5) k_finish_layer_many(const FillManySession* __restrict__ sessions, uint64_t n_sessions,
+                                                             const uint64_t* __restrict__ voff,
+                                                             const uint64_t* __restrict__ prefix, const uint32_t* __restrict__ sess_of,
+                                                             uint32_t cnt, uint32_t trips, uint32_t level, size_t work,
+                                                             uint32_t* __restrict__ verdict) {
+  __shared__ fr::QTab qtab;
+  fr::qtab_fill(qtab, threadIdx.x, TPB);
+  __syncthreads();
+  const size_t t = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (t >= work) return;
+  uint32_t lo = 0;
+  for (uint32_t s = trips; s-- > 0;) {
+    const uint32_t mid = lo + (1u << s);
+    if (mid < cnt && prefix[mid - 1] <= t) lo = mid;
+  }
+  const size_t j = t - (lo ? prefix[lo - 1] : 0);
+  const uint32_t k = sess_of[lo];
+  if (k >= n_sessions) return;
+  const FillManySession* d = sessions + k;
+  const uint64_t n = d->n_blocks, n_local = d->n_local;
+  const uint32_t depth = d->depth;
+  if (level >= depth || n == 0) return;
+  uint64_t off = 0;                                            // of layer `level`: n_local x the sizes of the layers below
+  for (uint32_t i = 0; i < level; ++i) off += ((n - 1) >> i) + 1;
+  off *= n_local;
+  const uint64_t m_in = ((n - 1) >> level) + 1, m_out = (m_in + 1) / 2;
+  const uint64_t s = j / m_out, node = j - s * m_out;
+  if (s >= n_local) return;
+  const bool last = level + 1 == depth;
+  const uint64_t dst = off + n_local * m_in + s * m_out + node;
+  if (dst >= d->n_rows) {                                      // (never: the host sized the buffer by the same rule)
+    if (last) verdict[voff[k] + s] = 1u;
+    return;
+  }
+  uint4* rows = reinterpret_cast<uint4*>(d->tree);
+  const uint4* src = rows + 2 * (off + s * m_in + 2 * node);
+  const bool pair = (2 * node + 1 < m_in);
+  State st;
+  st.x = load_fe_canonical(src);
+  st.y = pair ? load_fe_canonical(src + 2) : fr::fe_zero();
+  st.z = key_fe((level == 0 ? 1u : 0u) + (pair ? 0u : 2u));
+  p2::permute(st, qtab);
+  uint32_t w[8];
+  fr::to_canonical_words(st.x, w);
+  const uint4 r0 = make_uint4(w[0], w[1], w[2], w[3]), r1 = make_uint4(w[4], w[5], w[6], w[7]);
+  rows[2 * dst] = r0;
+  rows[2 * dst + 1] = r1;
+  if (!last) return;
+  const uint4* want = reinterpret_cast<const uint4*>(d->slot_roots) + 2 * s;
+  verdict[voff[k] + s] = rows_equal(r0, r1, want[0], want[1]) ? 0u : 1u;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1422,6 +1496,33 @@ hipError_t launch_compress_layers_ragged(void* rows, const uint64_t* tree_tab, c
     while (((uint64_t)1 << trips) < level_cnt[k]) ++trips;
     CP2K_LAUNCH(k_compress_layer_ragged, dim3(grid_for(level_work[k])), dim3(TPB), 0, st, (uint4*)rows, tree_tab, prefix + level_off[k],
                 tree_of + level_off[k], (uint32_t)level_cnt[k], trips, (uint32_t)k, (size_t)level_work[k]);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+hipError_t launch_finish_layers_many(const FillManySession* sessions, uint64_t n_sessions, const uint64_t* voff, const uint64_t* prefix,
+                                     const uint32_t* sess_of, const uint64_t* level_off, const uint64_t* level_cnt, const uint64_t* level_work,
+                                     size_t n_levels, uint32_t* verdict, hipStream_t st) {
+  size_t work = 0;
+  if (n_levels && (!level_off || !level_cnt || !level_work)) return hipErrorInvalidValue;
+  for (size_t k = 0; k < n_levels; ++k) {
+    if (level_work[k] && (level_cnt[k] == 0 || level_cnt[k] > 0xffffffffull || !fits_one_grid(level_work[k]))) return hipErrorInvalidValue;
+    work += level_work[k];
+  }
+  if (work == 0) return hipSuccess;
+  if (!sessions || !voff || !prefix || !sess_of || !verdict || n_sessions == 0 || n_sessions > 0xffffffffull || n_levels > 63)
+    return hipErrorInvalidValue;
+  if ((reinterpret_cast<uintptr_t>(sessions) & 7) || (reinterpret_cast<uintptr_t>(voff) & 7) || (reinterpret_cast<uintptr_t>(prefix) & 7) ||
+      (reinterpret_cast<uintptr_t>(sess_of) & 3) || (reinterpret_cast<uintptr_t>(verdict) & 3))
+    return hipErrorInvalidValue;
+  for (size_t k = 0; k < n_levels; ++k) {                    // in order on st: level k + 1 reads what level k wrote
+    if (level_work[k] == 0) continue;
+    uint32_t trips = 0;
+    while (((uint64_t)1 << trips) < level_cnt[k]) ++trips;
+    CP2K_LAUNCH(k_finish_layer_many, dim3(grid_for(level_work[k])), dim3(TPB), 0, st, sessions, n_sessions, voff, prefix + level_off[k],
+                sess_of + level_off[k], (uint32_t)level_cnt[k], trips, (uint32_t)k, (size_t)level_work[k], verdict);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }

@@ -154,6 +154,21 @@ hipError_t launch_block_path_commit_many(const void* fresh, const void* paths, c
                                          const uint64_t* slot_block, const uint64_t* dest, const uint64_t* anchor_row, bool keep_top, size_t n,
                                          uint32_t* verdict, void* scratch, hipStream_t st);
 
+// Finishing many fill sessions (fill_finish_many.cpp, k_finish_layer_many): every layer above layer 0 of every local slot tree of
+// n_sessions sessions, each in its own compact (layer-major) buffer, one launch per level in order on st, and on each session's last level
+// the comparison of the computed slot roots with its stated ones.  Device: `sessions` (of a descriptor tree, n_rows, slot_roots, n_local,
+// n_blocks and depth are read, layer_tab is not), voff (verdict offset of session k: the prefix sum of n_local, n_sessions entries),
+// prefix and sess_of (per level l the entries [level_off[l], + level_cnt[l]): the sessions with depth > l in order and the running sum of
+// their n_local * csizes[l + 1]), verdict (sum of n_local words; entry voff[k] + s = 0 when local slot s of session k ends in its stated
+// root, else 1; every entry is written exactly once, nothing needs clearing).  Host: level_off, level_cnt, level_work (the lanes of level
+// l: its last prefix), n_levels entries each.  Layer 0 is read, every other row of every session is written, nothing else; the computed
+// root is stored whatever the verdict.  A destination row >= n_rows is not stored and ends in verdict 1.  hipErrorInvalidValue, nothing
+// launched: a NULL or misaligned table with work to do, a level with work and no entries or more than 2^32, work that does not fit one
+// grid, more than 63 levels.  No work at any level: success, no launch.
+hipError_t launch_finish_layers_many(const FillManySession* sessions, uint64_t n_sessions, const uint64_t* voff, const uint64_t* prefix,
+                                     const uint32_t* sess_of, const uint64_t* level_off, const uint64_t* level_cnt, const uint64_t* level_work,
+                                     size_t n_levels, uint32_t* verdict, hipStream_t st);
+
 // Resuming a fill session (fill.cpp, k_block_root_recheck): verdict[i] = 0 when the 32-byte row i of `fresh` (the root a re-read block
 // hashed to) equals row dest[i] of `layer0` (n_rows rows), else 1 -- and then that row of layer0 is overwritten with zeros.  dest[i] >=
 // n_rows: verdict 1, nothing read or written.  The rows of one call are distinct.

@@ -130,6 +130,9 @@ proc cp2_fill_add_anchored(fill: pointer, slotBlock: ptr uint64, data: ptr byte,
 # nil (whole paths), paths packed in request order, nNew = nFills entries or nil; per session cp2_fill_add / cp2_fill_add_anchored's meaning
 proc cp2_fills_add_many(ctx: Cp2Ctx, fills: ptr pointer, nFills: csize_t, req: ptr uint64, data: ptr byte, levels: ptr uint32, paths: ptr byte,
                         n: csize_t, status: ptr uint32, nNew: ptr csize_t): cint {.importc.}
+# many complete fill sessions of one context finished in one pass: cachePaths nil, or nFills entries each of which may be nil; outp = nFills;
+# per session cp2_fill_finish's meaning, all or nothing
+proc cp2_fills_finish_many(ctx: Cp2Ctx, fills: ptr pointer, nFills: csize_t, cachePaths: ptr cstring, outp: ptr Cp2Dataset): cint {.importc.}
 # adopting blocks from disk: the absent blocks the slot files cover are read, hashed and kept where the tree above them reaches a node the
 # session knows (the stated slot root included); flags = 0 or CP2_ADOPT_NO_READ (judge what earlier calls read); nRead, nAdopted may be nil
 const CP2_ADOPT_NO_READ* = 1.cint

@@ -49,7 +49,8 @@ extern "C" {
  *                cp2_fill_adopt (adopting blocks from disk), cp2_fill_save_nodes and cp2_fill_resume_nodes (checkpoints with nodes),
  *                cp2_datasets_read_blocks and cp2_dataset_read_blocks (verified read-back of listed blocks),
  *                cp2_datasets_build_many (many datasets built in one pass), cp2_datasets_set_roots_many (their dataset trees in one pass),
- *                cp2_fills_add_many (proved blocks added to many fill sessions in one pass).
+ *                cp2_fills_add_many (proved blocks added to many fill sessions in one pass), cp2_fills_finish_many (many fill
+ *                sessions finished in one pass).
  *                MINOR stays 2 until the release that carries them: the bump to 1.3 goes in its own commit with that release.         */
 #define CP2_ABI_VERSION_MAJOR 1
 #define CP2_ABI_VERSION_MINOR 2
@@ -1068,6 +1069,37 @@ int cp2_fill_resume_nodes(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_sl
                           const char* path, int flags /* 0 or CP2_RESUME_TRUST_FILES */, void** out /* cp2_fill** */,
                           uint64_t* n_dropped /* may be NULL */, uint64_t* n_restored /* may be NULL */,
                           uint64_t* n_unproved /* may be NULL */, uint64_t* n_rejected /* may be NULL */);
+
+/* ---- many fill sessions finished in one pass ------------------------------------------------------------------------------------------------
+ * The step between the adds of many sessions (cp2_fills_add_many) and the dataset trees of what they become (cp2_datasets_set_roots_many).
+ * Per session cp2_fill_finish is one launch per layer of the tree over the block roots -- a lone wave or less in a one-slot session --, an
+ * upload, a comparison launch, a download and a drain.  cp2_fills_finish_many is ONE pass: level l of every session's trees is one launch
+ * (k_finish_layer_many, the session per lane from a table uploaded once), and the comparison with the stated roots rides on each tree's
+ * last level.  This lifts the many-session finish that the section of cp2_fills_add_many left out of scope.
+ *   Sessions   fills[0 .. n_fills): sessions of `ctx`.  They may differ in everything else: n_cells (so nBlocks and depth), n_local,
+ *              n_slots, cell and block size, source, and whether they keep nodes.
+ *   Meaning    by the call that exists.  After CP2_OK, out[k], fills[k] and the kept file of cache_paths[k] are what
+ *              cp2_fill_finish(fills[k], cache_paths[k], &out[k]) leaves, for every k: a compact dataset that owns the session's buffer (no
+ *              copy), source as begun; the kept form under cp2_dataset_build_cached's name rule; a session that accepts only cp2_fill_free.
+ *              cache_paths is NULL, or n_fills entries each of which may be NULL.
+ *   Refused    all or nothing: every check runs before any device or file work, and a refused call changes no session, file or out
+ *              entry.  CP2_ERR_INVALID with the fills index in cp2_last_error: a NULL ctx; with n_fills > 0, NULL fills or out; fills[k]
+ *              NULL, of another context, or finished; fills[k] listed twice; fills[k] with a block absent (the count and the first missing
+ *              pair, as cp2_fill_finish words it).  n_fills == 0: CP2_OK.  A context whose stream will not drain: CP2_ERR_HIP.
+ *   Device     one upload of the session table and the level tables, one launch per level for the sessions that still have it, one
+ *              download of one verdict per (session, local slot), one drain, all on the context's stream.
+ *   Verdicts   a tree that does not end in its stated root: CP2_ERR_IO, cp2_last_error names the first fills[k] in order and the dataset
+ *              slot in cp2_fill_finish's words.  No dataset is made and no session is finished.
+ *   Cache      after the verdicts and before any hand-over, serially in `fills` order.  The first save that fails returns its status: no
+ *              dataset, every session still complete and usable; kept files already written for earlier k stay (valid caches of complete
+ *              sessions).  Only after all saves are the n datasets made -- all n objects before the first hand-over, so CP2_ERR_ALLOC is
+ *              all or nothing too -- and the buffers handed over.
+ *   Trace      CP2_TRACE prints one line: sessions, slots, rows built, launches, kept forms saved, milliseconds.
+ * Out of scope: cp2_multi_*; a many-session begin, save or adopt (each session's own calls, as before); spreading the kept-file writes
+ * over threads. */
+int cp2_fills_finish_many(cp2_ctx* ctx, void* const* fills /* cp2_fill* each */, size_t n_fills,
+                          const char* const* cache_paths /* NULL, or n_fills entries each of which may be NULL */,
+                          cp2_dataset** out /* n_fills */);
 
 
 /* ---- e: every GPU of the node behind one handle ------------------------------------------------------ */
