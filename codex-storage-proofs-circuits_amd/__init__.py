@@ -240,6 +240,7 @@ def load_library():
         "cp2_fill_add_anchored": (i32, [vp, vp, vp, vp, vp, sz, vp, ctypes.POINTER(sz)]),
         "cp2_fills_add_many": (i32, [vp, vp, sz, vp, vp, vp, vp, sz, vp, vp]),
         "cp2_fills_finish_many": (i32, [vp, vp, sz, vp, vp]),
+        "cp2_fills_resume_many": (i32, [vp, vp, vp, vp, vp, sz, i32, vp, vp]),
         "cp2_fill_adopt": (i32, [vp, u64, u64, i32, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
         "cp2_fill_save_nodes": (i32, [vp, cp]),
         "cp2_fill_resume_nodes": (i32, [vp, ctypes.POINTER(Config), u64, u64, vp, cp, i32, pvp, ctypes.POINTER(u64), ctypes.POINTER(u64),
@@ -1181,6 +1182,42 @@ def fills_finish_many(ctx, sessions, cache_paths=None):
     for s in sessions:
         s.finished = True
     return [Dataset.adopt(ctx, s.cfg, ctypes.c_void_p(out[i]), s.first_slot, s.n_local) for i, s in enumerate(sessions)]
+
+
+def fills_resume_many(ctx, cfgs, slot_roots, paths, ranges=None, trust_files=False):
+    """cp2_fills_resume_many: many FillSessions of `ctx` resumed from their CP2FILL1 checkpoints in one pass.  cfgs, slot_roots and paths
+    hold one entry per session; ranges: None (every session covers all slots of its cfg) or one (first_slot, n_local) per session.  Per
+    session the meaning of Context.fill_resume; all of them, or an error and no session.  Returns (the FillSessions in the order of the
+    entries, each with its `n_dropped`; n_dropped as a uint64 array)."""
+    cfgs, paths, slot_roots = list(cfgs), list(paths), list(slot_roots)
+    k = len(cfgs)
+    if len(slot_roots) != k or len(paths) != k or (ranges is not None and len(ranges) != k):
+        raise ValueError("fills: %d entries need as many slot_roots, paths and ranges" % k)
+    # (thousands of entries: what is done per entry here is kept to a pointer and a size)
+    if ranges is None:
+        rg = np.array([(0, 0 if c is None else c.n_slots) for c in cfgs], dtype=np.uint64).reshape(-1, 2)
+    else:
+        rg = np.ascontiguousarray(np.asarray(ranges, dtype=np.uint64).reshape(-1, 2))
+    n_local = rg[:, 1].tolist()
+    roots = [r if r is None or (type(r) is np.ndarray and r.dtype == np.uint8 and r.flags.c_contiguous) else _u8(r) for r in slot_roots]
+    for i, r in enumerate(roots):
+        if r is not None and r.size != 32 * n_local[i]:
+            raise ValueError("fills: entry %d: %d local slot(s) need %d roots, got %d" % (i, n_local[i], n_local[i], r.size // 32))
+    cs = (ctypes.c_void_p * max(k, 1))(*[None if c is None else ctypes.addressof(c) for c in cfgs])
+    rs = (ctypes.c_void_p * max(k, 1))(*[None if r is None or not r.size else r.__array_interface__["data"][0] for r in roots])
+    ps = (ctypes.c_char_p * max(k, 1))(*[None if p is None else os.fsencode(p) for p in paths])
+    out = (ctypes.c_void_p * max(k, 1))()
+    dropped = np.zeros(k, dtype=np.uint64)
+    st = ctx.L.cp2_fills_resume_many(ctx.h, cs, _p(rg) if k else None, rs, ps, k, RESUME_TRUST_FILES if trust_files else 0, out,
+                                     _p(dropped) if k else None)
+    ctx._ck(st, "cp2_fills_resume_many")
+    sessions, first, handles, drops, new = [], rg[:, 0].tolist(), list(out), dropped.tolist(), FillSession.__new__
+    for i in range(k):
+        f = new(FillSession)
+        f.__dict__.update(ctx=ctx, cfg=cfgs[i], first_slot=first[i], n_local=n_local[i], h=ctypes.c_void_p(handles[i]), n_dropped=drops[i])
+        ctx._children.add(f)
+        sessions.append(f)
+    return sessions, dropped
 
 
 GATHER_AUTO, GATHER_RCCL, GATHER_HOST, GATHER_COPY = 0, 1, 2, 3

@@ -108,7 +108,7 @@ void fill_trace(size_t n, const uint32_t* status, size_t n_new, size_t block_siz
 }  // namespace
 
 // what cp2_fill_begin and cp2_fill_resume ask of (cfg, first_slot, n_local, slot_roots) before anything is allocated
-static int session_check(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local, const uint8_t* slot_roots) {
+int cp2i::fill_session_check(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local, const uint8_t* slot_roots) {
   CP2_REFUSE_STUCK(ctx);
   std::string err;
   if (!fill_check_range(cfg->n_slots, first_slot, n_local, cfg->max_depth, cfg->max_log2_nslots, cfg->n_cells, cfg->cell_size,
@@ -128,9 +128,10 @@ static int session_check(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slo
   return CP2_OK;
 }
 
-// the session of a checked (cfg, first_slot, n_local, slot_roots): the plan, the compact buffer (as allocated) and the roots on the device
-static int session_open(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local, const uint8_t* slot_roots,
-                        std::unique_ptr<cp2_fill_session>* out) {
+// the session of a checked (cfg, first_slot, n_local, slot_roots) with nothing uploaded yet: the plan, the compact buffer (as allocated),
+// the buffer of the roots and their canonical form on the host
+int cp2i::fill_session_alloc(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local, const uint8_t* slot_roots,
+                             std::unique_ptr<cp2_fill_session>* out) {
   CP2_HIP(ctx, hipSetDevice(ctx->device));
   std::unique_ptr<cp2_fill_session> f(new (std::nothrow) cp2_fill_session());
   if (!f) return CP2_ERR_ALLOC;
@@ -144,6 +145,15 @@ static int session_open(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot
   CP2_TRY(f->slot_roots.alloc(ctx, n_local * 32));
   f->roots.resize(n_local * 32);                                 // values of at least r are reduced, as everywhere else
   for (uint64_t s = 0; s < n_local; ++s) canonical_felt(slot_roots + s * 32, &f->roots[s * 32]);
+  *out = std::move(f);
+  return CP2_OK;
+}
+
+// ... and with the roots on the device
+static int session_open(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local, const uint8_t* slot_roots,
+                        std::unique_ptr<cp2_fill_session>* out) {
+  std::unique_ptr<cp2_fill_session> f;
+  CP2_TRY(fill_session_alloc(ctx, cfg, first_slot, n_local, slot_roots, &f));
   CP2_HIP(ctx, hipMemcpyAsync(f->slot_roots.p, f->roots.data(), f->roots.size(), hipMemcpyHostToDevice, ctx->stream));
   CP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
   *out = std::move(f);
@@ -153,7 +163,7 @@ static int session_open(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot
 extern "C" int cp2_fill_begin(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local, const uint8_t* slot_roots, void** out) try {
   if (!ctx || !cfg || !out) return CP2_ERR_INVALID;
   *out = nullptr;
-  CP2_TRY(session_check(ctx, cfg, first_slot, n_local, slot_roots));
+  CP2_TRY(fill_session_check(ctx, cfg, first_slot, n_local, slot_roots));
   std::unique_ptr<cp2_fill_session> f;
   CP2_TRY(session_open(ctx, cfg, first_slot, n_local, slot_roots, &f));
   *out = f.release();
@@ -393,17 +403,17 @@ int write_checkpoint_file(cp2_ctx* ctx, const char* path, const std::vector<uint
 // A checkpoint file of either format in memory.  Its fixed head is read first and head_ok(fixed, size, &why) compares what it announces with
 // the file's size before the buffer is sized; the whole file then goes to parse(buf, size, &why).
 template <class HeadOk, class Parse>
-int read_checkpoint_file(cp2_ctx* ctx, const char* path, HeadOk head_ok, Parse parse) {
+int read_checkpoint_file(std::string* err, const char* path, HeadOk head_ok, Parse parse) {
   const std::string name(path);
   const int fd = open(path, O_RDONLY | O_CLOEXEC);
   if (fd < 0) {
-    ctx->err = "fill: cannot open checkpoint " + name + ": " + std::strerror(errno);
+    *err = "fill: cannot open checkpoint " + name + ": " + std::strerror(errno);
     return CP2_ERR_IO;
   }
   const FdCloser closer{fd};
   struct stat sb;
   if (fstat(fd, &sb) != 0) {
-    ctx->err = "fill: cannot stat checkpoint " + name + ": " + std::strerror(errno);
+    *err = "fill: cannot stat checkpoint " + name + ": " + std::strerror(errno);
     return CP2_ERR_IO;
   }
   const size_t size = (size_t)sb.st_size;
@@ -414,20 +424,20 @@ int read_checkpoint_file(cp2_ctx* ctx, const char* path, HeadOk head_ok, Parse p
   std::vector<uint8_t> buf(ok ? size : 0);
   if (ok) e = slot_file_read_rest(fd, buf.data(), size, 0);
   if (e) {
-    ctx->err = "fill: cannot read checkpoint " + name + ": " + std::strerror(e);
+    *err = "fill: cannot read checkpoint " + name + ": " + std::strerror(e);
     return CP2_ERR_IO;
   }
   if (!ok || !parse(buf.data(), size, &why)) {
-    ctx->err = "fill: checkpoint " + name + " " + why;
+    *err = "fill: checkpoint " + name + " " + why;
     return CP2_ERR_IO;
   }
   return CP2_OK;
 }
 
 // a CP2FILL1 file: of exactly the size its header states
-int read_checkpoint(cp2_ctx* ctx, const char* path, FillCheckpoint* ck) {
+int read_checkpoint(std::string* err, const char* path, FillCheckpoint* ck) {
   return read_checkpoint_file(
-      ctx, path,
+      err, path,
       [](const uint8_t* fixed, size_t size, std::string* why) {
         FillCkptMeta m;
         FillCkptLayout l;
@@ -442,7 +452,7 @@ int read_checkpoint(cp2_ctx* ctx, const char* path, FillCheckpoint* ck) {
 // the same for a CP2FILL2 file, whose header bounds its size
 int read_node_checkpoint(cp2_ctx* ctx, const char* path, NodeCheckpoint* ck) {
   return read_checkpoint_file(
-      ctx, path,
+      &ctx->err, path,
       [](const uint8_t* fixed, size_t size, std::string* why) {
         FillCkptMeta m;
         NodeCkptLayout l;
@@ -520,6 +530,8 @@ int recheck_present(cp2_fill_session* f, std::vector<uint64_t>* dropped, uint64_
 }
 
 }  // namespace
+
+int cp2i::fill_read_checkpoint(std::string* err, const char* path, FillCheckpoint* ck) { return read_checkpoint(err, path, ck); }
 
 extern "C" int cp2_fill_save(const void* fill, const char* path) try {
   const cp2_fill_session* f = session(fill);
@@ -620,10 +632,10 @@ extern "C" int cp2_fill_resume(cp2_ctx* ctx, const cp2_config* cfg, uint64_t fir
     ctx->err = "fill: unknown resume flag bits";
     return CP2_ERR_INVALID;
   }
-  CP2_TRY(session_check(ctx, cfg, first_slot, n_local, slot_roots));
+  CP2_TRY(fill_session_check(ctx, cfg, first_slot, n_local, slot_roots));
   // the checkpoint: intact, then a description of exactly this session
   FillCheckpoint ck;
-  CP2_TRY(read_checkpoint(ctx, path, &ck));
+  CP2_TRY(read_checkpoint(&ctx->err, path, &ck));
   std::unique_ptr<cp2_fill_session> f;
   std::vector<uint64_t> dropped;
   CP2_TRY(resume_checked(ctx, cfg, first_slot, n_local, slot_roots, path, flags, ck, &f, &dropped));
@@ -1027,13 +1039,13 @@ extern "C" int cp2_fill_resume_nodes(cp2_ctx* ctx, const cp2_config* cfg, uint64
     ctx->err = "fill: unknown resume flag bits";
     return CP2_ERR_INVALID;
   }
-  CP2_TRY(session_check(ctx, cfg, first_slot, n_local, slot_roots));
+  CP2_TRY(fill_session_check(ctx, cfg, first_slot, n_local, slot_roots));
   const auto t0 = std::chrono::steady_clock::now();
   // either format: a CP2FILL1 file states no nodes, and the result is cp2_fill_resume followed by cp2_fill_keep_nodes
   NodeCheckpoint ck;
   const bool with_nodes = !file_has_magic(path, "CP2FILL1");
   if (with_nodes) CP2_TRY(read_node_checkpoint(ctx, path, &ck));
-  else CP2_TRY(read_checkpoint(ctx, path, &ck.base));
+  else CP2_TRY(read_checkpoint(&ctx->err, path, &ck.base));
   // layer 0 as the file states it: the shared resume zeroes the rows of the blocks it drops, and those rows are candidates
   const std::vector<uint8_t> stated0 = with_nodes ? ck.base.layer0 : std::vector<uint8_t>();
   std::unique_ptr<cp2_fill_session> f;

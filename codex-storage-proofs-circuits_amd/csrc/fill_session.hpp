@@ -1,5 +1,5 @@
-// The session behind the header's opaque cp2_fill, shared by fill.cpp (one session's calls), fill_many.cpp (cp2_fills_add_many) and
-// fill_finish_many.cpp (cp2_fills_finish_many): many sessions in one pass.  Not installed.
+// The session behind the header's opaque cp2_fill, shared by fill.cpp (one session's calls), fill_many.cpp (cp2_fills_add_many),
+// fill_finish_many.cpp (cp2_fills_finish_many) and fills_resume_many.cpp (cp2_fills_resume_many): many sessions in one pass.  Not installed.
 #pragma once
 #include <cstdint>
 #include <memory>
@@ -49,5 +49,15 @@ inline std::unique_ptr<cp2_dataset> fill_dataset_shell(const cp2_fill_session* f
   ds->coff = f->plan.coff;
   return ds;
 }
+
+// What cp2_fill_begin and cp2_fill_resume do before and for a session (fill.cpp), for cp2_fills_resume_many to do per entry:
+// the checks of (cfg, first_slot, n_local, slot_roots) before anything is allocated (CP2_ERR_INVALID, the reason in ctx->err) ...
+int fill_session_check(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local, const uint8_t* slot_roots);
+// ... the session of checked arguments, its two buffers as cp2_fill_begin allocates them and nothing uploaded or queued ...
+int fill_session_alloc(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_slot, uint64_t n_local, const uint8_t* slot_roots,
+                       std::unique_ptr<cp2_fill_session>* out);
+// ... and a CP2FILL1 checkpoint file read and parsed: CP2_ERR_IO with cp2_fill_resume's words in *err (any thread may call it)
+struct FillCheckpoint;
+int fill_read_checkpoint(std::string* err, const char* path, FillCheckpoint* ck);
 
 }  // namespace cp2i

@@ -22,6 +22,7 @@
 //   k_block_path_commit_anchored   the same walk, stopped per lane at a node the session's tree already holds (fill.cpp)
 //   k_block_path_commit_many   the anchored walk with the session taken per lane from a descriptor table (fill_many.cpp)
 //   k_block_root_recheck  re-read block roots against layer 0 of a resumed fill session; a row the disk no longer backs is zeroed (fill.cpp)
+//   k_block_root_recheck_addr the same with the kept row of every block at an absolute address (fills_resume_many.cpp: many sessions)
 //   k_adopt_layer, k_adopt_resolve   the tree over block roots read back from disk, judged against the nodes a fill session keeps (fill.cpp)
 //   k_nodes_restore_layer   the kept nodes a checkpoint states, authenticated top-down from the stated slot roots (fill.cpp)
 //
@@ -1241,19 +1242,41 @@ __global__ void __launch_bounds__(TPB) k_block_path_commit_many(const uint4* __r
 // back; the host clears the block's presence bit from the verdict.  The rows of one launch are distinct (the read plan names every present
 // block once), so no lane reads a row another lane zeroes.  A row at or past n_rows (never: the host computed every row) is a mismatch
 // and is neither read nor written.  No atomics, no LDS, no permutation.
+// The row form and the address form share this step: fresh row i against the kept row at k (never null here), which is zeroed where they differ.
+__device__ __forceinline__ uint32_t block_root_recheck_row(const uint4* __restrict__ fresh, size_t i, uint4* k) {
+  const uint32_t v = rows_equal(fresh[2 * i], fresh[2 * i + 1], k[0], k[1]) ? 0u : 1u;
+  if (v) {
+    k[0] = make_uint4(0, 0, 0, 0);
+    k[1] = make_uint4(0, 0, 0, 0);
+  }
+  return v;
+}
+
 __global__ void __launch_bounds__(TPB) k_block_root_recheck(const uint4* __restrict__ fresh, const uint64_t* __restrict__ dest, size_t n,
                                                               uint32_t* __restrict__ verdict, uint4* __restrict__ layer0, uint64_t n_rows) {
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
   const uint64_t r = dest[i];
   uint32_t v = 1;
-  if (r < n_rows) {
-    v = rows_equal(fresh[2 * i], fresh[2 * i + 1], layer0[2 * r], layer0[2 * r + 1]) ? 0u : 1u;
-    if (v) {
-      layer0[2 * r] = make_uint4(0, 0, 0, 0);
-      layer0[2 * r + 1] = make_uint4(0, 0, 0, 0);
-    }
-  }
+  if (r < n_rows) v = block_root_recheck_row(fresh, i, layer0 + 2 * r);
+  verdict[i] = v;
+}
+
+// Resuming many fill sessions in one pass (fills_resume_many.cpp): the kept row of re-read block i is the 32 bytes at the absolute device
+// address addr[i] -- layer 0 of the session the block belongs to, plus its row x 32 --, as k_repair_compare_addr takes the kept row of a
+// request, so that the present blocks of every session share each launch.  The fresh side is coalesced (64 lanes, 2 KiB in a run); the
+// kept side is one 32-byte row wherever the block's session lies, 8 bytes of table beside it.  A differing row is zeroed in its own
+// session's buffer, two 16-byte vector stores.  The addresses of one launch are distinct (the plan names every present block of every
+// session once, and every session owns its buffer), so no lane reads a row another lane zeroes.  addr[i] == 0, or an address that is not
+// 16-byte aligned (never: the host made the table from allocation bases and rows), is a mismatch and is neither read nor written.  No
+// atomics, no LDS, no permutation.
+__global__ void __launch_bounds__(TPB) k_block_root_recheck_addr(const uint4* __restrict__ fresh, const uint64_t* __restrict__ addr, size_t n,
+                                                                   uint32_t* __restrict__ verdict) {
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t a = addr[i];
+  uint32_t v = 1;
+  if (a != 0 && (a & 15) == 0) v = block_root_recheck_row(fresh, i, reinterpret_cast<uint4*>(a));
   verdict[i] = v;
 }
 
@@ -1777,6 +1800,14 @@ hipError_t launch_block_root_recheck(const void* fresh, const uint64_t* dest, si
   return for_slices(n, [&](size_t i0, size_t m) {
     hipLaunchKernelGGL(k_block_root_recheck, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)fresh + 2 * i0, dest + i0, m, verdict + i0, (uint4*)layer0,
                 n_rows);
+  });
+}
+
+hipError_t launch_block_root_recheck_addr(const void* fresh, const uint64_t* addr, size_t n, uint32_t* verdict, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  if (!fresh || !addr || !verdict) return hipErrorInvalidValue;
+  return for_slices(n, [&](size_t i0, size_t m) {
+    hipLaunchKernelGGL(k_block_root_recheck_addr, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)fresh + 2 * i0, addr + i0, m, verdict + i0);
   });
 }
 

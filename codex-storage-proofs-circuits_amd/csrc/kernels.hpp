@@ -174,6 +174,10 @@ hipError_t launch_finish_layers_many(const FillManySession* sessions, uint64_t n
 // n_rows: verdict 1, nothing read or written.  The rows of one call are distinct.
 hipError_t launch_block_root_recheck(const void* fresh, const uint64_t* dest, size_t n, uint32_t* verdict, void* layer0, uint64_t n_rows,
                                      hipStream_t st);
+// Resuming many fill sessions (fills_resume_many.cpp, k_block_root_recheck_addr): the same with the kept row of block i at the absolute
+// device address addr[i] (layer 0 of its own session), so that one call judges blocks of many sessions.  addr[i] == 0 or not 16-byte
+// aligned: verdict 1, nothing read or written.  The addresses of one call are distinct.  n == 0: success, no launch.
+hipError_t launch_block_root_recheck_addr(const void* fresh, const uint64_t* addr, size_t n, uint32_t* verdict, hipStream_t st);
 
 // Adopting blocks from disk (fill.cpp, cp2_fill_adopt).  `tree` is the session's compact buffer (n_rows rows of 32 bytes), `cand` a buffer of
 // the same shape whose layer 0 holds the block roots of the candidates, `flags` one byte per row: bit 0 (ADOPT_KNOWN) the session knows

@@ -7,7 +7,8 @@
 // block root the dataset keeps for it by k_repair_compare_addr -- one absolute address per request, so the requests of many datasets
 // share every launch.  The kept roots and the paths above them do not depend on what was read: one k_gather_addr and one download per
 // call fetch them all.  What the plan decides -- refusals, read order, chunks, packed path offsets, the address tables -- is
-// read_blocks_plan.hpp.  Chunk k + 1 is read on the context's ingestion threads while chunk k is uploaded and hashed.
+// read_blocks_plan.hpp.  Chunk k + 1 is read on the context's ingestion threads while chunk k is uploaded and hashed: the pass itself is
+// read_pass.hpp, which cp2_fills_resume_many runs with another judge.
 //
 // Where the time goes on the device: 1119 permutations per block in k_hash_cells and the block-tree layers, as in every other pass over
 // block bytes.  The compare and the gather are what this file adds there, a few bytes per block.
@@ -24,6 +25,7 @@
 
 #include "dataset_obj.hpp"
 #include "read_blocks_plan.hpp"
+#include "read_pass.hpp"
 #include "repair.hpp"
 
 using namespace cp2i;
@@ -32,104 +34,6 @@ static_assert(READ_BLOCKS_CHECK_ONLY == CP2_READ_CHECK_ONLY, "the plan's flag is
 static_assert(CP2_READ_OK == CP2_REPAIR_MATCH && CP2_READ_DAMAGED == CP2_REPAIR_MISMATCH, "repair_check_with's verdicts are the statuses");
 
 namespace {
-
-// Where the blocks of a pass come from.  read: the file-sourced requests of chunk k, each into row_of(i), on host threads (false: *err
-// is the message, CP2_ERR_IO).  fake (may be empty: none): per request, whether the device regenerates it from seeds[i] (cp2_slot_seed)
-// and firsts[i] (its first cell).  A later source over a fill session's present blocks is another `read` and nothing else.
-struct BlockSource {
-  size_t n_chunks = 0;
-  std::function<bool(size_t k, const std::function<uint8_t*(size_t)>& row_of, std::string* err)> read;
-  std::vector<uint8_t> fake;
-  std::vector<uint64_t> seeds, firsts;
-};
-
-// The middle of the pass: n requests in chunks of `chunk`, request i judged against the 32 bytes at addr[i]; addr (n + path rows
-// entries, read_blocks_addr_table) gathered whole into `gathered` (host, addr.size() x 32 bytes).  data (n x block_size, may be NULL):
-// every row is filled; nothing is zeroed here.  *touched: the requests whose rows may hold file bytes when the pass fails.
-int read_pass(cp2_ctx* ctx, size_t cell_size, size_t block_size, size_t n, size_t chunk, const std::vector<uint64_t>& addr, BlockSource& src,
-              uint8_t* data, uint8_t* gathered, uint32_t* status, size_t* touched) {
-  const size_t cpb = block_size / cell_size;
-  const bool any_fake = !src.fake.empty();
-  PinBuf ring[2];                                    // check only: two chunk buffers, whatever n is
-  if (!data)
-    for (auto& b : ring) CP2_TRY(b.alloc(ctx, std::min(n, chunk) * block_size));
-  DevBuf d_addr, d_gen;                              // (go after the streams have drained: DevBuf::release)
-  std::string read_err[2];
-  bool read_ok[2] = {true, true};
-  auto base_of = [&](size_t k) { return data ? data + k * chunk * block_size : ring[k & 1].u8(); };
-  {
-    Workers reader(1);                               // one chunk ahead; the chunk's files are spread over the ingestion threads inside
-    auto start = [&](size_t k) {
-      if (k >= src.n_chunks) return;
-      *touched = std::min(n, (k + 1) * chunk);
-      uint8_t* base = base_of(k);
-      const size_t c0 = k * chunk;
-      reader.submit([&, k, base, c0] {
-        read_ok[k & 1] = src.read(k, [&](size_t i) { return base + (i - c0) * block_size; }, &read_err[k & 1]);
-      });
-    };
-    // chunk k's rows, read; chunk k + 1 started.  A ring buffer is read into again only after the chunk that was uploaded from it is done.
-    auto take = [&](size_t c0, const uint8_t** out) -> int {
-      const size_t k = c0 / chunk;
-      reader.wait_idle();
-      if (!read_ok[k & 1]) {
-        ctx->err = read_err[k & 1];
-        return CP2_ERR_IO;
-      }
-      if (!data && k > 0) CP2_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      start(k + 1);
-      *out = base_of(k);
-      return CP2_OK;
-    };
-    RepairJudge judge;
-    judge.begin = [&](size_t) -> int {
-      CP2_TRY(d_addr.scratch(ctx, n * 8));
-      CP2_HIP(ctx, hipMemcpyAsync(d_addr.p, addr.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
-      if (any_fake) {
-        CP2_TRY(d_gen.scratch(ctx, n * 16));
-        CP2_HIP(ctx, hipMemcpyAsync(d_gen.p, src.seeds.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
-        CP2_HIP(ctx, hipMemcpyAsync(d_gen.u8() + n * 8, src.firsts.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
-      }
-      start(0);
-      return CP2_OK;
-    };
-    judge.host = [&](size_t c0, size_t, const uint8_t** out) -> int { return take(c0, out); };
-    judge.host_pinned = data ? host_array_pinned(data, n * block_size, (size_t)128 << 20) : true;
-    if (any_fake) {
-      // a chunk with regenerated blocks is put together on the device: runs of file rows uploaded, runs of fake rows generated in place
-      // (and downloaded into the caller's rows), all on the stream the chunk is hashed on
-      judge.cells = [&](size_t c0, size_t m, uint8_t* d_cells, hipStream_t st) -> int {
-        const uint8_t* rows = nullptr;
-        CP2_TRY(take(c0, &rows));
-        const uint64_t* seeds = static_cast<const uint64_t*>(d_gen.p);
-        for (size_t a = 0; a < m;) {
-          size_t b = a + 1;
-          while (b < m && src.fake[c0 + b] == src.fake[c0 + a]) ++b;
-          const size_t off = a * block_size, len = (b - a) * block_size;
-          if (src.fake[c0 + a]) {
-            CP2_HIP(ctx, cp2k::launch_gen_fake_cells_many(seeds + c0 + a, seeds + n + c0 + a, cpb, (b - a) * cpb, cell_size, d_cells + off, st));
-            if (data) CP2_HIP(ctx, hipMemcpyAsync(data + (c0 + a) * block_size, d_cells + off, len, hipMemcpyDeviceToHost, st));
-          } else {
-            CP2_HIP(ctx, hipMemcpyAsync(d_cells + off, rows + off, len, hipMemcpyHostToDevice, st));
-          }
-          a = b;
-        }
-        return CP2_OK;
-      };
-    }
-    judge.verdicts = [&](const uint8_t* fresh, size_t c0, size_t m, uint32_t* verdict, hipStream_t st) -> int {
-      CP2_HIP(ctx, cp2k::launch_repair_compare_addr(fresh, static_cast<const uint64_t*>(d_addr.p) + c0, m, verdict, st));
-      return CP2_OK;
-    };
-    const int r = repair_check_with(ctx, cell_size, block_size, nullptr, n, status, judge);
-    reader.wait_idle();                              // (a chunk read ahead of a pass that failed writes into rows of this scope)
-    if (r != CP2_OK) {
-      (void)hipStreamSynchronize(ctx->stream);       // nothing of the pass reads a ring buffer or writes a caller's row after this
-      return r;
-    }
-  }
-  return gather_rows_by_addr(ctx, addr, gathered);
-}
 
 ReadDataset describe(const cp2_ctx* ctx, cp2_dataset* const* ds, size_t k) {
   ReadDataset d;
@@ -222,7 +126,10 @@ int read_blocks(cp2_ctx* ctx, cp2_dataset* const* ds, size_t n_ds, const uint64_
   std::vector<uint32_t> st(n);
   std::vector<uint8_t> gathered(addr.size() * 32);
   size_t touched = 0;
-  const int r = read_pass(ctx, cs, bs, n, chunk, addr, src, data, gathered.data(), st.data(), &touched);
+  const ReadJudge compare = [&](const uint8_t* fresh, const uint64_t* d_addr, size_t m, uint32_t* verdict, hipStream_t stream) {
+    return cp2k::launch_repair_compare_addr(fresh, d_addr, m, verdict, stream);
+  };
+  const int r = read_pass(ctx, cs, bs, n, chunk, addr, src, compare, data, gathered.data(), st.data(), &touched);
   if (r != CP2_OK) {
     if (data) std::memset(data, 0, touched * bs);
     return r;

@@ -133,6 +133,11 @@ proc cp2_fills_add_many(ctx: Cp2Ctx, fills: ptr pointer, nFills: csize_t, req: p
 # many complete fill sessions of one context finished in one pass: cachePaths nil, or nFills entries each of which may be nil; outp = nFills;
 # per session cp2_fill_finish's meaning, all or nothing
 proc cp2_fills_finish_many(ctx: Cp2Ctx, fills: ptr pointer, nFills: csize_t, cachePaths: ptr cstring, outp: ptr Cp2Dataset): cint {.importc.}
+# many fill sessions of one context resumed from their CP2FILL1 checkpoints in one pass: cfgs = nFills pointers to Cp2Config, ranges =
+# nFills x (firstSlot, nLocal), slotRoots = nFills pointers (entry k: nLocal[k] x 32 bytes), paths = nFills checkpoint files, outp = nFills
+# sessions, nDropped = nFills entries or nil; per entry cp2_fill_resume's meaning, all or nothing
+proc cp2_fills_resume_many(ctx: Cp2Ctx, cfgs: ptr pointer, ranges: ptr uint64, slotRoots: ptr ptr byte, paths: ptr cstring, nFills: csize_t,
+                           flags: cint, outp: ptr pointer, nDropped: ptr uint64): cint {.importc.}
 # adopting blocks from disk: the absent blocks the slot files cover are read, hashed and kept where the tree above them reaches a node the
 # session knows (the stated slot root included); flags = 0 or CP2_ADOPT_NO_READ (judge what earlier calls read); nRead, nAdopted may be nil
 const CP2_ADOPT_NO_READ* = 1.cint

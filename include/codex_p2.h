@@ -50,7 +50,7 @@ extern "C" {
  *                cp2_datasets_read_blocks and cp2_dataset_read_blocks (verified read-back of listed blocks),
  *                cp2_datasets_build_many (many datasets built in one pass), cp2_datasets_set_roots_many (their dataset trees in one pass),
  *                cp2_fills_add_many (proved blocks added to many fill sessions in one pass), cp2_fills_finish_many (many fill
- *                sessions finished in one pass).
+ *                sessions finished in one pass), cp2_fills_resume_many (many fill sessions resumed in one pass).
  *                MINOR stays 2 until the release that carries them: the bump to 1.3 goes in its own commit with that release.         */
 #define CP2_ABI_VERSION_MAJOR 1
 #define CP2_ABI_VERSION_MINOR 2
@@ -1100,6 +1100,51 @@ int cp2_fill_resume_nodes(cp2_ctx* ctx, const cp2_config* cfg, uint64_t first_sl
 int cp2_fills_finish_many(cp2_ctx* ctx, void* const* fills /* cp2_fill* each */, size_t n_fills,
                           const char* const* cache_paths /* NULL, or n_fills entries each of which may be NULL */,
                           cp2_dataset** out /* n_fills */);
+
+/* ---- many fill sessions resumed in one pass -------------------------------------------------------------------------------------------------
+ * The restart side of the many-session life cycle.  After a crash or an upgrade every session comes back through cp2_fill_resume: per
+ * session a checkpoint read, two device allocations, two uploads with a drain each, and a re-check with a data-path set-up, launches and
+ * drains of its own, reading block by block on one thread.  cp2_fills_resume_many is ONE pass: the checkpoints are read on the context's
+ * ingestion threads, all sessions are opened and their roots and layer 0 go up through pinned staging with one drain, and every present
+ * block of every session is re-read by the chunked reader of cp2_datasets_read_blocks -- each file opened once per chunk, the files
+ * spread over the ingestion threads, one chunk ahead of the hashing -- and judged by one launch per chunk (k_block_root_recheck_addr,
+ * the kept row of a block at an absolute address inside its own session's buffer).
+ *   Sessions   entry k is (cfgs[k], first_slot = ranges[2k], n_local = ranges[2k + 1], slot_roots[k]: n_local x 32 bytes, paths[k]: a
+ *              CP2FILL1 checkpoint).  Entries may differ in n_cells (so nBlocks and depth), n_slots, range, source (slot files or
+ *              fake), base name and seed; they share cell_size and block_size (the data path has one shape: cp2_fills_add_many's
+ *              rule).  Two entries may name the same files or the same checkpoint: resume only reads.
+ *   Meaning    by the call that exists.  After CP2_OK, out[k] and n_dropped[k] are what cp2_fill_resume(ctx, cfgs[k], first_slot,
+ *              n_local, slot_roots[k], paths[k], flags, &out[k], &n_dropped[k]) leaves, for every k: the same presence bitmap, the
+ *              same layer 0 with the rows of dropped blocks zeroed, the same cp2_fill_missing list; a dropped block is accepted
+ *              again as CP2_FILL_NEW.  Every session owns its allocations as cp2_fill_begin makes them (cp2_fill_finish hands the
+ *              buffer over: nothing is shared) and keeps no nodes.  n_dropped may be NULL.
+ *   Refused    all or nothing, unlike the loop: every check of every entry runs before a session exists; on any failure no session
+ *              is created, every out[k] is NULL and n_dropped is untouched.  In this order, the lowest entry index first inside
+ *              each step, the index in cp2_last_error ("fills: entry k: ..."): (1) CP2_ERR_INVALID: a NULL ctx; unknown flag bits;
+ *              with n_fills > 0, NULL cfgs, ranges, slot_roots, paths or out; a NULL cfgs[k], slot_roots[k] or paths[k]; everything
+ *              cp2_fill_begin refuses for entry k; a cell_size or block_size other than entry 0's.  (2) the checkpoints: one that is
+ *              not intact (a CP2FILL2 file by its magic) is CP2_ERR_IO in cp2_fill_resume's words, naming the path; one that
+ *              describes another session is CP2_ERR_INVALID naming the first field that differs.  (3) slot files that cannot be
+ *              stat'ed: CP2_ERR_IO (a file that does not exist is a state: its blocks are dropped).  n_fills == 0: CP2_OK.  A
+ *              context whose stream will not drain: CP2_ERR_HIP.
+ *   Device     per session cp2_fill_begin's two allocations; roots and layer 0 of all sessions go up through pinned staging in pieces of
+ *              at most the staging size, each piece one copy and one k_scatter_rows_addr launch, and one drain;
+ *              then, without CP2_RESUME_TRUST_FILES, the re-check in chunks of half the staging size (cp2_datasets_read_blocks'
+ *              chunks): two pooled pinned buffers, fake-source blocks regenerated on the device, repair's hashing, one judge launch.
+ *   Failure    after the checks: a failed allocation is CP2_ERR_ALLOC and a slot-file read that fails is CP2_ERR_IO with the
+ *              builders' message (never a dropped block).  Either frees every session already opened and leaves every out[k] NULL;
+ *              the call returns only after the stream has drained and the reader is idle.
+ *   Trace      CP2_TRACE prints one line: sessions, blocks present in the checkpoints, re-read, dropped, chunks, bytes, seconds, GB/s
+ *              and the split (checkpoints, opens and uploads, re-check, host drops).
+ * Out of scope: cp2_multi_*; CP2FILL2 checkpoints and a many-session cp2_fill_keep_nodes, cp2_fill_resume_nodes, cp2_fill_adopt or save
+ * (each session's own calls, as before); a many-session begin; routing cp2_fill_resume or cp2_fill_adopt through this pass; O_DIRECT
+ * or mapped reads. */
+int cp2_fills_resume_many(cp2_ctx* ctx, const void* const* cfgs /* n_fills: const cp2_config* each */,
+                          const uint64_t* ranges /* n_fills x 2: first_slot, n_local */,
+                          const uint8_t* const* slot_roots /* n_fills entries, entry k: n_local[k] x 32 */,
+                          const char* const* paths /* n_fills checkpoint files, CP2FILL1 */, size_t n_fills,
+                          int flags /* 0 or CP2_RESUME_TRUST_FILES */, void** out /* n_fills: cp2_fill* each */,
+                          uint64_t* n_dropped /* n_fills, may be NULL */);
 
 
 /* ---- e: every GPU of the node behind one handle ------------------------------------------------------ */
