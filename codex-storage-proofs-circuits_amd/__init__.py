@@ -241,6 +241,7 @@ def load_library():
         "cp2_fills_add_many": (i32, [vp, vp, sz, vp, vp, vp, vp, sz, vp, vp]),
         "cp2_fills_finish_many": (i32, [vp, vp, sz, vp, vp]),
         "cp2_fills_resume_many": (i32, [vp, vp, vp, vp, vp, sz, i32, vp, vp]),
+        "cp2_datasets_repair_blocks_many": (i32, [vp, vp, sz, vp, vp, vp, vp, sz, i32, vp, vp, ctypes.POINTER(sz)]),
         "cp2_fill_adopt": (i32, [vp, u64, u64, i32, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
         "cp2_fill_save_nodes": (i32, [vp, cp]),
         "cp2_fill_resume_nodes": (i32, [vp, ctypes.POINTER(Config), u64, u64, vp, cp, i32, pvp, ctypes.POINTER(u64), ctypes.POINTER(u64),
@@ -649,6 +650,42 @@ class Context:
                                                  _p(paths) if want_paths else None, _p(off) if want_paths else None, _p(status), ctypes.byref(ok)),
                  "cp2_datasets_read_blocks")
         return data, roots, paths, off, status, ok.value
+
+    def repair_blocks_many(self, datasets, requests, data, paths=None, path_off=None, check_only=False, cache_paths=None):
+        """cp2_datasets_repair_blocks_many: candidate blocks (n x blockSize bytes) for requests (uint64[n, 3]: index into datasets, slot,
+        block) judged on the device in one pass and the matching ones written back, the slot files spread over the ingestion threads.
+        paths (uint8[rows, 32]) and path_off (uint64[n + 1]) are what read_blocks returns: request i's path is rows path_off[i] to
+        path_off[i + 1]; an empty one judges against the kept block root, a whole one walks to the dataset's own slot root (the only form a
+        roots-only dataset takes); both None: every path is empty.  cache_paths: None, or one entry (None or a path) per dataset.  `data`
+        as for Dataset.repair_blocks.  Returns (status: uint32[n] of REPAIR_*, n_written)."""
+        rq = np.ascontiguousarray(np.asarray(requests, dtype=np.uint64).reshape(-1, 3))
+        n, nd = rq.shape[0], len(datasets)
+        hs = (ctypes.c_void_p * max(nd, 1))(*[d.h for d in datasets])
+        bs = int(datasets[0].cfg.block_size) if nd else 0
+        d = np.ascontiguousarray(data) if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)   # (no copy of a contiguous array)
+        if d.nbytes != n * bs:
+            raise ValueError("repair many: %d request(s) need %d bytes of candidates, got %d" % (n, n * bs, d.nbytes))
+        if (paths is None) != (path_off is None):
+            raise ValueError("repair many: paths and path_off go together")
+        pp = po = None
+        if paths is not None:
+            po = np.ascontiguousarray(np.asarray(path_off, dtype=np.uint64).reshape(-1))
+            pp = np.ascontiguousarray(_u8(paths).reshape(-1, 32))
+            if po.shape[0] != n + 1 or (n and int(po.max()) > pp.shape[0]):
+                raise ValueError("repair many: path_off needs n + 1 = %d entries inside the %d row(s) of paths" % (n + 1, pp.shape[0]))
+            if pp.shape[0] == 0:
+                pp = np.zeros((1, 32), dtype=np.uint8)   # (an address to hand over: no row of it is read)
+        cps = None
+        if cache_paths is not None:
+            cache_paths = list(cache_paths)
+            assert len(cache_paths) == nd
+            cps = (ctypes.c_char_p * max(nd, 1))(*[c.encode() if c else None for c in cache_paths])
+        status = np.empty(n, dtype=np.uint32)
+        written = ctypes.c_size_t()
+        self._ck(self.L.cp2_datasets_repair_blocks_many(self.h, hs, nd, _p(rq) if n else None, _p(d) if n else None, _p(pp) if pp is not None else None,
+                                                        _p(po) if po is not None else None, n, REPAIR_CHECK_ONLY if check_only else 0, cps,
+                                                        _p(status) if n else None, ctypes.byref(written)), "cp2_datasets_repair_blocks_many")
+        return status, written.value
 
     def export_proof_inputs_many(self, requests, paths=None, threads=1, batch=0):
         """cp2_proof_inputs_export_many: generate + serialise (+ write paths[i] where it is not None) as a pipeline; returns the

@@ -17,6 +17,7 @@
 //   k_repair_compare_addr the same with the kept row of every request at an absolute address (read_blocks.cpp: many datasets)
 //   k_scatter_rows_addr   a batch's layer written to where every item's dataset keeps it, through an address table (build_many.cpp)
 //   k_block_path_roots    a13 candidate block roots walked up their Merkle paths to the slot root, merkle.nim:51-74 (block_proofs.cpp)
+//   k_repair_judge_many   the same walk over 0 or depth levels per lane, against a row at an absolute address (repair_many.cpp: many datasets)
 //   k_block_path_commit   the same walk; a proved block root is also stored into layer 0 of a fill session's compact buffer (fill.cpp)
 //   k_block_path_commit_nodes   the same walk; a proved path's 2 x depth + 1 nodes are stored where the session's tree has them (fill.cpp)
 //   k_block_path_commit_anchored   the same walk, stopped per lane at a node the session's tree already holds (fill.cpp)
@@ -1054,6 +1055,28 @@ __global__ void __launch_bounds__(TPB) k_block_path_roots(const uint4* __restric
 }
 
 // ------------------------------------------------------------------------------------------------
+// Repair across many datasets (repair_many.cpp): k_block_path_roots' walk and k_repair_compare_addr's table in one kernel, everything per
+// lane.  Lane i takes request i's freshly built block root (fresh row i) and its descriptor: it walks len levels (0, or its dataset's
+// depth) from j = blk over a first layer of n_blocks nodes, reading its siblings at row path_at of the chunk's staged paths, and compares
+// what it reaches with the 32-byte row at the absolute address `want` as canonical words -- the kept block root where len is 0 (the walk
+// returns the row itself), the dataset's own slot root otherwise.  One verdict word: 0 equal, 1 not; want == 0 or not 16-byte aligned is a
+// mismatch and is not read (never: the host made the table).  No other store, no atomics.  A wave that mixes depths and path-less
+// requests runs to its longest walk.
+__global__ void __launch_bounds__(TPB) k_repair_judge_many(const uint4* __restrict__ fresh, const uint4* __restrict__ paths,
+                                                             const RepairManyReq* __restrict__ reqs, size_t n, uint32_t* __restrict__ verdict) {
+  __shared__ fr::QTab qtab;
+  fr::qtab_fill(qtab, threadIdx.x, TPB);
+  __syncthreads();
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  const RepairManyReq q = reqs[i];
+  const Fe cur = walk_block_path<false>(load_fe_canonical(fresh + 2 * i), paths + 2 * q.path_at, nullptr, q.blk, q.n_blocks, q.len, qtab);
+  uint32_t v = 1;
+  if (q.want != 0 && (q.want & 15) == 0) v = fe_equal(cur, load_fe_canonical(reinterpret_cast<const uint4*>(q.want))) ? 0u : 1u;
+  verdict[i] = v;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Slot filling (fill.cpp): the same walk, with what a fill session keeps of a proved block.  Lane i takes request i's freshly built block
 // root, its (local slot, block) pair and its path, and compares the result with slot_roots[slot] as canonical words.  Where they are equal
 // it also copies the canonical block root (row i of `fresh`, as the layer kernel wrote it) to row dest[i] of `layer0`, the session's
@@ -1736,6 +1759,16 @@ hipError_t launch_block_path_roots(const void* fresh, const void* paths, const u
     hipLaunchKernelGGL(k_block_path_roots, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)fresh + 2 * i0, (const uint4*)paths + 2 * i0 * depth,
                 root_block + 2 * i0, (const uint4*)slot_roots, n_blocks, depth, m, verdict + i0, roots_out ? (uint4*)roots_out + 2 * i0 : nullptr);
   });
+}
+
+hipError_t launch_repair_judge_many(const void* fresh, const void* paths, const RepairManyReq* reqs, size_t n, uint32_t* verdict, hipStream_t st,
+                                    size_t slice) {
+  if (n == 0) return hipSuccess;
+  if (!fresh || !reqs || !verdict) return hipErrorInvalidValue;
+  return for_slices(n, [&](size_t i0, size_t m) {     // path_at is relative to `paths`, which stays where it is
+    hipLaunchKernelGGL(k_repair_judge_many, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)fresh + 2 * i0, (const uint4*)paths, reqs + i0, m,
+                       verdict + i0);
+  }, slice && slice < MAX_ITEMS ? slice : MAX_ITEMS);
 }
 
 hipError_t launch_block_path_commit(const void* fresh, const void* paths, const uint64_t* slot_block, const void* slot_roots, const uint64_t* dest,

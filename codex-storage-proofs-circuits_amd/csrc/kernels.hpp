@@ -100,6 +100,22 @@ hipError_t launch_repair_compare_addr(const void* fresh, const uint64_t* kept_ad
 hipError_t launch_block_path_roots(const void* fresh, const void* paths, const uint64_t* root_block, const void* slot_roots, uint64_t n_blocks,
                                    uint32_t depth, size_t n, uint32_t* verdict, void* roots_out, hipStream_t st);
 
+// Repair across many datasets (repair_many.cpp, k_repair_judge_many): launch_block_path_roots' walk and launch_repair_compare_addr's
+// absolute addresses with everything per request.  One descriptor per request, a device table uploaded once per call.
+struct RepairManyReq {
+  uint64_t want;         // device address of the 32-byte row to compare with, 16-byte aligned; 0 is none: a mismatch, not read
+  uint64_t blk;          // block of the slot: the walk's first index
+  uint64_t n_blocks;     // the walk's first layer size
+  uint64_t path_at;      // first row of the request's siblings in `paths` (canonical or not, bottom first)
+  uint32_t len;          // levels walked: 0 compares the row of `fresh` itself
+  uint32_t reserved;     // 0
+};
+// verdict[i] = 0 when the 32-byte row i of `fresh`, walked up len levels of reconstructRoot over rows path_at ... of `paths`, equals the row
+// at `want` as a field element, else 1.  `paths` may be NULL when every len is 0.  Nothing but verdict[0, n) is written.  Launched in
+// slices of at most `slice` requests (0: what one grid holds; the tests pass small ones): a chunk of a call is a slice of one table.
+hipError_t launch_repair_judge_many(const void* fresh, const void* paths, const RepairManyReq* reqs, size_t n, uint32_t* verdict, hipStream_t st,
+                                    size_t slice = 0);
+
 // Slot filling (fill.cpp, k_block_path_commit): launch_block_path_roots' walk over (local slot, block) pairs, slot_roots indexed by the
 // local slot.  Where request i is a match (verdict[i] = 0) the 32-byte row i of `fresh` is also stored to row dest[i] of `layer0` (n_rows
 // rows; the host computed dest[i] inside layer 0 of the compact layout); a mismatch stores nothing.

@@ -38,6 +38,7 @@ struct ReadDataset {
   std::string base;                                   // slot files "<base><slot>.dat"
   uint64_t seed = 0;                                  // fake source: the dataset seed
   uint64_t nodes = 0;                                 // device address of row 0 of the kept node buffer
+  uint64_t roots = 0;                                 // device address of the local slot roots, n_local x 32 bytes (repair_many_plan.hpp)
   // where the block roots are kept: every node -- boff.back(), bsizes.back() (repair_row_full); compact -- coff[0], csizes[0]
   uint64_t root_off = 0, root_size = 0;
   std::vector<uint64_t> offs, sizes;                  // the big tree's layers, depth + 1 of them: toff / tsizes, or coff / csizes

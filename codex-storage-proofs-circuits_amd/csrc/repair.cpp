@@ -32,13 +32,6 @@ namespace {
 constexpr size_t SMALL_BYTES = (size_t)32 << 20;     // pageable chunks up to this size: one upload, as cp2_hash_cells does
 constexpr size_t PIECE_BYTES = (size_t)128 << 20;    // caller-pinned chunks are uploaded and hashed in pieces of this size
 
-bool stat_stamp(const std::string& path, uint64_t out[2]) {
-  struct stat sb;
-  if (stat(path.c_str(), &sb) != 0) { out[0] = out[1] = ~0ULL; return false; }
-  out[0] = (uint64_t)sb.st_size;
-  out[1] = (uint64_t)sb.st_mtim.tv_sec * 1000000000ULL + (uint64_t)sb.st_mtim.tv_nsec;
-  return true;
-}
 }  // namespace
 
 int cp2i::repair_check(cp2_ctx* ctx, const RepairKept& k, size_t cell_size, size_t block_size, const uint8_t* data, const uint64_t* rows,
@@ -160,34 +153,19 @@ int cp2i::repair_write_rows(const std::string& base, size_t block_size, const ui
   std::vector<FileStamp> stamps(groups.size());
   for (size_t g = 0; g < groups.size(); ++g) {
     stamps[g].slot = groups[g].slot;
-    (void)stat_stamp(slot_file_name(base, groups[g].slot), stamps[g].before);
+    (void)repair_stat_stamp(slot_file_name(base, groups[g].slot), stamps[g].before);
   }
   for (size_t g = 0; g < groups.size(); ++g) {
     const std::string name = slot_file_name(base, groups[g].slot);
-    const char* what = nullptr;
-    const int fd = open(name.c_str(), O_WRONLY | O_CREAT | O_CLOEXEC, 0644);
-    if (fd < 0) what = std::strerror(errno);
-    for (size_t k = 0; !what && k < groups[g].reqs.size(); ++k) {
-      const size_t i = groups[g].reqs[k];
-      const uint8_t* p = data + (row ? row[i] : i) * block_size;
-      size_t left = block_size;
-      off_t off = (off_t)(slot_block[2 * i + 1] * block_size);
-      while (left) {
-        const ssize_t w = pwrite(fd, p, left, off);
-        if (w < 0 && errno == EINTR) continue;
-        if (w <= 0) { what = w < 0 ? std::strerror(errno) : "no progress"; break; }
-        p += w; left -= (size_t)w; off += w;
-      }
-    }
-    if (!what && fdatasync(fd) != 0) what = std::strerror(errno);
-    if (fd >= 0 && close(fd) != 0 && !what) what = std::strerror(errno);
+    const int what = repair_write_file(name, block_size, groups[g].reqs.size(), [&](size_t k) { return slot_block[2 * groups[g].reqs[k] + 1] * (uint64_t)block_size; },
+                                       [&](size_t k) { const size_t i = groups[g].reqs[k]; return data + (row ? row[i] : i) * block_size; });
     if (what) {
-      *err = "cannot write " + name + ": " + what;
+      *err = "cannot write " + name + ": " + repair_write_reason(what);
       for (size_t h = g; h < groups.size(); ++h)
         for (size_t i : groups[h].reqs) status[i] = CP2_REPAIR_UNWRITTEN;
       return CP2_ERR_IO;
     }
-    (void)stat_stamp(name, stamps[g].after);
+    (void)repair_stat_stamp(name, stamps[g].after);
     written->push_back(stamps[g]);
     *n_written += groups[g].reqs.size();
   }

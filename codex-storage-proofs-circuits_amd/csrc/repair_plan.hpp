@@ -3,8 +3,14 @@
 // the writes.  No HIP in here: tests/host_check/repair_plan_check.cpp walks it over random request sets on the CPU, under
 // AddressSanitizer + UBSan.
 #pragma once
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
 #include <algorithm>
+#include <cerrno>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -99,6 +105,33 @@ inline std::vector<WriteGroup> repair_write_groups(const uint64_t* slot_block, c
   return g;
 }
 
+// One file of the writer (repair_write_rows in repair.cpp; the threaded writer of repair_many_plan.hpp): opened once (created with mode
+// 0644 where it is missing), row q of its n rows -- block_size bytes at row_of(q) -- written with pwrite at byte offset off_of(q) in the
+// order given, synced once after the last, closed.  0, or what stopped it: the errno, REPAIR_WRITE_NO_PROGRESS for a pwrite that wrote
+// nothing.  Touches nothing but its own file and its arguments, so different files may be written from different threads.
+constexpr int REPAIR_WRITE_NO_PROGRESS = -1;
+template <typename OffOf, typename RowOf>
+inline int repair_write_file(const std::string& name, size_t block_size, size_t n, OffOf off_of, RowOf row_of) {
+  int what = 0;
+  const int fd = open(name.c_str(), O_WRONLY | O_CREAT | O_CLOEXEC, 0644);
+  if (fd < 0) return errno ? errno : EIO;
+  for (size_t q = 0; !what && q < n; ++q) {
+    const uint8_t* p = row_of(q);
+    size_t left = block_size;
+    off_t off = (off_t)off_of(q);
+    while (left) {
+      const ssize_t w = pwrite(fd, p, left, off);
+      if (w < 0 && errno == EINTR) continue;
+      if (w <= 0) { what = w < 0 ? errno : REPAIR_WRITE_NO_PROGRESS; break; }
+      p += w; left -= (size_t)w; off += w;
+    }
+  }
+  if (!what && fdatasync(fd) != 0) what = errno;
+  if (close(fd) != 0 && !what) what = errno;
+  return what;
+}
+inline std::string repair_write_reason(int what) { return what == REPAIR_WRITE_NO_PROGRESS ? "no progress" : std::strerror(what); }
+
 // ---- cache stamps ------------------------------------------------------------------------------------------------------------------
 // A cache holds one (size, mtime_ns) stamp per item (slot, or unit: several units stamp the file of their slot); a missing file stamps
 // as (~0, ~0).  After the writes, an item's stamp is replaced by the file's new stat only when its file was WRITTEN by this call and the
@@ -108,6 +141,14 @@ struct FileStamp {
   uint64_t slot = 0;
   uint64_t before[2] = {~0ULL, ~0ULL}, after[2] = {~0ULL, ~0ULL};
 };
+// the (size, mtime_ns) stamp of a file as the caches hold it; false and (~0, ~0) for a file that is not there
+inline bool repair_stat_stamp(const std::string& path, uint64_t out[2]) {
+  struct stat sb;
+  if (stat(path.c_str(), &sb) != 0) { out[0] = out[1] = ~0ULL; return false; }
+  out[0] = (uint64_t)sb.st_size;
+  out[1] = (uint64_t)sb.st_mtim.tv_sec * 1000000000ULL + (uint64_t)sb.st_mtim.tv_nsec;
+  return true;
+}
 inline std::vector<size_t> repair_restamp(std::vector<uint64_t>& stamps, uint64_t first_item, uint64_t units_per_slot,
                                           const std::vector<FileStamp>& written) {
   std::vector<size_t> changed;

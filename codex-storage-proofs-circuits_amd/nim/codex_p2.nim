@@ -102,6 +102,11 @@ proc cp2_blocks_verify(ctx: Cp2Ctx, cellSize, blockSize, nCells: csize_t, slotRo
                        data, paths: ptr byte, n: csize_t, status: ptr uint32, blockRoots: ptr byte): cint {.importc.}
 proc cp2_dataset_repair_blocks_proved(ds: Cp2Dataset, slotBlock: ptr uint64, data, paths: ptr byte, n: csize_t, flags: cint,
                                       cachePath: cstring, status: ptr uint32, nWritten: ptr csize_t): cint {.importc.}
+# repair across datasets in one pass: req = n x (index into ds, slot, block), paths packed with pathOff (n + 1 rows, both nil: every path
+# empty) as cp2_datasets_read_blocks returns them -- an empty path judges against the kept block root, a whole one walks to the slot root --,
+# cachePaths = nDs entries (nil, or entries nil), status = n x CP2_REPAIR_*; every slot file is attempted on its own
+proc cp2_datasets_repair_blocks_many(ctx: Cp2Ctx, ds: ptr Cp2Dataset, nDs: csize_t, req: ptr uint64, data, paths: ptr byte, pathOff: ptr uint64,
+                                     n: csize_t, flags: cint, cachePaths: ptr cstring, status: ptr uint32, nWritten: ptr csize_t): cint {.importc.}
 # fill sessions: a slot filled from proved blocks in any order, then handed over as a compact dataset without a second pass.  The
 # session handle is a plain `pointer` (cp2_fill is void in the header); slotBlock = n x (slot, block), status = n x CP2_FILL_*,
 # missing = cap x (slot, block) ascending

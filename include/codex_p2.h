@@ -50,7 +50,8 @@ extern "C" {
  *                cp2_datasets_read_blocks and cp2_dataset_read_blocks (verified read-back of listed blocks),
  *                cp2_datasets_build_many (many datasets built in one pass), cp2_datasets_set_roots_many (their dataset trees in one pass),
  *                cp2_fills_add_many (proved blocks added to many fill sessions in one pass), cp2_fills_finish_many (many fill
- *                sessions finished in one pass), cp2_fills_resume_many (many fill sessions resumed in one pass).
+ *                sessions finished in one pass), cp2_fills_resume_many (many fill sessions resumed in one pass),
+ *                cp2_datasets_repair_blocks_many (many datasets repaired in one pass).
  *                MINOR stays 2 until the release that carries them: the bump to 1.3 goes in its own commit with that release.         */
 #define CP2_ABI_VERSION_MAJOR 1
 #define CP2_ABI_VERSION_MINOR 2
@@ -726,6 +727,55 @@ int cp2_datasets_read_blocks(cp2_ctx* ctx, cp2_dataset* const* ds, size_t n_ds,
 int cp2_dataset_read_blocks(cp2_dataset* ds, const uint64_t* slot_block /* n x 2: dataset slot, block of the slot */, size_t n, int flags,
                             uint8_t* data, uint8_t* block_roots, uint8_t* paths /* n x depth x 32, may be NULL */,
                             uint32_t* status /* n */, size_t* n_ok);
+
+/* ---- repair many: replacement blocks of many datasets judged in ONE pass and written back on many threads ------------------------------
+ * After cp2_datasets_scrub_many or cp2_datasets_read_blocks has named the damaged blocks of many datasets, cp2_dataset_repair_blocks and
+ * cp2_dataset_repair_blocks_proved take the replacements one dataset per call: a pass set-up, a drain and serial file writes for a few
+ * blocks each.  cp2_datasets_repair_blocks_many takes the interleaved candidates of all datasets of one context in one pass.
+ *   Datasets   cp2_datasets_read_blocks' rule: all belong to ctx and share cell_size and block_size; they may differ in n_cells, n_slots,
+ *              local range, source, base name and residency -- every node kept, compact, or roots only.  A handle may be listed twice.
+ *   Requests   req (n x 3 uint64: index into ds, dataset slot inside that dataset's local range, block of the slot < its nBlocks), data
+ *              (n x blockSize bytes, request i at i x blockSize; the data path is cp2_dataset_repair_blocks').  Request i's path is rows
+ *              [path_off[i], path_off[i + 1]) of paths (32 bytes a row, bottom first): cp2_datasets_read_blocks' packing, so what that
+ *              call returns for a DAMAGED block goes straight back in.  An EMPTY path means "judge against the kept block root"
+ *              (cp2_dataset_repair_blocks' rule); a path of exactly the cp2_block_proof_depth of its dataset means "walk to this
+ *              dataset's own slot root" (cp2_dataset_repair_blocks_proved's rule), the only form a roots-only dataset accepts.  paths ==
+ *              NULL (then path_off == NULL too): every path is empty.  One launch judges both kinds.
+ *   Meaning    for any dataset k, the requests that name it get, in request order, the statuses the matching single call gives that
+ *              dataset (CP2_REPAIR_MATCH / _MISMATCH / _UNWRITTEN), and where no write fails the slot-file bytes, the cache stamps and
+ *              its share of *n_written are that call's too.  Unchanged: as documented for the single calls.
+ *   Refused    before any device or file work, CP2_ERR_INVALID, every output, file and cache untouched, the lowest offending dataset or
+ *              request index in cp2_last_error; arguments are checked first, then datasets, then requests: a NULL ctx; an unknown flag;
+ *              paths without path_off or the reverse; with n > 0 a NULL ds, req, data or status; path_off[0] != 0; ds[k] NULL, of another
+ *              context, of another cell_size or block_size than ds[0]; a dataset index >= n_ds; a decreasing path_off; a path length that
+ *              is neither 0 nor its dataset's depth; an empty path for a roots-only dataset or for one whose kept layers are not those of
+ *              whole slot trees; a slot outside the local range; a block >= nBlocks of its dataset; a request that names a fake-source
+ *              dataset without CP2_REPAIR_CHECK_ONLY; the same (slot file, block) twice, whether through one handle listed twice or two
+ *              handles over the same base name (fake-source datasets: the same (handle, slot, block)).  n == 0: CP2_OK, *n_written = 0.
+ *              A context whose stream will not drain is refused (CP2_ERR_HIP).
+ *   Write      the matched blocks are grouped by slot file (by NAME: two handles over one base name share their files), each file's
+ *              blocks written in ascending offset order and the file fdatasync'ed once; the files are spread over the context's
+ *              ingestion threads (cp2_set_ingest).  UNLIKE the single calls, which stop at the first file that fails, every file is
+ *              attempted on its own: a file that cannot be opened, written or synced leaves its own matched requests _UNWRITTEN, every
+ *              other file is still written and counted, and the call returns CP2_ERR_IO with "cannot write <file>: <reason>" naming
+ *              the failing file that comes first in (dataset index, slot) order, the dataset index being the lowest that names the
+ *              file.  Where no write fails the result equals the per-dataset loop's.
+ *   Cache      cache_paths (n_ds entries, may be NULL, entries may be NULL): <cache_paths[k]> and <cache_paths[k]>.kept are restamped as
+ *              cache_path of the single calls is, for the files this call wrote that hold a request naming ds[k]'s handle, under the
+ *              same rule: only where the stamp equalled the file's stat taken before its first write.  Two handles over one base name
+ *              that repair the SAME file in one call see one write of it, where the loop's second call would find the first call's
+ *              stamp stale.
+ *   Trace      CP2_TRACE prints one line per call: datasets, requests, chunks, requests with paths, matched, written, files, bytes,
+ *              seconds, GB/s, stamps restamped.
+ *   Out of scope   cp2_multi_* datasets (their shards by slots are plain datasets and may be listed). */
+int cp2_datasets_repair_blocks_many(cp2_ctx* ctx, cp2_dataset* const* ds, size_t n_ds,
+                                    const uint64_t* req /* n x 3: index into ds, dataset slot, block of the slot */,
+                                    const uint8_t* data /* n x blockSize */,
+                                    const uint8_t* paths /* packed 32-byte rows, may be NULL */,
+                                    const uint64_t* path_off /* n + 1 rows, NULL iff paths is */,
+                                    size_t n, int flags,
+                                    const char* const* cache_paths /* n_ds entries, may be NULL, entries may be NULL */,
+                                    uint32_t* status /* n */, size_t* n_written /* may be NULL */);
 
 /* ---- fill sessions: slots filled from proved blocks in any order into a compact dataset ----------------------------------------------
  * A node that takes on a slot holds only the manifest's slot root.  It receives the slot's network blocks from peers, in any order and
