@@ -224,6 +224,11 @@ def load_library():
         "cp2_block_proof_depth": (sz, [sz, sz, sz]),
         "cp2_dataset_block_proofs": (i32, [vp, vp, sz, vp, vp]),
         "cp2_blocks_verify": (i32, [vp, sz, sz, sz, vp, sz, vp, vp, vp, sz, vp, vp]),
+        "cp2_block_multiproof_rows": (sz, [sz, sz, sz, vp, sz]),
+        "cp2_block_multiproof_layout": (i32, [sz, sz, sz, vp, sz, vp]),
+        "cp2_dataset_block_multiproofs": (i32, [vp, vp, sz, vp, vp, vp, sz, vp]),
+        "cp2_blocks_verify_multi": (i32, [vp, sz, sz, sz, vp, sz, vp, sz, vp, vp, vp, sz, vp, vp]),
+        "cp2_fill_add_multi": (i32, [vp, vp, sz, vp, vp, vp, sz, vp, ctypes.POINTER(sz)]),
         "cp2_dataset_repair_blocks_proved": (i32, [vp, vp, vp, vp, sz, i32, cp, vp, ctypes.POINTER(sz)]),
         "cp2_datasets_read_blocks": (i32, [vp, vp, sz, vp, sz, i32, vp, vp, vp, vp, vp, ctypes.POINTER(sz)]),
         "cp2_dataset_read_blocks": (i32, [vp, vp, sz, i32, vp, vp, vp, vp, ctypes.POINTER(sz)]),
@@ -373,6 +378,25 @@ class Context:
         self._ck(self.L.cp2_blocks_verify(self.h, cell_size, block_size, n_cells, _p(r) if r.size else None, r.shape[0], _p(rb) if n else None,
                                           _p(d) if n else None, _p(p) if n else None, n, _p(status) if n else None,
                                           _p(roots) if want_roots and n else None), "cp2_blocks_verify")
+        return status, roots
+
+    def blocks_verify_multi(self, cell_size, block_size, n_cells, slot_roots, groups, blocks, data, nodes, want_roots=True):
+        """cp2_blocks_verify_multi: candidate blocks (n x block_size bytes) in groups, each group with its multiproof, checked against the
+        stated slot roots; groups = (index into slot_roots, count) pairs, blocks = the n block indices group after group, strictly
+        ascending inside a group, nodes = the groups' rows packed (uint8[n_rows, 32]).  Returns (status: uint32[n_groups] of BLOCK_*, one
+        per GROUP, block_roots: uint8[n, 32] or None)."""
+        r = _u8(slot_roots).reshape(-1, 32)
+        g, b = _groups(groups, blocks)
+        n, ng = b.shape[0], g.shape[0]
+        d = np.ascontiguousarray(data) if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
+        if d.nbytes != n * block_size:
+            raise ValueError("block verify multi: %d request(s) need %d bytes of candidates, got %d" % (n, n * block_size, d.nbytes))
+        rows = _u8(nodes).reshape(-1, 32)
+        status = np.empty(ng, dtype=np.uint32)
+        roots = np.empty((n, 32), dtype=np.uint8) if want_roots else None
+        self._ck(self.L.cp2_blocks_verify_multi(self.h, cell_size, block_size, n_cells, _p(r) if r.size else None, r.shape[0], _p(g) if ng else None, ng,
+                                                _p(b) if n else None, _p(d) if n else None, _p(rows) if rows.size else None, rows.shape[0],
+                                                _p(status) if ng else None, _p(roots) if want_roots and n else None), "cp2_blocks_verify_multi")
         return status, roots
 
     # -- a1
@@ -805,6 +829,34 @@ def block_proof_depth(cell_size, block_size, n_cells):
     return load_library().cp2_block_proof_depth(cell_size, block_size, n_cells)
 
 
+def _groups(groups, blocks):
+    """the (slot or root index, count) pairs and the block list of a multiproof call as contiguous uint64 arrays"""
+    g = np.ascontiguousarray(np.asarray(groups, dtype=np.uint64).reshape(-1, 2))
+    b = np.ascontiguousarray(np.asarray(blocks, dtype=np.uint64).reshape(-1))
+    if int(g[:, 1].sum()) != b.shape[0]:
+        raise ValueError("multiproof: the groups count %d block(s), blocks holds %d" % (int(g[:, 1].sum()), b.shape[0]))
+    return g, b
+
+
+def block_multiproof_rows(cell_size, block_size, n_cells, blocks):
+    """cp2_block_multiproof_rows: rows in the multiproof of `blocks` (strictly ascending) of one slot; host only.  ValueError for a refused
+    geometry or list."""
+    b = np.ascontiguousarray(np.asarray(blocks, dtype=np.uint64).reshape(-1))
+    rows = load_library().cp2_block_multiproof_rows(cell_size, block_size, n_cells, _p(b) if b.size else None, b.shape[0])
+    if rows == ctypes.c_size_t(-1).value:
+        raise ValueError("block multiproof: a geometry the tree builders refuse, or blocks that are not strictly ascending below nBlocks")
+    return rows
+
+
+def block_multiproof_layout(cell_size, block_size, n_cells, blocks):
+    """cp2_block_multiproof_layout: the (level, index) of every row of that multiproof, in order, as a list of pairs; host only"""
+    b = np.ascontiguousarray(np.asarray(blocks, dtype=np.uint64).reshape(-1))
+    li = np.zeros((block_multiproof_rows(cell_size, block_size, n_cells, b), 2), dtype=np.uint64)
+    if load_library().cp2_block_multiproof_layout(cell_size, block_size, n_cells, _p(b), b.shape[0], _p(li) if li.size else None) != 0:
+        raise ValueError("block multiproof: refused")
+    return [(int(l), int(i)) for l, i in li]
+
+
 def _candidates(what, data, n, block_size, paths, depth):
     """the candidate bytes without a copy (see _repair) and the paths as uint8[n, depth, 32]"""
     d = np.ascontiguousarray(data) if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
@@ -956,6 +1008,25 @@ class Dataset:
                      "cp2_dataset_block_proofs")
         return roots, paths
 
+    def block_multiproofs(self, groups, blocks, want_roots=True):
+        """cp2_dataset_block_multiproofs: (block_roots: uint8[n, 32] or None, nodes: uint8[n_rows, 32]) of groups of blocks -- groups =
+        (dataset slot, count) pairs, blocks strictly ascending inside a group -- from what the dataset keeps; the rows of the groups are
+        packed in group order (block_multiproof_layout names them)."""
+        g, b = _groups(groups, blocks)
+        n, ng = b.shape[0], g.shape[0]
+        roots = np.empty((n, 32), dtype=np.uint8) if want_roots else None
+        nodes, n_rows = np.empty((0, 32), dtype=np.uint8), ctypes.c_size_t(0)
+
+        def call():
+            return self.ctx.L.cp2_dataset_block_multiproofs(self.h, _p(g) if ng else None, ng, _p(b) if n else None, _p(roots) if want_roots and n else None,
+                                                            _p(nodes) if nodes.size else None, nodes.shape[0], ctypes.byref(n_rows))
+        st = call()                                    # without room: the call states the rows it needs and writes nothing
+        if st != 0 and n_rows.value:
+            nodes = np.empty((n_rows.value, 32), dtype=np.uint8)
+            st = call()
+        self.ctx._ck(st, "cp2_dataset_block_multiproofs")
+        return roots, nodes
+
     def read_blocks(self, slot_block, check_only=False, want_data=True, want_paths=True, data=None):
         """cp2_dataset_read_blocks: Context.read_blocks over this dataset alone, (slot, block) pairs.  Returns (data: uint8[n, blockSize] or
         None, block_roots: uint8[n, 32], paths: uint8[n, depth, 32] or None, status: uint32[n] of READ_*, n_ok)."""
@@ -1088,6 +1159,27 @@ class FillSession:
                                      ctypes.byref(new))
         try:
             self.ctx._ck(st, "cp2_fill_add")
+        except CodexP2Error as e:
+            e.fill_status, e.n_new = status, new.value
+            raise
+        return status, new.value
+
+    def add_multi(self, groups, blocks, data, nodes):
+        """cp2_fill_add_multi: groups of blocks, each with its multiproof: groups = (dataset slot, count) pairs, blocks = the block indices
+        group after group, strictly ascending inside a group, data = n x blockSize bytes in that order, nodes = the groups' rows packed
+        (uint8[n_rows, 32]).  A group proves or fails as a whole.  Returns (status: uint32[n] of FILL_*, one per request, n_new)."""
+        g, b = _groups(groups, blocks)
+        n, ng = b.shape[0], g.shape[0]
+        d = np.ascontiguousarray(data) if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
+        if d.nbytes != n * self.cfg.block_size:
+            raise ValueError("fill multi: %d request(s) need %d bytes of candidates, got %d" % (n, n * self.cfg.block_size, d.nbytes))
+        rows = _u8(nodes).reshape(-1, 32)
+        status = np.empty(n, dtype=np.uint32)
+        new = ctypes.c_size_t()
+        st = self.ctx.L.cp2_fill_add_multi(self.h, _p(g) if ng else None, ng, _p(b) if n else None, _p(d) if n else None,
+                                           _p(rows) if rows.size else None, rows.shape[0], _p(status) if n else None, ctypes.byref(new))
+        try:
+            self.ctx._ck(st, "cp2_fill_add_multi")
         except CodexP2Error as e:
             e.fill_status, e.n_new = status, new.value
             raise

@@ -1,7 +1,7 @@
 // Fill sessions behind the C ABI (include/codex_p2.h): cp2_fill_begin, cp2_fill_add, cp2_fill_missing, cp2_fill_finish, cp2_fill_free,
 // their checkpoints: cp2_fill_save, cp2_fill_resume, the sessions that serve while they fill: cp2_fill_keep_nodes, cp2_fill_block_proofs,
 // the adds whose paths stop at a node the session holds: cp2_fill_anchors, cp2_fill_add_anchored, and the blocks taken over from the slot
-// files on the strength of those nodes: cp2_fill_adopt.
+// files on the strength of those nodes: cp2_fill_adopt, and the add of groups of blocks with their multiproofs: cp2_fill_add_multi.
 //
 // A node that takes on a slot holds the manifest's slot root and receives the slot's network blocks from peers, in any order, each with
 // its Merkle path.  cp2_blocks_verify checks such blocks and forgets the block roots it computed; a session KEEPS them.  It owns the compact
@@ -40,6 +40,11 @@
 // cp2_fill_resume and cp2_fill_keep_nodes, after which the rows the file calls known are candidates in a buffer of their own: top-down, one
 // launch per layer, k_nodes_restore_layer recomputes every known parent that has a candidate child and takes the children over where the
 // parent comes out, so a resumed session knows exactly what the device has re-derived from the stated slot roots.
+//
+// Blocks of one slot that arrive together share the upper parts of their paths.  cp2_fill_add_multi takes them in groups, each with its
+// multiproof (multiproof_plan.hpp: every node the group cannot compute, once): the candidates go down the same data path, k_multiproof_layer
+// builds each group's subtree (multiproof_check, multiproofs.cpp), and k_multiproof_commit copies what the proved groups leave -- the rows
+// whole paths would have left -- into the buffer; the rest of the call is the other adds' tail (fill_add_tail).
 #include <hip/hip_runtime.h>
 
 #include <fcntl.h>
@@ -63,6 +68,7 @@
 #include "fill_checkpoint.hpp"
 #include "fill_plan.hpp"
 #include "fill_session.hpp"
+#include "multiproof_plan.hpp"
 #include "node_ckpt_plan.hpp"
 #include "repair.hpp"
 
@@ -174,6 +180,33 @@ extern "C" int cp2_fill_begin(cp2_ctx* ctx, const cp2_config* cfg, uint64_t firs
   return CP2_ERR_INVALID;
 }
 
+// What every add does once the device has judged its n requests (verdict[i] == 0: proved, its rows stored and marked): NEW / DUPLICATE, the
+// writer and its roll-back, presence after the sync, the outputs and the trace line.  One body for cp2_fill_add, cp2_fill_add_anchored and
+// cp2_fill_add_multi.
+static int fill_add_tail(cp2_fill_session* f, const uint64_t* slot_block, const uint8_t* data, size_t n, const uint32_t* verdict, uint32_t* status,
+                         size_t* n_new, std::chrono::steady_clock::time_point t0, uint64_t siblings, size_t depth) {
+  cp2_ctx* ctx = f->ctx;
+  const cp2_config& c = f->cfg;
+  FillPlan& plan = f->plan;
+  std::string err;
+  std::vector<uint32_t> st(n);
+  plan.resolve(slot_block, verdict, n, st.data());
+  int r = CP2_OK;
+  if (f->from_file) {                                // the NEW blocks into "<file_base><slot>.dat": repair's writer and its rules
+    std::vector<uint32_t> w = FillPlan::write_mask(st.data(), n);
+    size_t written_n = 0;
+    std::vector<FileStamp> written;
+    r = repair_write(f->file_base, c.block_size, slot_block, data, n, w.data(), &written_n, &written, &err);
+    FillPlan::roll_back(slot_block, w, st.data());
+  }
+  const size_t set = plan.commit(slot_block, st.data(), n);   // present only now: an UNWRITTEN block stays missing and can be sent again
+  std::copy(st.begin(), st.end(), status);
+  if (n_new) *n_new = set;
+  if (r != CP2_OK) ctx->err = err;
+  fill_trace(n, status, set, c.block_size, plan.n_missing(), std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), siblings, depth);
+  return r;
+}
+
 // What cp2_fill_add and cp2_fill_add_anchored do with n > 0 requests they have checked.  levels == NULL: every request brings its whole
 // path, `paths` is n x depth rows and the walk ends at the stated slot root; otherwise request i brings levels[i] siblings, `paths` is
 // packed in request order and the walk ends at the node the plan names.  Everything else is one body: the data path, the chunks,
@@ -249,27 +282,12 @@ static int fill_add_checked(cp2_fill_session* f, const uint64_t* slot_block, con
                                                 f->compact.p, plan.rows, st));
     return CP2_OK;
   };
-  std::vector<uint32_t> verdict(n), st(n);
+  std::vector<uint32_t> verdict(n);
   CP2_TRY(repair_check_with(ctx, c.cell_size, c.block_size, data, n, verdict.data(), judge));
   // written or not: the nodes of a proved path are authentic and stored
   if (levels) plan.mark_proved_anchored(slot_block, levels, verdict.data(), n);
   else if (keeps) plan.mark_proved(slot_block, verdict.data(), n);
-  plan.resolve(slot_block, verdict.data(), n, st.data());
-  int r = CP2_OK;
-  if (f->from_file) {                                // the NEW blocks into "<file_base><slot>.dat": repair's writer and its rules
-    std::vector<uint32_t> w = FillPlan::write_mask(st.data(), n);
-    size_t written_n = 0;
-    std::vector<FileStamp> written;
-    r = repair_write(f->file_base, c.block_size, slot_block, data, n, w.data(), &written_n, &written, &err);
-    FillPlan::roll_back(slot_block, w, st.data());
-  }
-  const size_t set = plan.commit(slot_block, st.data(), n);   // present only now: an UNWRITTEN block stays missing and can be sent again
-  std::copy(st.begin(), st.end(), status);
-  if (n_new) *n_new = set;
-  if (r != CP2_OK) ctx->err = err;
-  fill_trace(n, status, set, c.block_size, plan.n_missing(), std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(),
-             levels ? path_off[n] : WHOLE_PATHS, depth);
-  return r;
+  return fill_add_tail(f, slot_block, data, n, verdict.data(), status, n_new, t0, levels ? path_off[n] : WHOLE_PATHS, depth);
 }
 
 extern "C" int cp2_fill_add(void* fill, const uint64_t* slot_block, const uint8_t* data, const uint8_t* paths, size_t n, uint32_t* status,
@@ -291,6 +309,83 @@ extern "C" int cp2_fill_add(void* fill, const uint64_t* slot_block, const uint8_
     return CP2_OK;
   }
   return fill_add_checked(f, slot_block, data, paths, nullptr, n, status, n_new);
+} catch (const std::bad_alloc&) {
+  return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
+} catch (...) {
+  return CP2_ERR_INVALID;
+}
+
+extern "C" int cp2_fill_add_multi(void* fill, const uint64_t* groups, size_t n_groups, const uint64_t* blocks, const uint8_t* data, const uint8_t* nodes,
+                                  size_t n_rows, uint32_t* status, size_t* n_new) try {
+  cp2_fill_session* f = session(fill);
+  if (!f) return CP2_ERR_INVALID;
+  cp2_ctx* ctx = f->ctx;
+  const cp2_config& c = f->cfg;
+  FillPlan& plan = f->plan;
+  size_t n = 0;
+  if ((n_groups && !groups) || !multiproof_count(groups, n_groups, &n) || (n && (!blocks || !data || !status)) || (n_rows && !nodes)) {
+    ctx->err = "fill multi: groups, blocks, data and status must not be NULL when there are requests, nor nodes when n_rows > 0";
+    return CP2_ERR_INVALID;
+  }
+  std::string err;
+  if (!multiproof_validate("fill multi", "slot", groups, n_groups, blocks, plan.first_slot, plan.n_local, plan.n_blocks, true, n_rows, nullptr, &err) ||
+      !plan.validate(nullptr, 0, &err)) {            // ... and, last, a finished session
+    ctx->err = err;
+    return CP2_ERR_INVALID;
+  }
+  if (n_groups == 0) {
+    if (n_new) *n_new = 0;
+    return CP2_OK;
+  }
+  // the requests as every other add names them, and the plan of the groups' subtrees
+  std::vector<uint64_t> slot_block(2 * n), counts(n_groups), nb(n_groups, plan.n_blocks), local(n_groups), want(n_groups);
+  for (size_t g = 0, at = 0; g < n_groups; ++g) {
+    counts[g] = groups[2 * g + 1];
+    local[g] = groups[2 * g] - plan.first_slot;
+    want[g] = (uint64_t)reinterpret_cast<uintptr_t>(f->slot_roots.p) + local[g] * 32;
+    for (uint64_t j = 0; j < counts[g]; ++j, ++at) {
+      slot_block[2 * at] = groups[2 * g];
+      slot_block[2 * at + 1] = blocks[at];
+    }
+  }
+  MultiproofPlan mp;
+  if (!multiproof_plan(counts.data(), nb.data(), n_groups, blocks, &mp, &err)) {
+    ctx->err = err;
+    return CP2_ERR_INVALID;
+  }
+  CP2_REFUSE_STUCK(ctx);
+  CP2_HIP(ctx, hipSetDevice(ctx->device));
+  const auto t0 = std::chrono::steady_clock::now();
+  // what a proved group leaves in the buffer: its block roots always, and in a session that keeps nodes every sent and computed row, each
+  // where the compact layout has it (FillPlan::node_row) -- the rows mark_proved marks for whole paths.  Sent rows are stored as they
+  // stand, so they go up canonical, as a whole path's siblings are stored.
+  const size_t n_commit = plan.keeps_nodes ? mp.n_work : n;
+  std::vector<uint32_t> src(n_commit);
+  std::vector<uint64_t> dst(n_commit);
+  for (size_t r = 0; r < n_commit; ++r) {
+    src[r] = (uint32_t)r;
+    dst[r] = (uint64_t)reinterpret_cast<uintptr_t>(f->compact.p) + plan.node_row(mp.row_level[r], local[mp.row_group[r]], mp.row_index[r]) * 32;
+  }
+  std::vector<uint8_t> sent(n_rows * 32);
+  for (size_t r = 0; r < n_rows; ++r) canonical_felt(nodes + r * 32, &sent[r * 32]);
+  DevBuf d_src, d_dst, d_group;                      // (go after the streams have drained: DevBuf::release)
+  const auto commit = [&](const void* d_work, const uint32_t* d_verdict, hipStream_t st) -> int {
+    CP2_TRY(d_src.scratch(ctx, n_commit * 4));
+    CP2_TRY(d_dst.scratch(ctx, n_commit * 8));
+    CP2_TRY(d_group.scratch(ctx, n_commit * 4));
+    CP2_HIP(ctx, hipMemcpyAsync(d_src.p, src.data(), n_commit * 4, hipMemcpyHostToDevice, st));
+    CP2_HIP(ctx, hipMemcpyAsync(d_dst.p, dst.data(), n_commit * 8, hipMemcpyHostToDevice, st));
+    CP2_HIP(ctx, hipMemcpyAsync(d_group.p, mp.row_group.data(), n_commit * 4, hipMemcpyHostToDevice, st));
+    CP2_HIP(ctx, cp2k::launch_multiproof_commit(d_work, mp.n_work, static_cast<const uint32_t*>(d_src.p), static_cast<const uint64_t*>(d_dst.p),
+                                                static_cast<const uint32_t*>(d_group.p), d_verdict, (uint32_t)n_groups, n_commit, st));
+    return CP2_OK;
+  };
+  std::vector<uint32_t> group_verdict(n_groups), verdict(n);
+  CP2_TRY(multiproof_check(ctx, c.cell_size, c.block_size, mp, want.data(), n_groups, data, sent.data(), commit, group_verdict.data(), nullptr));
+  for (size_t i = 0; i < n; ++i) verdict[i] = group_verdict[mp.row_group[i]];
+  // written or not: the nodes of a proved group are authentic and stored
+  if (plan.keeps_nodes) plan.mark_proved_multi(mp.row_group.data(), mp.row_level.data(), mp.row_index.data(), mp.n_work, local.data(), group_verdict.data());
+  return fill_add_tail(f, slot_block.data(), data, n, verdict.data(), status, n_new, t0, n_rows, plan.depth());
 } catch (const std::bad_alloc&) {
   return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
 } catch (...) {

@@ -256,6 +256,15 @@ struct FillPlan {
       }
     }
   }
+  // The same bits for groups proved by multiproofs (cp2_fill_add_multi): the rows k_multiproof_commit stored are the rows of the call's
+  // work table -- leaves, sent rows and computed nodes, row r being node row_index[r] of layer row_level[r] of the tree of local slot
+  // group_local[row_group[r]] (multiproof_plan.hpp) -- of every group whose verdict is 0.  For a group of blocks that is the union of
+  // what mark_proved sets for each of them: a sibling on some block's path is a leaf, a sent row or another block's ancestor.
+  void mark_proved_multi(const uint32_t* row_group, const uint32_t* row_level, const uint64_t* row_index, size_t n_work, const uint64_t* group_local,
+                         const uint32_t* group_verdict) {
+    for (size_t r = 0; r < n_work; ++r)
+      if (group_verdict[row_group[r]] == 0) set_known(node_row(row_level[r], group_local[row_group[r]], row_index[r]));
+  }
   // What a session knows when node keeping is turned on, after every upper layer was built once from layer 0 (absent rows zeroed): a
   // block root is known where the block is present, and a parent where both children are; the last node of an odd layer (and the
   // singleton) has one child.  Parents of unknown children hold values nobody reads: their bits stay clear until a proved path stores them.

@@ -26,6 +26,8 @@
 //   k_block_root_recheck_addr the same with the kept row of every block at an absolute address (fills_resume_many.cpp: many sessions)
 //   k_adopt_layer, k_adopt_resolve   the tree over block roots read back from disk, judged against the nodes a fill session keeps (fill.cpp)
 //   k_nodes_restore_layer   the kept nodes a checkpoint states, authenticated top-down from the stated slot roots (fill.cpp)
+//   k_multiproof_layer    one level of the induced subtrees of many block multiproofs, one host-made job per inner node (multiproofs.cpp)
+//   k_multiproof_commit   the rows of the proved groups copied into a fill session's compact buffer (fill.cpp)
 //
 // All global-memory field elements are 32-byte little-endian canonical integers (the ABI format).
 #include "kernels.hpp"
@@ -1304,6 +1306,66 @@ __global__ void __launch_bounds__(TPB) k_block_root_recheck_addr(const uint4* __
 }
 
 // ------------------------------------------------------------------------------------------------
+// One level of the induced subtrees of many block multiproofs (multiproofs.cpp; the tables are multiproof_plan.hpp's).  `work` is the
+// call's work table of 32-byte rows: leaf rows, sent rows, then the computed rows level after level.  Lane t < n_jobs runs job t of the
+// level: it reads rows `left` and `right` (right == MULTIPROOF_ZERO: the zero beside an odd layer's last node), compresses them under the
+// job's key -- k_compress_layer's rule, the key made by the host -- and stores the result at row out_base + t.  Every row a job names
+// lies below out_base (an earlier level's output, a leaf or a sent row), so the rows a launch reads and the rows it writes are disjoint.
+//   A job with `last` set produces its group's top node: besides storing it, the lane compares it as a field element (fe_equal: a stated
+//   root >= r counts mod r, as every path row does) with the 32 bytes at want_addr[group] and writes verdict[group] = 0 or 1.  Every group
+//   has exactly one such job in a call, so nothing is cleared beforehand and there are no atomics.
+//   Defensive (the host never produces them): a want_addr that is 0 or not 16-byte aligned is a mismatch and is not read; a job whose
+//   left or right row is at or past out_base reads and stores nothing, and with `last` set its verdict is 1.
+// LDS is the QTab only; the register bound names k_compress_layer's 5 waves per SIMD, as k_finish_layer_many's does
+// (profiles/multiproof_kernel_resources.txt).
+__global__ void __launch_bounds__(TPB, 5) k_multiproof_layer(uint4* __restrict__ work, const MultiproofJob* __restrict__ jobs, size_t n_jobs,
+                                                            uint64_t out_base, const uint64_t* __restrict__ want_addr,
+                                                            uint32_t* __restrict__ verdict) {
+  __shared__ fr::QTab qtab;
+  fr::qtab_fill(qtab, threadIdx.x, TPB);
+  __syncthreads();
+  const size_t t = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (t >= n_jobs) return;
+  const MultiproofJob j = jobs[t];
+  const bool pair = j.right != MULTIPROOF_ZERO, last = (j.key_last >> 8) & 1u;
+  if (j.left >= out_base || (pair && j.right >= out_base)) {   // (never: the host numbers the rows level by level)
+    if (last) verdict[j.group] = 1u;
+    return;
+  }
+  State st;
+  st.x = load_fe_canonical(work + 2 * (size_t)j.left);
+  st.y = pair ? load_fe_canonical(work + 2 * (size_t)j.right) : fr::fe_zero();
+  st.z = key_fe(j.key_last & 3u);
+  p2::permute(st, qtab);
+  store_fe_canonical(work + 2 * (out_base + t), st.x);
+  if (!last) return;
+  const uint64_t a = want_addr[j.group];
+  uint32_t v = 1u;
+  if (a != 0 && (a & 15) == 0) v = fe_equal(st.x, load_fe_canonical(reinterpret_cast<const uint4*>(a))) ? 0u : 1u;
+  verdict[j.group] = v;
+}
+
+// ------------------------------------------------------------------------------------------------
+// What a fill session keeps of proved multiproofs (fill.cpp, cp2_fill_add_multi): lane i copies row src_row[i] of the work table to the
+// absolute address dst_addr[i] -- a row of the session's compact buffer -- when its group proved (verdict[group_of[i]] == 0), and does
+// nothing otherwise: a group that fails leaves nothing behind.  A row as it stands, two 16-byte loads and two 16-byte stores (the work
+// table holds canonical rows: k_multiproof_layer's stores, the block roots of the hashing, and sent rows, which the host made canonical).
+// Two lanes that name one destination carry identical bytes, k_block_path_commit's argument: every row of a proved group is the authentic
+// node of its place in the tree, and a place has one node.  Defensive (the host never produces them): a source row at or past n_work, a
+// group at or past n_groups and a destination that is 0 or not 16-byte aligned copy nothing.  No permutation, no LDS, no atomics.
+__global__ void __launch_bounds__(TPB) k_multiproof_commit(const uint4* __restrict__ work, uint64_t n_work, const uint32_t* __restrict__ src_row,
+                                                             const uint64_t* __restrict__ dst_addr, const uint32_t* __restrict__ group_of,
+                                                             const uint32_t* __restrict__ verdict, uint32_t n_groups, size_t n) {
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t g = group_of[i], r = src_row[i];
+  const uint64_t a = dst_addr[i];
+  if (g >= n_groups || r >= n_work || a == 0 || (a & 15) != 0) return;
+  if (verdict[g] != 0) return;
+  copy_row(reinterpret_cast<uint4*>(a), work + 2 * (size_t)r);
+}
+
+// ------------------------------------------------------------------------------------------------
 // The children of one node of a fill session's tree, ready for the keyed compression: rows rl and rl + 1 of the compact layout, each from
 // `tree` where the session knows it (known_l / known_r: the child's KNOWN bit, 0 or 1) and from `cand` otherwise.  The base address is
 // picked with an integer mask: the two bases differ in the bits the mask lets through.  Without a pair (the last node of an odd layer,
@@ -1573,6 +1635,48 @@ hipError_t launch_finish_layers_many(const FillManySession* sessions, uint64_t n
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+hipError_t launch_multiproof_layers(void* work, uint64_t n_work, const MultiproofJob* jobs, const uint64_t* level_off, const uint64_t* level_base,
+                                    size_t n_levels, const uint64_t* want_addr, uint32_t* verdict, hipStream_t st) {
+  if (n_levels == 0) return hipSuccess;
+  if (!level_off || !level_base || n_levels > 63) return hipErrorInvalidValue;
+  uint64_t top = 0;                                           // the rows below every level's output: no level writes what it may read
+  for (size_t k = 0; k < n_levels; ++k) {
+    if (level_off[k + 1] < level_off[k]) return hipErrorInvalidValue;
+    const uint64_t cnt = level_off[k + 1] - level_off[k];
+    if (cnt == 0) continue;
+    if (!fits_one_grid(cnt) || level_base[k] < top || level_base[k] >= MULTIPROOF_ZERO || cnt >= MULTIPROOF_ZERO - level_base[k])
+      return hipErrorInvalidValue;
+    top = level_base[k] + cnt;
+  }
+  if (top == 0) return hipSuccess;
+  if (!work || !jobs || !want_addr || !verdict || top > n_work) return hipErrorInvalidValue;
+  if ((reinterpret_cast<uintptr_t>(work) & 15) || (reinterpret_cast<uintptr_t>(jobs) & 15) || (reinterpret_cast<uintptr_t>(want_addr) & 7) ||
+      (reinterpret_cast<uintptr_t>(verdict) & 3))
+    return hipErrorInvalidValue;
+  for (size_t k = 0; k < n_levels; ++k) {                    // in order on st: level k + 1 reads what level k wrote
+    const uint64_t cnt = level_off[k + 1] - level_off[k];
+    if (cnt == 0) continue;
+    CP2K_LAUNCH(k_multiproof_layer, dim3(grid_for(cnt)), dim3(TPB), 0, st, (uint4*)work, jobs + level_off[k], (size_t)cnt, level_base[k], want_addr,
+                verdict);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+hipError_t launch_multiproof_commit(const void* work, uint64_t n_work, const uint32_t* src_row, const uint64_t* dst_addr, const uint32_t* group_of,
+                                    const uint32_t* verdict, uint32_t n_groups, size_t n, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  if (!work || !src_row || !dst_addr || !group_of || !verdict) return hipErrorInvalidValue;
+  if ((reinterpret_cast<uintptr_t>(work) & 15) || (reinterpret_cast<uintptr_t>(src_row) & 3) || (reinterpret_cast<uintptr_t>(dst_addr) & 7) ||
+      (reinterpret_cast<uintptr_t>(group_of) & 3) || (reinterpret_cast<uintptr_t>(verdict) & 3))
+    return hipErrorInvalidValue;
+  return for_slices(n, [&](size_t i0, size_t m) {
+    hipLaunchKernelGGL(k_multiproof_commit, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)work, n_work, src_row + i0, dst_addr + i0, group_of + i0,
+                       verdict, n_groups, m);
+  });
 }
 
 hipError_t launch_compress_pairs(const void* xy, uint32_t key, void* out, size_t n, hipStream_t st) {

@@ -185,6 +185,36 @@ hipError_t launch_finish_layers_many(const FillManySession* sessions, uint64_t n
                                      const uint32_t* sess_of, const uint64_t* level_off, const uint64_t* level_cnt, const uint64_t* level_work,
                                      size_t n_levels, uint32_t* verdict, hipStream_t st);
 
+// Block multiproofs (multiproofs.cpp, k_multiproof_layer): the induced subtrees of many groups of blocks, level by level, over one work
+// table of 32-byte rows (`work`, n_work rows, 16-byte aligned): leaf rows, sent rows, then the computed rows (multiproof_plan.hpp).  One
+// job per computed row, 16 bytes, the layout of cp2i::MultiproofJob.
+struct MultiproofJob {
+  uint32_t left;       // a row of the work table
+  uint32_t right;      // a row of the work table, or MULTIPROOF_ZERO: the zero beside an odd layer's last node
+  uint32_t key_last;   // the compression's key 0..3 | last << 8
+  uint32_t group;
+};
+constexpr uint32_t MULTIPROOF_ZERO = 0xFFFFFFFFu;
+// One launch per level in order on st, no host wait between them.  Device: jobs (16-byte aligned; level k's are [level_off[k],
+// level_off[k + 1])), want_addr (per group the absolute device address of its stated root, 32 bytes, 16-byte aligned; 0 or misaligned: a
+// mismatch, not read), verdict (one word per group).  Host: level_off (n_levels + 1 entries), level_base (n_levels).  Job t of level k
+// stores compress(left, right, key) at row level_base[k] + t; a job with `last` set also writes verdict[group] = 0 when its row equals the
+// stated root as a field element, else 1, the row stored as computed either way.  Every group has one such job, so each verdict word
+// has one writer and nothing is cleared beforehand.  A job that names a row at or past its level's base reads and stores nothing (with
+// `last`: verdict 1).  Nothing but the computed rows and the verdicts is written.  hipErrorInvalidValue, nothing launched: a NULL or
+// misaligned table with work to do, a level whose output starts below the end of an earlier level's or ends past n_work or reaches row 2^32 - 1,
+// level_off that descends, more than 63 levels.  No jobs at any level: success, no launch.
+hipError_t launch_multiproof_layers(void* work, uint64_t n_work, const MultiproofJob* jobs, const uint64_t* level_off, const uint64_t* level_base,
+                                    size_t n_levels, const uint64_t* want_addr, uint32_t* verdict, hipStream_t st);
+
+// What a fill session keeps of them (fill.cpp, k_multiproof_commit): lane i < n copies the 32-byte row src_row[i] of `work` to the absolute
+// device address dst_addr[i] (16-byte aligned) when verdict[group_of[i]] == 0, and does nothing otherwise.  Two lanes may name one
+// destination: they carry identical bytes (every row of a proved group is the authentic node of its place).  A source row at or past
+// n_work, a group at or past n_groups and a destination that is 0 or misaligned copy nothing.  hipErrorInvalidValue, nothing launched: a
+// NULL or misaligned table with n > 0.  n == 0: success, no launch.
+hipError_t launch_multiproof_commit(const void* work, uint64_t n_work, const uint32_t* src_row, const uint64_t* dst_addr, const uint32_t* group_of,
+                                    const uint32_t* verdict, uint32_t n_groups, size_t n, hipStream_t st);
+
 // Resuming a fill session (fill.cpp, k_block_root_recheck): verdict[i] = 0 when the 32-byte row i of `fresh` (the root a re-read block
 // hashed to) equals row dest[i] of `layer0` (n_rows rows), else 1 -- and then that row of layer0 is overwritten with zeros.  dest[i] >=
 // n_rows: verdict 1, nothing read or written.  The rows of one call are distinct.

@@ -57,6 +57,16 @@ int gather_block_proofs(cp2_ctx* ctx, const void* nodes, size_t n_rows, const st
 // The gather under it, by absolute device address (read_blocks.cpp: the rows of many datasets in one launch): out (host, addr.size() x 32
 // bytes) row r = the 32 bytes at addr[r], zeros for 0.  One upload of the table, one k_gather_addr, one download; the stream is drained.
 int gather_rows_by_addr(cp2_ctx* ctx, const std::vector<uint64_t>& addr, uint8_t* out);
+// Groups of candidates with their multiproofs judged against stated roots (multiproofs.cpp; cp2_blocks_verify_multi and
+// cp2_fill_add_multi): `plan` is the work table and job tables of the call's validated groups (multiproof_plan.hpp), want[g] the absolute
+// device address of group g's stated root (32 bytes, 16-byte aligned), data the plan.n candidates in request order, nodes the plan.n_rows
+// sent rows.  repair_check_with's data path, then k_multiproof_layer level by level, then `commit` (may be empty) with the work table and
+// the group verdicts in device memory, queued on the same stream; then group_verdict (host, n_groups: 0 proved, anything else not) and
+// block_roots (host, plan.n x 32 bytes, may be NULL: what each candidate hashed to) are downloaded and the stream is drained.
+struct MultiproofPlan;
+using MultiproofCommit = std::function<int(const void* d_work, const uint32_t* d_verdict, hipStream_t st)>;
+int multiproof_check(cp2_ctx* ctx, size_t cell_size, size_t block_size, const MultiproofPlan& plan, const uint64_t* want, size_t n_groups,
+                     const uint8_t* data, const uint8_t* nodes, const MultiproofCommit& commit, uint32_t* group_verdict, uint8_t* block_roots);
 // the requests whose status is CP2_REPAIR_MATCH written into "<base><slot>.dat", grouped by file in ascending offset order, each file synced
 // once.  The first file that cannot be opened, written or synced: CP2_ERR_IO, *err "cannot write <file>: <reason>", its matched requests and
 // those of every later file CP2_REPAIR_UNWRITTEN.  *n_written counts the blocks of the files written and synced, `written` their stamps.

@@ -102,6 +102,18 @@ proc cp2_blocks_verify(ctx: Cp2Ctx, cellSize, blockSize, nCells: csize_t, slotRo
                        data, paths: ptr byte, n: csize_t, status: ptr uint32, blockRoots: ptr byte): cint {.importc.}
 proc cp2_dataset_repair_blocks_proved(ds: Cp2Dataset, slotBlock: ptr uint64, data, paths: ptr byte, n: csize_t, flags: cint,
                                       cachePath: cstring, status: ptr uint32, nWritten: ptr csize_t): cint {.importc.}
+# block multiproofs: groups = nGroups x (slot or index into slotRoots, count), blocks = the counts' sum of block indices, strictly ascending
+# inside a group, nodes = the groups' rows packed (cp2_block_multiproof_layout names them: rows x (level, index)); status = nGroups x
+# CP2_BLOCK_*, one verdict per GROUP
+proc cp2_block_multiproof_rows(cellSize, blockSize, nCells: csize_t, blocks: ptr uint64, k: csize_t): csize_t {.importc.}
+proc cp2_block_multiproof_layout(cellSize, blockSize, nCells: csize_t, blocks: ptr uint64, k: csize_t, levelIndex: ptr uint64): cint {.importc.}
+proc cp2_dataset_block_multiproofs(ds: Cp2Dataset, groups: ptr uint64, nGroups: csize_t, blocks: ptr uint64, blockRoots, nodes: ptr byte,
+                                   cap: csize_t, nRows: ptr csize_t): cint {.importc.}
+proc cp2_blocks_verify_multi(ctx: Cp2Ctx, cellSize, blockSize, nCells: csize_t, slotRoots: ptr byte, nRoots: csize_t, groups: ptr uint64,
+                             nGroups: csize_t, blocks: ptr uint64, data, nodes: ptr byte, nRows: csize_t, status: ptr uint32,
+                             blockRoots: ptr byte): cint {.importc.}
+proc cp2_fill_add_multi(f: pointer, groups: ptr uint64, nGroups: csize_t, blocks: ptr uint64, data, nodes: ptr byte, nRows: csize_t,
+                        status: ptr uint32, nNew: ptr csize_t): cint {.importc.}
 # repair across datasets in one pass: req = n x (index into ds, slot, block), paths packed with pathOff (n + 1 rows, both nil: every path
 # empty) as cp2_datasets_read_blocks returns them -- an empty path judges against the kept block root, a whole one walks to the slot root --,
 # cachePaths = nDs entries (nil, or entries nil), status = n x CP2_REPAIR_*; every slot file is attempted on its own

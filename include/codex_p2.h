@@ -51,7 +51,9 @@ extern "C" {
  *                cp2_datasets_build_many (many datasets built in one pass), cp2_datasets_set_roots_many (their dataset trees in one pass),
  *                cp2_fills_add_many (proved blocks added to many fill sessions in one pass), cp2_fills_finish_many (many fill
  *                sessions finished in one pass), cp2_fills_resume_many (many fill sessions resumed in one pass),
- *                cp2_datasets_repair_blocks_many (many datasets repaired in one pass).
+ *                cp2_datasets_repair_blocks_many (many datasets repaired in one pass), cp2_block_multiproof_rows,
+ *                cp2_block_multiproof_layout, cp2_dataset_block_multiproofs, cp2_blocks_verify_multi and cp2_fill_add_multi
+ *                (block multiproofs).
  *                MINOR stays 2 until the release that carries them: the bump to 1.3 goes in its own commit with that release.         */
 #define CP2_ABI_VERSION_MAJOR 1
 #define CP2_ABI_VERSION_MINOR 2
@@ -1195,6 +1197,91 @@ int cp2_fills_resume_many(cp2_ctx* ctx, const void* const* cfgs /* n_fills: cons
                           const char* const* paths /* n_fills checkpoint files, CP2FILL1 */, size_t n_fills,
                           int flags /* 0 or CP2_RESUME_TRUST_FILES */, void** out /* n_fills: cp2_fill* each */,
                           uint64_t* n_dropped /* n_fills, may be NULL */);
+
+/* ---- block multiproofs: many blocks of a slot served, checked and filled with shared Merkle nodes -------------------------------------
+ * Every path-carrying call above takes one whole path per block.  Two blocks of one slot share every node above the point where their
+ * paths meet: with whole paths that node is sent twice, uploaded twice and hashed twice.  A multiproof of a set B of blocks of one slot
+ * sends only the nodes that cannot be computed from B and from each other, each once, and checking hashes each inner node of the
+ * induced subtree once: a whole 128-block slot costs 127 compressions and no sent row, where whole paths cost 128 x 7 of each.
+ *   Format     geometry as for block proofs: nBlocks = nCells / (blockSize / cellSize), depth = cp2_block_proof_depth, layer sizes m_0 =
+ *              nBlocks, m_{l+1} = (m_l + 1) >> 1; a parent is compress(left, right, key), key = 1 on level 0 and 0 above, and an odd
+ *              layer's last node (and the singleton) is compress(last, 0, key + 2).  For a non-empty set B of DISTINCT blocks let K_0 = B
+ *              and K_{l+1} = { i >> 1 : i in K_l }.  The multiproof of B is the list of rows (l, i ^ 1) over every level l < depth and
+ *              every i in K_l for which i ^ 1 is not in K_l and i ^ 1 < m_l, ordered by level ascending, then by index ascending.  Each
+ *              row is a 32-byte little-endian field element, a value >= r taken mod r.  An out-of-range sibling is NOT sent (the
+ *              single path carries a zero row there).  Checking computes every node of K_{l+1} from K_l and the sent rows, level by
+ *              level; the proof holds when the one node of K_depth equals the stated slot root.
+ *   Groups     requests come in groups: groups is n_groups x 2 uint64 (slot or root index, count), blocks holds the n = sum of the
+ *              counts block indices, group after group, STRICTLY ASCENDING inside a group, and nodes holds the groups' rows packed in
+ *              group order.  The same slot may appear in several groups: several proofs, perhaps from several peers, each with its
+ *              own verdict.
+ *   Verdict    belongs to the GROUP: one wrong block or one wrong row fails all of B, and the proof cannot say which one.  A caller who
+ *              must know falls back to whole paths (cp2_blocks_verify) or anchors for that group.
+ *
+ * cp2_block_multiproof_rows, cp2_block_multiproof_layout: host only.  The number of rows of the multiproof of blocks[0, k), and the
+ * (level, index) of every row in order (level_index: rows x 2 uint64).  SIZE_MAX / CP2_ERR_INVALID for a geometry the tree builders
+ * refuse, k == 0, a block >= nBlocks or a list that is not strictly ascending.
+ *
+ * cp2_dataset_block_multiproofs serves multiproofs from what a dataset keeps: every node, or the compact layers.
+ *   Requests   groups (dataset slot inside the local range, count) and blocks as above.
+ *   Result     *n_rows = the rows of all groups, always the full count; nodes (cap x 32 bytes) receives them packed in group order,
+ *              block_roots (n x 32 bytes, may be NULL) the block root of every request.  One upload of the row list, one gather on the
+ *              device (cp2_dataset_block_proofs' own), one download.  With cap < *n_rows: CP2_ERR_INVALID, the needed count in
+ *              cp2_last_error, and neither nodes nor block_roots is written.
+ *   Refused    CP2_ERR_INVALID, the group index or the request index (where there is one) in cp2_last_error: as
+ *              cp2_dataset_block_proofs, the roots-only dataset among them, and the request rules below.
+ *   Read-only  nothing of the dataset changes.
+ *
+ * cp2_blocks_verify_multi checks n candidate blocks in groups, each group with its multiproof, against slot roots the caller states.
+ *   Requests   slot_roots (n_roots x 32 bytes); groups (index into slot_roots, count); blocks; data (n x blockSize bytes, in the order
+ *              of blocks); nodes (n_rows x 32 bytes).  The data path is cp2_blocks_verify's, unchanged; the sent rows, the stated roots
+ *              and the job tables go up once.  Each chunk's fresh block roots are copied into a work table on the device; after the
+ *              pass k_multiproof_layer runs once per level (one lane and one compression per inner node of the induced subtrees, all
+ *              groups of the call in one launch), then one download of n_groups verdicts.
+ *   Result     status[g] = CP2_BLOCK_MATCH (the group's candidates and rows reconstruct slot_roots[root]) or CP2_BLOCK_MISMATCH, one
+ *              per GROUP; block_roots (n x 32 bytes, may be NULL) = what each candidate hashed to.  A wrong block or a wrong proof is
+ *              not an error: CP2_OK.
+ *   Trace      CP2_TRACE prints one line: groups, requests, matched groups, rows received against n x depth, compressions run against
+ *              n x depth, bytes, seconds, GB/s.
+ *
+ * cp2_fill_add_multi adds groups of proved blocks to a fill session: the same pass against the session's own stated roots, then
+ * k_multiproof_commit stores what the proved groups leave.
+ *   Requests   groups (dataset slot inside the session's range, count), blocks, data and nodes as for cp2_blocks_verify_multi.
+ *   Meaning    by the calls that exist.  When every group proves, the call leaves the same session state -- the compact buffer row for
+ *              row, the known bitmap, presence and cp2_fill_missing --, the same slot files and the same per-request status as ONE
+ *              cp2_fill_add of the same requests, in the same order, with each block's whole path from the true tree.  A group that
+ *              fails leaves nothing in the buffer, and every one of its requests gets CP2_FILL_MISMATCH.
+ *   Kept       the block roots go to layer 0 always; in a session that keeps nodes (cp2_fill_keep_nodes) the sent rows (stored
+ *              canonical) and the computed rows go where the compact layout has them: the rows whole paths would leave and mark known,
+ *              the union of the blocks' siblings and ancestors.
+ *   Result     status (n x CP2_FILL_*, one per REQUEST) and n_new: NEW / DUPLICATE over the groups' verdicts expanded per request (a
+ *              block in two proved groups of one call: the lower index is NEW, the other DUPLICATE), the writer, its roll-back,
+ *              CP2_FILL_UNWRITTEN, presence after the sync and the CP2_TRACE line are cp2_fill_add's, one body.
+ *
+ *   Refused    all or nothing, before any device or file work, CP2_ERR_INVALID with outputs untouched; the group index or the request index,
+ *              where there is one, goes into cp2_last_error.  The checks run in this order: (1) a NULL handle or context; (2) a
+ *              geometry the tree builders refuse; (3) NULL arrays with n > 0 (block_roots excepted; nodes may be NULL only when n_rows
+ *              == 0); (4) a group with count 0; (5) a slot outside the local range, or a root index >= n_roots; (6) a block >= nBlocks;
+ *              (7) blocks not strictly ascending inside a group; (8) n_rows different from the sum of the groups' layouts (both
+ *              numbers in the message); (9) for the fill, a finished session.  A call whose work table (requests, sent rows and computed nodes) would reach 2^32 - 1 rows is
+ *              refused too.  n_groups == 0: CP2_OK.  A context whose stream will not drain is refused (CP2_ERR_HIP).
+ * Out of scope: cp2_multi_*; a many-session form; multiproofs that stop at anchors; serving multiproofs from a fill session; repair with
+ * multiproofs; checkpoint formats. */
+size_t cp2_block_multiproof_rows(size_t cell_size, size_t block_size, size_t n_cells, const uint64_t* blocks /* k, strictly ascending */,
+                                 size_t k);
+int cp2_block_multiproof_layout(size_t cell_size, size_t block_size, size_t n_cells, const uint64_t* blocks /* k, strictly ascending */,
+                                size_t k, uint64_t* level_index /* rows x 2 */);
+int cp2_dataset_block_multiproofs(cp2_dataset* ds, const uint64_t* groups /* n_groups x 2: dataset slot, count */, size_t n_groups,
+                                  const uint64_t* blocks /* n */, uint8_t* block_roots /* n x 32, may be NULL */,
+                                  uint8_t* nodes /* cap x 32 */, size_t cap, size_t* n_rows);
+int cp2_blocks_verify_multi(cp2_ctx* ctx, size_t cell_size, size_t block_size, size_t n_cells, const uint8_t* slot_roots /* n_roots x 32 */,
+                            size_t n_roots, const uint64_t* groups /* n_groups x 2: index into slot_roots, count */, size_t n_groups,
+                            const uint64_t* blocks /* n */, const uint8_t* data /* n x block_size */,
+                            const uint8_t* nodes /* n_rows x 32 */, size_t n_rows, uint32_t* status /* n_groups */,
+                            uint8_t* block_roots /* n x 32, may be NULL */);
+int cp2_fill_add_multi(void* f /* cp2_fill* */, const uint64_t* groups /* n_groups x 2: dataset slot, count */, size_t n_groups,
+                       const uint64_t* blocks /* n */, const uint8_t* data /* n x block_size */, const uint8_t* nodes /* n_rows x 32 */,
+                       size_t n_rows, uint32_t* status /* n: CP2_FILL_* */, size_t* n_new);
 
 
 /* ---- e: every GPU of the node behind one handle ------------------------------------------------------ */
