@@ -229,6 +229,10 @@ def load_library():
         "cp2_dataset_block_multiproofs": (i32, [vp, vp, sz, vp, vp, vp, sz, vp]),
         "cp2_blocks_verify_multi": (i32, [vp, sz, sz, sz, vp, sz, vp, sz, vp, vp, vp, sz, vp, vp]),
         "cp2_fill_add_multi": (i32, [vp, vp, sz, vp, vp, vp, sz, vp, ctypes.POINTER(sz)]),
+        "cp2_fill_multiproof_want": (i32, [vp, vp, sz, vp, vp, sz, ctypes.POINTER(sz), vp]),
+        "cp2_dataset_block_tree_rows": (i32, [vp, vp, sz, vp]),
+        "cp2_fill_block_tree_rows": (i32, [vp, vp, sz, vp, vp]),
+        "cp2_fill_add_multi_anchored": (i32, [vp, vp, sz, vp, vp, vp, sz, vp, ctypes.POINTER(sz)]),
         "cp2_dataset_repair_blocks_proved": (i32, [vp, vp, vp, vp, sz, i32, cp, vp, ctypes.POINTER(sz)]),
         "cp2_datasets_read_blocks": (i32, [vp, vp, sz, vp, sz, i32, vp, vp, vp, vp, vp, ctypes.POINTER(sz)]),
         "cp2_dataset_read_blocks": (i32, [vp, vp, sz, i32, vp, vp, vp, vp, ctypes.POINTER(sz)]),
@@ -1027,6 +1031,15 @@ class Dataset:
         self.ctx._ck(st, "cp2_dataset_block_multiproofs")
         return roots, nodes
 
+    def block_tree_rows(self, places):
+        """cp2_dataset_block_tree_rows: uint8[n, 32], the tree rows at (dataset slot, level, index) places -- level depth is the slot root --
+        from what the dataset keeps: the rows a fill session's multiproof_want names."""
+        pl = np.ascontiguousarray(np.asarray(places, dtype=np.uint64).reshape(-1, 3))
+        n = pl.shape[0]
+        rows = np.empty((n, 32), dtype=np.uint8)
+        self.ctx._ck(self.ctx.L.cp2_dataset_block_tree_rows(self.h, _p(pl) if n else None, n, _p(rows) if n else None), "cp2_dataset_block_tree_rows")
+        return rows
+
     def read_blocks(self, slot_block, check_only=False, want_data=True, want_paths=True, data=None):
         """cp2_dataset_read_blocks: Context.read_blocks over this dataset alone, (slot, block) pairs.  Returns (data: uint8[n, blockSize] or
         None, block_roots: uint8[n, 32], paths: uint8[n, depth, 32] or None, status: uint32[n] of READ_*, n_ok)."""
@@ -1070,6 +1083,7 @@ class Dataset:
 FILL_NEW, FILL_MISMATCH, FILL_DUPLICATE, FILL_UNWRITTEN = 0, 1, 2, 3   # CP2_FILL_* (include/codex_p2.h): the per-request results of cp2_fill_add
 RESUME_TRUST_FILES = 1                                                 # CP2_RESUME_TRUST_FILES: cp2_fill_resume reads no slot byte
 FILL_PROOF_OK, FILL_PROOF_ABSENT, FILL_PROOF_PARTIAL = 0, 1, 2         # CP2_FILL_PROOF_*: the per-request results of cp2_fill_block_proofs
+FILL_ROW_KNOWN, FILL_ROW_UNKNOWN = 0, 1                                # CP2_FILL_ROW_*: the per-place results of cp2_fill_block_tree_rows
 ADOPT_NO_READ = 1                                                      # CP2_ADOPT_NO_READ: cp2_fill_adopt judges what earlier calls read
 
 
@@ -1180,6 +1194,53 @@ class FillSession:
                                            _p(rows) if rows.size else None, rows.shape[0], _p(status) if n else None, ctypes.byref(new))
         try:
             self.ctx._ck(st, "cp2_fill_add_multi")
+        except CodexP2Error as e:
+            e.fill_status, e.n_new = status, new.value
+            raise
+        return status, new.value
+
+    def multiproof_want(self, groups, blocks):
+        """cp2_fill_multiproof_want: (level_index: uint64[n_rows, 2], group_rows: uint64[n_groups]), the rows groups of blocks still need
+        from a peer, laid out against what the session knows now: (level, index) pairs packed in group order; host only."""
+        g, b = _groups(groups, blocks)
+        n, ng = b.shape[0], g.shape[0]
+        per = np.zeros(ng, dtype=np.uint64)
+        n_rows = ctypes.c_size_t(0)
+        L = self.ctx.L
+        self.ctx._ck(L.cp2_fill_multiproof_want(self.h, _p(g) if ng else None, ng, _p(b) if n else None, None, 0, ctypes.byref(n_rows),
+                                                _p(per) if ng else None), "cp2_fill_multiproof_want")
+        li = np.zeros((n_rows.value, 2), dtype=np.uint64)
+        if n_rows.value:
+            self.ctx._ck(L.cp2_fill_multiproof_want(self.h, _p(g), ng, _p(b), _p(li), li.shape[0], ctypes.byref(n_rows), None), "cp2_fill_multiproof_want")
+        return li, per
+
+    def block_tree_rows(self, places, statuses_only=False):
+        """cp2_fill_block_tree_rows: (status: uint32[n] of FILL_ROW_*, rows: uint8[n, 32]) of (dataset slot, level, index) places from the
+        session's own buffer; an unknown row is zeros.  statuses_only: just the statuses, from the host bitmap, no device work."""
+        pl = np.ascontiguousarray(np.asarray(places, dtype=np.uint64).reshape(-1, 3))
+        n = pl.shape[0]
+        status = np.empty(n, dtype=np.uint32)
+        rows = None if statuses_only else np.empty((n, 32), dtype=np.uint8)
+        self.ctx._ck(self.ctx.L.cp2_fill_block_tree_rows(self.h, _p(pl) if n else None, n, _p(status) if n else None,
+                                                         _p(rows) if n and not statuses_only else None), "cp2_fill_block_tree_rows")
+        return status if statuses_only else (status, rows)
+
+    def add_multi_anchored(self, groups, blocks, data, nodes):
+        """cp2_fill_add_multi_anchored: add_multi for a session that keeps nodes, with nodes = the rows of the groups' want lists
+        (multiproof_want) packed in group order: what the session holds is neither sent nor hashed again.  Returns (status: uint32[n] of
+        FILL_*, one per request, n_new)."""
+        g, b = _groups(groups, blocks)
+        n, ng = b.shape[0], g.shape[0]
+        d = np.ascontiguousarray(data) if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
+        if d.nbytes != n * self.cfg.block_size:
+            raise ValueError("fill multi anchored: %d request(s) need %d bytes of candidates, got %d" % (n, n * self.cfg.block_size, d.nbytes))
+        rows = _u8(nodes).reshape(-1, 32) if nodes is not None else np.empty((0, 32), dtype=np.uint8)   # (nothing wanted: nothing sent)
+        status = np.empty(n, dtype=np.uint32)
+        new = ctypes.c_size_t()
+        st = self.ctx.L.cp2_fill_add_multi_anchored(self.h, _p(g) if ng else None, ng, _p(b) if n else None, _p(d) if n else None,
+                                                    _p(rows) if rows.size else None, rows.shape[0], _p(status) if n else None, ctypes.byref(new))
+        try:
+            self.ctx._ck(st, "cp2_fill_add_multi_anchored")
         except CodexP2Error as e:
             e.fill_status, e.n_new = status, new.value
             raise

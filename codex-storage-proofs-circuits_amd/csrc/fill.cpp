@@ -45,6 +45,12 @@
 // multiproof (multiproof_plan.hpp: every node the group cannot compute, once): the candidates go down the same data path, k_multiproof_layer
 // builds each group's subtree (multiproof_check, multiproofs.cpp), and k_multiproof_commit copies what the proved groups leave -- the rows
 // whole paths would have left -- into the buffer; the rest of the call is the other adds' tail (fill_add_tail).
+//
+// Multiproofs and kept nodes together: cp2_fill_multiproof_want lays a group out against what the session knows
+// (multiproof_anchor_plan.hpp: only the rows it can neither compute nor already holds), cp2_fill_block_tree_rows serves such rows by their
+// place from a session that is still filling, and cp2_fill_add_multi_anchored is cp2_fill_add_multi over that layout: the kept inputs are
+// gathered from the buffer into the work table, the layers run as they are, and every group's tops are compared with the rows the session
+// keeps (k_multiproof_tops, k_multiproof_fold) where cp2_fill_add_multi compares one top with the stated root.
 #include <hip/hip_runtime.h>
 
 #include <fcntl.h>
@@ -68,6 +74,7 @@
 #include "fill_checkpoint.hpp"
 #include "fill_plan.hpp"
 #include "fill_session.hpp"
+#include "multiproof_anchor_plan.hpp"
 #include "multiproof_plan.hpp"
 #include "node_ckpt_plan.hpp"
 #include "repair.hpp"
@@ -385,6 +392,203 @@ extern "C" int cp2_fill_add_multi(void* fill, const uint64_t* groups, size_t n_g
   for (size_t i = 0; i < n; ++i) verdict[i] = group_verdict[mp.row_group[i]];
   // written or not: the nodes of a proved group are authentic and stored
   if (plan.keeps_nodes) plan.mark_proved_multi(mp.row_group.data(), mp.row_level.data(), mp.row_index.data(), mp.n_work, local.data(), group_verdict.data());
+  return fill_add_tail(f, slot_block.data(), data, n, verdict.data(), status, n_new, t0, n_rows, plan.depth());
+} catch (const std::bad_alloc&) {
+  return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
+} catch (...) {
+  return CP2_ERR_INVALID;
+}
+
+// ---- multiproofs against what the session knows -------------------------------------------------------------------------------------------
+namespace {
+
+// known(group, level, index) of a call's groups against the session as it stands; a session that keeps no nodes knows its roots only
+auto session_knows(const FillPlan& plan, const uint64_t* groups) {
+  return [&plan, groups](size_t g, size_t l, uint64_t i) {
+    return plan.keeps_nodes && plan.is_known(plan.node_row(l, groups[2 * g] - plan.first_slot, i));
+  };
+}
+
+}  // namespace
+
+extern "C" int cp2_fill_multiproof_want(const void* fill, const uint64_t* groups, size_t n_groups, const uint64_t* blocks, uint64_t* level_index,
+                                        size_t cap, size_t* n_rows, uint64_t* group_rows) try {
+  const cp2_fill_session* f = session(fill);
+  if (!f) return CP2_ERR_INVALID;
+  cp2_ctx* ctx = f->ctx;
+  const FillPlan& plan = f->plan;
+  size_t n = 0;
+  if (!n_rows || (n_groups && !groups) || !multiproof_count(groups, n_groups, &n) || (n && !blocks)) {
+    ctx->err = "fill multiproof want: groups, blocks and n_rows must not be NULL when there are requests";
+    return CP2_ERR_INVALID;
+  }
+  std::string err;
+  std::vector<uint64_t> li, per(n_groups);
+  uint64_t rows = 0;
+  if (!multiproof_anchor_validate("fill multiproof want", groups, n_groups, blocks, plan.first_slot, plan.n_local, plan.n_blocks,
+                                  session_knows(plan, groups), false, 0, &rows, per.data(), &li, &err) ||
+      !plan.validate(nullptr, 0, &err)) {            // ... and, last, a finished session
+    ctx->err = err;
+    return CP2_ERR_INVALID;
+  }
+  *n_rows = (size_t)rows;
+  if (group_rows) std::copy(per.begin(), per.end(), group_rows);
+  if (rows && level_index && cap >= rows) std::memcpy(level_index, li.data(), li.size() * 8);
+  return CP2_OK;
+} catch (const std::bad_alloc&) {
+  return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
+} catch (...) {
+  return CP2_ERR_INVALID;
+}
+
+extern "C" int cp2_fill_block_tree_rows(void* fill, const uint64_t* places, size_t n, uint32_t* status, uint8_t* rows) try {
+  cp2_fill_session* f = session(fill);
+  if (!f) return CP2_ERR_INVALID;
+  cp2_ctx* ctx = f->ctx;
+  const FillPlan& plan = f->plan;
+  if (n && (!places || !status)) {
+    ctx->err = "fill tree rows: places and status must not be NULL when n > 0";
+    return CP2_ERR_INVALID;
+  }
+  if (plan.finished) {
+    ctx->err = "fill tree rows: the session is finished: its rows come from the dataset (cp2_dataset_block_tree_rows)";
+    return CP2_ERR_INVALID;
+  }
+  if (!plan.keeps_nodes) {
+    ctx->err = "fill tree rows: this session does not keep the nodes of the paths it proves: call cp2_fill_keep_nodes first";
+    return CP2_ERR_INVALID;
+  }
+  std::string err;
+  if (!tree_places_validate("fill tree rows", places, n, plan.first_slot, plan.n_local, plan.csizes, &err)) {
+    ctx->err = err;
+    return CP2_ERR_INVALID;
+  }
+  if (n == 0) return CP2_OK;
+  // the statuses from the host's bitmap; the stated slot root is known from the start and is served from the session's copy of it
+  std::vector<uint32_t> st(n);
+  std::vector<uint64_t> addr(n, 0);
+  for (size_t i = 0; i < n; ++i) {
+    const uint64_t local = places[3 * i] - plan.first_slot, l = places[3 * i + 1], r = plan.node_row((size_t)l, local, places[3 * i + 2]);
+    if (l == plan.depth()) addr[i] = (uint64_t)reinterpret_cast<uintptr_t>(f->slot_roots.p) + local * 32;
+    else if (plan.is_known(r)) addr[i] = (uint64_t)reinterpret_cast<uintptr_t>(f->compact.p) + r * 32;
+    st[i] = addr[i] ? CP2_FILL_ROW_KNOWN : CP2_FILL_ROW_UNKNOWN;
+  }
+  if (rows) {                                        // an unknown row names no address: k_gather_addr leaves zeros there
+    CP2_REFUSE_STUCK(ctx);
+    CP2_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<uint8_t> out(n * 32);
+    CP2_TRY(gather_rows_by_addr(ctx, addr, out.data()));
+    std::memcpy(rows, out.data(), n * 32);
+  }
+  std::copy(st.begin(), st.end(), status);
+  return CP2_OK;
+} catch (const std::bad_alloc&) {
+  return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
+} catch (...) {
+  return CP2_ERR_INVALID;
+}
+
+extern "C" int cp2_fill_add_multi_anchored(void* fill, const uint64_t* groups, size_t n_groups, const uint64_t* blocks, const uint8_t* data,
+                                           const uint8_t* nodes, size_t n_rows, uint32_t* status, size_t* n_new) try {
+  cp2_fill_session* f = session(fill);
+  if (!f) return CP2_ERR_INVALID;
+  cp2_ctx* ctx = f->ctx;
+  const cp2_config& c = f->cfg;
+  FillPlan& plan = f->plan;
+  size_t n = 0;
+  if ((n_groups && !groups) || !multiproof_count(groups, n_groups, &n) || (n && (!blocks || !data || !status)) || (n_rows && !nodes)) {
+    ctx->err = "fill multi anchored: groups, blocks, data and status must not be NULL when there are requests, nor nodes when n_rows > 0";
+    return CP2_ERR_INVALID;
+  }
+  std::string err;
+  // (8): a want list made before another add landed is stale: the session needs other rows now, and mostly fewer
+  if (!multiproof_anchor_validate("fill multi anchored", groups, n_groups, blocks, plan.first_slot, plan.n_local, plan.n_blocks,
+                                  session_knows(plan, groups), true, n_rows, nullptr, nullptr, nullptr, &err) ||
+      !plan.validate(nullptr, 0, &err)) {
+    ctx->err = err;
+    return CP2_ERR_INVALID;
+  }
+  if (!plan.keeps_nodes) {
+    ctx->err = "fill multi anchored: this session does not keep the nodes of the paths it proves: call cp2_fill_keep_nodes first, or use cp2_fill_add_multi";
+    return CP2_ERR_INVALID;
+  }
+  if (n_groups == 0) {
+    if (n_new) *n_new = 0;
+    return CP2_OK;
+  }
+  std::vector<uint64_t> slot_block(2 * n), counts(n_groups), nb(n_groups, plan.n_blocks), local(n_groups);
+  for (size_t g = 0, at = 0; g < n_groups; ++g) {
+    counts[g] = groups[2 * g + 1];
+    local[g] = groups[2 * g] - plan.first_slot;
+    for (uint64_t j = 0; j < counts[g]; ++j, ++at) {
+      slot_block[2 * at] = groups[2 * g];
+      slot_block[2 * at + 1] = blocks[at];
+    }
+  }
+  MultiproofAnchorPlan mp;
+  if (!multiproof_anchor_plan(
+          counts.data(), nb.data(), n_groups, blocks, [&](size_t g, size_t l, uint64_t i) { return plan.is_known(plan.node_row(l, local[g], i)); }, &mp,
+          &err)) {
+    ctx->err = err;
+    return CP2_ERR_INVALID;
+  }
+  CP2_REFUSE_STUCK(ctx);
+  CP2_HIP(ctx, hipSetDevice(ctx->device));
+  const auto t0 = std::chrono::steady_clock::now();
+  // the plan's places made addresses: the kept inputs and what every top is compared with are rows of the session's buffer (the top of
+  // level depth: the stated slot root); the commit list goes where node_row has each row
+  const uint64_t compact = (uint64_t)reinterpret_cast<uintptr_t>(f->compact.p), roots = (uint64_t)reinterpret_cast<uintptr_t>(f->slot_roots.p);
+  const auto addr_of = [&](size_t r) { return compact + plan.node_row(mp.row_level[r], local[mp.row_group[r]], mp.row_index[r]) * 32; };
+  std::vector<uint64_t> kept_addr(mp.n_kept), top_want(mp.n_tops());
+  std::vector<uint32_t> top_row_group(2 * mp.n_tops());
+  for (size_t k = 0; k < mp.n_kept; ++k) kept_addr[k] = addr_of(mp.kept_base() + k);
+  for (size_t t = 0; t < mp.n_tops(); ++t) {
+    top_row_group[2 * t] = mp.top_row[t];
+    top_row_group[2 * t + 1] = mp.top_group[t];
+    top_want[t] = mp.top_level[t] == plan.depth() ? roots + local[mp.top_group[t]] * 32
+                                                  : compact + plan.node_row(mp.top_level[t], local[mp.top_group[t]], mp.top_index[t]) * 32;
+  }
+  MultiproofAnchors anchors;
+  anchors.n_kept = mp.n_kept;
+  anchors.n_tops = mp.n_tops();
+  anchors.kept_addr = kept_addr.data();
+  anchors.top_row_group = top_row_group.data();
+  anchors.top_want = top_want.data();
+  anchors.top_off = mp.top_off.data();
+  const size_t n_commit = mp.commit.size();
+  std::vector<uint64_t> dst(n_commit);
+  std::vector<uint32_t> c_group(n_commit), c_level(n_commit);
+  std::vector<uint64_t> c_index(n_commit);
+  for (size_t k = 0; k < n_commit; ++k) {
+    const size_t r = mp.commit[k];
+    dst[k] = addr_of(r);
+    c_group[k] = mp.row_group[r];
+    c_level[k] = mp.row_level[r];
+    c_index[k] = mp.row_index[r];
+  }
+  std::vector<uint8_t> sent(n_rows * 32);            // stored as they stand, so they go up canonical
+  for (size_t r = 0; r < n_rows; ++r) canonical_felt(nodes + r * 32, &sent[r * 32]);
+  DevBuf d_src, d_dst, d_group;                      // (go after the streams have drained: DevBuf::release)
+  const auto commit = [&](const void* d_work, const uint32_t* d_verdict, hipStream_t st) -> int {
+    if (n_commit == 0) return CP2_OK;                // (every block root was known already)
+    CP2_TRY(d_src.scratch(ctx, n_commit * 4));
+    CP2_TRY(d_dst.scratch(ctx, n_commit * 8));
+    CP2_TRY(d_group.scratch(ctx, n_commit * 4));
+    CP2_HIP(ctx, hipMemcpyAsync(d_src.p, mp.commit.data(), n_commit * 4, hipMemcpyHostToDevice, st));
+    CP2_HIP(ctx, hipMemcpyAsync(d_dst.p, dst.data(), n_commit * 8, hipMemcpyHostToDevice, st));
+    CP2_HIP(ctx, hipMemcpyAsync(d_group.p, c_group.data(), n_commit * 4, hipMemcpyHostToDevice, st));
+    CP2_HIP(ctx, cp2k::launch_multiproof_commit(d_work, mp.n_work, static_cast<const uint32_t*>(d_src.p), static_cast<const uint64_t*>(d_dst.p),
+                                                static_cast<const uint32_t*>(d_group.p), d_verdict, (uint32_t)n_groups, n_commit, st));
+    return CP2_OK;
+  };
+  std::vector<uint32_t> group_verdict(n_groups), verdict(n);
+  CP2_TRY(multiproof_check(ctx, c.cell_size, c.block_size, mp, nullptr, n_groups, data, sent.data(), commit, group_verdict.data(), nullptr, &anchors));
+  for (size_t i = 0; i < n; ++i) verdict[i] = group_verdict[mp.row_group[i]];
+  // written or not: the nodes of a proved group are authentic and stored
+  plan.mark_proved_multi(c_group.data(), c_level.data(), c_index.data(), n_commit, local.data(), group_verdict.data());
+  if (std::getenv("CP2_TRACE"))
+    std::fprintf(stderr, "[cp2 trace] fill add multi anchored: %zu group(s), %zu top(s), %zu kept input(s), %zu compression(s)\n", n_groups, mp.n_tops(),
+                 mp.n_kept, mp.computed());
   return fill_add_tail(f, slot_block.data(), data, n, verdict.data(), status, n_new, t0, n_rows, plan.depth());
 } catch (const std::bad_alloc&) {
   return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI

@@ -28,6 +28,7 @@
 //   k_nodes_restore_layer   the kept nodes a checkpoint states, authenticated top-down from the stated slot roots (fill.cpp)
 //   k_multiproof_layer    one level of the induced subtrees of many block multiproofs, one host-made job per inner node (multiproofs.cpp)
 //   k_multiproof_commit   the rows of the proved groups copied into a fill session's compact buffer (fill.cpp)
+//   k_multiproof_tops, k_multiproof_fold   the tops of multiproofs that stop at kept nodes compared with those nodes, one verdict per group (fill.cpp)
 //
 // All global-memory field elements are 32-byte little-endian canonical integers (the ABI format).
 #include "kernels.hpp"
@@ -1366,6 +1367,39 @@ __global__ void __launch_bounds__(TPB) k_multiproof_commit(const uint4* __restri
 }
 
 // ------------------------------------------------------------------------------------------------
+// The verdicts of multiproofs that stop at nodes a fill session holds (fill.cpp, cp2_fill_add_multi_anchored;
+// multiproof_anchor_plan.hpp).  A group of such a call has one or more TOPS: rows of the work table -- a fresh block root or a node
+// k_multiproof_layer computed -- that must equal an authentic row the session keeps.  Lane t compares row tops[t].row with the 32 bytes
+// at want_addr[t] as field elements (fe_equal on canonical loads, as k_multiproof_layer compares its top) and writes top_verdict[t] = 0
+// or 1.  No permutation, no LDS, no atomics.  Defensive (the host never produces them): a row at or past n_work and an address that is 0
+// or not 16-byte aligned are a mismatch and are not read.
+__global__ void __launch_bounds__(TPB) k_multiproof_tops(const uint4* __restrict__ work, uint64_t n_work, const MultiproofTop* __restrict__ tops,
+                                                           const uint64_t* __restrict__ want_addr, size_t n_tops, uint32_t* __restrict__ top_verdict) {
+  const size_t t = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (t >= n_tops) return;
+  const uint32_t r = tops[t].row;
+  const uint64_t a = want_addr[t];
+  uint32_t v = 1u;
+  if (r < n_work && a != 0 && (a & 15) == 0)
+    v = fe_equal(load_fe_canonical(work + 2 * (size_t)r), load_fe_canonical(reinterpret_cast<const uint4*>(a))) ? 0u : 1u;
+  top_verdict[t] = v;
+}
+
+// ... and the group's verdict: lane g ORs top_verdict over its group's range [top_off[g], top_off[g + 1]) (the tops are group-major)
+// into verdict[g]; a group without a top has nothing that vouches for it and gets 1.  Every word has one writer; nothing is cleared
+// beforehand.  A range that descends or ends past n_tops (the launcher refuses them) reads nothing and gives 1.
+__global__ void __launch_bounds__(TPB) k_multiproof_fold(const uint32_t* __restrict__ top_verdict, size_t n_tops, const uint64_t* __restrict__ top_off,
+                                                           size_t n_groups, uint32_t* __restrict__ verdict) {
+  const size_t g = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (g >= n_groups) return;
+  const uint64_t t0 = top_off[g], t1 = top_off[g + 1];
+  uint32_t v = t1 <= t0 || t1 > n_tops ? 1u : 0u;
+  if (v == 0u)
+    for (uint64_t t = t0; t < t1; ++t) v |= top_verdict[t] != 0u ? 1u : 0u;
+  verdict[g] = v;
+}
+
+// ------------------------------------------------------------------------------------------------
 // The children of one node of a fill session's tree, ready for the keyed compression: rows rl and rl + 1 of the compact layout, each from
 // `tree` where the session knows it (known_l / known_r: the child's KNOWN bit, 0 or 1) and from `cand` otherwise.  The base address is
 // picked with an integer mask: the two bases differ in the bits the mask lets through.  Without a pair (the last node of an odd layer,
@@ -1677,6 +1711,27 @@ hipError_t launch_multiproof_commit(const void* work, uint64_t n_work, const uin
     hipLaunchKernelGGL(k_multiproof_commit, dim3(grid_for(m)), dim3(TPB), 0, st, (const uint4*)work, n_work, src_row + i0, dst_addr + i0, group_of + i0,
                        verdict, n_groups, m);
   });
+}
+
+hipError_t launch_multiproof_tops(const void* work, uint64_t n_work, const MultiproofTop* tops, const uint64_t* want_addr, size_t n_tops,
+                                  const uint64_t* top_off, const uint64_t* d_top_off, size_t n_groups, uint32_t* top_verdict, uint32_t* verdict,
+                                  hipStream_t st) {
+  if (n_groups == 0) return hipSuccess;
+  if (!top_off || !d_top_off || !verdict || !fits_one_grid(n_groups) || (n_tops && !fits_one_grid(n_tops))) return hipErrorInvalidValue;
+  for (size_t g = 0; g < n_groups; ++g)
+    if (top_off[g + 1] < top_off[g]) return hipErrorInvalidValue;
+  if (top_off[n_groups] > n_tops) return hipErrorInvalidValue;
+  if (n_tops && (!work || !tops || !want_addr || !top_verdict)) return hipErrorInvalidValue;
+  if ((reinterpret_cast<uintptr_t>(work) & 15) || (reinterpret_cast<uintptr_t>(tops) & 7) || (reinterpret_cast<uintptr_t>(want_addr) & 7) ||
+      (reinterpret_cast<uintptr_t>(d_top_off) & 7) || (reinterpret_cast<uintptr_t>(top_verdict) & 3) || (reinterpret_cast<uintptr_t>(verdict) & 3))
+    return hipErrorInvalidValue;
+  if (n_tops) {
+    CP2K_LAUNCH(k_multiproof_tops, dim3(grid_for(n_tops)), dim3(TPB), 0, st, (const uint4*)work, n_work, tops, want_addr, n_tops, top_verdict);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  CP2K_LAUNCH(k_multiproof_fold, dim3(grid_for(n_groups)), dim3(TPB), 0, st, top_verdict, n_tops, d_top_off, n_groups, verdict);
+  return hipGetLastError();
 }
 
 hipError_t launch_compress_pairs(const void* xy, uint32_t key, void* out, size_t n, hipStream_t st) {

@@ -215,6 +215,23 @@ hipError_t launch_multiproof_layers(void* work, uint64_t n_work, const Multiproo
 hipError_t launch_multiproof_commit(const void* work, uint64_t n_work, const uint32_t* src_row, const uint64_t* dst_addr, const uint32_t* group_of,
                                     const uint32_t* verdict, uint32_t n_groups, size_t n, hipStream_t st);
 
+// Multiproofs that stop at nodes a fill session holds (fill.cpp, cp2_fill_add_multi_anchored; k_multiproof_tops, k_multiproof_fold): a
+// group has one or more tops, rows of the work table that must each equal an authentic kept row.  Device: tops (n_tops, group-major),
+// want_addr (per top the absolute address of the kept row, 32 bytes, 16-byte aligned), d_top_off (n_groups + 1: group g's tops are
+// [d_top_off[g], d_top_off[g + 1])), top_verdict (n_tops words), verdict (n_groups words).  Host: top_off, the same n_groups + 1 values.
+// Two launches in order on st: lane t writes top_verdict[t] = 0 when row tops[t].row equals the row at want_addr[t] as a field element,
+// else 1 (a row at or past n_work, an address that is 0 or misaligned: 1, nothing read); then lane g writes verdict[g] = the OR of its
+// range, 1 for an empty range.  Every word has one writer, nothing is cleared beforehand, nothing else is written.
+// hipErrorInvalidValue, nothing launched: a NULL or misaligned table with work to do, a top_off that descends or ends past n_tops, work
+// that does not fit one grid.  n_groups == 0: success, no launch.
+struct MultiproofTop {
+  uint32_t row;        // a row of the work table
+  uint32_t group;
+};
+hipError_t launch_multiproof_tops(const void* work, uint64_t n_work, const MultiproofTop* tops, const uint64_t* want_addr, size_t n_tops,
+                                  const uint64_t* top_off, const uint64_t* d_top_off, size_t n_groups, uint32_t* top_verdict, uint32_t* verdict,
+                                  hipStream_t st);
+
 // Resuming a fill session (fill.cpp, k_block_root_recheck): verdict[i] = 0 when the 32-byte row i of `fresh` (the root a re-read block
 // hashed to) equals row dest[i] of `layer0` (n_rows rows), else 1 -- and then that row of layer0 is overwritten with zeros.  dest[i] >=
 // n_rows: verdict 1, nothing read or written.  The rows of one call are distinct.

@@ -7,7 +7,10 @@
 // inner node of the induced subtree once.  A dataset SERVES the rows with the gather block proofs use; a node that holds nothing but
 // slot roots CHECKS groups of blocks against them: the candidates go down repair's data path (repair_check_with, repair.cpp), their block
 // roots land in a work table beside the sent rows, and k_multiproof_layer builds every group's subtree level by level, one launch per
-// level, one verdict per group.
+// level, one verdict per group.  A fill session that keeps nodes runs the same pass with groups that stop at the nodes it holds
+// (cp2_fill_add_multi_anchored, fill.cpp; multiproof_anchor_plan.hpp): the kept inputs are gathered into the work table first and the
+// verdicts come from every group's tops (k_multiproof_tops, k_multiproof_fold).  cp2_dataset_block_tree_rows serves the rows such a
+// session asks for, by their place in the tree.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,6 +23,7 @@
 #include <vector>
 
 #include "dataset_obj.hpp"
+#include "multiproof_anchor_plan.hpp"
 #include "multiproof_plan.hpp"
 #include "repair.hpp"
 
@@ -27,6 +31,7 @@ using namespace cp2i;
 
 static_assert(sizeof(MultiproofJob) == 16 && sizeof(cp2k::MultiproofJob) == 16 && MULTIPROOF_ZERO == cp2k::MULTIPROOF_ZERO,
               "the plan's jobs are uploaded as the kernel's");
+static_assert(sizeof(cp2k::MultiproofTop) == 8, "the tops go up as (row, group) pairs of 32-bit words");
 
 namespace {
 
@@ -40,18 +45,33 @@ size_t blocks_of(size_t cell_size, size_t block_size, size_t n_cells) { return n
 // nothing special.  The sent rows and the job tables go up once, before the first chunk.  After the pass k_multiproof_layer runs level by
 // level, then `commit` (may be empty: what a fill keeps), then one download of the n_groups verdicts (and the n block roots) and one drain.
 int cp2i::multiproof_check(cp2_ctx* ctx, size_t cell_size, size_t block_size, const MultiproofPlan& plan, const uint64_t* want, size_t n_groups,
-                           const uint8_t* data, const uint8_t* nodes, const MultiproofCommit& commit, uint32_t* group_verdict, uint8_t* block_roots) {
+                           const uint8_t* data, const uint8_t* nodes, const MultiproofCommit& commit, uint32_t* group_verdict, uint8_t* block_roots,
+                           const MultiproofAnchors* anchors) {
   const size_t n = plan.n, n_rows = plan.n_rows;
-  DevBuf d_work, d_jobs, d_want, d_group_verdict;    // (go after the streams have drained: DevBuf::release)
+  // with anchors the stated addresses are per top, and the tops' tables go up beside the jobs
+  const size_t n_want = anchors ? anchors->n_tops : n_groups, n_kept = anchors ? anchors->n_kept : 0;
+  DevBuf d_work, d_jobs, d_want, d_group_verdict, d_kept_addr, d_tops, d_top_off, d_top_verdict;   // (go after the streams have drained: DevBuf::release)
   RepairJudge judge;
   judge.begin = [&](size_t) -> int {
     CP2_TRY(d_work.scratch(ctx, plan.n_work * 32));
     CP2_TRY(d_jobs.scratch(ctx, plan.jobs.size() * sizeof(MultiproofJob)));
-    CP2_TRY(d_want.scratch(ctx, n_groups * 8));
+    CP2_TRY(d_want.scratch(ctx, n_want * 8));
     CP2_TRY(d_group_verdict.scratch(ctx, n_groups * 4));
     if (n_rows) CP2_HIP(ctx, hipMemcpyAsync(d_work.u8() + n * 32, nodes, n_rows * 32, hipMemcpyHostToDevice, ctx->stream));
-    CP2_HIP(ctx, hipMemcpyAsync(d_jobs.p, plan.jobs.data(), plan.jobs.size() * sizeof(MultiproofJob), hipMemcpyHostToDevice, ctx->stream));
-    CP2_HIP(ctx, hipMemcpyAsync(d_want.p, want, n_groups * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (!plan.jobs.empty())                          // (a group whose tops are all block roots has none)
+      CP2_HIP(ctx, hipMemcpyAsync(d_jobs.p, plan.jobs.data(), plan.jobs.size() * sizeof(MultiproofJob), hipMemcpyHostToDevice, ctx->stream));
+    CP2_HIP(ctx, hipMemcpyAsync(d_want.p, anchors ? anchors->top_want : want, n_want * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (!anchors) return CP2_OK;
+    CP2_TRY(d_tops.scratch(ctx, anchors->n_tops * sizeof(cp2k::MultiproofTop)));
+    CP2_TRY(d_top_off.scratch(ctx, (n_groups + 1) * 8));
+    CP2_TRY(d_top_verdict.scratch(ctx, anchors->n_tops * 4));
+    CP2_HIP(ctx, hipMemcpyAsync(d_tops.p, anchors->top_row_group, anchors->n_tops * sizeof(cp2k::MultiproofTop), hipMemcpyHostToDevice, ctx->stream));
+    CP2_HIP(ctx, hipMemcpyAsync(d_top_off.p, anchors->top_off, (n_groups + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (n_kept) {                                    // the kept inputs, once: rows [n + n_rows, n + n_rows + n_kept) of the work table
+      CP2_TRY(d_kept_addr.scratch(ctx, n_kept * 8));
+      CP2_HIP(ctx, hipMemcpyAsync(d_kept_addr.p, anchors->kept_addr, n_kept * 8, hipMemcpyHostToDevice, ctx->stream));
+      CP2_HIP(ctx, cp2k::launch_gather_addr(static_cast<const uint64_t*>(d_kept_addr.p), n_kept, 32, d_work.u8() + (n + n_rows) * 32, ctx->stream));
+    }
     return CP2_OK;
   };
   judge.verdicts = [&](const uint8_t* fresh, size_t c0, size_t m, uint32_t* verdict, hipStream_t st) -> int {
@@ -64,6 +84,11 @@ int cp2i::multiproof_check(cp2_ctx* ctx, size_t cell_size, size_t block_size, co
   uint32_t* d_verdict = static_cast<uint32_t*>(d_group_verdict.p);
   CP2_HIP(ctx, cp2k::launch_multiproof_layers(d_work.p, plan.n_work, static_cast<const cp2k::MultiproofJob*>(d_jobs.p), plan.level_off.data(),
                                               plan.level_base.data(), plan.levels(), static_cast<const uint64_t*>(d_want.p), d_verdict, ctx->stream));
+  if (anchors)
+    CP2_HIP(ctx, cp2k::launch_multiproof_tops(d_work.p, plan.n_work, static_cast<const cp2k::MultiproofTop*>(d_tops.p),
+                                              static_cast<const uint64_t*>(d_want.p), anchors->n_tops, anchors->top_off,
+                                              static_cast<const uint64_t*>(d_top_off.p), n_groups, static_cast<uint32_t*>(d_top_verdict.p), d_verdict,
+                                              ctx->stream));
   if (commit) CP2_TRY(commit(d_work.p, d_verdict, ctx->stream));
   CP2_HIP(ctx, hipMemcpyAsync(group_verdict, d_verdict, n_groups * 4, hipMemcpyDeviceToHost, ctx->stream));
   if (block_roots) CP2_HIP(ctx, hipMemcpyAsync(block_roots, d_work.p, n * 32, hipMemcpyDeviceToHost, ctx->stream));
@@ -166,6 +191,57 @@ extern "C" int cp2_dataset_block_multiproofs(cp2_dataset* ds, const uint64_t* gr
   CP2_TRY(gather_rows_by_addr(ctx, addr, out.data()));
   if (rows_needed) std::memcpy(nodes, out.data(), (size_t)rows_needed * 32);
   if (block_roots) std::memcpy(block_roots, out.data() + (size_t)rows_needed * 32, n * 32);
+  return CP2_OK;
+} catch (const std::bad_alloc&) {
+  return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI
+} catch (...) {
+  return CP2_ERR_INVALID;
+}
+
+// Tree rows by their place (the rows a fill session's want list names: cp2_fill_multiproof_want, fill.cpp), from every node kept or the
+// compact layers, with the row arithmetic block proofs use; one upload of the address list, one gather, one download.
+extern "C" int cp2_dataset_block_tree_rows(cp2_dataset* ds, const uint64_t* places, size_t n, uint8_t* rows) try {
+  if (!ds) return CP2_ERR_INVALID;
+  cp2_ctx* ctx = ds->ctx;
+  const cp2_config& c = ds->cfg;
+  if (n && (!places || !rows)) {
+    ctx->err = "block tree rows: places and rows must not be NULL when n > 0";
+    return CP2_ERR_INVALID;
+  }
+  if (repair_dataset_mode(ds) == 0) {
+    ctx->err = "block tree rows: this dataset keeps only its slot roots, no block roots and no layers above them to take a row from: build it with "
+               "every node or the compact layers kept (cp2_set_keep_trees)";
+    return CP2_ERR_INVALID;
+  }
+  const uint64_t n_blocks = blocks_of(c.cell_size, c.block_size, c.n_cells);
+  const size_t per = block_proof_depth(n_blocks) + 1;
+  const std::vector<size_t>& offs = ds->trees ? ds->trees->toff : ds->coff;
+  const std::vector<size_t>& sizes = ds->trees ? ds->trees->tsizes : ds->csizes;
+  if (offs.size() != per || sizes.size() != per || (ds->trees && ds->trees->units_per_slot != 1)) {
+    ctx->err = "block tree rows: the kept layers of this dataset are not those of whole slot trees";
+    return CP2_ERR_INVALID;
+  }
+  std::string err;
+  if (!tree_places_validate("block tree rows", places, n, ds->first_slot, ds->n_local, sizes, &err)) {
+    ctx->err = err;
+    return CP2_ERR_INVALID;
+  }
+  if (n == 0) return CP2_OK;
+  CP2_REFUSE_STUCK(ctx);
+  CP2_HIP(ctx, hipSetDevice(ctx->device));
+  const RepairKept k = repair_dataset_kept(ds);
+  std::vector<uint64_t> addr(n);
+  for (size_t i = 0; i < n; ++i) {
+    const uint64_t l = places[3 * i + 1], r = offs[l] + (places[3 * i] - ds->first_slot) * sizes[l] + places[3 * i + 2];
+    if (r >= k.rows) {
+      ctx->err = "block tree rows: a row lies outside the kept nodes";
+      return CP2_ERR_INVALID;
+    }
+    addr[i] = (uint64_t)reinterpret_cast<uintptr_t>(k.nodes) + r * 32;
+  }
+  std::vector<uint8_t> out(n * 32);
+  CP2_TRY(gather_rows_by_addr(ctx, addr, out.data()));
+  std::memcpy(rows, out.data(), n * 32);
   return CP2_OK;
 } catch (const std::bad_alloc&) {
   return CP2_ERR_ALLOC;   // nothing may unwind across the C ABI

@@ -63,10 +63,23 @@ int gather_rows_by_addr(cp2_ctx* ctx, const std::vector<uint64_t>& addr, uint8_t
 // sent rows.  repair_check_with's data path, then k_multiproof_layer level by level, then `commit` (may be empty) with the work table and
 // the group verdicts in device memory, queued on the same stream; then group_verdict (host, n_groups: 0 proved, anything else not) and
 // block_roots (host, plan.n x 32 bytes, may be NULL: what each candidate hashed to) are downloaded and the stream is drained.
+//   With `anchors` (cp2_fill_add_multi_anchored; multiproof_anchor_plan.hpp) the groups stop at nodes a fill session holds: the work
+// table has n_kept rows between the sent rows and the computed ones, gathered once, before the layers, from the absolute device
+// addresses kept_addr (k_gather_addr); no job of the plan compares, `want` is not looked at, and the group verdicts come from the
+// n_tops tops ((work row, group), group-major; top_off: n_groups + 1) compared with the kept rows at top_want (k_multiproof_tops,
+// k_multiproof_fold) before `commit` runs.
 struct MultiproofPlan;
+struct MultiproofAnchors {
+  size_t n_kept = 0, n_tops = 0;
+  const uint64_t* kept_addr = nullptr;   // n_kept
+  const uint32_t* top_row_group = nullptr;   // n_tops x 2: the layout of cp2k::MultiproofTop
+  const uint64_t* top_want = nullptr;    // n_tops
+  const uint64_t* top_off = nullptr;     // n_groups + 1
+};
 using MultiproofCommit = std::function<int(const void* d_work, const uint32_t* d_verdict, hipStream_t st)>;
 int multiproof_check(cp2_ctx* ctx, size_t cell_size, size_t block_size, const MultiproofPlan& plan, const uint64_t* want, size_t n_groups,
-                     const uint8_t* data, const uint8_t* nodes, const MultiproofCommit& commit, uint32_t* group_verdict, uint8_t* block_roots);
+                     const uint8_t* data, const uint8_t* nodes, const MultiproofCommit& commit, uint32_t* group_verdict, uint8_t* block_roots,
+                     const MultiproofAnchors* anchors = nullptr);
 // the requests whose status is CP2_REPAIR_MATCH written into "<base><slot>.dat", grouped by file in ascending offset order, each file synced
 // once.  The first file that cannot be opened, written or synced: CP2_ERR_IO, *err "cannot write <file>: <reason>", its matched requests and
 // those of every later file CP2_REPAIR_UNWRITTEN.  *n_written counts the blocks of the files written and synced, `written` their stamps.

@@ -114,6 +114,18 @@ proc cp2_blocks_verify_multi(ctx: Cp2Ctx, cellSize, blockSize, nCells: csize_t, 
                              blockRoots: ptr byte): cint {.importc.}
 proc cp2_fill_add_multi(f: pointer, groups: ptr uint64, nGroups: csize_t, blocks: ptr uint64, data, nodes: ptr byte, nRows: csize_t,
                         status: ptr uint32, nNew: ptr csize_t): cint {.importc.}
+# multiproofs against what a fill session knows: cp2_fill_multiproof_want lays groups out against the session's kept nodes (levelIndex =
+# cap x (level, index), written when cap >= nRows[]; groupRows may be nil), the two _block_tree_rows calls serve such rows by their place
+# (places = n x (slot, level, index); the fill's status = n x CP2_FILL_ROW_*, its rows may be nil), and cp2_fill_add_multi_anchored is
+# cp2_fill_add_multi with nodes = the want lists' rows
+const CP2_FILL_ROW_KNOWN* = 0'u32
+const CP2_FILL_ROW_UNKNOWN* = 1'u32
+proc cp2_fill_multiproof_want(f: pointer, groups: ptr uint64, nGroups: csize_t, blocks: ptr uint64, levelIndex: ptr uint64, cap: csize_t,
+                              nRows: ptr csize_t, groupRows: ptr uint64): cint {.importc.}
+proc cp2_dataset_block_tree_rows(ds: Cp2Dataset, places: ptr uint64, n: csize_t, rows: ptr byte): cint {.importc.}
+proc cp2_fill_block_tree_rows(f: pointer, places: ptr uint64, n: csize_t, status: ptr uint32, rows: ptr byte): cint {.importc.}
+proc cp2_fill_add_multi_anchored(f: pointer, groups: ptr uint64, nGroups: csize_t, blocks: ptr uint64, data, nodes: ptr byte, nRows: csize_t,
+                                 status: ptr uint32, nNew: ptr csize_t): cint {.importc.}
 # repair across datasets in one pass: req = n x (index into ds, slot, block), paths packed with pathOff (n + 1 rows, both nil: every path
 # empty) as cp2_datasets_read_blocks returns them -- an empty path judges against the kept block root, a whole one walks to the slot root --,
 # cachePaths = nDs entries (nil, or entries nil), status = n x CP2_REPAIR_*; every slot file is attempted on its own

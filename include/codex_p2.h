@@ -53,7 +53,8 @@ extern "C" {
  *                sessions finished in one pass), cp2_fills_resume_many (many fill sessions resumed in one pass),
  *                cp2_datasets_repair_blocks_many (many datasets repaired in one pass), cp2_block_multiproof_rows,
  *                cp2_block_multiproof_layout, cp2_dataset_block_multiproofs, cp2_blocks_verify_multi and cp2_fill_add_multi
- *                (block multiproofs).
+ *                (block multiproofs), cp2_fill_multiproof_want, cp2_dataset_block_tree_rows, cp2_fill_block_tree_rows and
+ *                cp2_fill_add_multi_anchored (multiproofs against what a fill session knows).
  *                MINOR stays 2 until the release that carries them: the bump to 1.3 goes in its own commit with that release.         */
 #define CP2_ABI_VERSION_MAJOR 1
 #define CP2_ABI_VERSION_MINOR 2
@@ -1265,8 +1266,7 @@ int cp2_fills_resume_many(cp2_ctx* ctx, const void* const* cfgs /* n_fills: cons
  *              (7) blocks not strictly ascending inside a group; (8) n_rows different from the sum of the groups' layouts (both
  *              numbers in the message); (9) for the fill, a finished session.  A call whose work table (requests, sent rows and computed nodes) would reach 2^32 - 1 rows is
  *              refused too.  n_groups == 0: CP2_OK.  A context whose stream will not drain is refused (CP2_ERR_HIP).
- * Out of scope: cp2_multi_*; a many-session form; multiproofs that stop at anchors; serving multiproofs from a fill session; repair with
- * multiproofs; checkpoint formats. */
+ * Out of scope: cp2_multi_*; a many-session form; repair with multiproofs; checkpoint formats. */
 size_t cp2_block_multiproof_rows(size_t cell_size, size_t block_size, size_t n_cells, const uint64_t* blocks /* k, strictly ascending */,
                                  size_t k);
 int cp2_block_multiproof_layout(size_t cell_size, size_t block_size, size_t n_cells, const uint64_t* blocks /* k, strictly ascending */,
@@ -1282,6 +1282,69 @@ int cp2_blocks_verify_multi(cp2_ctx* ctx, size_t cell_size, size_t block_size, s
 int cp2_fill_add_multi(void* f /* cp2_fill* */, const uint64_t* groups /* n_groups x 2: dataset slot, count */, size_t n_groups,
                        const uint64_t* blocks /* n */, const uint8_t* data /* n x block_size */, const uint8_t* nodes /* n_rows x 32 */,
                        size_t n_rows, uint32_t* status /* n: CP2_FILL_* */, size_t* n_new);
+
+/* ---- multiproofs against what a fill session knows; tree rows served by place ---------------------------------------------------------
+ * cp2_fill_add_multi knows only the stated slot root: a half-filled session that keeps nodes is still sent every sibling up to the root.
+ * cp2_fill_add_anchored stops at kept nodes but takes one path per block: two blocks under one unknown subtree send their shared
+ * siblings twice.  These calls take the minimum of both: for a set B of blocks, only the rows the session can neither compute from B nor
+ * already holds, and peers -- a finished dataset, or a session that is still filling -- serve those rows by their place in the tree.
+ *   Format     the geometry of block multiproofs.  known(l, i) is the session's KNOWN bit of node i of level l of the slot; (depth, 0),
+ *              the stated slot root, always counts as known.  For a non-empty set B of DISTINCT blocks let A_0 = B.  For l = 0 .. depth
+ *              and every i in A_l: when known(l, i), (l, i) is a TOP: the value that reaches it is compared with the kept row (at depth:
+ *              the stated root); a top puts nothing into A_{l+1}, and a top of level 0 costs no compression (the fresh block root is
+ *              compared).  Otherwise i >> 1 is in A_{l+1}, and when i ^ 1 < m_l the sibling is taken (a) from the call, when i ^ 1 is in
+ *              A_l and unknown; (b) from the session's buffer, when known(l, i ^ 1): a KEPT INPUT, never sent, the kept row being used
+ *              even when i ^ 1 is a top too; (c) otherwise it is SENT.  The WANT LIST is the sent rows (l, i ^ 1), by level ascending,
+ *              then by index ascending: cp2_block_multiproof_layout's order, and its rows when only the root is known.
+ *   Verdict    belongs to the GROUP: it proves when every one of its tops matches.  Every leaf lies under a top, the root being known.
+ *   Kept       a proved group leaves the block roots of B that were not known, the sent rows (stored canonical) and every computed node
+ *              that is not a top, each where the compact layout has it; a row that was known when the call began is never written.
+ *              That is what ONE cp2_fill_add_anchored of the same requests leaves, with levels = cp2_fill_anchors' answers and paths
+ *              from the true tree.  A slot of nBlocks blocks filled in any grouping receives at most nBlocks - 1 rows in all: a sent
+ *              row is the sibling of an unknown node whose parent the call computes, and after the proof both children are known.
+ *
+ * cp2_fill_multiproof_want: host only, read-only.  groups (dataset slot, count) and blocks as for cp2_fill_add_multi.
+ *   Result     *n_rows = the rows of all groups, always the full count; level_index (cap x 2 uint64: level, index) receives them packed
+ *              in group order only when cap >= *n_rows; group_rows (n_groups, may be NULL) the count per group.  Every group is laid out
+ *              against the session as it stands; groups of one call do not see each other.  A session that keeps no nodes is not
+ *              refused: only the root is known, and the answer is cp2_block_multiproof_layout's.
+ *   Refused    CP2_ERR_INVALID, outputs untouched, in this order: (1) a NULL session; (2) NULL arrays with requests; (3) a group with
+ *              count 0; (4) a slot outside the range; (5) a block >= nBlocks; (6) blocks not strictly ascending; (7) a finished session.
+ *
+ * cp2_dataset_block_tree_rows, cp2_fill_block_tree_rows serve tree rows by place: places is n x 3 uint64 (dataset slot, level in
+ * [0, depth], index < m_level); level depth is the slot root.  One upload of the address list, one gather on the device
+ * (cp2_dataset_block_proofs' own), one download.  Read-only.
+ *   Dataset    from every node kept or from the compact layers; a roots-only dataset is refused, as in cp2_dataset_block_proofs.
+ *   Fill       also status[i] = CP2_FILL_ROW_KNOWN or CP2_FILL_ROW_UNKNOWN; an unknown row comes back as zeros.  With rows == NULL the
+ *              statuses come from the host bitmap, with no device work.  A session that keeps no nodes is refused, and so is a
+ *              finished one, as in cp2_fill_block_proofs.
+ *   Refused    CP2_ERR_INVALID, the request index in cp2_last_error, outputs untouched: NULL arrays with n > 0, a slot outside the
+ *              range, a level above depth, an index at or past its layer's size.
+ *
+ * cp2_fill_add_multi_anchored is cp2_fill_add_multi with nodes = the groups' want lists' rows, packed in group order.
+ *   Data path  cp2_blocks_verify's, unchanged.  The work table holds the leaves, the sent rows, the kept inputs (gathered from the
+ *              session's buffer by address, once, before the layers) and the computed rows; k_multiproof_layer runs as it is, level by
+ *              level; k_multiproof_tops compares every top with its kept row, k_multiproof_fold ORs them into one verdict per group;
+ *              k_multiproof_commit stores what the proved groups leave.  The rest is cp2_fill_add's tail.
+ *   Result     status (n x CP2_FILL_*, one per REQUEST) and n_new, as cp2_fill_add_multi.  A group of present blocks: all DUPLICATE, 0
+ *              rows; an absent block whose root is known: NEW from its bare bytes.
+ *   Trace      CP2_TRACE prints cp2_fill_add_multi's line, and before it the number of tops and of kept inputs.
+ *   Refused    all or nothing, before any device or file work: cp2_fill_add_multi's checks in their order, where (8) compares n_rows with
+ *              the sum of the groups' want lists against the session AS IT STANDS NOW (both numbers in the message: a list made
+ *              before another add landed is stale and shows here); then a session that keeps no nodes (it uses cp2_fill_add_multi).
+ * Out of scope: cp2_multi_*; a many-session form; cp2_blocks_verify_multi against known nodes the caller supplies; repair with
+ * multiproofs; checkpoint formats. */
+enum { CP2_FILL_ROW_KNOWN = (0), CP2_FILL_ROW_UNKNOWN = (1) };   /* (an enum: the macros named CP2_FILL_* stay the statuses of the adds and of the proofs) */
+int cp2_fill_multiproof_want(const void* f /* cp2_fill* */, const uint64_t* groups /* n_groups x 2: dataset slot, count */, size_t n_groups,
+                             const uint64_t* blocks /* n */, uint64_t* level_index /* cap x 2 */, size_t cap, size_t* n_rows,
+                             uint64_t* group_rows /* n_groups, may be NULL */);
+int cp2_dataset_block_tree_rows(cp2_dataset* ds, const uint64_t* places /* n x 3: dataset slot, level, index */, size_t n,
+                                uint8_t* rows /* n x 32 */);
+int cp2_fill_block_tree_rows(void* f /* cp2_fill* */, const uint64_t* places /* n x 3: dataset slot, level, index */, size_t n,
+                             uint32_t* status /* n: CP2_FILL_ROW_* */, uint8_t* rows /* n x 32, may be NULL */);
+int cp2_fill_add_multi_anchored(void* f /* cp2_fill* */, const uint64_t* groups /* n_groups x 2: dataset slot, count */, size_t n_groups,
+                                const uint64_t* blocks /* n */, const uint8_t* data /* n x block_size */,
+                                const uint8_t* nodes /* n_rows x 32 */, size_t n_rows, uint32_t* status /* n: CP2_FILL_* */, size_t* n_new);
 
 
 /* ---- e: every GPU of the node behind one handle ------------------------------------------------------ */
